@@ -1,9 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the BGM / CausalBGM posterior-sampling hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline line (with `roofline`, which
+comes from the HIP events of the timed steps themselves).  --dump-outputs DIR writes what the last timed step
+returned (the ADRF and its interval, as a caller of CausalBGM.predict receives them) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.  What takes
+runs of its own -- the objects listed below except `roofline`, `kernel_paths`, and at N > 1 the all-reduce
+timing and `fit_dp` -- is measured only with --full.
 
 Metric (BASELINE.json): posterior samples/sec, whole job = MCMC transitions of per-observation
 latent chains per second, CausalBGM continuous treatment, Sim_Hirano_Imbens panel N=1e6 (per GPU,
@@ -13,7 +20,7 @@ panel with the inputs already resident in HBM: burn_in + n_mcmc Metropolis-Hasti
 every row, the fused dose-response inference for the retained draws, the slot reduction, (N>1) the
 ADRF all-reduce, and the posterior mean / quantiles.
 
-The JSON line also carries
+The JSON line also carries (all but roofline with --full only)
   roofline     -- the dominant kernel instance by share of kernel time (at the BASELINE iteration counts that is the keep-phase
                   instance causal_mh_kernel<EFFECT=1>: one transition + the outcome net at 20 doses per retained draw; the
                   burn-in instance <EFFECT=0> is listed beside it under "instances"), fp32 MFMA: algorithmic FLOP/launch
@@ -992,6 +999,11 @@ def main():
     ap.add_argument("--plumbing-only", action="store_true",
                     help="launch / rendezvous check without a device: every rank joins the process group over gloo on the CPU, the rank "
                          "count is all-reduced and rank 0 prints {n_gpus, n_ranks_in_collective}; no kernel runs (tests/test_bench_launch.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's ADRF and interval (what CausalBGM.predict returns) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: kernel_paths, the secondary legs (the --no-* "
+                         "options select among them), and at N > 1 the all-reduce timing and fit_dp; off by default")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1090,10 +1102,14 @@ def main():
     elapsed = float(t.item())
     eng.timing_enable(False)
     seed_counter_last = model._seed_counter
+    if args.dump_outputs and rank == 0:      # the ADRF is all-reduced: every rank holds the job's result
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("adrf", adrf), ("interval", interval)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float32))      # predict returns fp32
 
     # the one collective of the step (C3: ADRF draw sums [n_doses x n_mcmc], float64) timed alone, for its share of a step
     allreduce_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         buf = torch.zeros((len(x_values), args.n_mcmc), dtype=torch.float64, device=device)
         dist.all_reduce(buf)
         torch.cuda.synchronize()
@@ -1105,19 +1121,21 @@ def main():
 
     # which kernels each rank ran: the sampling path, and the minibatch-step path a data-parallel fit at the reference batch size
     # (32 rows in total, 32 // world per rank) would take on this rank (bgm_causal_describe inside a fit session)
-    b_fit = max(1, 32 // world)
-    eng.fit_begin(n_loc, b_fit)
-    try:
-        path = f"rank {rank}: rows [{row_lo}, {row_lo + n_loc}) {eng.describe(b_fit)}"
-    finally:
-        eng.fit_end()
-    paths = [path]
-    if world > 1:
-        paths = [None] * world
-        dist.all_gather_object(paths, path)
-    if rank == 0:
-        for line in paths:
-            print(line, file=sys.stderr)
+    paths = None
+    if args.full:
+        b_fit = max(1, 32 // world)
+        eng.fit_begin(n_loc, b_fit)
+        try:
+            path = f"rank {rank}: rows [{row_lo}, {row_lo + n_loc}) {eng.describe(b_fit)}"
+        finally:
+            eng.fit_end()
+        paths = [path]
+        if world > 1:
+            paths = [None] * world
+            dist.all_gather_object(paths, path)
+        if rank == 0:
+            for line in paths:
+                print(line, file=sys.stderr)
 
     out = None
     if rank == 0:
@@ -1201,16 +1219,17 @@ def main():
             "roofline": roof,
             "kernel_paths": paths,
         }
-        if not args.no_cpu_baseline and world == 1:
+        secondary = args.full and world == 1      # the secondary legs: one GPU, --full only
+        if not args.no_cpu_baseline and secondary:
             out["cpu_baseline"] = cpu_baseline(params, p, z_dims)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
             out["parity"] = parity_leg(model, x, y, v, z_dims, p, x_values)
-        if not args.no_configs and world == 1:      # (before anything retrains `model`: the encoder of the bench weights)
+        if not args.no_configs and secondary:      # (before anything retrains `model`: the encoder of the bench weights)
             out["encoder"] = encoder_leg(model, v, n_loc, p, z_dims, check_against_oracle=not args.no_cpu_baseline)
-        if world == 1:
+        if secondary:
             out["outcome_cache"] = outcome_cache_leg(model, data, x_values, n_loc, args, seed_counter_last, adrf, value, mode=True)
             out["outcome_cache"]["per_wave"] = outcome_cache_leg(model, data, x_values, n_loc, args, seed_counter_last, adrf, value, mode="wave")
-        if not args.no_bf16x3 and world == 1:      # before the fit leg, which trains (changes) the weights of `model`
+        if not args.no_bf16x3 and secondary:      # before the fit leg, which trains (changes) the weights of `model`
             out["bf16x3"] = bf16x3_leg(model, data, x_values, n_loc, args, z_dims, info.flop_per_row_transition, flop_keep_row, seed_counter_last)
             out["bf16x3"]["speedup_vs_fp32"] = out["bf16x3"]["value"] / value
             out["bf16x3"]["adrf_max_abs_diff_vs_fp32"] = float(np.abs(out["bf16x3"].pop("adrf") - adrf).max())
@@ -1220,17 +1239,17 @@ def main():
             f16["adrf_max_abs_diff_vs_fp32"] = float(np.abs(f16.pop("adrf") - adrf).max())
             out["bf16x3"]["f16x3"] = f16
         trained = None
-        if not args.no_end_to_end and world == 1:
+        if not args.no_end_to_end and secondary:
             out["end_to_end"], trained = end_to_end_leg(params, x, y, v, x_values, n_loc, args, use_bnn=False)
-        if not args.no_accuracy and world == 1:
+        if not args.no_accuracy and secondary:
             out["accuracy"] = accuracy_leg(params, data, x_values, n_loc, args, m=trained)
-        if args.end_to_end_bnn > 0 and world == 1:
+        if args.end_to_end_bnn > 0 and secondary:
             out["end_to_end_bayesian"], _ = end_to_end_leg(params, x, y, v, x_values, n_loc, args, use_bnn=True, epochs=args.end_to_end_bnn, tag="bnn")
-        if not args.no_bayesian and world == 1:
+        if not args.no_bayesian and secondary:
             out["bayesian_nets"] = bayesian_leg(params, data, x_values, n_loc, args, device)
-        if not args.no_bgm and world == 1:
+        if not args.no_bgm and secondary:
             out["bgm_hmc"] = bgm_hmc_leg(device)
-        if not args.no_configs and world == 1:
+        if not args.no_configs and secondary:
             import contextlib
             with contextlib.redirect_stdout(sys.stderr):      # (the classes print progress lines as the reference does)
                 out["config_c1"] = config_c1_leg(device)
@@ -1244,17 +1263,17 @@ def main():
                     bx3 = config_c4_share_leg(device, use_bnn=True, precision="f16x3")
                     bx3["speedup_vs_fp32"] = out["config_c4_share"]["use_bnn"]["predict_seconds"] / bx3["predict_seconds"]
                     out["config_c4_share"]["use_bnn"]["f16x3"] = bx3
-        if not args.no_general_width and world == 1:
+        if not args.no_general_width and secondary:
             out["general_width_engine"] = general_width_leg(p, z_dims, device)
             import contextlib
             with contextlib.redirect_stdout(sys.stderr):
                 out["wide_bayesian_nets"] = wide_bayesian_leg(device)
-        if not args.no_fit and world == 1:
+        if not args.no_fit and secondary:
             out["fit"] = fit_leg(model, x, y, v, n_loc)
             out["fit_dp"] = fit_dp_leg(model, x, y, v, n_loc, 1, device)      # the data-parallel call on a one-rank communicator
             out["fit_dp"]["vs_single_process_epoch_call"] = out["fit_dp"]["us_per_minibatch"] / out["fit"]["us_per_minibatch"]
             out["training_steps"] = training_leg(params, x, y, v, device)
-    if world > 1 and not args.no_fit:
+    if world > 1 and args.full and not args.no_fit:
         # every rank: the data-parallel minibatch loop with its gradient all-reduce (configs[3], fit side) -- AFTER everything of the
         # headline is measured, and under a watchdog: this is where the library's own RCCL communicator is created, and the headline
         # line must survive whatever a first multi-GPU run does here (a failure or a stall is reported in the line, not instead of it)

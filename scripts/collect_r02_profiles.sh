@@ -20,9 +20,9 @@ pmc3() {   # name, command...
 for w in $WHAT; do
   case $w in
     bench)
-      python bench.py --steps 2 --warmup 1 > $OUT/r02_bench_N1e6_1gpu.json 2> $OUT/bench.err
-      timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o kt -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy > $OUT/kt_bench.log 2>&1
-      { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy"; summ $OUT/kt_bench; } > $OUT/r02_kernel_trace_bench_N1e6.txt ;;
+      python bench.py --full --steps 2 --warmup 1 > $OUT/r02_bench_N1e6_1gpu.json 2> $OUT/bench.err
+      timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o kt -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy > $OUT/kt_bench.log 2>&1
+      { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy"; summ $OUT/kt_bench; } > $OUT/r02_kernel_trace_bench_N1e6.txt ;;
     mh) pmc3 mh_N1e6_60burn_40keep python scripts/probe_mh.py 1e6 100 40 ;;
     encode)
       python scripts/probe_encode.py 1e6 200 20 > $OUT/r02_encode_N1e6.json 2> $OUT/encode.err

@@ -24,9 +24,9 @@ passes() {   # tag, command...
 for w in $WHAT; do
   case $w in
     bench)
-      python bench.py --steps 2 --warmup 1 > $OUT/r04_bench_N1e6_1gpu.json 2> $OUT/bench.err
-      timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o kt -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy --no-bgm > $OUT/kt_bench.log 2>&1
-      { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy --no-bgm"; summ $OUT/kt_bench; } > $OUT/r04_kernel_trace_bench_N1e6.txt
+      python bench.py --full --steps 2 --warmup 1 > $OUT/r04_bench_N1e6_1gpu.json 2> $OUT/bench.err
+      timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o kt -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy --no-bgm > $OUT/kt_bench.log 2>&1
+      { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy --no-bgm"; summ $OUT/kt_bench; } > $OUT/r04_kernel_trace_bench_N1e6.txt
       rm -rf $OUT/kt_bench ;;
     keep) passes causal_mh python scripts/probe_mh.py 1e6 100 40 ;;
     bx3) passes causal_mh_bf16x3 python scripts/probe_mh.py 1e6 100 40 bf16x3 ;;

@@ -24,9 +24,9 @@ passes() {   # tag, command...
 for w in $WHAT; do
   case $w in
     bench)
-      timeout 1500 python bench.py --steps 2 --warmup 1 > $OUT/r05_bench_N1e6_1gpu.json 2> $OUT/bench.err < /dev/null
-      timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o kt -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy --no-bgm --no-end-to-end --no-bf16x3 > $OUT/kt_bench.log 2>&1 < /dev/null
-      { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy --no-bgm --no-end-to-end --no-bf16x3   (one headline predict with the outcome cache off, one per chain = event form, one per wave)"; summ $OUT/kt_bench; } > $OUT/r05_kernel_trace_bench_N1e6.txt
+      timeout 1500 python bench.py --full --steps 2 --warmup 1 > $OUT/r05_bench_N1e6_1gpu.json 2> $OUT/bench.err < /dev/null
+      timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o kt -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy --no-bgm --no-end-to-end --no-bf16x3 > $OUT/kt_bench.log 2>&1 < /dev/null
+      { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-bayesian --no-fit --no-accuracy --no-bgm --no-end-to-end --no-bf16x3   (one headline predict with the outcome cache off, one per chain = event form, one per wave)"; summ $OUT/kt_bench; } > $OUT/r05_kernel_trace_bench_N1e6.txt
       rm -rf $OUT/kt_bench ;;
     # the retained phase at the bench shape: 60 burn-in + 82 retained iterations (two segments of the event form at the default budget),
     # outcome cache off / per wave / per chain (event form) twice

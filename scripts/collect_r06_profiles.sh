@@ -53,8 +53,8 @@ for w in $WHAT; do
       for w in 8 12 16; do echo "BGM_X3_WAVES=$w"; BGM_X3_WAVES=$w BGM_PROBE_PRECISION=f16x3 python scripts/probe_bgm_wide.py 2e5 4; done > $OUT/r06_bgm_hmc_f16x3_waves.txt 2>&1
       python scripts/probe_bgm_wide.py 2e5 4 >> $OUT/r06_bgm_hmc_f16x3_waves.txt 2>&1 ;;
     bench)
-      timeout 1500 rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o kt -- python bench.py > $OUT/kt_bench.log 2>&1 < /dev/null
-      { echo "# rocprofv3 --kernel-trace --stats -- python bench.py   (the default invocation)"; summ $OUT/kt_bench; } > $OUT/r06_kernel_trace_bench_N1e6.txt
+      timeout 1500 rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o kt -- python bench.py --full > $OUT/kt_bench.log 2>&1 < /dev/null
+      { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full   (every leg)"; summ $OUT/kt_bench; } > $OUT/r06_kernel_trace_bench_N1e6.txt
       grep -E "^\{" $OUT/kt_bench.log | tail -1 > $OUT/r06_bench_N1e6_1gpu_under_rocprof.json
       rm -rf $OUT/kt_bench ;;
     # what the Rademacher sign applications / all epilogues of the Flipout layers cost (development builds, csrc/build/abl/)
@@ -63,7 +63,7 @@ for w in $WHAT; do
         lib=bayesgm_amd/csrc/build/abl/lib_$v.so
         [ $v = product ] && lib=bayesgm_amd/libbgm_hip.so
         [ -f $lib ] || continue
-        BGM_HIP_LIB=$PWD/$lib timeout 600 python bench.py --steps 1 --warmup 0 --burn-in 500 --n-mcmc 300 --no-cpu-baseline --no-fit --no-bgm --no-general-width --no-bf16x3 --no-accuracy --no-end-to-end --no-configs 2> $OUT/abl_$v.err | python -c "
+        BGM_HIP_LIB=$PWD/$lib timeout 600 python bench.py --full --steps 1 --warmup 0 --burn-in 500 --n-mcmc 300 --no-cpu-baseline --no-fit --no-bgm --no-general-width --no-bf16x3 --no-accuracy --no-end-to-end --no-configs 2> $OUT/abl_$v.err | python -c "
 import json, sys
 d = json.loads(sys.stdin.readline())['bayesian_nets']
 print('$v', json.dumps({k: d[k] for k in ('burn_in_iteration_ms', 'kept_iteration_ms', 'sampler_frac_of_fp32_mfma_peak', 'effects_frac_of_fp32_mfma_peak', 'value')}))" >> $OUT/r06_bnf_ablation.txt

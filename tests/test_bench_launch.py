@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,7 +58,7 @@ def test_refuses_more_ranks_than_devices():
 def test_bare_two_rank_bench_on_one_device():
     """the whole step (sharded predict, ADRF all-reduce, max-over-ranks timing) from the driver's bare command form; both ranks on GPU 0
     over gloo -- the RCCL form of the same launch is tests/test_gpu_rccl.py, which needs two devices"""
-    r = _bare(["--gpus", "2", "--rows", "4096", "--burn-in", "40", "--n-mcmc", "20", "--steps", "1", "--warmup", "1"],
+    r = _bare(["--gpus", "2", "--rows", "4096", "--burn-in", "40", "--n-mcmc", "20", "--steps", "1", "--warmup", "1", "--full"],
               env_extra={"BGM_BENCH_SINGLE_DEVICE": "1", "BGM_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -68,3 +69,21 @@ def test_bare_two_rank_bench_on_one_device():
     f = d["fit_dp"]
     assert "error" not in f, f
     assert f["n_ranks_in_collective"] == 2 and f["global_minibatch"] == 64 and f["us_per_minibatch"] > 0 and 0 < f["allreduce_share_of_minibatch"] < 1
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """a plain run is the headline alone (the secondary legs need --full); --dump-outputs writes the last timed step's ADRF and interval,
+    the same from run to run (seeded panel, weights and Philox streams)"""
+    got = []
+    for k in range(2):
+        r = _bare(["--rows", "4096", "--burn-in", "40", "--n-mcmc", "20", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / str(k))])
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = _json_line(r.stdout)
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["roofline"]["frac"] > 0
+        assert d["kernel_paths"] is None and not {"cpu_baseline", "outcome_cache", "fit", "fit_dp", "accuracy"} & set(d)
+        got.append({n: np.load(str(tmp_path / str(k) / (n + ".npy"))) for n in ("adrf", "interval")})
+    assert got[0]["adrf"].shape == (20,) and got[0]["interval"].shape == (20, 2)
+    assert [float(a) for a in got[1]["adrf"][:3]] == d["adrf_head"]      # the ADRF of the line's last timed step
+    for n in got[0]:
+        assert got[0][n].dtype == np.float32 and np.array_equal(got[0][n], got[1][n])

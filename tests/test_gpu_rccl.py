@@ -68,7 +68,7 @@ def test_bare_bench_over_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "BGM_BENCH_SINGLE_DEVICE",
                                                             "BGM_BENCH_BACKEND")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "65536", "--burn-in", "100", "--n-mcmc", "50",
-                        "--steps", "1", "--warmup", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--steps", "1", "--warmup", "1", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _lines(r)[-1]
     assert d["n_gpus"] == 2 and d["n_ranks_in_collective"] == 2 and d["config"]["rows_total"] == 131072
     assert d["adrf_allreduce_ms"] is not None and d["value"] > 0
