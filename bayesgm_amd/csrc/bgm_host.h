@@ -56,6 +56,14 @@ struct bgm_handle {
   float *sblob_dev = nullptr;
   size_t sblob_cap = 0;
   bool sblob_valid = false;
+  // Gram copy of the sampling blob for the fp32 MH kernels (causal_kernels.h, g_last_gram): g's output layer replaced by G = W W^T,
+  // the anchor a0 and the variance column; rebuilt whenever the sampling copy is.  gram_w_dev: [p][64] W^T, then m0 [p], for the
+  // per-call pre-pass over the panel (uc_dev: [n][64] 2 u, then [n] c).  mh_direct: BGM_MH_DIRECT_LIKELIHOOD at bgm_create
+  float *gblob_dev = nullptr, *gram_w_dev = nullptr, *uc_dev = nullptr;
+  size_t gblob_cap = 0, gram_w_cap = 0, uc_cap = 0;
+  bool gram_valid = false;
+  bool mh_direct = false;
+  CausalMeta gmeta{};
   // split-precision (bf16 x 3) sampling blob (causal_bx3_api.hip); precision: 0 fp32 (default), 1 bf16x3, 2 f16x3 (bgm_causal_set_precision)
   int precision = 0;
   void *bx_blob_dev = nullptr;

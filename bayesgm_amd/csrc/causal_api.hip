@@ -31,6 +31,9 @@ extern "C" int bgm_create(bgm_handle **out, int device) {
   bgm_handle *h = new bgm_handle();
   h->device = device;
   h->n_cus = prop.multiProcessorCount;
+  // BGM_MH_DIRECT_LIKELIHOOD=1: the fp32 MH kernels keep the direct form of g's likelihood on every shape (A/B runs, fallback)
+  const char *direct = std::getenv("BGM_MH_DIRECT_LIKELIHOOD");
+  h->mh_direct = direct != nullptr && std::strcmp(direct, "0") != 0;
   *out = h;
   return BGM_OK;
 }
@@ -47,6 +50,9 @@ extern "C" int bgm_destroy(bgm_handle *h) {
   if (h->blob_dev) hipFree(h->blob_dev);
   if (h->eblob_dev) hipFree(h->eblob_dev);
   if (h->sblob_dev) hipFree(h->sblob_dev);
+  if (h->gblob_dev) hipFree(h->gblob_dev);
+  if (h->gram_w_dev) hipFree(h->gram_w_dev);
+  if (h->uc_dev) hipFree(h->uc_dev);
   if (h->bx_blob_dev) hipFree(h->bx_blob_dev);
   if (h->acc_scratch) hipFree(h->acc_scratch);
   if (h->eff_cache) hipFree(h->eff_cache);
@@ -267,10 +273,139 @@ int bgm_causal_sampling_blob(bgm_handle *h, hipStream_t stream) {
     BGM_HIP_CHECK(hipMalloc(&h->sblob_dev, n * sizeof(float)));
     h->sblob_cap = n;
   }
+  h->gram_valid = false;      // the Gram copy derives from this one
   hipLaunchKernelGGL(causal_scale_blob_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, h->blob_dev, h->sblob_dev,
                      h->meta, h->NTL);
   BGM_HIP_CHECK(hipGetLastError());
   h->sblob_valid = true;
+  return BGM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Gram form of g's likelihood for the fp32 MH kernels (causal_kernels.h, g_last_gram): on the shapes with NTL > 2 output tiles
+// the 16 NTL MFMAs of g's output layer become the 16 of one 64 x 64 product with G = W W^T.
+// ---------------------------------------------------------------------------
+static bool gram_wanted(const bgm_handle *h, int NTL) { return !h->mh_direct && h->precision == 0 && NTL > 2; }
+
+// element (input row i, output column o) of a 64-row layer packed by pack_layer with the identity row map
+static float packed_w(const std::vector<float> &b, int off, int NT, int i, int o) {
+  const int t = o >> 4;
+  int T0 = 0, GS = group_size(NT);
+  while (t >= T0 + GS) { T0 += GS; GS = group_size(NT - T0); }
+  return b[(size_t)off + (size_t)64 * 16 * T0 + ((size_t)i * 16 + (o & 15)) * GS + (t - T0)];
+}
+
+// The Gram copy of the sampling blob (h->gblob_dev, h->gmeta) and the pre-pass operands (h->gram_w_dev), derived from the scaled
+// weights of the sampling copy in float64 and rounded once:  a0 = g's last hidden activation at z = 0, m0 = W^T a0 + b (from the
+// rounded a0), G = W W^T over the p mean columns, w_sig / b_sig = the variance column.  Layout: the sampling blob up to g's
+// hidden layers, then G [64 x 64] packed as a hidden layer (gmeta.wgl), [a0 64 | w_sig 64 | b_sig, 0, 0, 0] (gmeta.bgl), then
+// the f / h part of the sampling blob.  It does not grow with p.
+static int bgm_causal_gram_blob(bgm_handle *h, hipStream_t stream) {
+  if (h->gram_valid) return BGM_OK;
+  const CausalMeta &m = h->meta;
+  const int p = m.p, NTL = h->NTL;
+  std::vector<float> sb((size_t)m.total);
+  BGM_HIP_CHECK(hipMemcpyAsync(sb.data(), h->sblob_dev, sb.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+  BGM_HIP_CHECK(hipStreamSynchronize(stream));
+  auto lrs = [](double x) { return x + (double)BGM_LRS * std::fabs(x); };      // lrelu_s
+  std::vector<double> act(64), nxt(64);
+  for (int o = 0; o < 64; ++o) act[o] = lrs((double)sb[m.b1g + o]);
+  for (int l = 0; l < m.n_gh; ++l) {
+    for (int o = 0; o < 64; ++o) {
+      double s = sb[m.bg + l * 64 + o];
+      for (int i = 0; i < 64; ++i) s += (double)packed_w(sb, m.wg + l * 4096, 4, i, o) * act[i];
+      nxt[o] = lrs(s);
+    }
+    act.swap(nxt);
+  }
+  std::vector<float> a0(64), W((size_t)64 * p), wt((size_t)65 * p), G(64 * 64);
+  for (int i = 0; i < 64; ++i) a0[i] = (float)act[i];
+  for (int i = 0; i < 64; ++i)
+    for (int c = 0; c < p; ++c) W[(size_t)i * p + c] = packed_w(sb, m.wgl, NTL, i, c);
+  for (int c = 0; c < p; ++c) {
+    double s = sb[m.bgl + c];
+    for (int i = 0; i < 64; ++i) { s += (double)W[(size_t)i * p + c] * (double)a0[i]; wt[(size_t)c * 64 + i] = W[(size_t)i * p + c]; }
+    wt[(size_t)64 * p + c] = (float)s;
+  }
+  for (int i = 0; i < 64; ++i)
+    for (int k = 0; k <= i; ++k) {
+      double s = 0.0;
+      for (int c = 0; c < p; ++c) s += (double)W[(size_t)i * p + c] * (double)W[(size_t)k * p + c];
+      G[i * 64 + k] = G[k * 64 + i] = (float)s;
+    }
+  CausalMeta gm = m;
+  gm.bgl = m.wgl + 4096;
+  const int shift = (gm.bgl + 132) - m.wf2;           // the f / h part follows [a0 | w_sig | b_sig + padding]
+  for (int CausalMeta::*f : {&CausalMeta::wf2, &CausalMeta::bf2, &CausalMeta::wf3, &CausalMeta::bf3, &CausalMeta::wf4, &CausalMeta::bf4,
+                             &CausalMeta::wh2, &CausalMeta::bh2, &CausalMeta::wh3, &CausalMeta::bh3, &CausalMeta::wh4, &CausalMeta::bh4,
+                             &CausalMeta::wxf, &CausalMeta::total})
+    gm.*f += shift;
+  std::vector<float> gb((size_t)gm.total, 0.0f);
+  std::copy(sb.begin(), sb.begin() + m.wgl, gb.begin());
+  pack_layer(gb, gm.wgl, G.data(), 64, 64, 4, 4, [](int rho) { return rho; });
+  for (int i = 0; i < 64; ++i) { gb[gm.bgl + i] = a0[i]; gb[gm.bgl + 64 + i] = packed_w(sb, m.wgl, NTL, i, m.sig_slot); }
+  gb[gm.bgl + 128] = sb[m.bgl + m.sig_slot];
+  std::copy(sb.begin() + m.wf2, sb.end(), gb.begin() + gm.wf2);
+  if (h->gblob_cap < gb.size()) {
+    if (h->gblob_dev) BGM_HIP_CHECK(hipFree(h->gblob_dev));
+    BGM_HIP_CHECK(hipMalloc(&h->gblob_dev, gb.size() * sizeof(float)));
+    h->gblob_cap = gb.size();
+  }
+  if (h->gram_w_cap < wt.size()) {
+    if (h->gram_w_dev) BGM_HIP_CHECK(hipFree(h->gram_w_dev));
+    BGM_HIP_CHECK(hipMalloc(&h->gram_w_dev, wt.size() * sizeof(float)));
+    h->gram_w_cap = wt.size();
+  }
+  BGM_HIP_CHECK(hipMemcpyAsync(h->gblob_dev, gb.data(), gb.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+  BGM_HIP_CHECK(hipMemcpyAsync(h->gram_w_dev, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+  BGM_HIP_CHECK(hipStreamSynchronize(stream));  // stack-local staging buffers
+  h->gmeta = gm;
+  h->gram_valid = true;
+  return BGM_OK;
+}
+
+// Per-call pre-pass over the panel: uc[row][0..63] = 2 W (m0 - v_row), uc[64 n + row] = |m0 - v_row|^2.  One thread per row with a
+// fixed summation order: a row's values depend on that row alone (row blocking, sharding and chunking leave them bit-identical).
+static __global__ __launch_bounds__(256) void causal_gram_prepass_kernel(const float *wt, const float *v, long long n, int p, float *uc) {
+  extern __shared__ __attribute__((aligned(16))) float sw[];     // [p][64] W^T, then m0 [p]
+  for (int i = threadIdx.x; i < 65 * p; i += blockDim.x) sw[i] = wt[i];
+  __syncthreads();
+  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  const float *vr = v + row * p;
+  f32x4 acc[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  float c = 0.0f;
+  for (int col = 0; col < p; ++col) {
+    const float d = sw[64 * p + col] - vr[col];
+    c = fmaf(d, d, c);
+    const f32x4 *w = reinterpret_cast<const f32x4 *>(sw + 64 * col);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const f32x4 wv = w[k];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[k][r] = fmaf(wv[r], d, acc[k][r]);
+    }
+  }
+  f32x4 *out = reinterpret_cast<f32x4 *>(uc + row * 64);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) out[k] = acc[k] + acc[k];
+  uc[64 * n + row] = c;
+}
+
+static int causal_gram_prepare(bgm_handle *h, const float *v, int64_t n, hipStream_t stream) {
+  int rc = bgm_causal_gram_blob(h, stream);
+  if (rc) return rc;
+  const size_t need = (size_t)n * 65;
+  if (h->uc_cap < need) {
+    if (h->uc_dev) BGM_HIP_CHECK(hipFree(h->uc_dev));
+    BGM_HIP_CHECK(hipMalloc(&h->uc_dev, need * sizeof(float)));
+    h->uc_cap = need;
+  }
+  hipLaunchKernelGGL(causal_gram_prepass_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)65 * h->p * sizeof(float), stream,
+                     h->gram_w_dev, v, (long long)n, h->p, h->uc_dev);
+  BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;
 }
 
@@ -374,7 +509,8 @@ static int launch_mh(bgm_handle *h, const CausalMhKArgs &ka, int grid, int lds, 
   int rc;
 #define X(KT1_, KSL1_, NTL_)                                                                   \
   if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \
-    auto k = causal_mh_kernel<KT1_, KSL1_, NTL_, MH_R, MH_WAVES, EFFECT>;                      \
+    auto k = ka.uc ? causal_mh_kernel<KT1_, KSL1_, NTL_, MH_R, MH_WAVES, EFFECT, 0, (NTL_ > 2)>  \
+                   : causal_mh_kernel<KT1_, KSL1_, NTL_, MH_R, MH_WAVES, EFFECT>;              \
     rc = set_lds(k, lds);                                                                      \
     if (rc) return rc;                                                                         \
     hipLaunchKernelGGL(k, dim3(grid), dim3(64 * MH_WAVES), lds, stream, ka);                   \
@@ -410,17 +546,23 @@ extern "C" int bgm_causal_mh_run(bgm_handle *h, const bgm_mh_args *a, void *stre
   }
   int rc = bgm_causal_sampling_blob(h, stream);
   if (rc) return rc;
+  // fp32 kernels on the shapes with NTL > 2: g's likelihood in the Gram form (the Gram blob and the rows' 2 u, c of this call).
+  // Every launch of the call, the burn-in's initial log posterior included, uses the same form; so does every earlier call of the
+  // handle whose cached log posterior (init = 0) this one continues
+  const bool gram = gram_wanted(h, h->NTL);
+  if (gram && (rc = causal_gram_prepare(h, a->v_dev, a->n, stream))) return rc;
   const int grid = mh_grid(h, a->n);
-  const int lds = h->meta.total * 4 + 64;   // + per-wave progress counters
+  const int lds = (gram ? h->gmeta.total : h->meta.total) * 4 + 64;   // + per-wave progress counters
 
   CausalMhKArgs ka{};
-  ka.blob = h->sblob_dev; ka.x = a->x_dev; ka.y = a->y_dev; ka.v = a->v_dev;
+  ka.blob = gram ? h->gblob_dev : h->sblob_dev; ka.x = a->x_dev; ka.y = a->y_dev; ka.v = a->v_dev;
+  ka.uc = gram ? h->uc_dev : nullptr;
   ka.n = a->n; ka.row_base = a->row_base; ka.state = a->state_dev; ka.logp = a->logp_dev;
   ka.burn_in = a->burn_in; ka.q_sd = a->q_sd;
   ka.k0 = (unsigned)(a->seed & 0xFFFFFFFFull); ka.k1 = (unsigned)(a->seed >> 32);
   ka.acc_count = a->acc_count_dev; ka.draws = a->draws_dev; ka.n_keep = a->n_keep;
   ka.sample_y = a->sample_y; ka.n_doses = a->n_doses; ka.x_values = a->x_values_dev;
-  ka.adrf_partial = a->adrf_partial_dev; ka.ite = a->ite_dev; ka.clk = (unsigned long long *)a->clock_dev; ka.m = h->meta;
+  ka.adrf_partial = a->adrf_partial_dev; ka.ite = a->ite_dev; ka.clk = (unsigned long long *)a->clock_dev; ka.m = gram ? h->gmeta : h->meta;
 
   // Split the segment at burn_in: the burn-in part runs the pure-transition kernel.
   struct Seg { int begin, n, effect, init, ev; };       // ev: 0 fused kernels; 1 / 2 = first / later segment of the event form
@@ -692,10 +834,10 @@ extern "C" int bgm_causal_mh_info(bgm_handle *h, int64_t n, bgm_mh_info *info) {
   info->rows_per_wave = 16 * MH_R;
   info->waves_per_block = MH_WAVES;
   info->grid_blocks = mh_grid(h, n);
-  // issued MFMAs per 16 rows, times R row groups
-  const int per16 = 3 * ks1 * 4 + n_gh * 64 + 16 * NTL + 2 * (32 + 8 + 4);
+  // issued MFMAs per 16 rows, times R row groups (g's output layer: 16 NTL in the direct form, 16 x 4 in the Gram form)
+  const int per16 = 3 * ks1 * 4 + n_gh * 64 + (gram_wanted(h, NTL) ? 16 * 4 : 16 * NTL) + 2 * (32 + 8 + 4);
   info->mfma_per_transition_per_wave = per16 * MH_R;
-  info->lds_bytes = h->blob_valid ? h->meta.total * 4 : 0;
+  info->lds_bytes = !h->blob_valid ? 0 : (gram_wanted(h, NTL) && h->gram_valid) ? h->gmeta.total * 4 : h->meta.total * 4;
   double macs = 0.0;
   for (int id : {BGM_NET_G, BGM_NET_F, BGM_NET_H}) {
     const HostNet &nn = h->nets[id];

@@ -110,7 +110,8 @@ int bgm_causal_event_mh_launch(bgm_handle *h, CausalMhKArgs &ka, int grid, int l
   int rc;
 #define X(KT1_, KSL1_, NTL_)                                                                   \
   if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \
-    auto k = causal_mh_kernel<KT1_, KSL1_, NTL_, EV_MH_R, EV_MH_WAVES, 3>;                     \
+    auto k = ka.uc ? causal_mh_kernel<KT1_, KSL1_, NTL_, EV_MH_R, EV_MH_WAVES, 3, 0, (NTL_ > 2)> \
+                   : causal_mh_kernel<KT1_, KSL1_, NTL_, EV_MH_R, EV_MH_WAVES, 3>;             \
     if ((rc = ev_set_lds(k, lds))) return rc;                                                  \
     hipLaunchKernelGGL(k, dim3(grid), dim3(64 * EV_MH_WAVES), lds, stream, ka);                \
     BGM_HIP_CHECK(hipGetLastError());                                                          \

@@ -22,7 +22,7 @@ struct CausalMeta {
   // LDS blob offsets (floats)
   int w1g, w1f, w1h, b1g, b1f, b1h;
   int wg, bg;           // n_gh consecutive [64][64] / [64]
-  int wgl, bgl;         // last g layer [64][16*NTL] / [16*NTL]
+  int wgl, bgl;         // last g layer [64][16*NTL] / [16*NTL]  (Gram copy of the blob: G [64][64] / [a0 | w_sig | b_sig], g_last_gram)
   int wf2, bf2, wf3, bf3, wf4, bf4;
   int wh2, bh2, wh3, bh3, wh4, bh4;
   int wxf;              // f L1 x-row, accumulator layout [64]
@@ -32,6 +32,7 @@ struct CausalMeta {
 struct CausalMhKArgs {
   const float *blob;    // packed weights (global)
   const float *x, *y, *v;
+  const float *uc;          // Gram form of g's likelihood (GRAM): [n][64] 2 u, then [n] c per local row (causal_gram_prepass_kernel); else NULL
   long long n, row_base;
   float *state, *logp;
   int init, it_begin, n_iters, burn_in;
@@ -64,6 +65,7 @@ struct CausalMhKArgs {
 // log p(z | x, y, v) for R x 16 chains held by one wave.
 //   zin  : L1 input tiles, feature 16 t + 4 r + g  (z features, then x at index q, then 0)
 //   vreg : (bias of g's last layer) - (V row), feature 16 t + 4 g + r (load_v_rows); the variance slot holds the bias alone
+//          (GRAM: the row's 2 u and c instead, load_gram_rows / g_last_gram)
 // Returns logp[rr] replicated over the four lane groups.
 // ---------------------------------------------------------------------------
 template <int T0, int KT, int NTL, int R>
@@ -137,6 +139,75 @@ __device__ __forceinline__ void g_last_groups(const float *wl, const float *bl, 
   }
 }
 
+// ---------------------------------------------------------------------------
+// Gram form of g's Gaussian term (the MH kernel on the shapes where it issues fewer MFMAs, NTL > 2).  With a = g's last hidden
+// activation (lrelu_s scaling), W [64 x p] / b the mean columns of the (scaled) output layer, a0 the activation at z = 0 and
+// m0 = W^T a0 + b (per model), and per row u = W (m0 - v), c = |m0 - v|^2:
+//     |W^T a + b - v|^2 = d^T (G d + 2 u) + c,   d = a - a0,  G = W W^T  [64 x 64]
+// so the 16 NTL MFMAs of the output layer become the 16 of one 64 x 64 product.  The anchor a0 keeps the cancellation relative
+// to |g(0) - v|^2; d is formed explicitly in fp32 (folding a0 into u would give back the unanchored form).
+// LDS (the Gram copy of the sampling blob, bgm_causal_gram_blob): m.wgl = G packed as a hidden layer, m.bgl = [a0 | w_sig | b_sig],
+// natural feature order.  vreg: tiles 0-3 = 2 u in accumulator layout (feature 16 t + 4 g + r), tile 4 = (c, 0, 0, 0) in lane
+// group 0 and zero elsewhere (load_gram_rows).  Returns per-lane partials of the squared residual (summed over g by the caller)
+// and the raw variance output s = w_sig . a + b_sig, valid in every lane.
+// ---------------------------------------------------------------------------
+template <int R>
+__device__ __forceinline__ void g_last_gram(const float *lds, const CausalMeta &m, int lane_off, int g, const f32x4 (&h)[R][4],
+                                            const f32x4 (&vreg)[R][5], float (&ssq)[R], float (&sraw)[R]) {
+  const float *a0 = lds + m.bgl + 4 * g, *ws = a0 + 64;
+  f32x4 d[R][4];
+  float sp[R];
+#pragma unroll
+  for (int rr = 0; rr < R; ++rr) sp[rr] = 0.0f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const f32x4 a0t = *reinterpret_cast<const f32x4 *>(a0 + 16 * t);
+    const f32x4 wst = *reinterpret_cast<const f32x4 *>(ws + 16 * t);
+#pragma unroll
+    for (int rr = 0; rr < R; ++rr)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        d[rr][t][r] = h[rr][t][r] - a0t[r];
+        sp[rr] = fmaf(wst[r], h[rr][t][r], sp[rr]);
+      }
+  }
+  f32x4 y[R][4];
+  const float *base = lds + m.wgl + lane_off * 4;
+  bool done = false;
+#ifndef BGM_NO_ASM_DENSE
+  if constexpr (R == 1) {
+    dense_group4_k64_asm_c(lds_byte_addr(base), d[0], vreg[0][0], vreg[0][1], vreg[0][2], vreg[0][3], y[0][0], y[0][1], y[0][2], y[0][3]);
+    done = true;
+  }
+#endif
+  if (!done) {
+#pragma unroll
+    for (int rr = 0; rr < R; ++rr)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) y[rr][u] = vreg[rr][u];
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+      AFrag<4> af;
+      af.load(base + (16 * (ks >> 2) + (ks & 3)) * 16 * 4);
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int rr = 0; rr < R; ++rr) y[rr][u] = BGM_MFMA(af.get(u), d[rr][ks >> 2][ks & 3], y[rr][u]);
+    }
+  }
+  const float bs = lds[m.bgl + 128];
+#pragma unroll
+  for (int rr = 0; rr < R; ++rr) {
+    float s = vreg[rr][4][0];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s = fmaf(d[rr][t][r], y[rr][t][r], s);
+    ssq[rr] = s;
+    sraw[rr] = sum_over_g(sp[rr]) + bs;
+  }
+}
+
 // f / h tail:  64 -> 32 -> 8 -> 2   (f_units = h_units = [64, 32, 8]); a1 is the
 // activated first hidden layer.  Returns the raw outputs (mu, s) of every row group, valid in every lane
 // (the sampling blob replicates the two output columns for all lane groups, see above causal_effects).
@@ -164,10 +235,10 @@ __device__ __forceinline__ void fh_tail(const float *lds, int w2, int b2, int w3
 #else
 #define PMARK(i)
 #endif
-template <int KT1, int KSL1, int NTL, int R>
+template <int KT1, int KSL1, int NTL, int R, bool GRAM = false>
 __device__ __forceinline__ void causal_logp(const float *lds, const CausalMeta &m, int lane_off, int g,
                                             int j, const f32x4 (&zin)[R][KT1],
-                                            const f32x4 (&vreg)[R][NTL], const float (&xr)[R],
+                                            const f32x4 (&vreg)[R][GRAM ? 5 : NTL], const float (&xr)[R],
                                             const float (&yr)[R], float (&logp)[R]
 #ifdef BGM_PROF
                                             , unsigned long long (&tsec)[8], unsigned long long &tlast
@@ -207,10 +278,14 @@ __device__ __forceinline__ void causal_logp(const float *lds, const CausalMeta &
     PMARK(2);
 #pragma unroll
     for (int rr = 0; rr < R; ++rr) { ssq[rr] = 0.0f; sraw_v[rr] = 0.0f; }
-    const int pc = m.sig_pc;  // position of the variance column inside the last tile (see bgm_g_last_padded)
-    g_last_groups<0, 4, NTL, R>(lds + m.wgl, lds + m.bgl, lane_off, g, pc - 4 * g, h, vreg, ssq, sraw_v);
+    if constexpr (GRAM) {
+      g_last_gram<R>(lds, m, lane_off, g, h, vreg, ssq, sraw_v);
+    } else {
+      const int pc = m.sig_pc;  // position of the variance column inside the last tile (see bgm_g_last_padded)
+      g_last_groups<0, 4, NTL, R>(lds + m.wgl, lds + m.bgl, lane_off, g, pc - 4 * g, h, vreg, ssq, sraw_v);
 #pragma unroll
-    for (int rr = 0; rr < R; ++rr) sraw_v[rr] = __shfl(sraw_v[rr], j + 16 * (pc >> 2));
+      for (int rr = 0; rr < R; ++rr) sraw_v[rr] = __shfl(sraw_v[rr], j + 16 * (pc >> 2));
+    }
     PMARK(3);
   }
   // ---- f : (z0, z1, x) -> (mu_y, s_y)   (base.py:793-798)  and  h : (z0, z2) -> (mu_x | logit, s_x)   (:786-791)
@@ -313,6 +388,21 @@ __device__ __forceinline__ void load_v_rows(const float *v, const float *bl, lon
         const int c = 16 * t + 4 * g + r;
         vreg[rr][t][r] = bl[c] - ((c < p) ? vr[c] : 0.0f);
       }
+  }
+}
+
+// Gram form: 2 u (tiles 0-3, accumulator layout, 16-byte loads) and c (tile 4, lane group 0) of the tile's rows (see g_last_gram)
+template <int R>
+__device__ __forceinline__ void load_gram_rows(const float *uc, long long n, long long row0, int j, int g, f32x4 (&vreg)[R][5]) {
+#pragma unroll
+  for (int rr = 0; rr < R; ++rr) {
+    long long row = row0 + 16 * rr + j;
+    row = row < n ? row : n - 1;
+    const f32x4 *ur = reinterpret_cast<const f32x4 *>(uc + row * 64);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) vreg[rr][t] = ur[4 * t + g];
+    const float c = uc[64 * n + row];
+    vreg[rr][4] = f32x4{g == 0 ? c : 0.0f, 0.0f, 0.0f, 0.0f};
   }
 }
 
@@ -696,7 +786,8 @@ __device__ __forceinline__ void causal_event_append(const CausalMhKArgs &a, int 
 // ---------------------------------------------------------------------------
 // Persistent random-walk Metropolis-Hastings over a segment of iterations.
 // ---------------------------------------------------------------------------
-template <int KT1, int KSL1, int NTL, int R, int WAVES, int EFFECT, int PRIOR = 0>
+// GRAM: g's Gaussian term in the Gram form (g_last_gram; a.blob / a.m are the Gram copy of the sampling blob, a.uc the rows' 2 u, c)
+template <int KT1, int KSL1, int NTL, int R, int WAVES, int EFFECT, int PRIOR = 0, bool GRAM = false>
 __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) {
   static_assert(PRIOR == 0 || R == 1, "conditional prior: one row tile per wave");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -736,8 +827,9 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
       yr[rr] = a.y[row];
       rowid[rr] = (unsigned)(a.row_base + row);
     }
-    f32x4 vreg[R][NTL];
-    load_v_rows<NTL, R>(a.v, lds + m.bgl, n, m.p, row0, j, g, vreg);
+    f32x4 vreg[R][GRAM ? 5 : NTL];
+    if constexpr (GRAM) load_gram_rows<R>(a.uc, n, row0, j, g, vreg);
+    else load_v_rows<NTL, R>(a.v, lds + m.bgl, n, m.p, row0, j, g, vreg);
     PriorRow<KT1> pr;
     if constexpr (PRIOR) pr.load(a.seg, a.prior_tab, (row0 + j < n) ? row0 + j : n - 1, m.q, g);
     f32x4 zs[R][KT1];
@@ -756,9 +848,9 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
         }
 #ifdef BGM_PROF
       { unsigned long long tsec0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast0 = 0;
-        causal_logp<KT1, KSL1, NTL, R>(lds, m, lane_off, g, j, zs, vreg, xr, yr, lp, tsec0, tlast0); }
+        causal_logp<KT1, KSL1, NTL, R, GRAM>(lds, m, lane_off, g, j, zs, vreg, xr, yr, lp, tsec0, tlast0); }
 #else
-      causal_logp<KT1, KSL1, NTL, R>(lds, m, lane_off, g, j, zs, vreg, xr, yr, lp);
+      causal_logp<KT1, KSL1, NTL, R, GRAM>(lds, m, lane_off, g, j, zs, vreg, xr, yr, lp);
 #endif
       if constexpr (PRIOR) lp[0] += pr.correction(zs[0], m.q, g);
     } else {
@@ -812,9 +904,9 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
       float lpp[R];
       PMARK(0);
 #ifdef BGM_PROF
-      causal_logp<KT1, KSL1, NTL, R>(lds, m, lane_off, g, j, zp, vreg, xr, yr, lpp, tsec, tlast);
+      causal_logp<KT1, KSL1, NTL, R, GRAM>(lds, m, lane_off, g, j, zp, vreg, xr, yr, lpp, tsec, tlast);
 #else
-      causal_logp<KT1, KSL1, NTL, R>(lds, m, lane_off, g, j, zp, vreg, xr, yr, lpp);
+      causal_logp<KT1, KSL1, NTL, R, GRAM>(lds, m, lane_off, g, j, zp, vreg, xr, yr, lpp);
 #endif
       if constexpr (PRIOR) lpp[0] += pr.correction(zp[0], m.q, g);
       PMARK(5);

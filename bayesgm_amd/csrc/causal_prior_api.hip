@@ -50,7 +50,8 @@ static int pr_launch_mh(bgm_handle *h, const CausalMhKArgs &ka, int grid, int ld
   int rc;
 #define X(KT1_, KSL1_, NTL_)                                                                   \
   if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \
-    auto k = causal_mh_kernel<KT1_, KSL1_, NTL_, 1, PR_WAVES, EFFECT, 1>;                      \
+    auto k = ka.uc ? causal_mh_kernel<KT1_, KSL1_, NTL_, 1, PR_WAVES, EFFECT, 1, (NTL_ > 2)>    \
+                   : causal_mh_kernel<KT1_, KSL1_, NTL_, 1, PR_WAVES, EFFECT, 1>;              \
     rc = pr_set_lds(k, lds);                                                                   \
     if (rc) return rc;                                                                         \
     hipLaunchKernelGGL(k, dim3(grid), dim3(64 * PR_WAVES), lds, stream, ka);                   \
