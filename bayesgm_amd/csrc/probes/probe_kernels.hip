@@ -218,3 +218,44 @@ extern "C" int bgm_probe_bf16x3(int device, int32_t mode, int32_t iters, const f
   hipFree(W); hipFree(x); hipFree(out); hipEventDestroy(e0); hipEventDestroy(e1);
   return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Measurement aid (DESIGN.md "Latent dimensions"): the FP64 matrix rate.  Every wave of `waves_per_cu` x n_cus issues `iters` x 16
+// back-to-back v_mfma_f64_16x16x4_f64 on 8 independent accumulators (2048 flop each).
+// ---------------------------------------------------------------------------
+typedef double probe_f64x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(512) void mfma_f64_probe_kernel(int iters, double *sink) {
+  probe_f64x4 acc[8];
+  for (int k = 0; k < 8; ++k) acc[k] = probe_f64x4{0.0, 0.0, 0.0, 0.0};
+  const double a = 1.0 + threadIdx.x * 1e-9, b = 0.5;
+  for (int i = 0; i < iters; ++i) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[k], 0, 0, 0);
+  }
+  double s = 0.0;
+  for (int k = 0; k < 8; ++k) s += acc[k][0];
+  if (s == 123.456) sink[0] = s;
+}
+
+extern "C" int bgm_probe_mfma_f64(int device, int32_t waves_per_cu, int32_t iters, double *tflops) {
+  if (iters <= 0 || waves_per_cu <= 0 || waves_per_cu > 8) return -2;
+  const int n_cus = probe_n_cus(device);
+  PROBE_CHECK(hipSetDevice(device));
+  double *sink;
+  PROBE_CHECK(hipMalloc(&sink, 8));
+  hipEvent_t e0, e1;
+  PROBE_CHECK(hipEventCreate(&e0)); PROBE_CHECK(hipEventCreate(&e1));
+  hipLaunchKernelGGL(mfma_f64_probe_kernel, dim3(n_cus), dim3(64 * waves_per_cu), 0, 0, iters / 8 + 1, sink);   // warm
+  PROBE_CHECK(hipEventRecord(e0, 0));
+  hipLaunchKernelGGL(mfma_f64_probe_kernel, dim3(n_cus), dim3(64 * waves_per_cu), 0, 0, iters, sink);
+  PROBE_CHECK(hipEventRecord(e1, 0));
+  PROBE_CHECK(hipEventSynchronize(e1));
+  float ms = 0.f;
+  PROBE_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  if (tflops) *tflops = (double)n_cus * waves_per_cu * iters * 16.0 * 2048.0 / (ms * 1e-3) / 1e12;
+  hipFree(sink); hipEventDestroy(e0); hipEventDestroy(e1);
+  return 0;
+}

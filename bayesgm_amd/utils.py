@@ -1,5 +1,6 @@
 """Host-side helpers either side of the hot path: the analytic dose-response truths the accuracy numbers are measured
-against, and the input / result file formats of the command line.
+against, the input / result file formats of the command line, and (from latent_dims.py) the latent-dimension split
+estimate_latent_dims with its SIR helpers get_SDR_dim / slice_y.
 
 Names and call signatures follow the reference's ``bayesgm.utils`` (utils/helpers.py:8-66, utils/data_io.py:8-150) since
 callers import them by name; the code is the build's own.  Behaviour is pinned by fixtures produced with the reference's
@@ -10,6 +11,7 @@ import os
 import numpy as np
 
 from .datasets import _column_standardize
+from .latent_dims import estimate_latent_dims, get_SDR_dim, slice_y  # noqa: F401  (helpers.py:69-222)
 
 # True average dose-response curves of the reference's three continuous-treatment simulations, as functions of a float32
 # dose grid (helpers.py:59-64).  'Imbens' is the panel of BASELINE.json's headline config.

@@ -245,6 +245,26 @@ BGM_API int bgm_row_mean_quantiles(bgm_handle *h, const float *in_dev, int64_t n
                            double q_lo, double q_hi, float *mean_dev, float *lo_dev,
                            float *hi_dev, void *stream);
 
+/* Moments of a covariate panel for the latent-dimension estimate (SIR + PCA), float64, in one read of V.
+ * With w_i = v_i - shift (shift_dev: p doubles, or NULL for no shift), out_dev receives (row-major, doubles)
+ *     out[0][j]              = sum_i w_ij                                  (column sums)
+ *     out[1 + k][j]          = sum_{i: labels0_i = k} w_ij,  k < n_slices0 (slice sums of labeling 0)
+ *     out[1 + n_slices0 + k] = sum_{i: labels1_i = k} w_ij,  k < n_slices1 (slice sums of labeling 1)
+ *     then p x p             = sum_i w_i w_i^T                             (symmetric Gram)
+ * i.e. (1 + n_slices0 + n_slices1) * p + p * p doubles.  v_dev: n rows of p values with leading dimension ldv >= p, float32
+ * (v_is_f64 = 0) or float64 (v_is_f64 = 1).  labels*_dev: n int32 per labeling (NULL when its n_slices is 0); a label outside
+ * [0, n_slices) is counted in no slice.  Limits: p <= 2048, n_slices0, n_slices1 <= 1024 (BGM_E_UNSUPPORTED beyond, with a
+ * message).  workspace_dev: bgm_sdr_moments_workspace bytes of device memory.  Per-workgroup partials and a fixed-order reduction:
+ * repeated calls give bit-identical output.
+ * replaces: the QRs of get_SDR_dim and the PCA of estimate_latent_dims, utils/helpers.py:140-222 (restated in
+ * bayesgm_amd/latent_dims.py). */
+BGM_API int bgm_sdr_moments_workspace(bgm_handle *h, int64_t n, int32_t p, int32_t n_slices0, int32_t n_slices1,
+                                      int64_t *bytes);
+BGM_API int bgm_sdr_moments(bgm_handle *h, const void *v_dev, int32_t v_is_f64, int64_t n, int32_t p, int64_t ldv,
+                            const double *shift_dev, const int32_t *labels0_dev, int32_t n_slices0,
+                            const int32_t *labels1_dev, int32_t n_slices1, double *out_dev, void *workspace_dev,
+                            int64_t workspace_bytes, void *stream);
+
 /* Outcome-net cache of the fused effect samplers (bgm_causal_mh_run with BGM_EFFECT_ADRF / BGM_EFFECT_ITE on the LDS-resident kernels).
  * infer_from_latent_posterior (causalbgm/base.py:671-763) evaluates f(z, x_e) for every retained draw; consecutive draws of a
  * Metropolis-Hastings chain are equal whenever the proposal was rejected (base.py:868-871), and f is deterministic, so its (mean, sd)

@@ -13,4 +13,5 @@ def load():
     lib.bgm_probe_group.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.bgm_probe_clock.argtypes = [C.c_int, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.bgm_probe_bf16x3.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+    lib.bgm_probe_mfma_f64.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     return lib
