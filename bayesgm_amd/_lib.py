@@ -122,7 +122,10 @@ SYMBOLS = {
     "bgm_sdr_moments_workspace": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "bgm_sdr_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "bgm_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "bgm_chain_diagnostics_workspace": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "bgm_chain_diagnostics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p]),
+    "bgm_timing_enable":(C.c_int, [C.c_void_p, C.c_int]),
     "bgm_timing_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int]),
     "bgm_causal_set_outcome_cache": (C.c_int, [C.c_void_p, C.c_int32]),
     "bgm_causal_set_event_budget": (C.c_int, [C.c_void_p, C.c_int64]),

@@ -28,6 +28,8 @@ def _glorot(rs, fan_in, fan_out):
 
 
 class BGM(object):
+    mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last tfp_mcmc_sampler(diagnostics=True)
+
     def __new__(cls, params=None, *args, **kwargs):
         if cls is BGM and isinstance(params, dict) and params.get("use_bnn", _DEFAULTS["use_bnn"]):
             from .bgm_bnn import BGMBayes
@@ -339,8 +341,9 @@ class BGM(object):
         return self.engine.logpost(self._dev(data_z), self._dev(x)).cpu().numpy()
 
     def tfp_mcmc_sampler(self, data, ind_x1=None, n_mcmc=3000, burn_in=5000, step_size=0.01, num_leapfrog_steps=10,
-                         seed=42):
-        """Posterior samples of Z, shape (n_mcmc, n, z_dim) (bgm/base.py:709-830)."""
+                         seed=42, diagnostics=False):
+        """Posterior samples of Z, shape (n_mcmc, n, z_dim) (bgm/base.py:709-830).  diagnostics=True: split R-hat / effective
+        sample size of every chain, computed on the device before the copy to the host, in ``self.mcmc_diagnostics_``."""
         x = np.array(data, dtype=np.float32, copy=True)
         if ind_x1 is not None:
             keep = np.zeros(x.shape, bool)
@@ -355,7 +358,14 @@ class BGM(object):
         out = self.engine.hmc_sample(self._dev(x), n_mcmc, burn_in, step_size, num_leapfrog_steps, seed)
         self.last_acceptance_rate = float(out["acc_count"][burn_in:].sum().item()) / max(1, n_mcmc * x.shape[0])
         print(f"TFP MCMC Acceptance Rate: {self.last_acceptance_rate:.4f}")
+        if diagnostics:
+            self._store_diagnostics(out["draws"])
         return out["draws"].cpu().numpy()
+
+    def _store_diagnostics(self, draws_dev):
+        from .. import diagnostics as dg         # the sampler's `diagnostics` flag shadows the module in its body
+        self.mcmc_diagnostics_ = dg.chain_diagnostics(draws_dev)
+        dg.warn_if_not_mixed(self.mcmc_diagnostics_, self.params, type(self).__name__ + ".tfp_mcmc_sampler")
 
     def predict_on_posteriors(self, data_posterior_z, seed=0):
         """x ~ N(mu(z), sigma^2(z)) for every draw (bgm/base.py:511-525) -> (n_mcmc, n, x_dim)."""

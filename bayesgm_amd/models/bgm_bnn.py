@@ -366,8 +366,10 @@ class BGMBayes(BGM):
             x[~keep] = np.nan
         return self.engine.logpost(self._dev(data_z), self._dev(x), self._new_seed() if seed is None else seed, 0).cpu().numpy()
 
-    def tfp_mcmc_sampler(self, data, ind_x1=None, n_mcmc=3000, burn_in=5000, step_size=0.01, num_leapfrog_steps=10, seed=42):
-        """Posterior samples of Z, shape (n_mcmc, n, z_dim) (bgm/base.py:709-830), stochastic target."""
+    def tfp_mcmc_sampler(self, data, ind_x1=None, n_mcmc=3000, burn_in=5000, step_size=0.01, num_leapfrog_steps=10, seed=42,
+                         diagnostics=False):
+        """Posterior samples of Z, shape (n_mcmc, n, z_dim) (bgm/base.py:709-830), stochastic target.  diagnostics=True: as
+        BGM.tfp_mcmc_sampler."""
         x = np.array(data, dtype=np.float32, copy=True)
         if ind_x1 is not None:
             keep = np.zeros(x.shape, bool)
@@ -383,6 +385,8 @@ class BGMBayes(BGM):
         out = self.engine.hmc_sample(self._dev(x), n_mcmc, burn_in, step_size, num_leapfrog_steps, seed)
         self.last_acceptance_rate = float(out["acc_count"][burn_in:].sum().item()) / max(1, n_mcmc * x.shape[0])
         print(f"TFP MCMC Acceptance Rate: {self.last_acceptance_rate:.4f}")
+        if diagnostics:
+            self._store_diagnostics(out["draws"])
         return out["draws"].cpu().numpy()
 
     def predict_on_posteriors(self, data_posterior_z, seed=0):

@@ -56,6 +56,8 @@ def _disc_norm(p):
 
 
 class CausalBGM(object):
+    mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last sampler call that asked for them
+
     def __new__(cls, params, *args, **kwargs):
         # params['use_bnn'] (default True, base.py:64): the Bayesian-network model lives in causalbgm_bnn.py
         if cls is CausalBGM and dict(_DEFAULTS, **params)["use_bnn"]:
@@ -516,12 +518,16 @@ class CausalBGM(object):
 
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
-                bs=10000, verbose=1):
+                bs=10000, verbose=1, diagnose_rows=0):
         """Causal effects with posterior intervals from latent MCMC samples (base.py:573-668).
 
         ``bs`` bounded the host memory of the reference; here all rows are sampled in one launch per
         segment (row-blocked only if the ITE draw matrix would exceed device memory) and the result does
-        not depend on it.  Under torch.distributed the rows are sharded by rank and results gathered."""
+        not depend on it.  Under torch.distributed the rows are sharded by rank and results gathered.
+
+        ``diagnose_rows = k > 0`` (fixed ``q_sd`` only): after the run the chains of k rows are sampled once more with their
+        draws kept, and their split R-hat / effective sample size stored in ``self.mcmc_diagnostics_``
+        (diagnostics.ChainDiagnostics, row indices in ``.rows``); the result and the seed sequence are unchanged."""
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         binary = bool(self._p['binary_treatment'])
@@ -533,6 +539,10 @@ class CausalBGM(object):
         n_test = len(data_x)
         bs = max(1, int(bs))
         adaptive = (q_sd is None) or (q_sd <= 0)
+        diagnose_rows = int(diagnose_rows or 0)
+        if diagnose_rows > 0 and adaptive:
+            raise ValueError("predict(diagnose_rows=...) needs a fixed q_sd: with the adaptive scale (q_sd None or <= 0) every block's "
+                             "scale schedule depends on the whole block's acceptance and cannot be reproduced from a window of rows")
         seed = self._next_seed()
         if verbose:
             print('MCMC Latent Variable Sampling ...')
@@ -573,6 +583,8 @@ class CausalBGM(object):
                 sums += out["adrf"].double() * float(e0 - s0)
             acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
         self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
+        if diagnose_rows > 0:
+            self._diagnose_rows(data, diagnose_rows, burn_in, n_mcmc, q_sd, seed)
         if binary:
             parallel.all_reduce_sum_(res)                         # disjoint row sets: the sum is the gather
             res = res.cpu().numpy()
@@ -581,6 +593,44 @@ class CausalBGM(object):
         causal_effects = (sums / float(n_test)).float().contiguous()
         adrf, lo, hi = eng.row_mean_quantiles(causal_effects, alpha / 2, 1 - alpha / 2)
         return adrf.cpu().numpy(), torch.stack([lo, hi], dim=1).cpu().numpy()
+
+    @staticmethod
+    def _diagnose_windows(n_test, k):
+        """Up to 8 evenly spaced contiguous row windows [start, stop) over the panel holding k rows in all (all rows when
+        k >= n_test)."""
+        k = min(int(k), n_test)
+        if k <= 0:
+            return []
+        n_win = min(8, k)
+        sizes = [k // n_win + (1 if i < k % n_win else 0) for i in range(n_win)]
+        if n_win == 1:
+            return [(0, sizes[0])]
+        # window i starts at the i-th of n_win evenly spaced positions of [0, n_test - size_last]; the starts are at least one
+        # window apart because n_test >= k
+        wins, prev_stop = [], 0
+        for i, sz in enumerate(sizes):
+            start = max(prev_stop, (i * (n_test - sizes[-1])) // (n_win - 1))
+            start = min(start, n_test - sum(sizes[i:]))
+            wins.append((start, start + sz))
+            prev_stop = start + sz
+        return wins
+
+    def _diagnose_rows(self, data, k, burn_in, n_mcmc, q_sd, seed):
+        """Re-run the chains of k rows of predict's panel with their draws kept (the Philox stream is keyed by the global row, so
+        with the same seed and row_base these are the chains predict ran) and store their diagnostics.  Every rank computes the
+        same windows; no collectives and no new seed."""
+        data_x, data_y, data_v = data
+        eng = self.engine
+        parts, rows = [], []
+        for (s0, e0) in self._diagnose_windows(len(data_x), k):
+            out = eng.mh_sample(self._dev(data_x[s0:e0]).reshape(-1), self._dev(data_y[s0:e0]).reshape(-1), self._dev(data_v[s0:e0]),
+                                burn_in, n_mcmc, q_sd, seed, want_draws=True, row_base=s0)
+            parts.append(out["draws"])
+            rows.append(np.arange(s0, e0))
+        d = diagnostics.chain_diagnostics(torch.cat(parts, dim=1))
+        d.rows = np.concatenate(rows)
+        self.mcmc_diagnostics_ = d
+        diagnostics.warn_if_not_mixed(d, self.params, "CausalBGM.predict")
 
     def _report_acceptance(self, acc_tail, window, n_test, verbose):
         t = torch.tensor([acc_tail], dtype=torch.float64, device=self.engine.device)
@@ -591,8 +641,9 @@ class CausalBGM(object):
 
     def metropolis_hastings_sampler(self, data, initial_q_sd=1.0, q_sd=None, burn_in=5000, n_keep=3000,
                                     target_acceptance_rate=0.25, tolerance=0.05, adjustment_interval=50,
-                                    adaptive_sd=None, window_size=100):
-        """Posterior samples of Z, shape (n_keep, n, q) (base.py:820-904)."""
+                                    adaptive_sd=None, window_size=100, diagnostics=False):
+        """Posterior samples of Z, shape (n_keep, n, q) (base.py:820-904).  diagnostics=True: split R-hat / effective sample
+        size of every chain, computed on the device before the copy to the host, in ``self.mcmc_diagnostics_``."""
         data_x, data_y, data_v = data
         if adaptive_sd is None:
             adaptive_sd = (q_sd is None or q_sd <= 0)
@@ -604,7 +655,14 @@ class CausalBGM(object):
         w = min(window_size, tot)
         self.last_acceptance_rate = float(out["acc_count"][tot - w:].sum().item()) / (w * len(data_x))
         print(f"Final MCMC Acceptance Rate: {self.last_acceptance_rate:.4f}")
+        if diagnostics:
+            self._store_diagnostics(out["draws"], "metropolis_hastings_sampler")
         return out["draws"].cpu().numpy()
+
+    def _store_diagnostics(self, draws_dev, where):
+        from .. import diagnostics as dg         # the samplers' `diagnostics` flag shadows the module in their bodies
+        self.mcmc_diagnostics_ = dg.chain_diagnostics(draws_dev)
+        dg.warn_if_not_mixed(self.mcmc_diagnostics_, self.params, type(self).__name__ + "." + where)
 
     def infer_from_latent_posterior(self, data_posterior_z, x_values=None, sample_y=True, eps=1e-6, seed=None):
         """Causal effects from posterior draws of Z, shape (n_keep, n, q) (base.py:671-763): binary treatment -> ITE draws

@@ -516,8 +516,9 @@ class CausalBGMBayes(CausalBGM):
 
     def metropolis_hastings_sampler(self, data, initial_q_sd=1.0, q_sd=None, burn_in=5000, n_keep=3000,
                                     target_acceptance_rate=0.25, tolerance=0.05, adjustment_interval=50,
-                                    adaptive_sd=None, window_size=100):
-        """Posterior samples of Z, shape (n_keep, n, q) (base.py:820-904): the rows given are ONE block."""
+                                    adaptive_sd=None, window_size=100, diagnostics=False):
+        """Posterior samples of Z, shape (n_keep, n, q) (base.py:820-904): the rows given are ONE block.  diagnostics=True: as
+        CausalBGM.metropolis_hastings_sampler."""
         data_x, data_y, data_v = data
         if adaptive_sd is None:
             adaptive_sd = (q_sd is None or q_sd <= 0)
@@ -528,6 +529,8 @@ class CausalBGMBayes(CausalBGM):
                                              target=target_acceptance_rate, tol=tolerance, adj_int=adjustment_interval, window=window_size, draws=draws)
         self.last_acceptance_rate = acc_tail / float(tail * n)
         print(f"Final MCMC Acceptance Rate: {self.last_acceptance_rate:.4f}")
+        if diagnostics:
+            self._store_diagnostics(draws, "metropolis_hastings_sampler")
         return draws.cpu().numpy()
 
     def infer_from_latent_posterior(self, data_posterior_z, x_values=None, sample_y=True, eps=1e-6, seed=None):

@@ -228,7 +228,7 @@ class IdentifiableCausalBGMBayes(CausalBGMBayes):
             self._clear_prior()
 
     def metropolis_hastings_sampler(self, data, initial_q_sd=1.0, q_sd=None, burn_in=5000, n_keep=3000, target_acceptance_rate=0.25,
-                                    tolerance=0.05, adjustment_interval=50, adaptive_sd=None, window_size=100):
+                                    tolerance=0.05, adjustment_interval=50, adaptive_sd=None, window_size=100, diagnostics=False):
         """(samples [n_keep, n, q], data_u one-hot [n, n_segments]) (:557-614)."""
         segs = self._segments_for(len(data[0]))
         self._set_prior(torch.from_numpy(segs.astype(np.int32)).to(self.engine.device))
@@ -236,7 +236,7 @@ class IdentifiableCausalBGMBayes(CausalBGMBayes):
             samples = CausalBGMBayes.metropolis_hastings_sampler(self, data, initial_q_sd=initial_q_sd, q_sd=q_sd, burn_in=burn_in, n_keep=n_keep,
                                                                  target_acceptance_rate=target_acceptance_rate, tolerance=tolerance,
                                                                  adjustment_interval=adjustment_interval, adaptive_sd=adaptive_sd,
-                                                                 window_size=window_size)
+                                                                 window_size=window_size, diagnostics=diagnostics)
         finally:
             self._clear_prior()
         return samples, np.eye(int(self.params['n_segments']), dtype=np.float32)[segs]

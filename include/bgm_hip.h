@@ -265,6 +265,30 @@ BGM_API int bgm_sdr_moments(bgm_handle *h, const void *v_dev, int32_t v_is_f64, 
                             const int32_t *labels1_dev, int32_t n_slices1, double *out_dev, void *workspace_dev,
                             int64_t workspace_bytes, void *stream);
 
+/* MCMC chain diagnostics: split R-hat and effective sample size (ESS) of every sampled series, float64 sums over float32 draws.
+ * draws_dev: [n_chains x n_draws x n_series] float32, contiguous -- with n_series = n * q and n_chains = 1 the draws_dev of
+ * bgm_causal_mh_run, bgm_bnn_mh_run, bgm_bgm_hmc_run and bgm_bvn_hmc_run; n_chains > 1: independent runs of the same rows, stacked.
+ * out_dev: [6 x n_series] doubles: mean, standard deviation (all draws of all chains pooled, denominator count - 1), split R-hat,
+ * ESS, Monte-Carlo standard error of the mean (sd / sqrt(ESS)), number of moves (t with x[t] != x[t-1], summed over the chains).
+ * flags_dev: [n_series] int32.  Bit 0: the series is constant (R-hat, ESS and MCSE are NaN).  Bit 1: the Geyer sum was still
+ * non-negative at max_lag, the ESS is an upper bound.  Bit 2: the series holds a non-finite value (all six statistics are NaN and no
+ * other bit is set).
+ * Definitions (the Stan / ArviZ "mean" forms, no rank normalisation).  h = n_draws / 2; every chain is cut into its first and its
+ * next h draws (an odd last draw enters mean, sd and moves only): m = 2 n_chains half-chains.  W = mean of their variances
+ * (denominator h - 1), B / h = variance of their means (denominator m - 1), var+ = (h - 1) / h W + B / h, R-hat = sqrt(var+ / W).
+ * acov(k) = mean over the half-chains of (1 / h) sum_t d[t] d[t + k], d centred on the half-chain's mean; rho(0) = 1,
+ * rho(k) = 1 - (W - acov(k)) / var+.  The pairs P_j = rho(2j) + rho(2j + 1) are summed while P_j >= 0 and 2j + 1 <= max_lag, each
+ * replaced by min(P_j, P_{j-1}); tau = -1 + 2 sum P_j, ESS = m h / tau, capped at m h log10(m h) (also when tau <= 0).
+ * Limits: n_draws >= 8 (BGM_E_INVALID), 1 <= n_chains <= 8, 1 <= max_lag <= 1024 (BGM_E_UNSUPPORTED above, BGM_E_INVALID below);
+ * max_lag is clamped to n_draws / 2 - 1.  workspace_dev: bgm_chain_diagnostics_workspace bytes of device memory.  Fixed summation
+ * order, no atomics: repeated calls give bit-identical output.
+ * replaces: nothing -- the reference reports one acceptance rate and has no per-chain diagnostic. */
+BGM_API int bgm_chain_diagnostics_workspace(bgm_handle *h, int32_t n_chains, int32_t n_draws, int64_t n_series, int32_t max_lag,
+                                            int64_t *bytes);
+BGM_API int bgm_chain_diagnostics(bgm_handle *h, const float *draws_dev, int32_t n_chains, int32_t n_draws, int64_t n_series,
+                                  int32_t max_lag, double *out_dev, int32_t *flags_dev, void *workspace_dev,
+                                  int64_t workspace_bytes, void *stream);
+
 /* Outcome-net cache of the fused effect samplers (bgm_causal_mh_run with BGM_EFFECT_ADRF / BGM_EFFECT_ITE on the LDS-resident kernels).
  * infer_from_latent_posterior (causalbgm/base.py:671-763) evaluates f(z, x_e) for every retained draw; consecutive draws of a
  * Metropolis-Hastings chain are equal whenever the proposal was rejected (base.py:868-871), and f is deterministic, so its (mean, sd)
