@@ -108,6 +108,7 @@ SYMBOLS = {
     "bgm_causal_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "bgm_bnn_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "bgm_causal_set_prior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "bgm_causal_set_row_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float]),
     "bgm_destroy": (C.c_int, [C.c_void_p]),
     "bgm_causal_configure": (C.c_int, [C.c_void_p, C.POINTER(CausalConfig)]),
     "bgm_causal_set_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),

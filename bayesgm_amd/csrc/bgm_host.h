@@ -88,6 +88,11 @@ struct bgm_handle {
   const int32_t *prior_seg = nullptr;
   const float *prior_tab = nullptr;
   int prior_segments = 0;
+  // per-chain proposal scale of the fp32 LDS-resident MH kernels (causal_rowadapt_api.hip, bgm_causal_set_row_scale); NULL = the call's q_sd
+  float *ra_scale = nullptr;
+  const float *ra_up = nullptr, *ra_dn = nullptr;
+  int ra_n = 0;
+  float ra_min = 0.0f, ra_max = 0.0f;
   // encoder blob
   float *eblob_dev = nullptr;
   size_t eblob_cap = 0;
@@ -178,6 +183,8 @@ int causal_pack_forward(bgm_handle *h, const HostNet &G, const HostNet &F, const
 int bgm_causal_prior_logpost(bgm_handle *h, const float *x, const float *y, const float *v, const float *z, int64_t n, float *out, int grid,
                              hipStream_t stream);
 int bgm_causal_prior_mh_launch(bgm_handle *h, const CausalMhKArgs &a, int effect, int grid, int lds, hipStream_t stream);
+// per-chain proposal scale (causal_rowadapt_api.hip): the ROWADAPT instantiations, effect 0 / 1 / 2 or 3 = event form
+int bgm_causal_rowadapt_mh_launch(bgm_handle *h, const CausalMhKArgs &a, int effect, int grid, int lds, hipStream_t stream);
 // split-precision sampling path (causal_bx3_api.hip)
 int bgm_causal_bx3_blob(bgm_handle *h, hipStream_t stream);
 int bgm_causal_bx3_logpost(bgm_handle *h, const float *x, const float *y, const float *v, const float *z, int64_t n, float *out, int grid,

@@ -179,6 +179,7 @@ extern "C" int bgm_bnn_logpost(bgm_handle *h, const float *x, const float *y, co
 
 extern "C" int bgm_bnn_mh_run(bgm_handle *h, const bgm_bnn_mh_args *g, void *stream_) {
   BnnState *s; BnsPlan pl;
+  if (h && h->ra_scale) { bgm_set_error("bgm_bnn_mh_run: the per-chain proposal scale (bgm_causal_set_row_scale) does not exist for the Bayesian networks"); return BGM_E_UNSUPPORTED; }
   int rc = bns_session(h, "bgm_bnn_mh_run", s, pl);
   if (rc) return rc;
   if (!g || !g->x_dev || !g->y_dev || !g->v_dev || !g->state_dev || g->n < 1 || g->block_rows < 2 || g->n_iters < 0) {

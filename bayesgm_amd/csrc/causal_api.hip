@@ -537,6 +537,14 @@ extern "C" int bgm_causal_mh_run(bgm_handle *h, const bgm_mh_args *a, void *stre
   if ((a->effect != BGM_EFFECT_NONE || a->draws_dev) && it_end - a->burn_in > a->n_keep) { bgm_set_error("bgm_causal_mh_run: iterations beyond burn_in + n_keep"); return BGM_E_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   BGM_HIP_CHECK(hipSetDevice(h->device));
+  if (h->ra_scale) {      // per-chain proposal scale (bgm_causal_set_row_scale): the fp32 LDS-resident kernels with the standard-normal prior
+    const char *path = gx_wanted(h) ? "the general-width engine (hidden widths outside the compiled families)"
+                       : bnf_det_wanted(h) ? "the streamed-fragment kernels (no LDS-resident compiled shape holds the model)"
+                       : h->precision != 0 ? "the split-precision kernels (bgm_causal_set_precision)"
+                       : h->prior_seg ? "the conditional latent prior (bgm_causal_set_prior)"
+                       : MH_R != 1 ? "builds with more than one row tile per wave" : nullptr;
+    if (path) { bgm_set_error(std::string("bgm_causal_mh_run: the per-chain proposal scale (bgm_causal_set_row_scale) does not exist for ") + path); return BGM_E_UNSUPPORTED; }
+  }
   if (gx_wanted(h)) {
     return gx_mh_run(h, a, stream);
   }
@@ -563,6 +571,7 @@ extern "C" int bgm_causal_mh_run(bgm_handle *h, const bgm_mh_args *a, void *stre
   ka.acc_count = a->acc_count_dev; ka.draws = a->draws_dev; ka.n_keep = a->n_keep;
   ka.sample_y = a->sample_y; ka.n_doses = a->n_doses; ka.x_values = a->x_values_dev;
   ka.adrf_partial = a->adrf_partial_dev; ka.ite = a->ite_dev; ka.clk = (unsigned long long *)a->clock_dev; ka.m = gram ? h->gmeta : h->meta;
+  ka.row_scale = h->ra_scale; ka.ra_up = h->ra_up; ka.ra_dn = h->ra_dn; ka.ra_n = h->ra_n; ka.ra_min = h->ra_min; ka.ra_max = h->ra_max;
 
   // Split the segment at burn_in: the burn-in part runs the pure-transition kernel.
   struct Seg { int begin, n, effect, init, ev; };       // ev: 0 fused kernels; 1 / 2 = first / later segment of the event form
@@ -634,6 +643,7 @@ extern "C" int bgm_causal_mh_run(bgm_handle *h, const bgm_mh_args *a, void *stre
       rc = bgm_causal_event_finish(h, ka, grid, ka.ev_first, stream, a->effect);
     } else if (h->precision != 0) rc = bgm_causal_bx3_mh_launch(h, ka, segs[s].effect, grid, stream);      // (carries the conditional prior)
     else if (h->prior_seg) rc = bgm_causal_prior_mh_launch(h, ka, segs[s].effect, grid, lds, stream);
+    else if (ka.row_scale) rc = bgm_causal_rowadapt_mh_launch(h, ka, segs[s].effect, grid, lds, stream);
     else if (segs[s].effect == BGM_EFFECT_ADRF) rc = launch_mh<1>(h, ka, grid, lds, stream);
     else if (segs[s].effect == BGM_EFFECT_ITE) rc = launch_mh<2>(h, ka, grid, lds, stream);
     else rc = launch_mh<0>(h, ka, grid, lds, stream);

@@ -107,6 +107,8 @@ int bgm_causal_event_mh_launch(bgm_handle *h, CausalMhKArgs &ka, int grid, int l
   if (h->precision != 0) return bgm_causal_bx3_mh_launch(h, ka, 3, grid, stream);
   // conditional latent prior (IdentifiableCausalBGM): the PRIOR = 1 instantiation; the outcome net does not see the prior
   if (h->prior_seg) return bgm_causal_prior_mh_launch(h, ka, 3, grid, lds, stream);
+  // per-chain proposal scale (bgm_causal_set_row_scale): the ROWADAPT instantiation
+  if (ka.row_scale) return bgm_causal_rowadapt_mh_launch(h, ka, 3, grid, lds, stream);
   int rc;
 #define X(KT1_, KSL1_, NTL_)                                                                   \
   if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \

@@ -59,6 +59,11 @@ struct CausalMhKArgs {
   long long ev_cap;         // events a slot's region holds (a multiple of 16)
   int ev_first;             // 1: every chain emits its state at the launch's first iteration (nothing is carried from an earlier launch)
   CausalMeta m;
+  // ROWADAPT (bgm_causal_set_row_scale; behind m: the kernel arguments of the fixed-scale instantiations keep their offsets):
+  float *row_scale;         // [n] proposal scale of every local row, in / out (written from q_sd when init = 1)
+  const float *ra_up, *ra_dn;   // [ra_n]: factor applied to a chain's scale after iteration it < ra_n, accepted / rejected
+  int ra_n;                 // iterations >= ra_n leave the scale alone (burn_in through the classes: the retained chain is plain MH)
+  float ra_min, ra_max;     // clamp of the scale
 };
 
 // ---------------------------------------------------------------------------
@@ -787,7 +792,15 @@ __device__ __forceinline__ void causal_event_append(const CausalMhKArgs &a, int 
 // Persistent random-walk Metropolis-Hastings over a segment of iterations.
 // ---------------------------------------------------------------------------
 // GRAM: g's Gaussian term in the Gram form (g_last_gram; a.blob / a.m are the Gram copy of the sampling blob, a.uc the rows' 2 u, c)
-template <int KT1, int KSL1, int NTL, int R, int WAVES, int EFFECT, int PRIOR = 0, bool GRAM = false>
+// ROWADAPT: every chain proposes with a scale of its own (a.row_scale), multiplied after each of the first a.ra_n accept decisions by a
+// host-made factor -- a.ra_up[it] if the chain moved, a.ra_dn[it] if not -- and clamped: ONE fp32 multiply, no exp, so float32 on the
+// host reproduces the scale bit for bit.  A scale depends on (seed, global row, the row's data) only.  It lives in one register per
+// chain (sc[rr], replicated over the four lane groups like lp), loaded from a.row_scale at tile start (a.q_sd when a.init) and stored
+// back beside state / logp at tile end; the factor is ONE per-lane load of (accepted ? a.ra_up : a.ra_dn)[it] after the decision (the
+// lanes of a chain read the same word).  No LDS is used for it.  The variants that were compiled and rejected -- the scale in LDS, both
+// factors by wave-uniform loads ahead of the networks -- and the register figures are in DESIGN.md section 4m.  Compile-time, so that
+// the fixed-scale instantiations keep their bits.
+template <int KT1, int KSL1, int NTL, int R, int WAVES, int EFFECT, int PRIOR = 0, bool GRAM = false, bool ROWADAPT = false>
 __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) {
   static_assert(PRIOR == 0 || R == 1, "conditional prior: one row tile per wave");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -863,6 +876,17 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
       }
     }
 
+    [[maybe_unused]] float sc[R];        // ROWADAPT: the chains' proposal scales
+    if constexpr (ROWADAPT) {
+#pragma unroll
+      for (int rr = 0; rr < R; ++rr) {
+        long long row = row0 + 16 * rr + j;
+        row = row < n ? row : n - 1;
+        const float s_in = a.row_scale[row];       // (unconditional in-bounds load, then select: see PriorRow::load)
+        sc[rr] = a.init ? a.q_sd : s_in;
+      }
+    }
+
     uint4 uacc[R];
     [[maybe_unused]] const int ev_tile0 = ev_cnt;
     bool eff_cached = false;      // the slot's cache holds the outcome-net values of the tile's current states
@@ -894,11 +918,13 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
       for (int rr = 0; rr < R; ++rr)
 #pragma unroll
         for (int t = 0; t < KT1; ++t) {
+          float qs;
+          if constexpr (ROWADAPT) qs = sc[rr]; else qs = a.q_sd;
           const f32x4 e = box_muller4(philox4x32_10(rowid[rr], (unsigned)it, (unsigned)(g + 4 * t), TAG_PROP, a.k0, a.k1));
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int f = 16 * t + 4 * r + g;
-            zp[rr][t][r] = (f < m.q) ? fmaf(a.q_sd, e[r], zs[rr][t][r]) : zs[rr][t][r];
+            zp[rr][t][r] = (f < m.q) ? fmaf(qs, e[r], zs[rr][t][r]) : zs[rr][t][r];
           }
         }
       float lpp[R];
@@ -929,6 +955,9 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
 #pragma unroll
           for (int r = 0; r < 4; ++r) zs[rr][t][r] = acc ? zp[rr][t][r] : zs[rr][t][r];
         lp[rr] = acc ? lpp[rr] : lp[rr];
+        if constexpr (ROWADAPT) {
+          if (it < a.ra_n) sc[rr] = fminf(fmaxf(sc[rr] * (acc ? a.ra_up : a.ra_dn)[it], a.ra_min), a.ra_max);
+        }
         accmask += __popcll(__ballot(acc && valid[rr] && g == 0));
       }
       // per-(wave slot, iteration) counter, slot-private: a shared per-iteration word would take ~1e8
@@ -997,6 +1026,9 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
     for (int rr = 0; rr < R; ++rr) {
       const long long row = row0 + 16 * rr + j;
       if (g == 0 && row < n) a.logp[row] = lp[rr];
+      if constexpr (ROWADAPT) {
+        if (g == 0 && row < n) a.row_scale[row] = sc[rr];
+      }
     }
     ++tiles_done;
   }

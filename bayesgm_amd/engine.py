@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import row_adapt as RA
 
 DEFAULT_G_UNITS = [64, 64, 64, 64, 64]
 DEFAULT_FH_UNITS = [64, 32, 8]
@@ -278,6 +279,14 @@ class CausalEngine(object):
         _lib.check(self.lib.bgm_causal_set_prior(self.h, _ptr(seg), _ptr(tab), 0 if tab is None else int(tab.shape[0])),
                    "bgm_causal_set_prior")
 
+    def set_row_scale(self, scale=None, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX):
+        """Per-chain proposal scale of the mh_run calls made afterwards (bgm_causal_set_row_scale): scale float32 [n] (device, in / out,
+        aligned with the rows of those calls; written from q_sd by a call with init=True), up / dn float32 [n_table] (device): factor
+        of iteration it < n_table for a chain that moved / did not.  scale=None switches back to the single q_sd."""
+        self._row_scale_keep = (scale, up, dn)          # keep the buffers alive while set
+        _lib.check(self.lib.bgm_causal_set_row_scale(self.h, _ptr(scale), _ptr(up), _ptr(dn), 0 if up is None else int(up.numel()),
+                                                     float(s_min), float(s_max)), "bgm_causal_set_row_scale")
+
     def get_weights(self, net_id, dims):
         """Device parameters of one net -> [(W, b), ...] (Keras order)."""
         count = sum(dims[i] * dims[i + 1] + dims[i + 1] for i in range(len(dims) - 1))
@@ -411,12 +420,37 @@ class CausalEngine(object):
     # -- whole-sampler conveniences -------------------------------------------
     def mh_sample(self, x, y, v, burn_in, n_keep, q_sd, seed, chunk=None, want_draws=False,
                   effect=_lib.EFFECT_NONE, x_values=None, sample_y=True, row_base=0, adaptive=False,
-                  initial_q_sd=1.0, target=0.25, tol=0.05, adj_int=50, window=100, acc_reduce=None, n_total=None):
+                  initial_q_sd=1.0, target=0.25, tol=0.05, adj_int=50, window=100, acc_reduce=None, n_total=None, row_adapt=None,
+                  row_adapt_table=None):
         """metropolis_hastings_sampler (+ fused infer_from_latent_posterior) over all rows.
 
         Returns dict(state, logp, acc_count [burn_in+n_keep], draws | None, adrf [n_doses,n_keep] | None,
         ite [n, n_keep] | None, q_sd).  acc_reduce / n_total: with the rows of one sampler run sharded over ranks, the all-reduce (sum)
-        of the window's acceptance count and the total number of rows, so that every rank adapts the proposal scale identically."""
+        of the window's acceptance count and the total number of rows, so that every rank adapts the proposal scale identically.
+
+        row_adapt = target acceptance rate (True = 0.25): every chain adapts a proposal scale of its own during burn-in, starting from
+        q_sd (row_adapt.py; the fp32 LDS-resident kernels with the standard-normal prior, else RuntimeError).  One mh_run per chunk,
+        no block-wide decisions; the result carries row_scale [n], the chains' final scales.  row_adapt_table = (up, dn) replaces the
+        schedule of row_adapt_factors(burn_in, target)."""
+        ra_target = RA.resolve_target(row_adapt)
+        if ra_target is not None or row_adapt_table is not None:
+            if adaptive:
+                raise ValueError("mh_sample: row_adapt and the block-wide adaptive scale (adaptive=True) exclude each other")
+            if q_sd is None or not float(q_sd) > 0:
+                raise ValueError("mh_sample: row_adapt starts every chain from q_sd, which must be positive; got %r" % (q_sd,))
+            up, dn = row_adapt_table if row_adapt_table is not None else RA.row_adapt_factors(burn_in, ra_target)
+            up, dn = (_f32(np.asarray(t, dtype=np.float32).reshape(-1), self.device) for t in (up, dn))
+            if up.numel() != dn.numel():
+                raise ValueError("mh_sample: row_adapt_table = (up, dn) of equal length")
+            scale = torch.empty(v.shape[0], device=self.device, dtype=torch.float32)
+            self.set_row_scale(scale, up if up.numel() else None, dn if dn.numel() else None)
+            try:
+                out = self.mh_sample(x, y, v, burn_in, n_keep, q_sd, seed, chunk=chunk, want_draws=want_draws, effect=effect,
+                                     x_values=x_values, sample_y=sample_y, row_base=row_base)
+            finally:
+                self.set_row_scale(None)
+            out["row_scale"] = scale
+            return out
         dev = self.device
         x, y, v = (_f32(t, dev) for t in (x, y, v))
         x = x.reshape(-1)

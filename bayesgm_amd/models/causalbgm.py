@@ -23,6 +23,7 @@ DISC_NORM_DEFAULT = "fixed"
 BNN_NORM_DEFAULT = "fixed"
 
 from .. import _lib, diagnostics, host_rng, parallel
+from .. import row_adapt as row_adapt_mod
 from ..engine import CausalEngine
 from ..datasets import Gaussian_sampler
 from ..utils import save_data
@@ -57,6 +58,7 @@ def _disc_norm(p):
 
 class CausalBGM(object):
     mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last sampler call that asked for them
+    mh_row_scale_ = None             # per-row proposal scales (NumPy, global row order) of the last predict / sampler call; None when it ran without row adaptation
 
     def __new__(cls, params, *args, **kwargs):
         # params['use_bnn'] (default True, base.py:64): the Bayesian-network model lives in causalbgm_bnn.py
@@ -518,7 +520,7 @@ class CausalBGM(object):
 
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
-                bs=10000, verbose=1, diagnose_rows=0):
+                bs=10000, verbose=1, diagnose_rows=0, row_adapt=False):
         """Causal effects with posterior intervals from latent MCMC samples (base.py:573-668).
 
         ``bs`` bounded the host memory of the reference; here all rows are sampled in one launch per
@@ -527,7 +529,14 @@ class CausalBGM(object):
 
         ``diagnose_rows = k > 0`` (fixed ``q_sd`` only): after the run the chains of k rows are sampled once more with their
         draws kept, and their split R-hat / effective sample size stored in ``self.mcmc_diagnostics_``
-        (diagnostics.ChainDiagnostics, row indices in ``.rows``); the result and the seed sequence are unchanged."""
+        (diagnostics.ChainDiagnostics, row indices in ``.rows``); the result and the seed sequence are unchanged.
+
+        ``row_adapt = True`` (target acceptance 0.25) or a target in (0, 1): every chain adapts a proposal scale of its own during
+        burn-in (row_adapt.py), starting from ``q_sd`` (1.0 if ``q_sd`` is None or <= 0), and keeps it for the retained draws.  A
+        chain depends on its own row only, so a rank's shard is sampled in one piece, the result does not depend on ``bs`` or the
+        rank count, and ``diagnose_rows`` works.  The scales are left in ``self.mh_row_scale_``."""
+        ra_target = self._row_adapt_target(row_adapt)
+        self.mh_row_scale_ = None
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         binary = bool(self._p['binary_treatment'])
@@ -539,6 +548,8 @@ class CausalBGM(object):
         n_test = len(data_x)
         bs = max(1, int(bs))
         adaptive = (q_sd is None) or (q_sd <= 0)
+        if ra_target is not None:        # per-chain scales replace the block-wide one; q_sd is where they start
+            q_sd, adaptive = row_adapt_mod.start_scale(q_sd), False
         diagnose_rows = int(diagnose_rows or 0)
         if diagnose_rows > 0 and adaptive:
             raise ValueError("predict(diagnose_rows=...) needs a fixed q_sd: with the adaptive scale (q_sd None or <= 0) every block's "
@@ -564,6 +575,7 @@ class CausalBGM(object):
             if not adaptive:
                 blocks = [(s0, min(s0 + max_rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, max_rows)]
         acc_tail = 0.0
+        row_scale = torch.zeros(n_test, device=dev, dtype=torch.float32) if ra_target is not None else None
         if binary:
             res = torch.zeros((3, n_test), device=dev, dtype=torch.float32)     # mean, lower, upper (this rank's rows filled)
         else:
@@ -574,17 +586,21 @@ class CausalBGM(object):
             v = self._dev(data_v[s0:e0])
             if binary:
                 out = eng.mh_sample(x, y, v, burn_in, n_mcmc, q_sd, seed, effect=_lib.EFFECT_ITE, sample_y=sample_y,
-                                    row_base=s0, adaptive=adaptive)
+                                    row_base=s0, adaptive=adaptive, row_adapt=ra_target)
                 mean, lo, hi = eng.row_mean_quantiles(out["ite"], alpha / 2, 1 - alpha / 2)
                 res[0, s0:e0], res[1, s0:e0], res[2, s0:e0] = mean, lo, hi
             else:
                 out = eng.mh_sample(x, y, v, burn_in, n_mcmc, q_sd, seed, effect=_lib.EFFECT_ADRF, x_values=x_values,
-                                    sample_y=sample_y, row_base=s0, adaptive=adaptive)
+                                    sample_y=sample_y, row_base=s0, adaptive=adaptive, row_adapt=ra_target)
                 sums += out["adrf"].double() * float(e0 - s0)
+            if row_scale is not None:
+                row_scale[s0:e0] = out["row_scale"]
             acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
         self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
+        if row_scale is not None:
+            self.mh_row_scale_ = parallel.all_reduce_sum_(row_scale).cpu().numpy()      # disjoint row sets: the sum is the gather
         if diagnose_rows > 0:
-            self._diagnose_rows(data, diagnose_rows, burn_in, n_mcmc, q_sd, seed)
+            self._diagnose_rows(data, diagnose_rows, burn_in, n_mcmc, q_sd, seed, row_adapt=ra_target)
         if binary:
             parallel.all_reduce_sum_(res)                         # disjoint row sets: the sum is the gather
             res = res.cpu().numpy()
@@ -615,7 +631,25 @@ class CausalBGM(object):
             prev_stop = start + sz
         return wins
 
-    def _diagnose_rows(self, data, k, burn_in, n_mcmc, q_sd, seed):
+    def _row_adapt_target(self, row_adapt):
+        """row_adapt of predict / adaptive_sd='row' -> None or the target acceptance rate; ValueError where the per-chain scale does
+        not exist (needs no device)."""
+        target = row_adapt_mod.resolve_target(row_adapt)
+        if target is not None:
+            row_adapt_mod.check_supported(type(self).__name__, self._p)
+        return target
+
+    def _adaptive_sd_target(self, adaptive_sd, target_acceptance_rate):
+        """adaptive_sd of metropolis_hastings_sampler -> None (None / bool: the fixed or the block-wide scale) or, for 'row', the
+        target acceptance rate of the per-chain scale; ValueError for another string or where that scale does not exist."""
+        if not isinstance(adaptive_sd, str):
+            return None
+        if adaptive_sd != 'row':
+            raise ValueError("adaptive_sd must be None, a bool or 'row'; got %r" % (adaptive_sd,))
+        row_adapt_mod.check_supported(type(self).__name__, self._p)
+        return self._row_adapt_target(target_acceptance_rate)
+
+    def _diagnose_rows(self, data, k, burn_in, n_mcmc, q_sd, seed, row_adapt=None):
         """Re-run the chains of k rows of predict's panel with their draws kept (the Philox stream is keyed by the global row, so
         with the same seed and row_base these are the chains predict ran) and store their diagnostics.  Every rank computes the
         same windows; no collectives and no new seed."""
@@ -624,7 +658,7 @@ class CausalBGM(object):
         parts, rows = [], []
         for (s0, e0) in self._diagnose_windows(len(data_x), k):
             out = eng.mh_sample(self._dev(data_x[s0:e0]).reshape(-1), self._dev(data_y[s0:e0]).reshape(-1), self._dev(data_v[s0:e0]),
-                                burn_in, n_mcmc, q_sd, seed, want_draws=True, row_base=s0)
+                                burn_in, n_mcmc, q_sd, seed, want_draws=True, row_base=s0, row_adapt=row_adapt)
             parts.append(out["draws"])
             rows.append(np.arange(s0, e0))
         d = diagnostics.chain_diagnostics(torch.cat(parts, dim=1))
@@ -643,14 +677,23 @@ class CausalBGM(object):
                                     target_acceptance_rate=0.25, tolerance=0.05, adjustment_interval=50,
                                     adaptive_sd=None, window_size=100, diagnostics=False):
         """Posterior samples of Z, shape (n_keep, n, q) (base.py:820-904).  diagnostics=True: split R-hat / effective sample
-        size of every chain, computed on the device before the copy to the host, in ``self.mcmc_diagnostics_``."""
+        size of every chain, computed on the device before the copy to the host, in ``self.mcmc_diagnostics_``.
+
+        ``adaptive_sd='row'``: every chain adapts a proposal scale of its own during burn-in towards ``target_acceptance_rate``
+        (row_adapt.py), starting from ``q_sd`` if positive, else ``initial_q_sd``; the scales are left in ``self.mh_row_scale_``."""
         data_x, data_y, data_v = data
+        ra_target = self._adaptive_sd_target(adaptive_sd, target_acceptance_rate)
+        self.mh_row_scale_ = None
+        if ra_target is not None:
+            q_sd, adaptive_sd = row_adapt_mod.start_scale(q_sd, initial_q_sd), False
         if adaptive_sd is None:
             adaptive_sd = (q_sd is None or q_sd <= 0)
         out = self.engine.mh_sample(self._dev(data_x).reshape(-1), self._dev(data_y).reshape(-1), self._dev(data_v),
                                     burn_in, n_keep, q_sd, self._next_seed(), want_draws=True, adaptive=adaptive_sd,
                                     initial_q_sd=initial_q_sd, target=target_acceptance_rate, tol=tolerance,
-                                    adj_int=adjustment_interval, window=window_size)
+                                    adj_int=adjustment_interval, window=window_size, row_adapt=ra_target)
+        if ra_target is not None:
+            self.mh_row_scale_ = out["row_scale"].cpu().numpy()
         tot = burn_in + n_keep
         w = min(window_size, tot)
         self.last_acceptance_rate = float(out["acc_count"][tot - w:].sum().item()) / (w * len(data_x))

@@ -458,9 +458,10 @@ class CausalBGMBayes(CausalBGM):
         return state, acc_tail, tail
 
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
-                bs=10000, verbose=1):
+                bs=10000, verbose=1, row_adapt=False):
         """Causal effects with posterior intervals (base.py:573-668).  With Bayesian nets the rows of one block of ``bs``
         rows share their input statistics and weight perturbations, as in the reference; all blocks advance together."""
+        self._row_adapt_target(row_adapt)      # (raises for anything but False: the per-chain proposal scale does not exist here)
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         binary = bool(self._p['binary_treatment'])
@@ -519,6 +520,7 @@ class CausalBGMBayes(CausalBGM):
                                     adaptive_sd=None, window_size=100, diagnostics=False):
         """Posterior samples of Z, shape (n_keep, n, q) (base.py:820-904): the rows given are ONE block.  diagnostics=True: as
         CausalBGM.metropolis_hastings_sampler."""
+        self._adaptive_sd_target(adaptive_sd, target_acceptance_rate)      # (adaptive_sd='row' raises: the per-chain proposal scale does not exist here)
         data_x, data_y, data_v = data
         if adaptive_sd is None:
             adaptive_sd = (q_sd is None or q_sd <= 0)

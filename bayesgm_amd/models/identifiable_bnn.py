@@ -230,6 +230,7 @@ class IdentifiableCausalBGMBayes(CausalBGMBayes):
     def metropolis_hastings_sampler(self, data, initial_q_sd=1.0, q_sd=None, burn_in=5000, n_keep=3000, target_acceptance_rate=0.25,
                                     tolerance=0.05, adjustment_interval=50, adaptive_sd=None, window_size=100, diagnostics=False):
         """(samples [n_keep, n, q], data_u one-hot [n, n_segments]) (:557-614)."""
+        self._adaptive_sd_target(adaptive_sd, target_acceptance_rate)      # (adaptive_sd='row' raises: the per-chain proposal scale does not exist here)
         segs = self._segments_for(len(data[0]))
         self._set_prior(torch.from_numpy(segs.astype(np.int32)).to(self.engine.device))
         try:
@@ -241,10 +242,12 @@ class IdentifiableCausalBGMBayes(CausalBGMBayes):
             self._clear_prior()
         return samples, np.eye(int(self.params['n_segments']), dtype=np.float32)[segs]
 
-    def predict(self, data, alpha=0.01, n_mcmc=3000, x_values=None, q_sd=1.0, sample_y=True, bs=100, burn_in=5000, verbose=1):
+    def predict(self, data, alpha=0.01, n_mcmc=3000, x_values=None, q_sd=1.0, sample_y=True, bs=100, burn_in=5000, verbose=1,
+                row_adapt=False):
         """Causal effects with posterior intervals (:348-420): ONE sampler run over all rows with a fresh random U (the panel is one
         block: one perturbation per network call for all rows), effects of every retained draw fused behind it; `bs` only chunked the
         host-side effect pass of the reference and does not change the result."""
+        self._row_adapt_target(row_adapt)      # (raises for anything but False: the per-chain proposal scale does not exist here)
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         binary = bool(self._p['binary_treatment'])

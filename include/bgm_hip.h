@@ -91,6 +91,17 @@ BGM_API int bgm_causal_set_precision(bgm_handle *h, int32_t mode);
  * every LOCAL row of those calls (int32), tab_dev [n_segments x (q + 2)] = per segment mu [q], 1 / sigma^2, (q / 2) log sigma^2.
  * Both NULL: back to the standard-normal prior.  The buffers must stay valid while set. */
 BGM_API int bgm_causal_set_prior(bgm_handle *h, const int32_t *seg_dev, const float *tab_dev, int32_t n_segments);
+/* Per-chain proposal scale for the bgm_causal_mh_run calls made afterwards.  scale_dev [n], in / out, aligned with the rows of the
+ * call (written from q_sd when init = 1); up_dev / dn_dev [n_table]: after the accept decision of iteration it < n_table a chain's
+ * scale is multiplied by up_dev[it] (accepted) or dn_dev[it] (rejected) and clamped to [s_min, s_max]; frozen afterwards.
+ * One fp32 multiply per chain and iteration: float32 on the host reproduces every scale bit for bit, and a chain remains a function
+ * of (seed, global row, its data) alone.  Exists for the fp32 LDS-resident kernels with the standard-normal prior (all effects, both
+ * likelihood forms, every outcome-cache mode); with the conditional prior, split precision, the general-width engine, shapes outside
+ * the LDS-resident families or the Bayesian networks the sampling call answers BGM_E_UNSUPPORTED.  The buffers must stay valid
+ * while set.  scale_dev = NULL switches back to the single q_sd.
+ * replaces: the block-wide q_sd *= 0.9 / 1.1 of base.py:880-893 (opt-in). */
+BGM_API int bgm_causal_set_row_scale(bgm_handle *h, float *scale_dev, const float *up_dev, const float *dn_dev,
+                                     int32_t n_table, float s_min, float s_max);
 
 /* The prior network of IdentifiableCausalBGM, prior_net = BaseFullyConnectedNet(n_segments -> prior_units -> q + 1)
  * (identifiable.py:76-78; LeakyReLU(0.2) hidden layers, linear output).  Parameters, gradients and Adam slots live in caller-owned
