@@ -87,11 +87,7 @@ static int build_eblob(bgm_handle *h, EncMeta &m, hipStream_t stream) {
   const int LE = (int)E.dims.size() - 2;
   pack_layer(blob, m.wl, E.W(LE), 64, q, 4, NTQ, ident); pack_bias(blob, m.bl, E.b(LE), q, NTQ);
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  if (h->eblob_cap < blob.size()) {
-    if (h->eblob_dev) BGM_HIP_CHECK(hipFree(h->eblob_dev));
-    BGM_HIP_CHECK(hipMalloc(&h->eblob_dev, blob.size() * sizeof(float)));
-    h->eblob_cap = blob.size();
-  }
+  if (int rc = bgm_reserve(h->eblob_dev, h->eblob_cap, blob.size())) return rc;
   BGM_HIP_CHECK(hipMemcpyAsync(h->eblob_dev, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice, stream));
   BGM_HIP_CHECK(hipStreamSynchronize(stream));
   h->eblob_valid = true;

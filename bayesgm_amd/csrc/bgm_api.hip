@@ -111,11 +111,7 @@ static int bgm_build_blob(bgm_handle *h, hipStream_t stream) {
     o += p;
   }
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  if (s->blob_cap < blob.size()) {
-    if (s->blob_dev) BGM_HIP_CHECK(hipFree(s->blob_dev));
-    BGM_HIP_CHECK(hipMalloc(&s->blob_dev, blob.size() * sizeof(float)));
-    s->blob_cap = blob.size();
-  }
+  if (int rc = bgm_reserve(s->blob_dev, s->blob_cap, blob.size())) return rc;
   BGM_HIP_CHECK(hipMemcpyAsync(s->blob_dev, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice, stream));
   std::vector<unsigned short> hx3;
   if (s->precision != 0) {
@@ -200,11 +196,7 @@ static int bgm_build_blob(bgm_handle *h, hipStream_t stream) {
       for (int tx = 0; tx < NTX; ++tx)      // the head blocks as packed above
         std::memcpy(&sx[(size_t)(FT + tx / BGM_X3_STEP) * step_h + (size_t)(tx % BGM_X3_STEP) * (BGM_X3_BLOCK_BYTES / 2)],
                     &hx3[(size_t)tx * (BGM_X3_BLOCK_BYTES / 2)], BGM_X3_BLOCK_BYTES);
-      if (s->sx3_cap < sx.size() * 2) {
-        if (s->sx3_dev) BGM_HIP_CHECK(hipFree(s->sx3_dev));
-        BGM_HIP_CHECK(hipMalloc((void **)&s->sx3_dev, sx.size() * 2));
-        s->sx3_cap = sx.size() * 2;
-      }
+      if (int rc = bgm_reserve(s->sx3_dev, s->sx3_cap, sx.size() * 2)) return rc;
       BGM_HIP_CHECK(hipMemcpy(s->sx3_dev, sx.data(), sx.size() * 2, hipMemcpyHostToDevice));
       // biases: [b1' (64) | hidden (NH - 1) x 64 | heads 2 x 16 NTX] in the posterior blob's own order, the stage behind them
       BgmMeta &xm = s->sx3_meta;
@@ -217,11 +209,7 @@ static int bgm_build_blob(bgm_handle *h, hipStream_t stream) {
       for (int k = 0; k < 64; ++k) xb[xm.b1 + k] = blob[m.b1 + k];
       for (int k = 0; k < 64 * m.n_hh; ++k) xb[xm.bh + k] = blob[m.bh + k];
       for (int k = 0; k < 2 * 16 * NTX; ++k) xb[xm.bhd + k] = blob[m.bhd + k];
-      if (s->sx3_bias_cap < xb.size()) {
-        if (s->sx3_bias_dev) BGM_HIP_CHECK(hipFree(s->sx3_bias_dev));
-        BGM_HIP_CHECK(hipMalloc((void **)&s->sx3_bias_dev, xb.size() * sizeof(float)));
-        s->sx3_bias_cap = xb.size();
-      }
+      if (int rc = bgm_reserve(s->sx3_bias_dev, s->sx3_bias_cap, xb.size())) return rc;
       BGM_HIP_CHECK(hipMemcpy(s->sx3_bias_dev, xb.data(), xb.size() * sizeof(float), hipMemcpyHostToDevice));
       s->lds_bytes_sx3 = (xm.stage + 2 * BGM_X3_STEP * (BGM_X3_BLOCK_BYTES / 4)) * 4;
     }

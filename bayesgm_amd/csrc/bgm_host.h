@@ -20,6 +20,19 @@ void bgm_set_error(const std::string &msg);
     }                                                                                        \
   } while (0)
 
+// Grow-only device buffer of `count` elements: when the capacity is short, frees the old allocation and makes a new one (the contents
+// are not carried over).  A failed allocation is an error; the event buffers, where it is a signal to fall back, have their own
+// helper (ev_try_reserve, causal_event_api.hip).
+template <class T>
+static int bgm_reserve(T *&ptr, size_t &cap, size_t count) {
+  if (cap >= count) return BGM_OK;
+  if (ptr) BGM_HIP_CHECK(hipFree(ptr));
+  ptr = nullptr; cap = 0;
+  BGM_HIP_CHECK(hipMalloc((void **)&ptr, count * sizeof(T)));
+  cap = count;
+  return BGM_OK;
+}
+
 struct HostNet {
   std::vector<int> dims;    // [in, h1, ..., out]
   std::vector<float> theta; // Keras order: W0 [in x out], b0, W1, b1, ...
@@ -66,7 +79,7 @@ struct bgm_handle {
   CausalMeta gmeta{};
   // split-precision (bf16 x 3) sampling blob (causal_bx3_api.hip); precision: 0 fp32 (default), 1 bf16x3, 2 f16x3 (bgm_causal_set_precision)
   int precision = 0;
-  void *bx_blob_dev = nullptr;
+  unsigned char *bx_blob_dev = nullptr;
   size_t bx_cap = 0;
   // per-wave-slot (mean, sd) of the outcome net at every dose, kept between the retained iterations of an ADRF launch (causal_kernels.h)
   float *eff_cache = nullptr;
@@ -143,8 +156,9 @@ struct bgm_handle {
 // tiles are zero weights (and zero-padded data), so results are unchanged and only some MFMAs are wasted.
 //   first layers (extended input z, x: q + 1 features):  (KT1, KSL1) = (1, 3) for q + 1 <= 12, (2, 1) for q + 1 <= 20
 //   g's last layer (p + 1 outputs):  NTL in {2, 7, 13} 16-wide tiles ({2, 7, 10} with KT1 = 2: LDS budget)
-// Returns false when no compiled shape contains the model.
-static inline bool bgm_causal_shape(int q1, int p1, int &KT1, int &KSL1, int &NTL) {
+// Returns false when no compiled shape contains the model.  causal_launch.h holds the table of compiled shapes and proves at build time
+// that it lists every triple this function can return.
+constexpr bool bgm_causal_shape(int q1, int p1, int &KT1, int &KSL1, int &NTL) {
   if (q1 <= 12) { KT1 = 1; KSL1 = 3; }
   else if (q1 <= 20) { KT1 = 2; KSL1 = 1; }
   else return false;

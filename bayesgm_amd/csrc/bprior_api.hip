@@ -124,12 +124,7 @@ int bprior_rows(bgm_handle *h, BnnState *s, long long n, int bs, int block0, uin
   const BPriorNet &net = s->bp_net;
   const int q = s->q, n_blocks = (int)((n + bs - 1) / bs);
   const size_t need = (size_t)n_states * (size_t)n * (size_t)(q + 2);
-  if (s->bp_rows_cap < need) {
-    if (s->bp_rows) BGM_HIP_CHECK(hipFree(s->bp_rows));
-    s->bp_rows = nullptr; s->bp_rows_cap = 0;
-    BGM_HIP_CHECK(hipMalloc((void **)&s->bp_rows, need * sizeof(float)));
-    s->bp_rows_cap = need;
-  }
+  if (int rc = bgm_reserve(s->bp_rows, s->bp_rows_cap, need)) return rc;
   int tot = 0;
   for (int l = 0; l <= net.n_layers; ++l) tot += BPRIOR_ROWS_CHUNK * net.dims[l];
   const size_t lds = sizeof(float) * ((size_t)tot + (size_t)net.n_kernel + (size_t)BPRIOR_ROWS_CHUNK * net.words + BPRIOR_ROWS_CHUNK);
@@ -139,12 +134,7 @@ int bprior_rows(bgm_handle *h, BnnState *s, long long n, int bs, int block0, uin
     if (rib0 != 0) { bgm_set_error("conditional prior: a share of one block needs the inference-mode normalisation"); return BGM_E_UNSUPPORTED; }
     if (s->bp_hist_n != n || s->bp_hist_bs != bs) {      // the segments of the panel do not change between the calls of a run
       const size_t cnt = (size_t)n_blocks * (size_t)net.dims[0];
-      if (s->bp_hist_cap < cnt) {
-        if (s->bp_hist) BGM_HIP_CHECK(hipFree(s->bp_hist));
-        s->bp_hist = nullptr; s->bp_hist_cap = 0;
-        BGM_HIP_CHECK(hipMalloc((void **)&s->bp_hist, cnt * sizeof(int)));
-        s->bp_hist_cap = cnt;
-      }
+      if (int rc = bgm_reserve(s->bp_hist, s->bp_hist_cap, cnt)) return rc;
       hipLaunchKernelGGL(bprior_hist_kernel, dim3(n_blocks), dim3(256), 0, stream, s->bp_seg, n, bs, net.dims[0], s->bp_hist);
       BGM_HIP_CHECK(hipGetLastError());
       s->bp_hist_n = n; s->bp_hist_bs = bs;

@@ -9,7 +9,7 @@
 #include <cstring>
 #include <cstdlib>
 
-#include "bgm_host.h"
+#include "causal_launch.h"
 #include "bnf_det_host.h"
 #include "gx_host.h"
 
@@ -268,11 +268,7 @@ int bgm_causal_sampling_blob(bgm_handle *h, hipStream_t stream) {
   if (rc) return rc;
   if (h->sblob_valid) return BGM_OK;
   const size_t n = (size_t)h->meta.total;
-  if (h->sblob_cap < n) {
-    if (h->sblob_dev) BGM_HIP_CHECK(hipFree(h->sblob_dev));
-    BGM_HIP_CHECK(hipMalloc(&h->sblob_dev, n * sizeof(float)));
-    h->sblob_cap = n;
-  }
+  if ((rc = bgm_reserve(h->sblob_dev, h->sblob_cap, n))) return rc;
   h->gram_valid = false;      // the Gram copy derives from this one
   hipLaunchKernelGGL(causal_scale_blob_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, h->blob_dev, h->sblob_dev,
                      h->meta, h->NTL);
@@ -346,16 +342,8 @@ static int bgm_causal_gram_blob(bgm_handle *h, hipStream_t stream) {
   for (int i = 0; i < 64; ++i) { gb[gm.bgl + i] = a0[i]; gb[gm.bgl + 64 + i] = packed_w(sb, m.wgl, NTL, i, m.sig_slot); }
   gb[gm.bgl + 128] = sb[m.bgl + m.sig_slot];
   std::copy(sb.begin() + m.wf2, sb.end(), gb.begin() + gm.wf2);
-  if (h->gblob_cap < gb.size()) {
-    if (h->gblob_dev) BGM_HIP_CHECK(hipFree(h->gblob_dev));
-    BGM_HIP_CHECK(hipMalloc(&h->gblob_dev, gb.size() * sizeof(float)));
-    h->gblob_cap = gb.size();
-  }
-  if (h->gram_w_cap < wt.size()) {
-    if (h->gram_w_dev) BGM_HIP_CHECK(hipFree(h->gram_w_dev));
-    BGM_HIP_CHECK(hipMalloc(&h->gram_w_dev, wt.size() * sizeof(float)));
-    h->gram_w_cap = wt.size();
-  }
+  if (int rc = bgm_reserve(h->gblob_dev, h->gblob_cap, gb.size())) return rc;
+  if (int rc = bgm_reserve(h->gram_w_dev, h->gram_w_cap, wt.size())) return rc;
   BGM_HIP_CHECK(hipMemcpyAsync(h->gblob_dev, gb.data(), gb.size() * sizeof(float), hipMemcpyHostToDevice, stream));
   BGM_HIP_CHECK(hipMemcpyAsync(h->gram_w_dev, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice, stream));
   BGM_HIP_CHECK(hipStreamSynchronize(stream));  // stack-local staging buffers
@@ -397,12 +385,7 @@ static __global__ __launch_bounds__(256) void causal_gram_prepass_kernel(const f
 static int causal_gram_prepare(bgm_handle *h, const float *v, int64_t n, hipStream_t stream) {
   int rc = bgm_causal_gram_blob(h, stream);
   if (rc) return rc;
-  const size_t need = (size_t)n * 65;
-  if (h->uc_cap < need) {
-    if (h->uc_dev) BGM_HIP_CHECK(hipFree(h->uc_dev));
-    BGM_HIP_CHECK(hipMalloc(&h->uc_dev, need * sizeof(float)));
-    h->uc_cap = need;
-  }
+  if ((rc = bgm_reserve(h->uc_dev, h->uc_cap, (size_t)n * 65))) return rc;
   hipLaunchKernelGGL(causal_gram_prepass_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)65 * h->p * sizeof(float), stream,
                      h->gram_w_dev, v, (long long)n, h->p, h->uc_dev);
   BGM_HIP_CHECK(hipGetLastError());
@@ -418,11 +401,7 @@ int bgm_causal_build_blob(bgm_handle *h, hipStream_t stream) {
   int rc = causal_pack_forward(h, h->nets[BGM_NET_G], h->nets[BGM_NET_F], h->nets[BGM_NET_H], blob);
   if (rc) return rc;
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  if (h->blob_cap < blob.size()) {
-    if (h->blob_dev) BGM_HIP_CHECK(hipFree(h->blob_dev));
-    BGM_HIP_CHECK(hipMalloc(&h->blob_dev, blob.size() * sizeof(float)));
-    h->blob_cap = blob.size();
-  }
+  if ((rc = bgm_reserve(h->blob_dev, h->blob_cap, blob.size()))) return rc;
   BGM_HIP_CHECK(hipMemcpyAsync(h->blob_dev, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice, stream));
   BGM_HIP_CHECK(hipStreamSynchronize(stream));  // blob is a stack-local staging buffer
   h->blob_valid = true;
@@ -430,34 +409,10 @@ int bgm_causal_build_blob(bgm_handle *h, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------
-// kernel variants.  (KT1, KSL1, NTL): first-layer K tiling and number of
-// 16-wide output tiles of g's last layer.
-//   (1,3,13): z_dims [1,1,1,7], p = 200   (configs/Sim_Hirano_Imbens.yaml)
-//   (2,1, 7): z_dims [3,3,6,6], p = 100   (cli/cli.py defaults)
-//   (1,3, 2): z_dims [1,1,1,7], p <= 31   (small panels / tests)
-//   (2,1, 2): z_dims [3,3,6,6], p <= 31
+// launches (shape table, dispatch and geometry: causal_launch.h)
 // ---------------------------------------------------------------------------
-#ifndef BGM_MH_R
-#define BGM_MH_R 1
-#endif
-#ifndef BGM_MH_WAVES
-#define BGM_MH_WAVES 8
-#endif
-static constexpr int MH_R = BGM_MH_R, MH_WAVES = BGM_MH_WAVES;
-
-#define BGM_CAUSAL_VARIANTS(X) X(1, 3, 13) X(1, 3, 7) X(1, 3, 2) X(2, 1, 10) X(2, 1, 7) X(2, 1, 2)
-
-template <class K>
-static int set_lds(K kernel, int bytes) {
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return BGM_OK;
-}
-
-static int mh_grid(const bgm_handle *h, int64_t n) {
-  const int64_t tiles = (n + 16 * MH_R - 1) / (16 * MH_R);
-  const int64_t blocks = (tiles + MH_WAVES - 1) / MH_WAVES;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(blocks, h->n_cus));
-}
+static int mh_grid(const bgm_handle *h, int64_t n) { return bgm_causal_grid(h, n, MH_R); }
+static int eval_grid(const bgm_handle *h, int64_t n) { return bgm_causal_grid(h, n, 1); }      // the evaluate / effects kernels: one row tile per wave
 
 extern "C" int bgm_causal_mh_slots(bgm_handle *h, int64_t n, int32_t *n_slots) {
   if (!h || !n_slots) { bgm_set_error("bgm_causal_mh_slots: NULL"); return BGM_E_INVALID; }
@@ -486,42 +441,21 @@ extern "C" int bgm_causal_logpost(bgm_handle *h, const float *x, const float *y,
   const int grid = mh_grid(h, n);
   if (h->precision != 0) return bgm_causal_bx3_logpost(h, x, y, v, z, n, out, grid, stream);      // (carries the conditional prior, if one is set)
   if (h->prior_seg) return bgm_causal_prior_logpost(h, x, y, v, z, n, out, grid, stream);
-  const int lds = h->meta.total * 4;
-#define X(KT1_, KSL1_, NTL_)                                                                   \
-  if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \
-    auto k = causal_logpost_kernel<KT1_, KSL1_, NTL_, MH_R, MH_WAVES>;                         \
-    rc = set_lds(k, lds);                                                                      \
-    if (rc) return rc;                                                                         \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * MH_WAVES), lds, stream, h->sblob_dev, h->meta,  \
-                       x, y, v, z, (long long)n, out, (const int *)nullptr, (const float *)nullptr); \
-    BGM_HIP_CHECK(hipGetLastError());                                                          \
-    return BGM_OK;                                                                             \
-  }
-  BGM_CAUSAL_VARIANTS(X)
-#undef X
-  bgm_set_error("no compiled kernel variant for (KT1,KSL1,NTL)=(" + std::to_string(h->KT1) + "," +
-                std::to_string(h->KSL1) + "," + std::to_string(h->NTL) + ")");
-  return BGM_E_UNSUPPORTED;
+  return bgm_causal_dispatch(h, "kernel", [&](auto s) {
+    using S = decltype(s);
+    return bgm_causal_launch(causal_logpost_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES>, grid, MH_WAVES, h->meta.total * 4, stream,
+                             h->sblob_dev, h->meta, x, y, v, z, n, out, nullptr, nullptr);
+  });
 }
 
 template <int EFFECT>
 static int launch_mh(bgm_handle *h, const CausalMhKArgs &ka, int grid, int lds, hipStream_t stream) {
-  int rc;
-#define X(KT1_, KSL1_, NTL_)                                                                   \
-  if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \
-    auto k = ka.uc ? causal_mh_kernel<KT1_, KSL1_, NTL_, MH_R, MH_WAVES, EFFECT, 0, (NTL_ > 2)>  \
-                   : causal_mh_kernel<KT1_, KSL1_, NTL_, MH_R, MH_WAVES, EFFECT>;              \
-    rc = set_lds(k, lds);                                                                      \
-    if (rc) return rc;                                                                         \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * MH_WAVES), lds, stream, ka);                   \
-    BGM_HIP_CHECK(hipGetLastError());                                                          \
-    return BGM_OK;                                                                             \
-  }
-  BGM_CAUSAL_VARIANTS(X)
-#undef X
-  bgm_set_error("no compiled MH kernel variant for (KT1,KSL1,NTL)=(" + std::to_string(h->KT1) + "," +
-                std::to_string(h->KSL1) + "," + std::to_string(h->NTL) + ")");
-  return BGM_E_UNSUPPORTED;
+  return bgm_causal_dispatch(h, "MH kernel", [&](auto s) {
+    using S = decltype(s);
+    return bgm_causal_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2)>
+                                   : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT>,
+                             grid, MH_WAVES, lds, stream, ka);
+  });
 }
 
 extern "C" int bgm_causal_mh_run(bgm_handle *h, const bgm_mh_args *a, void *stream_) {
@@ -541,8 +475,7 @@ extern "C" int bgm_causal_mh_run(bgm_handle *h, const bgm_mh_args *a, void *stre
     const char *path = gx_wanted(h) ? "the general-width engine (hidden widths outside the compiled families)"
                        : bnf_det_wanted(h) ? "the streamed-fragment kernels (no LDS-resident compiled shape holds the model)"
                        : h->precision != 0 ? "the split-precision kernels (bgm_causal_set_precision)"
-                       : h->prior_seg ? "the conditional latent prior (bgm_causal_set_prior)"
-                       : MH_R != 1 ? "builds with more than one row tile per wave" : nullptr;
+                       : h->prior_seg ? "the conditional latent prior (bgm_causal_set_prior)" : nullptr;
     if (path) { bgm_set_error(std::string("bgm_causal_mh_run: the per-chain proposal scale (bgm_causal_set_row_scale) does not exist for ") + path); return BGM_E_UNSUPPORTED; }
   }
   if (gx_wanted(h)) {
@@ -602,12 +535,7 @@ extern "C" int bgm_causal_mh_run(bgm_handle *h, const bgm_mh_args *a, void *stre
   const int nseg = (int)segs.size();
   if (a->effect != BGM_EFFECT_NONE && it_end > split) {
     if (a->effect == BGM_EFFECT_ADRF) {      // (mean, sd) of the outcome net per wave slot, pass and lane: causal_effects_cached
-      const size_t need = (size_t)n_slots * (size_t)((a->n_doses + 3) / 4) * 64 * 2;
-      if (h->eff_cache_cap < need) {
-        if (h->eff_cache) BGM_HIP_CHECK(hipFree(h->eff_cache));
-        BGM_HIP_CHECK(hipMalloc(&h->eff_cache, need * sizeof(float)));
-        h->eff_cache_cap = need;
-      }
+      if ((rc = bgm_reserve(h->eff_cache, h->eff_cache_cap, (size_t)n_slots * (size_t)((a->n_doses + 3) / 4) * 64 * 2))) return rc;
       ka.eff_cache = h->eff_cache;
     }                                        // (binary treatment: the two arms' pairs stay in registers, causal_ite_cached)
     ka.eff_skip = h->outcome_cache ? 1 : 0;
@@ -623,11 +551,7 @@ extern "C" int bgm_causal_mh_run(bgm_handle *h, const bgm_mh_args *a, void *stre
     ka.it_begin = segs[s].begin; ka.n_iters = segs[s].n; ka.init = segs[s].init;
     if (a->acc_count_dev) {   // slot-private counters for this launch, reduced into acc_count_dev afterwards
       const size_t need = (size_t)n_slots * segs[s].n;
-      if (h->acc_scratch_cap < need) {
-        if (h->acc_scratch) BGM_HIP_CHECK(hipFree(h->acc_scratch));
-        BGM_HIP_CHECK(hipMalloc(&h->acc_scratch, need * sizeof(unsigned)));
-        h->acc_scratch_cap = need;
-      }
+      if ((rc = bgm_reserve(h->acc_scratch, h->acc_scratch_cap, need))) return rc;
       BGM_HIP_CHECK(hipMemsetAsync(h->acc_scratch, 0, need * sizeof(unsigned), stream));
       ka.acc_count = h->acc_scratch;
     }
@@ -663,20 +587,10 @@ extern "C" int bgm_causal_mh_run(bgm_handle *h, const bgm_mh_args *a, void *stre
 
 template <int EFFECT>
 static int launch_eval(bgm_handle *h, const CausalEvalKArgs &ka, int grid, int lds, hipStream_t stream) {
-  int rc;
-#define X(KT1_, KSL1_, NTL_)                                                                   \
-  if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \
-    auto k = causal_eval_kernel<KT1_, KSL1_, NTL_, MH_WAVES, EFFECT>;                          \
-    rc = set_lds(k, lds);                                                                      \
-    if (rc) return rc;                                                                         \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * MH_WAVES), lds, stream, ka);                   \
-    BGM_HIP_CHECK(hipGetLastError());                                                          \
-    return BGM_OK;                                                                             \
-  }
-  BGM_CAUSAL_VARIANTS(X)
-#undef X
-  bgm_set_error("no compiled evaluate kernel variant for this shape");
-  return BGM_E_UNSUPPORTED;
+  return bgm_causal_dispatch(h, "evaluate kernel", [&](auto s) {
+    using S = decltype(s);
+    return bgm_causal_launch(causal_eval_kernel<S::KT1, S::KSL1, S::NTL, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka);
+  });
 }
 
 extern "C" int bgm_causal_evaluate(bgm_handle *h, const float *x, const float *y, const float *v, const float *z,
@@ -697,28 +611,17 @@ extern "C" int bgm_causal_evaluate(bgm_handle *h, const float *x, const float *y
   CausalEvalKArgs ka{};
   ka.blob = h->sblob_dev; ka.x = x; ka.y = y; ka.v = v; ka.z = z; ka.n = n; ka.sums = sums;
   ka.x_values = x_values; ka.n_doses = binary ? 2 : n_doses; ka.adrf_partial = adrf_partial; ka.ite = ite; ka.m = h->meta;
-  const int64_t tiles = (n + 15) / 16;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + MH_WAVES - 1) / MH_WAVES, h->n_cus));
+  const int grid = eval_grid(h, n);
   const int lds = h->meta.total * 4;
   return binary ? launch_eval<2>(h, ka, grid, lds, stream) : launch_eval<1>(h, ka, grid, lds, stream);
 }
 
 template <int EFFECT>
 static int launch_effects(bgm_handle *h, const CausalEffKArgs &ka, int grid, int lds, hipStream_t stream) {
-  int rc;
-#define X(KT1_, KSL1_, NTL_)                                                                   \
-  if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \
-    auto k = causal_effects_kernel<KT1_, KSL1_, MH_WAVES, EFFECT>;                             \
-    rc = set_lds(k, lds);                                                                      \
-    if (rc) return rc;                                                                         \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * MH_WAVES), lds, stream, ka);                   \
-    BGM_HIP_CHECK(hipGetLastError());                                                          \
-    return BGM_OK;                                                                             \
-  }
-  BGM_CAUSAL_VARIANTS(X)
-#undef X
-  bgm_set_error("no compiled effects kernel variant for this shape");
-  return BGM_E_UNSUPPORTED;
+  return bgm_causal_dispatch(h, "effects kernel", [&](auto s) {
+    using S = decltype(s);
+    return bgm_causal_launch(causal_effects_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka);
+  });
 }
 
 extern "C" int bgm_causal_effects(bgm_handle *h, const float *x, const float *draws, int64_t n, int64_t row_base, int32_t n_keep,
@@ -741,8 +644,7 @@ extern "C" int bgm_causal_effects(bgm_handle *h, const float *x, const float *dr
   ka.blob = h->sblob_dev; ka.x = x; ka.draws = draws; ka.n = n; ka.row_base = row_base; ka.n_keep = n_keep; ka.burn_in = burn_in;
   ka.sample_y = sample_y; ka.n_doses = binary ? 2 : n_doses; ka.x_values = x_values; ka.adrf_partial = adrf_partial; ka.ite = ite;
   ka.k0 = (unsigned)(seed & 0xFFFFFFFFull); ka.k1 = (unsigned)(seed >> 32); ka.m = h->meta;
-  const int64_t tiles = (n + 15) / 16;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + MH_WAVES - 1) / MH_WAVES, h->n_cus));
+  const int grid = eval_grid(h, n);
   const int lds = h->meta.total * 4 + 64;
   return binary ? launch_effects<2>(h, ka, grid, lds, stream) : launch_effects<1>(h, ka, grid, lds, stream);
 }
@@ -751,8 +653,7 @@ extern "C" int bgm_causal_evaluate_slots(bgm_handle *h, int64_t n, int32_t *n_sl
   if (!h || !n_slots) { bgm_set_error("bgm_causal_evaluate_slots: NULL"); return BGM_E_INVALID; }
   if (h->configured && gx_wanted(h)) { *n_slots = gx_slots(h, n); return BGM_OK; }
   if (h->configured && bnf_det_wanted(h)) { *n_slots = bnf_det_slots(h); return BGM_OK; }
-  const int64_t tiles = (n + 15) / 16;
-  *n_slots = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + MH_WAVES - 1) / MH_WAVES, h->n_cus)) * MH_WAVES;
+  *n_slots = eval_grid(h, n) * MH_WAVES;
   return BGM_OK;
 }
 

@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "bgm_host.h"
+#include "causal_launch.h"
 #define BX_NS bxb
 #define BX_F16 0
 #include "causal_bx3_kernels.h"
@@ -19,9 +19,6 @@
 #include "causal_bx3_kernels.h"
 #undef BX_NS
 #undef BX_F16
-
-static constexpr int BX_WAVES = 8;
-#define BGM_BX3_VARIANTS(X) X(1, 13) X(1, 7) X(1, 2) X(2, 10) X(2, 7) X(2, 2)
 
 // round-to-nearest-even fp32 -> bf16 (finite inputs)
 static inline uint16_t bx_bf16_bits(float f) {
@@ -162,11 +159,12 @@ static int bx_pack(bgm_handle *h, std::vector<unsigned char> &blob, BxMeta &m) {
   auto s2 = [](float s) { return s > 0.0f ? s * s : -1.0f; };
   m.sig2_v = s2(h->cfg.sigma_v); m.sig2_x = s2(h->cfg.sigma_x); m.sig2_y = s2(h->cfg.sigma_y);
   m.n_gh = h->cfg.n_hidden_g - 1;
-  bool done = false;
-#define X(KT1_, NTL_) if (KT1 == KT1_ && NTL == NTL_) { bx_fill<KT1_, NTL_>(h, blob, m); done = true; }
-  BGM_BX3_VARIANTS(X)
-#undef X
-  if (!done) { bgm_set_error("bf16x3: no compiled kernel variant for this shape"); return BGM_E_UNSUPPORTED; }
+  // (the split-precision kernels and their layout depend on KT1 and NTL alone)
+  const int rc = bgm_causal_dispatch(CausalShapes{}, KT1, KSL1, NTL, "bf16x3: kernel", [&](auto s) {
+    bx_fill<decltype(s)::KT1, decltype(s)::NTL>(h, blob, m);
+    return BGM_OK;
+  });
+  if (rc) return rc;
   if (m.total_bytes + 64 > 160 * 1024) {
     bgm_set_error("bf16x3: model does not fit the 160 KiB LDS-resident layout (" + std::to_string(m.total_bytes) + " B)");
     return BGM_E_UNSUPPORTED;
@@ -185,11 +183,7 @@ int bgm_causal_bx3_blob(bgm_handle *h, hipStream_t stream) {
   int rc = bx_pack(h, blob, m);
   if (rc) return rc;
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  if (h->bx_cap < blob.size()) {
-    if (h->bx_blob_dev) BGM_HIP_CHECK(hipFree(h->bx_blob_dev));
-    BGM_HIP_CHECK(hipMalloc(&h->bx_blob_dev, blob.size()));
-    h->bx_cap = blob.size();
-  }
+  if ((rc = bgm_reserve(h->bx_blob_dev, h->bx_cap, blob.size()))) return rc;
   BGM_HIP_CHECK(hipMemcpyAsync(h->bx_blob_dev, blob.data(), blob.size(), hipMemcpyHostToDevice, stream));
   BGM_HIP_CHECK(hipStreamSynchronize(stream));
   static_assert(sizeof(BxMeta) <= sizeof(h->bx_meta_store), "bx_meta_store too small");
@@ -205,54 +199,20 @@ extern "C" int bgm_causal_set_precision(bgm_handle *h, int32_t mode) {
   return BGM_OK;
 }
 
-template <class K>
-static int bx_set_lds(K kernel, int bytes) {
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return BGM_OK;
-}
-
 int bgm_causal_bx3_logpost(bgm_handle *h, const float *x, const float *y, const float *v, const float *z, int64_t n, float *out,
                            int grid, hipStream_t stream) {
   int rc = bgm_causal_bx3_blob(h, stream);
   if (rc) return rc;
   BxMeta m;
   std::memcpy(&m, h->bx_meta_store, sizeof(m));
-  const int lds = m.total_bytes;
-#define X(KT1_, NTL_)                                                                                              \
-  if (h->KT1 == KT1_ && h->NTL == NTL_) {                                                                          \
-    auto k = h->precision == 2 ? bxh::causal_logpost_bx3_kernel<KT1_, NTL_, BX_WAVES> : bxb::causal_logpost_bx3_kernel<KT1_, NTL_, BX_WAVES>; \
-    rc = bx_set_lds(k, lds);                                                                                       \
-    if (rc) return rc;                                                                                             \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * BX_WAVES), lds, stream, (const unsigned char *)h->bx_blob_dev, m, x, y, v, z, \
-                       (long long)n, out, (const int *)h->prior_seg, (const float *)h->prior_tab);                 \
-    BGM_HIP_CHECK(hipGetLastError());                                                                              \
-    return BGM_OK;                                                                                                 \
-  }
-  BGM_BX3_VARIANTS(X)
-#undef X
-  bgm_set_error("bf16x3: no compiled kernel variant for this shape");
-  return BGM_E_UNSUPPORTED;
+  return bgm_causal_dispatch(h, "bf16x3: kernel", [&](auto s) {
+    constexpr int KT1 = decltype(s)::KT1, NTL = decltype(s)::NTL;
+    return bgm_causal_launch(h->precision == 2 ? bxh::causal_logpost_bx3_kernel<KT1, NTL, MH_WAVES> : bxb::causal_logpost_bx3_kernel<KT1, NTL, MH_WAVES>,
+                             grid, MH_WAVES, m.total_bytes, stream, h->bx_blob_dev, m, x, y, v, z, n, out, h->prior_seg, h->prior_tab);
+  });
 }
 
-template <int EFFECT>
-static int bx_launch_mh(bgm_handle *h, const CausalBxKArgs &ka, int grid, int lds, hipStream_t stream) {
-  int rc;
-#define X(KT1_, NTL_)                                                                          \
-  if (h->KT1 == KT1_ && h->NTL == NTL_) {                                                      \
-    auto k = h->precision == 2 ? bxh::causal_mh_bx3_kernel<KT1_, NTL_, BX_WAVES, EFFECT> : bxb::causal_mh_bx3_kernel<KT1_, NTL_, BX_WAVES, EFFECT>; \
-    rc = bx_set_lds(k, lds);                                                                   \
-    if (rc) return rc;                                                                         \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * BX_WAVES), lds, stream, ka);                   \
-    BGM_HIP_CHECK(hipGetLastError());                                                          \
-    return BGM_OK;                                                                             \
-  }
-  BGM_BX3_VARIANTS(X)
-#undef X
-  bgm_set_error("bf16x3: no compiled MH kernel variant for this shape");
-  return BGM_E_UNSUPPORTED;
-}
-
-// one launch of the split-precision MH kernel with the fp32 kernel's argument block (effect: 0 none, 1 ADRF, 2 ITE)
+// one launch of the split-precision MH kernel with the fp32 kernel's argument block (effect: 0 none, 1 ADRF, 2 ITE, 3 event form)
 int bgm_causal_bx3_mh_launch(bgm_handle *h, const CausalMhKArgs &a, int effect, int grid, hipStream_t stream) {
   int rc = bgm_causal_bx3_blob(h, stream);
   if (rc) return rc;
@@ -263,8 +223,11 @@ int bgm_causal_bx3_mh_launch(bgm_handle *h, const CausalMhKArgs &a, int effect, 
   ka.bblob = (const unsigned char *)h->bx_blob_dev;
   std::memcpy(&ka.bx, h->bx_meta_store, sizeof(BxMeta));
   const int lds = ka.bx.total_bytes + 64;
-  if (effect == 3) return bx_launch_mh<3>(h, ka, grid, lds, stream);        // event form of the retained phase (causal_event_api.hip)
-  if (effect == BGM_EFFECT_ADRF) return bx_launch_mh<1>(h, ka, grid, lds, stream);
-  if (effect == BGM_EFFECT_ITE) return bx_launch_mh<2>(h, ka, grid, lds, stream);
-  return bx_launch_mh<0>(h, ka, grid, lds, stream);
+  return bgm_causal_with_effect(effect, [&](auto e) {
+    return bgm_causal_dispatch(h, "bf16x3: MH kernel", [&](auto s) {
+      constexpr int KT1 = decltype(s)::KT1, NTL = decltype(s)::NTL, EFFECT = decltype(e)::value;
+      return bgm_causal_launch(h->precision == 2 ? bxh::causal_mh_bx3_kernel<KT1, NTL, MH_WAVES, EFFECT> : bxb::causal_mh_bx3_kernel<KT1, NTL, MH_WAVES, EFFECT>,
+                               grid, MH_WAVES, lds, stream, ka);
+    });
+  });
 }

@@ -6,29 +6,24 @@
 #include <cstdlib>
 #include <string>
 
-#include "bgm_host.h"
+#include "causal_launch.h"
 #include "causal_event_kernels.h"
 
-#ifndef BGM_MH_R
-#define BGM_MH_R 1
-#endif
-#ifndef BGM_MH_WAVES
-#define BGM_MH_WAVES 8
-#endif
-static constexpr int EV_MH_R = BGM_MH_R, EV_MH_WAVES = BGM_MH_WAVES, EV_SPREAD_WAVES = 4, EV_SPREAD_LDS_FLOATS = 8192;
-#define BGM_CAUSAL_VARIANTS(X) X(1, 3, 13) X(1, 3, 7) X(1, 3, 2) X(2, 1, 10) X(2, 1, 7) X(2, 1, 2)
+static constexpr int EV_SPREAD_WAVES = 4, EV_SPREAD_LDS_FLOATS = 8192;
 
 // served by the event form: dose-response sums on the LDS-resident kernels (fp32 or split precision, with either prior),
 // doses in registers
 bool bgm_causal_event_wanted(const bgm_handle *h, int effect, int n_doses) {
   static const bool off = std::getenv("BGM_NO_EVENT_SPLIT") != nullptr;      // dev A/B
-  if (off || EV_MH_R != 1 || h->outcome_cache != 2) return false;
+  if (off || h->outcome_cache != 2) return false;
   if (effect == BGM_EFFECT_ITE) return h->cfg.binary_treatment != 0;         // the two arms of a binary treatment (round 6)
   return effect == BGM_EFFECT_ADRF && n_doses >= 1 && (n_doses + 3) / 4 <= EV_NCMAX;
 }
 
+// Not bgm_reserve (bgm_host.h): here a failed allocation is no error but the signal (+1) that the event buffers do not fit the device,
+// on which bgm_causal_mh_run falls back to the per-wave cache
 template <class T>
-static int ev_reserve(T *&ptr, size_t &cap, size_t need) {
+static int ev_try_reserve(T *&ptr, size_t &cap, size_t need) {
   if (cap >= need) return BGM_OK;
   if (ptr) BGM_HIP_CHECK(hipFree(ptr));
   ptr = nullptr; cap = 0;
@@ -77,12 +72,12 @@ int bgm_causal_event_plan(bgm_handle *h, long long n, int n_slots, int n_doses, 
   const long long cap = tps * 16 * S;
   const size_t ev_total = (size_t)n_slots * (size_t)cap;
   int rc;
-  if ((rc = ev_reserve(h->ev_z, h->ev_z_cap, ev_total * (size_t)h->q))) return rc;
-  if ((rc = ev_reserve(h->ev_meta, h->ev_meta_cap, ev_total))) return rc;
-  if ((rc = ev_reserve(h->ev_tile, h->ev_tile_cap, (size_t)n_tiles * 2))) return rc;
-  if ((rc = ev_reserve(h->ev_slot_cnt, h->ev_slot_cap, (size_t)n_slots))) return rc;
-  if ((rc = ev_reserve(h->ev_out, h->ev_out_cap, ev_total / 16 * (size_t)n_calls * 64 * 2))) return rc;
-  if ((rc = ev_reserve(h->ev_carry, h->ev_carry_cap, 2 * (size_t)n_tiles * (size_t)n_calls * 64 * 2))) return rc;      // two buffers, alternating
+  if ((rc = ev_try_reserve(h->ev_z, h->ev_z_cap, ev_total * (size_t)h->q))) return rc;
+  if ((rc = ev_try_reserve(h->ev_meta, h->ev_meta_cap, ev_total))) return rc;
+  if ((rc = ev_try_reserve(h->ev_tile, h->ev_tile_cap, (size_t)n_tiles * 2))) return rc;
+  if ((rc = ev_try_reserve(h->ev_slot_cnt, h->ev_slot_cap, (size_t)n_slots))) return rc;
+  if ((rc = ev_try_reserve(h->ev_out, h->ev_out_cap, ev_total / 16 * (size_t)n_calls * 64 * 2))) return rc;
+  if ((rc = ev_try_reserve(h->ev_carry, h->ev_carry_cap, 2 * (size_t)n_tiles * (size_t)n_calls * 64 * 2))) return rc;      // two buffers, alternating
   *seg_len = (int)S; *ev_cap = cap;
   return BGM_OK;
 }
@@ -94,12 +89,6 @@ void bgm_causal_event_free(bgm_handle *h) {
   h->ev_z_cap = h->ev_meta_cap = h->ev_tile_cap = h->ev_slot_cap = h->ev_out_cap = h->ev_carry_cap = 0;
 }
 
-template <class K>
-static int ev_set_lds(K kernel, int bytes) {
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return BGM_OK;
-}
-
 // transitions of one segment; ka carries the segment (it_begin, n_iters, ev_first) and everything bgm_causal_mh_run filled in
 int bgm_causal_event_mh_launch(bgm_handle *h, CausalMhKArgs &ka, int grid, int lds, hipStream_t stream) {
   ka.ev_z = h->ev_z; ka.ev_meta = h->ev_meta; ka.tile_ev = h->ev_tile; ka.slot_cnt = h->ev_slot_cnt;
@@ -109,20 +98,12 @@ int bgm_causal_event_mh_launch(bgm_handle *h, CausalMhKArgs &ka, int grid, int l
   if (h->prior_seg) return bgm_causal_prior_mh_launch(h, ka, 3, grid, lds, stream);
   // per-chain proposal scale (bgm_causal_set_row_scale): the ROWADAPT instantiation
   if (ka.row_scale) return bgm_causal_rowadapt_mh_launch(h, ka, 3, grid, lds, stream);
-  int rc;
-#define X(KT1_, KSL1_, NTL_)                                                                   \
-  if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \
-    auto k = ka.uc ? causal_mh_kernel<KT1_, KSL1_, NTL_, EV_MH_R, EV_MH_WAVES, 3, 0, (NTL_ > 2)> \
-                   : causal_mh_kernel<KT1_, KSL1_, NTL_, EV_MH_R, EV_MH_WAVES, 3>;             \
-    if ((rc = ev_set_lds(k, lds))) return rc;                                                  \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * EV_MH_WAVES), lds, stream, ka);                \
-    BGM_HIP_CHECK(hipGetLastError());                                                          \
-    return BGM_OK;                                                                             \
-  }
-  BGM_CAUSAL_VARIANTS(X)
-#undef X
-  bgm_set_error("no compiled MH kernel variant for this shape (event form)");
-  return BGM_E_UNSUPPORTED;
+  return bgm_causal_dispatch(h, "event-form MH kernel", [&](auto s) {
+    using S = decltype(s);
+    return bgm_causal_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, 3, 0, (S::NTL > 2)>
+                                   : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, 3>,
+                             grid, MH_WAVES, lds, stream, ka);
+  });
 }
 
 // outcome net on the segment's events, then the spread over its retained iterations
@@ -130,25 +111,20 @@ int bgm_causal_event_finish(bgm_handle *h, const CausalMhKArgs &ka, int grid, in
   CausalEventFArgs fa{};
   fa.blob = ka.blob; fa.ev_z = h->ev_z; fa.slot_cnt = h->ev_slot_cnt; fa.ev_cap = ka.ev_cap; fa.n_doses = ka.n_doses;
   fa.x_values = ka.x_values; fa.ev_out = reinterpret_cast<float2 *>(h->ev_out); fa.eff_stats = ka.eff_stats; fa.m = ka.m;
-  int rc = BGM_E_UNSUPPORTED;
-  bool done = false;
   constexpr int FW = 4, WPS = 2;       // waves per workgroup, waves per sampler slot
+  // the outcome net f alone (its first layer depends on KT1, KSL1; g's NTL plays no part)
+  const int rc = bgm_causal_dispatch(h, "event-form outcome-net kernel", [&](auto s) {
+    using S = decltype(s);
+    const int lds = 4 * (16 * S::KT1 * 64 + 64 + 64 * 32 + 32 + 32 * 16 + 16 + 16 * 16 + 16 + 64);
+    return bgm_causal_launch(effect == BGM_EFFECT_ITE ? causal_event_f_ite_kernel<S::KT1, S::KSL1, FW, WPS>
+                                                      : causal_event_f_kernel<S::KT1, S::KSL1, FW, WPS>,
+                             grid * MH_WAVES * WPS / FW, FW, lds, stream, fa);
+  });
+  if (rc) return rc;
   if (effect == BGM_EFFECT_ITE) {      // binary treatment: the two arms per event, then one thread per chain (causal_event_kernels.h)
-#define X(KT1_, KSL1_)                                                                         \
-    if (!done && h->KT1 == KT1_ && h->KSL1 == KSL1_) {                                         \
-      const int lds = 4 * (16 * KT1_ * 64 + 64 + 64 * 32 + 32 + 32 * 16 + 16 + 16 * 16 + 16 + 64); \
-      auto k = causal_event_f_ite_kernel<KT1_, KSL1_, FW, WPS>;                                \
-      if ((rc = ev_set_lds(k, lds))) return rc;                                                \
-      hipLaunchKernelGGL(k, dim3(grid * EV_MH_WAVES * WPS / FW), dim3(64 * FW), lds, stream, fa); \
-      BGM_HIP_CHECK(hipGetLastError());                                                        \
-      done = true;                                                                             \
-    }
-    X(1, 3) X(2, 1)
-#undef X
-    if (!done) { bgm_set_error("no compiled outcome-net kernel for this shape (event form, binary treatment)"); return BGM_E_UNSUPPORTED; }
     CausalEventIteArgs ia{};
     ia.n = ka.n; ia.row_base = ka.row_base; ia.it_begin = ka.it_begin; ia.n_iters = ka.n_iters; ia.burn_in = ka.burn_in; ia.n_keep = ka.n_keep;
-    ia.sample_y = ka.sample_y; ia.n_slots = grid * EV_MH_WAVES; ia.k0 = ka.k0; ia.k1 = ka.k1;
+    ia.sample_y = ka.sample_y; ia.n_slots = grid * MH_WAVES; ia.k0 = ka.k0; ia.k1 = ka.k1;
     ia.ev_meta = h->ev_meta; ia.tile_ev = h->ev_tile; ia.ev_cap = ka.ev_cap; ia.ev_out = reinterpret_cast<const float4 *>(h->ev_out);
     const size_t carry_floats = (size_t)((ka.n + 15) / 16) * 64 * 2;      // (one Philox call's worth per tile: >= 16 bytes per chain)
     h->ev_carry_flip = first ? 0 : (h->ev_carry_flip ^ 1);
@@ -159,18 +135,6 @@ int bgm_causal_event_finish(bgm_handle *h, const CausalMhKArgs &ka, int grid, in
     BGM_HIP_CHECK(hipGetLastError());
     return BGM_OK;
   }
-#define X(KT1_, KSL1_)                                                                         \
-  if (!done && h->KT1 == KT1_ && h->KSL1 == KSL1_) {                                           \
-    const int lds = 4 * (16 * KT1_ * 64 + 64 + 64 * 32 + 32 + 32 * 16 + 16 + 16 * 16 + 16 + 64); \
-    auto k = causal_event_f_kernel<KT1_, KSL1_, FW, WPS>;                                      \
-    if ((rc = ev_set_lds(k, lds))) return rc;                                                  \
-    hipLaunchKernelGGL(k, dim3(grid * EV_MH_WAVES * WPS / FW), dim3(64 * FW), lds, stream, fa); \
-    BGM_HIP_CHECK(hipGetLastError());                                                          \
-    done = true;                                                                               \
-  }
-  X(1, 3) X(2, 1)
-#undef X
-  if (!done) { bgm_set_error("no compiled outcome-net kernel for this shape (event form)"); return BGM_E_UNSUPPORTED; }
   CausalEventSpreadArgs sa{};
   sa.n = ka.n; sa.row_base = ka.row_base; sa.it_begin = ka.it_begin; sa.n_iters = ka.n_iters; sa.burn_in = ka.burn_in; sa.n_keep = ka.n_keep;
   sa.sample_y = ka.sample_y; sa.n_doses = ka.n_doses; sa.k0 = ka.k0; sa.k1 = ka.k1;
@@ -181,7 +145,7 @@ int bgm_causal_event_finish(bgm_handle *h, const CausalMhKArgs &ka, int grid, in
   sa.carry_out = reinterpret_cast<float2 *>(h->ev_carry + h->ev_carry_flip * carry_floats);
   sa.first = first; sa.adrf_partial = ka.adrf_partial;
   // one block of EV_SPREAD_WAVES waves per sampler slot
-  hipLaunchKernelGGL(causal_event_spread_kernel<EV_SPREAD_WAVES>, dim3(grid * EV_MH_WAVES), dim3(64 * EV_SPREAD_WAVES),
+  hipLaunchKernelGGL(causal_event_spread_kernel<EV_SPREAD_WAVES>, dim3(grid * MH_WAVES), dim3(64 * EV_SPREAD_WAVES),
                      sizeof(float) * (size_t)ka.n_iters * (size_t)ka.n_doses, stream, sa);
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;

@@ -6,11 +6,8 @@
 #include <cmath>
 #include <string>
 
-#include "bgm_host.h"
+#include "causal_launch.h"
 #include "prior_kernels.h"
-
-static constexpr int PR_WAVES = 8;
-#define BGM_PRIOR_VARIANTS(X) X(1, 3, 13) X(1, 3, 7) X(1, 3, 2) X(2, 1, 10) X(2, 1, 7) X(2, 1, 2)
 
 extern "C" int bgm_causal_set_prior(bgm_handle *h, const int32_t *seg_dev, const float *tab_dev, int32_t n_segments) {
   if (!h || !h->configured) { bgm_set_error("bgm_causal_set_prior: handle not configured"); return BGM_E_STATE; }
@@ -19,59 +16,28 @@ extern "C" int bgm_causal_set_prior(bgm_handle *h, const int32_t *seg_dev, const
   return BGM_OK;
 }
 
-template <class K>
-static int pr_set_lds(K kernel, int bytes) {
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return BGM_OK;
-}
-
 int bgm_causal_prior_logpost(bgm_handle *h, const float *x, const float *y, const float *v, const float *z, int64_t n, float *out,
                              int grid, hipStream_t stream) {
-  int rc;
-  const int lds = h->meta.total * 4;
-#define X(KT1_, KSL1_, NTL_)                                                                                     \
-  if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                                    \
-    auto k = causal_logpost_kernel<KT1_, KSL1_, NTL_, 1, PR_WAVES, 1>;                                           \
-    rc = pr_set_lds(k, lds);                                                                                     \
-    if (rc) return rc;                                                                                           \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * PR_WAVES), lds, stream, (const float *)h->sblob_dev, h->meta, x, y, v, z, \
-                       (long long)n, out, (const int *)h->prior_seg, h->prior_tab);                              \
-    BGM_HIP_CHECK(hipGetLastError());                                                                            \
-    return BGM_OK;                                                                                               \
-  }
-  BGM_PRIOR_VARIANTS(X)
-#undef X
-  bgm_set_error("conditional prior: no compiled kernel variant for this shape");
-  return BGM_E_UNSUPPORTED;
-}
-
-template <int EFFECT>
-static int pr_launch_mh(bgm_handle *h, const CausalMhKArgs &ka, int grid, int lds, hipStream_t stream) {
-  int rc;
-#define X(KT1_, KSL1_, NTL_)                                                                   \
-  if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                  \
-    auto k = ka.uc ? causal_mh_kernel<KT1_, KSL1_, NTL_, 1, PR_WAVES, EFFECT, 1, (NTL_ > 2)>    \
-                   : causal_mh_kernel<KT1_, KSL1_, NTL_, 1, PR_WAVES, EFFECT, 1>;              \
-    rc = pr_set_lds(k, lds);                                                                   \
-    if (rc) return rc;                                                                         \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * PR_WAVES), lds, stream, ka);                   \
-    BGM_HIP_CHECK(hipGetLastError());                                                          \
-    return BGM_OK;                                                                             \
-  }
-  BGM_PRIOR_VARIANTS(X)
-#undef X
-  bgm_set_error("conditional prior: no compiled MH kernel variant for this shape");
-  return BGM_E_UNSUPPORTED;
+  return bgm_causal_dispatch(h, "conditional prior: kernel", [&](auto s) {
+    using S = decltype(s);
+    return bgm_causal_launch(causal_logpost_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, 1>, grid, MH_WAVES, h->meta.total * 4, stream,
+                             h->sblob_dev, h->meta, x, y, v, z, n, out, h->prior_seg, h->prior_tab);
+  });
 }
 
 int bgm_causal_prior_mh_launch(bgm_handle *h, const CausalMhKArgs &a, int effect, int grid, int lds, hipStream_t stream) {
   CausalMhKArgs ka = a;
   ka.seg = (const int *)h->prior_seg;
   ka.prior_tab = h->prior_tab;
-  if (effect == 3) return pr_launch_mh<3>(h, ka, grid, lds, stream);         // event form of the retained phase (causal_event_api.hip)
-  if (effect == BGM_EFFECT_ADRF) return pr_launch_mh<1>(h, ka, grid, lds, stream);
-  if (effect == BGM_EFFECT_ITE) return pr_launch_mh<2>(h, ka, grid, lds, stream);
-  return pr_launch_mh<0>(h, ka, grid, lds, stream);
+  return bgm_causal_with_effect(effect, [&](auto e) {
+    return bgm_causal_dispatch(h, "conditional prior: MH kernel", [&](auto s) {
+      using S = decltype(s);
+      constexpr int EFFECT = decltype(e)::value;
+      return bgm_causal_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 1, (S::NTL > 2)>
+                                     : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 1>,
+                               grid, MH_WAVES, lds, stream, ka);
+    });
+  });
 }
 
 
@@ -114,10 +80,7 @@ extern "C" int bgm_prior_table(bgm_handle *h, const bgm_prior_config *cfg, const
   if (n.dims[n.n_layers] != h->q + 1) { bgm_set_error("bgm_prior_table: the prior net must end in q + 1 outputs"); return BGM_E_INVALID; }
   if ((size_t)lf * 4 > 150 * 1024) { bgm_set_error("bgm_prior_table: prior net too wide for one workgroup's LDS"); return BGM_E_UNSUPPORTED; }
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(prior_table_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lf * 4));
-  hipLaunchKernelGGL(prior_table_kernel, dim3(1), dim3(PRIOR_THREADS), lf * 4, (hipStream_t)stream_, n, theta_dev, table_dev, h->q);
-  BGM_HIP_CHECK(hipGetLastError());
-  return BGM_OK;
+  return bgm_causal_launch(prior_table_kernel, 1, PRIOR_THREADS / 64, lf * 4, (hipStream_t)stream_, n, theta_dev, table_dev, h->q);
 }
 
 static int prior_step_impl(bgm_handle *h, const bgm_prior_config *cfg, float *theta_dev, float *m_dev, float *v_dev, const int32_t *seg_dev,
@@ -141,10 +104,7 @@ static int prior_step_impl(bgm_handle *h, const bgm_prior_config *cfg, float *th
   a.b1 = 0.9f; a.b2 = 0.99f; a.eps = 1e-7f;        // tf.keras.optimizers.Adam(lr, beta_1=0.9, beta_2=0.99), identifiable.py:88-95
   a.out = out_dev; a.inv_B = 1.0f / (float)batch_global; a.grad = grad_dev; a.apply = apply;
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(prior_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  hipLaunchKernelGGL(prior_step_kernel, dim3(1), dim3(PRIOR_THREADS), bytes, (hipStream_t)stream_, a);
-  BGM_HIP_CHECK(hipGetLastError());
-  return BGM_OK;
+  return bgm_causal_launch(prior_step_kernel, 1, PRIOR_THREADS / 64, (int)bytes, (hipStream_t)stream_, a);
 }
 
 extern "C" int bgm_prior_step(bgm_handle *h, const bgm_prior_config *cfg, float *theta_dev, float *m_dev, float *v_dev, const int32_t *seg_dev,

@@ -6,19 +6,7 @@
 #include <cmath>
 #include <string>
 
-#include "bgm_host.h"
-
-// the launch geometry of bgm_causal_mh_run (causal_api.hip sizes the grid, the slot-private counters, the ADRF partial sums and the event
-// regions with BGM_MH_WAVES waves per workgroup and BGM_MH_R row tiles per wave): the same build options, one row tile per wave
-#ifndef BGM_MH_R
-#define BGM_MH_R 1
-#endif
-#ifndef BGM_MH_WAVES
-#define BGM_MH_WAVES 8
-#endif
-static constexpr int RA_WAVES = BGM_MH_WAVES;
-// (the kernels are instantiated with one row tile per wave; a build with BGM_MH_R != 1 is refused by bgm_causal_mh_run before it gets here)
-#define BGM_ROWADAPT_VARIANTS(X) X(1, 3, 13) X(1, 3, 7) X(1, 3, 2) X(2, 1, 10) X(2, 1, 7) X(2, 1, 2)
+#include "causal_launch.h"
 
 extern "C" int bgm_causal_set_row_scale(bgm_handle *h, float *scale_dev, const float *up_dev, const float *dn_dev, int32_t n_table,
                                         float s_min, float s_max) {
@@ -33,35 +21,15 @@ extern "C" int bgm_causal_set_row_scale(bgm_handle *h, float *scale_dev, const f
   return BGM_OK;
 }
 
-template <class K>
-static int ra_set_lds(K kernel, int bytes) {
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return BGM_OK;
-}
-
-template <int EFFECT>
-static int ra_launch_mh(bgm_handle *h, const CausalMhKArgs &ka, int grid, int lds, hipStream_t stream) {
-  int rc;
-#define X(KT1_, KSL1_, NTL_)                                                                          \
-  if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                         \
-    auto k = ka.uc ? causal_mh_kernel<KT1_, KSL1_, NTL_, 1, RA_WAVES, EFFECT, 0, (NTL_ > 2), true>    \
-                   : causal_mh_kernel<KT1_, KSL1_, NTL_, 1, RA_WAVES, EFFECT, 0, false, true>;        \
-    rc = ra_set_lds(k, lds);                                                                          \
-    if (rc) return rc;                                                                                \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * RA_WAVES), lds, stream, ka);                          \
-    BGM_HIP_CHECK(hipGetLastError());                                                                 \
-    return BGM_OK;                                                                                    \
-  }
-  BGM_ROWADAPT_VARIANTS(X)
-#undef X
-  bgm_set_error("per-chain proposal scale: no compiled MH kernel variant for this shape");
-  return BGM_E_UNSUPPORTED;
-}
-
 int bgm_causal_rowadapt_mh_launch(bgm_handle *h, const CausalMhKArgs &ka, int effect, int grid, int lds, hipStream_t stream) {
   if (!ka.row_scale || ka.seg) { bgm_set_error("per-chain proposal scale: launched without a scale buffer / with a conditional prior"); return BGM_E_STATE; }
-  if (effect == 3) return ra_launch_mh<3>(h, ka, grid, lds, stream);         // event form of the retained phase (causal_event_api.hip)
-  if (effect == BGM_EFFECT_ADRF) return ra_launch_mh<1>(h, ka, grid, lds, stream);
-  if (effect == BGM_EFFECT_ITE) return ra_launch_mh<2>(h, ka, grid, lds, stream);
-  return ra_launch_mh<0>(h, ka, grid, lds, stream);
+  return bgm_causal_with_effect(effect, [&](auto e) {
+    return bgm_causal_dispatch(h, "per-chain proposal scale: MH kernel", [&](auto s) {
+      using S = decltype(s);
+      constexpr int EFFECT = decltype(e)::value;
+      return bgm_causal_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2), true>
+                                     : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, false, true>,
+                               grid, MH_WAVES, lds, stream, ka);
+    });
+  });
 }

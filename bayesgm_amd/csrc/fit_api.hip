@@ -4,7 +4,7 @@
 #include <cstring>
 #include <numeric>
 
-#include "bgm_host.h"
+#include "causal_launch.h"
 #include "comm_host.h"
 #include "bnf_det_host.h"
 #include "gx_host.h"
@@ -481,8 +481,6 @@ extern "C" int bgm_causal_fit_begin(bgm_handle *h, int64_t n_rows, int32_t max_b
   return fit_chain_setup(h, theta);
 }
 
-#define BGM_FIT_VARIANTS(X) X(1, 3, 13) X(1, 3, 7) X(1, 3, 2) X(2, 1, 10) X(2, 1, 7) X(2, 1, 2)
-
 static int fit_grid(const bgm_handle *h, int B) {
   const int tiles = (B + 15) / 16;
   return std::max(1, std::min((tiles + FIT_WAVES - 1) / FIT_WAVES, h->n_cus));
@@ -490,26 +488,14 @@ static int fit_grid(const bgm_handle *h, int B) {
 
 static int launch_fwd_bwd(bgm_handle *h, FitKArgs &ka, hipStream_t stream) {
   const int grid = fit_grid(h, ka.B);
-#define X(KT1_, KSL1_, NTL_)                                                                           \
-  if (h->KT1 == KT1_ && h->KSL1 == KSL1_ && h->NTL == NTL_) {                                          \
-    auto kf = fit_fwd_kernel<KT1_, KSL1_, NTL_, FIT_WAVES>;                                            \
-    auto kb = fit_bwd_kernel<KT1_, KSL1_, NTL_, FIT_WAVES>;                                            \
-    const int lds_f = h->meta.total * 4, lds_b = h->fit_meta.total * 4;                                \
-    BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, lds_f)); \
-    BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, lds_b)); \
-    ka.blob = h->blob_dev;                                                                             \
-    hipLaunchKernelGGL(kf, dim3(grid), dim3(64 * FIT_WAVES), lds_f, stream, ka);                       \
-    BGM_HIP_CHECK(hipGetLastError());                                                                  \
-    ka.blob = h->bblob_dev;                                                                            \
-    ka.loss = nullptr;                                                                                 \
-    hipLaunchKernelGGL(kb, dim3(grid), dim3(64 * FIT_WAVES), lds_b, stream, ka);                       \
-    BGM_HIP_CHECK(hipGetLastError());                                                                  \
-    return BGM_OK;                                                                                     \
-  }
-  BGM_FIT_VARIANTS(X)
-#undef X
-  bgm_set_error("no compiled fit kernel variant for this shape");
-  return BGM_E_UNSUPPORTED;
+  return bgm_causal_dispatch(h, "fit kernel", [&](auto s) {
+    using S = decltype(s);
+    ka.blob = h->blob_dev;
+    if (int rc = bgm_causal_launch(fit_fwd_kernel<S::KT1, S::KSL1, S::NTL, FIT_WAVES>, grid, FIT_WAVES, h->meta.total * 4, stream, ka)) return rc;
+    ka.blob = h->bblob_dev;
+    ka.loss = nullptr;
+    return bgm_causal_launch(fit_bwd_kernel<S::KT1, S::KSL1, S::NTL, FIT_WAVES>, grid, FIT_WAVES, h->fit_meta.total * 4, stream, ka);
+  });
 }
 
 static int fit_check(bgm_handle *h, const void *x, const void *y, const void *v, const void *z, int batch, int bg, const char *who) {

@@ -335,11 +335,7 @@ int gx_mh_run(bgm_handle *h, const bgm_mh_args *a, hipStream_t stream) {
   const int it_end = a->it_begin + a->n_iters;
   if (a->effect != BGM_EFFECT_NONE && it_end > a->burn_in) {      // outcome-net cache of the retained iterations (bgm_causal_set_outcome_cache)
     const size_t need = (size_t)grid * (size_t)(a->effect == BGM_EFFECT_ITE ? 2 : a->n_doses) * (gw ? GW_WAVES * GW_ROWS : GX_ROWS) * 2;
-    if (h->eff_cache_cap < need) {
-      if (h->eff_cache) BGM_HIP_CHECK(hipFree(h->eff_cache));
-      BGM_HIP_CHECK(hipMalloc(&h->eff_cache, need * sizeof(float)));
-      h->eff_cache_cap = need;
-    }
+    if (int rc = bgm_reserve(h->eff_cache, h->eff_cache_cap, need)) return rc;
     if (!h->eff_stats_dev) {
       BGM_HIP_CHECK(hipMalloc(&h->eff_stats_dev, 2 * sizeof(unsigned long long)));
       BGM_HIP_CHECK(hipMemsetAsync(h->eff_stats_dev, 0, 2 * sizeof(unsigned long long), stream));
