@@ -106,6 +106,9 @@ struct bgm_handle {
   const float *ra_up = nullptr, *ra_dn = nullptr;
   int ra_n = 0;
   float ra_min = 0.0f, ra_max = 0.0f;
+  // HMC latent sampler (causal_hmc_api.hip): the dual-access copy of the Gram blob; rebuilt whenever the Gram copy is
+  void *hmc_state = nullptr;
+  bool hmc_valid = false;
   // encoder blob
   float *eblob_dev = nullptr;
   size_t eblob_cap = 0;
@@ -199,6 +202,9 @@ int bgm_causal_prior_logpost(bgm_handle *h, const float *x, const float *y, cons
 int bgm_causal_prior_mh_launch(bgm_handle *h, const CausalMhKArgs &a, int effect, int grid, int lds, hipStream_t stream);
 // per-chain proposal scale (causal_rowadapt_api.hip): the ROWADAPT instantiations, effect 0 / 1 / 2 or 3 = event form
 int bgm_causal_rowadapt_mh_launch(bgm_handle *h, const CausalMhKArgs &a, int effect, int grid, int lds, hipStream_t stream);
+// Gram form for callers outside causal_api.hip: the sampling blob, its Gram copy (gblob_dev / gmeta) and this panel's 2 u, c (uc_dev)
+int bgm_causal_gram_prepare(bgm_handle *h, const float *v, int64_t n, hipStream_t stream);
+void bgm_causal_hmc_free(bgm_handle *h);      // causal_hmc_api.hip
 // split-precision sampling path (causal_bx3_api.hip)
 int bgm_causal_bx3_blob(bgm_handle *h, hipStream_t stream);
 int bgm_causal_bx3_logpost(bgm_handle *h, const float *x, const float *y, const float *v, const float *z, int64_t n, float *out, int grid,

@@ -58,6 +58,7 @@ extern "C" int bgm_destroy(bgm_handle *h) {
   if (h->eff_cache) hipFree(h->eff_cache);
   if (h->eff_stats_dev) hipFree(h->eff_stats_dev);
   bgm_causal_event_free(h);
+  bgm_causal_hmc_free(h);
   bnf_det_free(h);
   bgm_causal_fit_end(h, nullptr);
   gx_free(h);
@@ -349,6 +350,7 @@ static int bgm_causal_gram_blob(bgm_handle *h, hipStream_t stream) {
   BGM_HIP_CHECK(hipStreamSynchronize(stream));  // stack-local staging buffers
   h->gmeta = gm;
   h->gram_valid = true;
+  h->hmc_valid = false;      // the HMC copy (causal_hmc_api.hip) derives from this one
   return BGM_OK;
 }
 
@@ -390,6 +392,11 @@ static int causal_gram_prepare(bgm_handle *h, const float *v, int64_t n, hipStre
                      h->gram_w_dev, v, (long long)n, h->p, h->uc_dev);
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;
+}
+
+int bgm_causal_gram_prepare(bgm_handle *h, const float *v, int64_t n, hipStream_t stream) {
+  if (int rc = bgm_causal_sampling_blob(h, stream)) return rc;
+  return causal_gram_prepare(h, v, n, stream);
 }
 
 int bgm_causal_build_blob(bgm_handle *h, hipStream_t stream) {

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import causal_hmc as HM
 from . import row_adapt as RA
 
 DEFAULT_G_UNITS = [64, 64, 64, 64, 64]
@@ -114,6 +115,59 @@ class CausalEngine(object):
         _lib.check(self.lib.bgm_causal_logpost(self.h, _ptr(x), _ptr(y), _ptr(v), _ptr(z), n, _ptr(out),
                                                self._stream()), "bgm_causal_logpost")
         return out
+
+    def logpost_grad(self, x, y, v, z):
+        """get_log_posterior and its gradient with respect to z -> (logp [n], grad [n, q]) on the device (bgm_causal_logpost_grad:
+        g's Gaussian term in the Gram form on every shape; fp32 LDS-resident shapes with the standard-normal prior)."""
+        x, y, v, z = (_f32(t, self.device) for t in (x, y, v, z))
+        n = v.shape[0]
+        out = torch.empty(n, device=self.device, dtype=torch.float32)
+        grad = torch.empty((n, self.q), device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.bgm_causal_logpost_grad(self.h, _ptr(x), _ptr(y), _ptr(v), _ptr(z), n, _ptr(out), _ptr(grad),
+                                                    self._stream()), "bgm_causal_logpost_grad")
+        return out, grad
+
+    def hmc_run(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False, row_base=0,
+                up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0):
+        """One segment of the HMC latent sampler for all rows (bgm_causal_hmc_run); state / logp / grad / step are in / out."""
+        _lib.check(self.lib.bgm_causal_hmc_run(self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp),
+                                               _ptr(grad), _ptr(step), _ptr(up), _ptr(dn), 0 if up is None else int(up.numel()),
+                                               float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters), int(burn_in),
+                                               int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws),
+                                               int(n_keep), self._stream()), "bgm_causal_hmc_run")
+
+    def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
+                   adapt=HM.DEFAULT_TARGET, adapt_table=None):
+        """HMC over the latent posterior of every row, one chain per row with a step size of its own.
+
+        adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
+        step by the factor of row_adapt.row_adapt_factors(burn_in, adapt) for "moved" / "did not" and clamps it; the retained chain
+        is plain HMC.  adapt_table = (up, dn) replaces that schedule.  One launch per chunk of iterations (None: one launch).
+        Returns dict(draws [n_keep, n, q] | None, state, logp, grad, acc_count [burn_in + n_keep], row_step [n])."""
+        HM.check_args(step_size, n_leapfrog, adapt)
+        dev = self.device
+        x, y, v = (_f32(t, dev) for t in (x, y, v))
+        x, y = x.reshape(-1), y.reshape(-1)
+        n, total = v.shape[0], int(burn_in) + int(n_keep)
+        up = dn = None
+        if adapt_table is not None or adapt is not None:
+            up, dn = adapt_table if adapt_table is not None else RA.row_adapt_factors(burn_in, float(adapt))
+            up, dn = (_f32(np.asarray(t, dtype=np.float32).reshape(-1), dev) for t in (up, dn))
+            if up.numel() != dn.numel():
+                raise ValueError("hmc_sample: adapt_table = (up, dn) of equal length")
+            if up.numel() == 0:
+                up = dn = None
+        state = torch.empty((n, self.q), device=dev, dtype=torch.float32)
+        logp = torch.empty(n, device=dev, dtype=torch.float32)
+        grad = torch.empty((n, self.q), device=dev, dtype=torch.float32)
+        step = torch.full((n,), float(np.float32(step_size)), device=dev, dtype=torch.float32)
+        acc = torch.zeros(total, device=dev, dtype=torch.int32)
+        draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
+        chunk = total if chunk is None else max(1, int(chunk))
+        for it in range(0, total, chunk):
+            self.hmc_run(x, y, v, state, logp, grad, step, it, min(chunk, total - it), burn_in, n_leapfrog, seed, init=(it == 0),
+                         row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep)
+        return dict(draws=draws, state=state, logp=logp, grad=grad, acc_count=acc, row_step=step)
 
     def encode(self, v):
         v = _f32(v, self.device)

@@ -24,6 +24,7 @@ BNN_NORM_DEFAULT = "fixed"
 
 from .. import _lib, diagnostics, host_rng, parallel
 from .. import row_adapt as row_adapt_mod
+from .. import causal_hmc as hmc_mod
 from ..engine import CausalEngine
 from ..datasets import Gaussian_sampler
 from ..utils import save_data
@@ -58,6 +59,7 @@ def _disc_norm(p):
 
 class CausalBGM(object):
     mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last sampler call that asked for them
+    hmc_row_step_ = None             # per-row HMC step sizes (NumPy, global row order) of the last predict(sampler='hmc') / hmc_sampler call
     mh_row_scale_ = None             # per-row proposal scales (NumPy, global row order) of the last predict / sampler call; None when it ran without row adaptation
 
     def __new__(cls, params, *args, **kwargs):
@@ -520,8 +522,17 @@ class CausalBGM(object):
 
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
-                bs=10000, verbose=1, diagnose_rows=0, row_adapt=False):
+                bs=10000, verbose=1, diagnose_rows=0, row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None,
+                draw_budget_bytes=None):
         """Causal effects with posterior intervals from latent MCMC samples (base.py:573-668).
+
+        ``sampler='hmc'`` (opt-in; ``'mh'`` is the reference's sampler and the default): the latents are sampled by Hamiltonian Monte
+        Carlo with ``n_leapfrog`` steps per transition and a step size per chain that starts from ``step_size`` and adapts during
+        burn-in towards an acceptance rate of 0.75 (causal_hmc.py; None = that module's defaults).  This rank's rows are sampled in
+        blocks whose retained draws fit ``draw_budget_bytes`` (default 2 GiB) and the effects are computed from each block's draws
+        on the device; a chain depends on its own row only, so the block size does not change a row's draws.  ``q_sd`` is not
+        used, ``row_adapt`` and a non-positive ``q_sd`` are refused, ``diagnose_rows`` works.  The steps are left in
+        ``self.hmc_row_step_``.
 
         ``bs`` bounded the host memory of the reference; here all rows are sampled in one launch per
         segment (row-blocked only if the ITE draw matrix would exceed device memory) and the result does
@@ -537,6 +548,10 @@ class CausalBGM(object):
         rank count, and ``diagnose_rows`` works.  The scales are left in ``self.mh_row_scale_``."""
         ra_target = self._row_adapt_target(row_adapt)
         self.mh_row_scale_ = None
+        self.hmc_row_step_ = None
+        hmc = None                       # (step size, leapfrog steps, target acceptance rate) of sampler='hmc'
+        if hmc_mod.check_predict_options(sampler, q_sd, row_adapt):
+            hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         binary = bool(self._p['binary_treatment'])
@@ -574,8 +589,11 @@ class CausalBGM(object):
             max_rows = max(16, int((32 << 30) // (4 * max(1, n_mcmc))))
             if not adaptive:
                 blocks = [(s0, min(s0 + max_rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, max_rows)]
+        if hmc is not None:              # the retained draws of a block are kept: blocks within the draw budget
+            rows = hmc_mod.block_rows(n_mcmc, eng.q, draw_budget_bytes)
+            blocks = [(s0, min(s0 + rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, rows)]
         acc_tail = 0.0
-        row_scale = torch.zeros(n_test, device=dev, dtype=torch.float32) if ra_target is not None else None
+        row_scale = torch.zeros(n_test, device=dev, dtype=torch.float32) if (ra_target is not None or hmc is not None) else None
         if binary:
             res = torch.zeros((3, n_test), device=dev, dtype=torch.float32)     # mean, lower, upper (this rank's rows filled)
         else:
@@ -584,7 +602,18 @@ class CausalBGM(object):
             x = self._dev(data_x[s0:e0]).reshape(-1)
             y = self._dev(data_y[s0:e0]).reshape(-1)
             v = self._dev(data_v[s0:e0])
-            if binary:
+            if hmc is not None:          # draws kept, effects from the draws (engine.effects), accumulated as below
+                out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2])
+                if binary:
+                    ite = eng.effects(x, out["draws"], burn_in, seed, sample_y=sample_y, row_base=s0)          # [n_mcmc, rows]
+                    mean, lo, hi = eng.row_mean_quantiles(ite.t().contiguous(), alpha / 2, 1 - alpha / 2)
+                    res[0, s0:e0], res[1, s0:e0], res[2, s0:e0] = mean, lo, hi
+                else:
+                    adrf = eng.effects(x, out["draws"], burn_in, seed, x_values=x_values, sample_y=sample_y, row_base=s0)
+                    sums += adrf.double() * float(e0 - s0)
+                out["row_scale"] = out["row_step"]
+                del out["draws"]
+            elif binary:
                 out = eng.mh_sample(x, y, v, burn_in, n_mcmc, q_sd, seed, effect=_lib.EFFECT_ITE, sample_y=sample_y,
                                     row_base=s0, adaptive=adaptive, row_adapt=ra_target)
                 mean, lo, hi = eng.row_mean_quantiles(out["ite"], alpha / 2, 1 - alpha / 2)
@@ -598,9 +627,13 @@ class CausalBGM(object):
             acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
         self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
         if row_scale is not None:
-            self.mh_row_scale_ = parallel.all_reduce_sum_(row_scale).cpu().numpy()      # disjoint row sets: the sum is the gather
+            gathered = parallel.all_reduce_sum_(row_scale).cpu().numpy()      # disjoint row sets: the sum is the gather
+            if hmc is not None:
+                self.hmc_row_step_ = gathered
+            else:
+                self.mh_row_scale_ = gathered
         if diagnose_rows > 0:
-            self._diagnose_rows(data, diagnose_rows, burn_in, n_mcmc, q_sd, seed, row_adapt=ra_target)
+            self._diagnose_rows(data, diagnose_rows, burn_in, n_mcmc, q_sd, seed, row_adapt=ra_target, hmc=hmc)
         if binary:
             parallel.all_reduce_sum_(res)                         # disjoint row sets: the sum is the gather
             res = res.cpu().numpy()
@@ -639,6 +672,12 @@ class CausalBGM(object):
             row_adapt_mod.check_supported(type(self).__name__, self._p)
         return target
 
+    def _refuse_hmc(self, sampler, q_sd, row_adapt, step_size, n_leapfrog):
+        """predict of the subclasses without an HMC path: sampler='hmc' raises the ValueError that names what is in the way."""
+        if hmc_mod.check_predict_options(sampler, q_sd, row_adapt):
+            hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
+            raise ValueError("sampler='hmc' is not available for %s" % type(self).__name__)
+
     def _adaptive_sd_target(self, adaptive_sd, target_acceptance_rate):
         """adaptive_sd of metropolis_hastings_sampler -> None (None / bool: the fixed or the block-wide scale) or, for 'row', the
         target acceptance rate of the per-chain scale; ValueError for another string or where that scale does not exist."""
@@ -649,7 +688,7 @@ class CausalBGM(object):
         row_adapt_mod.check_supported(type(self).__name__, self._p)
         return self._row_adapt_target(target_acceptance_rate)
 
-    def _diagnose_rows(self, data, k, burn_in, n_mcmc, q_sd, seed, row_adapt=None):
+    def _diagnose_rows(self, data, k, burn_in, n_mcmc, q_sd, seed, row_adapt=None, hmc=None):
         """Re-run the chains of k rows of predict's panel with their draws kept (the Philox stream is keyed by the global row, so
         with the same seed and row_base these are the chains predict ran) and store their diagnostics.  Every rank computes the
         same windows; no collectives and no new seed."""
@@ -657,8 +696,11 @@ class CausalBGM(object):
         eng = self.engine
         parts, rows = [], []
         for (s0, e0) in self._diagnose_windows(len(data_x), k):
-            out = eng.mh_sample(self._dev(data_x[s0:e0]).reshape(-1), self._dev(data_y[s0:e0]).reshape(-1), self._dev(data_v[s0:e0]),
-                                burn_in, n_mcmc, q_sd, seed, want_draws=True, row_base=s0, row_adapt=row_adapt)
+            xyv = (self._dev(data_x[s0:e0]).reshape(-1), self._dev(data_y[s0:e0]).reshape(-1), self._dev(data_v[s0:e0]))
+            if hmc is not None:
+                out = eng.hmc_sample(*xyv, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2])
+            else:
+                out = eng.mh_sample(*xyv, burn_in, n_mcmc, q_sd, seed, want_draws=True, row_base=s0, row_adapt=row_adapt)
             parts.append(out["draws"])
             rows.append(np.arange(s0, e0))
         d = diagnostics.chain_diagnostics(torch.cat(parts, dim=1))
@@ -700,6 +742,26 @@ class CausalBGM(object):
         print(f"Final MCMC Acceptance Rate: {self.last_acceptance_rate:.4f}")
         if diagnostics:
             self._store_diagnostics(out["draws"], "metropolis_hastings_sampler")
+        return out["draws"].cpu().numpy()
+
+    def hmc_sampler(self, data, n_keep=3000, burn_in=5000, step_size=hmc_mod.DEFAULT_STEP_SIZE, n_leapfrog=hmc_mod.DEFAULT_N_LEAPFROG,
+                    target_acceptance_rate=hmc_mod.DEFAULT_TARGET, adapt=True, diagnostics=False):
+        """Posterior samples of Z, shape (n_keep, n, q), by Hamiltonian Monte Carlo on get_log_posterior: ``n_leapfrog`` steps per
+        transition, identity mass, one chain per row.  ``adapt=True``: every chain adapts a step size of its own during burn-in
+        towards ``target_acceptance_rate``, starting from ``step_size`` (causal_hmc.py); the retained chain is plain HMC.  The steps
+        are left in ``self.hmc_row_step_``.  diagnostics=True: as in metropolis_hastings_sampler."""
+        step_size, n_leapfrog, target = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, target_acceptance_rate, adapt)
+        self.hmc_row_step_ = None
+        data_x, data_y, data_v = data
+        out = self.engine.hmc_sample(self._dev(data_x).reshape(-1), self._dev(data_y).reshape(-1), self._dev(data_v), burn_in, n_keep,
+                                     step_size, n_leapfrog, self._next_seed(), want_draws=True, adapt=target)
+        self.hmc_row_step_ = out["row_step"].cpu().numpy()
+        tot = burn_in + n_keep
+        w = min(100, tot)
+        self.last_acceptance_rate = float(out["acc_count"][tot - w:].sum().item()) / (max(1, w) * len(data_x))
+        print(f"Final MCMC Acceptance Rate: {self.last_acceptance_rate:.4f}")
+        if diagnostics:
+            self._store_diagnostics(out["draws"], "hmc_sampler")
         return out["draws"].cpu().numpy()
 
     def _store_diagnostics(self, draws_dev, where):

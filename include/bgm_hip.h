@@ -362,6 +362,32 @@ BGM_API int bgm_causal_effects(bgm_handle *h, const float *x_dev, const float *d
                        int32_t n_keep, int32_t burn_in, uint64_t seed, int32_t sample_y, const float *x_values_dev,
                        int32_t n_doses, float *adrf_partial_dev, float *ite_dev, void *stream);
 
+/* log p(z | x, y, v) + const and its gradient dlogp/dz for n rows: out_logp_dev [n], out_grad_dev [n x q].  g's Gaussian term is
+ * evaluated in the anchored Gram form of the MH kernels on every shape (csrc/causal_hmc_kernels.h).  Exists for the fp32
+ * LDS-resident shapes with the standard-normal prior; the conditional prior, split precision, the general-width engine, shapes
+ * outside the LDS-resident families and the Bayesian networks answer BGM_E_UNSUPPORTED.
+ * replaces: get_log_posterior, causalbgm/base.py:765-817, together with the tf.GradientTape gradient with respect to z that
+ * update_latent_variable_sgd (:246-302) takes of the same expression. */
+BGM_API int bgm_causal_logpost_grad(bgm_handle *h, const float *x_dev, const float *y_dev, const float *v_dev, const float *z_dev,
+                                    int64_t n, float *out_logp_dev, float *out_grad_dev, void *stream);
+
+/* Hamiltonian Monte Carlo on the latent posterior of CausalBGM, one chain per row, identity mass, n_leapfrog steps per transition,
+ * iterations [it_begin, it_begin + n_iters) in one persistent launch.  state_dev [n x q], logp_dev [n], grad_dev [n x q] and
+ * step_dev [n] (the step size of every chain) are in / out and carry a run from one call to the next: a run cut into segments at
+ * any iteration is bit-identical to one call.  init = 1: the state is drawn (the TAG_INIT stream bgm_causal_mh_run starts from) and
+ * logp / grad are computed; step_dev is always read.  up_dev / dn_dev [n_table]: after the accept decision of iteration
+ * it < n_table a chain's step is multiplied by up_dev[it] (it moved) or dn_dev[it] (it did not) and clamped to [s_min, s_max]
+ * (one fp32 multiply, the table of bgm_causal_set_row_scale); up_dev = NULL: the steps stay as given.  acc_count_dev [>= it_begin +
+ * n_iters] (+=) or NULL; draws_dev [n_keep x n x q] receives the states of iterations >= burn_in, or NULL.  Momentum: Philox tag 4,
+ * accept uniform: tag 5, as bgm_bgm_hmc_run.  Refuses what bgm_causal_logpost_grad refuses.
+ * replaces: nothing in causalbgm/base.py (its latent sampler is metropolis_hastings_sampler, :820-904); the transition is the
+ * tfp.mcmc.HamiltonianMonteCarlo of bgm/base.py:709-830 on get_log_posterior, causalbgm/base.py:765-817 (opt-in). */
+BGM_API int bgm_causal_hmc_run(bgm_handle *h, const float *x_dev, const float *y_dev, const float *v_dev, int64_t n, int64_t row_base,
+                               float *state_dev, float *logp_dev, float *grad_dev, float *step_dev, const float *up_dev,
+                               const float *dn_dev, int32_t n_table, float s_min, float s_max, int32_t init, int32_t it_begin,
+                               int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed, uint32_t *acc_count_dev,
+                               float *draws_dev, int32_t n_keep, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * CausalBGM.fit step functions (iterative theta / Z updates).
  * replaces: update_g_net :156-180, update_h_net :183-214, update_f_net :217-243,
