@@ -294,3 +294,51 @@ def test_unsupported_paths_refuse(torch):
     for bad in (dict(step_size=0.0), dict(n_leapfrog=0), dict(adapt=1.0)):
         with pytest.raises(ValueError):
             eng.hmc_sample(x, y, v, 5, 5, **dict(dict(step_size=0.1, n_leapfrog=2, seed=7), **bad))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. the second trip of the tile loop: more 16-row tiles than wave slots (the grid is capped at one workgroup per CU)
+# ---------------------------------------------------------------------------------------------------------------------
+def _two_trip_panel(torch, seed):
+    """the smallest model and n = 16 * waves * n_cus + 17 rows: every wave slot takes one tile, the first of them a second one, the last
+    tile is ragged.  Returns (engine, model, x, y, v, n, wave slots)."""
+    m = _model(seed, [1, 1, 1, 7], 20)
+    eng = _engine(m)
+    n_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    waves = int(eng.mh_info(16).waves_per_block)
+    n = 16 * waves * n_cus + 17
+    slots = eng.mh_slots(n)                                   # grid * waves of bgm_causal_grid: the grid of the HMC kernels too
+    assert waves == 8 and slots == waves * n_cus
+    assert (n + 15) // 16 > slots                             # more tiles than wave slots: the loop takes a second trip
+    x, y, v = _data(n, 20, seed + 1)
+    return eng, m, x, y, v, n, slots
+
+
+def test_logpost_grad_beyond_one_trip_of_the_tile_loop(torch):
+    eng, m, x, y, v, n, slots = _two_trip_panel(torch, 61)
+    z = np.random.RandomState(63).randn(n, 10).astype(np.float32)
+    lp, gr = eng.logpost_grad(x.ravel(), y.ravel(), v, z)
+    assert lp.shape == (n,) and gr.shape == (n, 10)
+    _check_logp_grad(lp.cpu().numpy(), gr.cpu().numpy(), *_ref64(m, x, y, v, z), "p = 20, n = %d (%d tiles, %d wave slots)" % (n, (n + 15) // 16, slots))
+    for s, e in ((0, 64), (n - 64, n)):                       # first-trip rows and second-trip rows (ragged tile included) alone
+        assert (e - s + 15) // 16 <= slots
+        lp1, gr1 = eng.logpost_grad(x[s:e].ravel(), y[s:e].ravel(), v[s:e], z[s:e])
+        assert torch.equal(lp[s:e], lp1) and torch.equal(gr[s:e], gr1), (s, e)
+
+
+def test_hmc_beyond_one_trip_of_the_tile_loop(torch):
+    """The full run against three runs over a partition of the rows, each within one trip, each with its own row_base, the first
+    boundary inside a tile: bit for bit (test_bit_identities_and_cached_values establishes the piecewise identity at small n)."""
+    burn, keep, L, step0, seed = 3, 2, 2, 0.1, 4242
+    eng, m, x, y, v, n, slots = _two_trip_panel(torch, 65)
+    kw = dict(want_draws=True, adapt=TARGET)
+    full = eng.hmc_sample(x, y, v, burn, keep, step0, L, seed, **kw)
+    cuts = [0, n // 3 // 16 * 16 + 7, 2 * n // 3 // 16 * 16, n]
+    assert cuts[1] % 16 != 0 and all((e - s + 15) // 16 <= slots for s, e in zip(cuts[:-1], cuts[1:]))
+    parts = [eng.hmc_sample(x[s:e], y[s:e], v[s:e], burn, keep, step0, L, seed, row_base=s, **kw) for s, e in zip(cuts[:-1], cuts[1:])]
+    assert torch.equal(full["draws"], torch.cat([p["draws"] for p in parts], dim=1))
+    for k in ("state", "logp", "grad", "row_step"):
+        assert torch.equal(full[k], torch.cat([p[k] for p in parts], dim=0)), k
+    assert torch.equal(full["acc_count"], sum(p["acc_count"] for p in parts))
+    assert bool(torch.isfinite(full["draws"]).all()) and 0 < int(full["acc_count"].sum()) < (burn + keep) * n
+    assert float(full["row_step"].min()) < float(full["row_step"].max())
