@@ -3,13 +3,25 @@
 Every chain (one per row) runs Hamiltonian Monte Carlo with identity mass on log p(z | x, y, v) and carries a step size of its own,
 adapted during burn-in by the table of row_adapt.py (one float32 multiply after each accept decision, towards the target acceptance
 rate) and frozen afterwards.  The kernels are csrc/causal_hmc_kernels.h.  Nothing here touches the GPU.
+
+``mass='diag'`` (opt-in): a chain also carries a scale per coordinate, s in R^q, the metric M^-1 = diag(s^2) in the scaled form
+(the step of coordinate i is eps s_i; momentum and kinetic energy are those of identity mass).  s is estimated by the chain alone
+from its own burn-in draws, in the windows of ``mass_windows``, and frozen afterwards; the step table restarts its Robbins-Monro gain
+at every change of the metric (``mass_schedule``).
 """
+import numpy as np
+
 from . import row_adapt as RA
 
 DEFAULT_TARGET = 0.75             # the target of the project's other HMC (tfp SimpleStepSizeAdaptation, bgm/base.py:709-830)
 DEFAULT_STEP_SIZE = 0.1           # provisional: see README, "Results (HMC latent sampler)"
 DEFAULT_N_LEAPFROG = 5
 DRAW_BUDGET_BYTES = 2 << 30       # predict(sampler='hmc'): retained draws of one row block
+MASS_INIT_BUFFER, MASS_BASE_WINDOW, MASS_TERM_BUFFER = 75, 25, 50      # Stan's warm-up windows (init_buffer, base_window, term_buffer)
+MASS_MIN_BURN_IN = 20             # below this no window is long enough to estimate a variance from
+MASS_SHRINK = 5.0                 # weight (in draws) of the shrinkage target in the regularised variances (Stan's 5)
+MASS_SHRINK_TARGET = 1e-3         # the target, in units of the chain's mean variance (Stan's 1e-3 presumes unit scale)
+MASS_S_MIN, MASS_S_MAX = 0.05, 20.0      # clamp of a coordinate's scale relative to the chain's geometric mean
 
 
 def check_args(step_size, n_leapfrog, target):
@@ -71,3 +83,86 @@ def block_rows(n_keep, q, budget_bytes=None):
         raise ValueError("draw_budget_bytes must be positive; got %r" % (budget_bytes,))
     rows = budget // (4 * max(1, int(n_keep)) * max(1, int(q)))
     return max(16, rows // 16 * 16)
+
+
+def check_mass(mass, hmc=True, adapt=True, burn_in=None):
+    """mass of predict / hmc_sampler -> None ('identity' or None) or 'diag'; ValueError for anything else, for 'diag' without the HMC
+    sampler, without step adaptation, or with a burn-in too short for one window."""
+    if mass is None or mass == "identity":
+        return None
+    if mass != "diag":
+        raise ValueError("mass must be 'identity' or 'diag'; got %r" % (mass,))
+    if not hmc:
+        raise ValueError("mass='diag' belongs to sampler='hmc': the MH sampler has no metric (its per-chain scale is row_adapt)")
+    if adapt is None or adapt is False:
+        raise ValueError("mass='diag' needs adapt=True: a change of the metric without re-adapting the step leaves the step of the old metric")
+    if burn_in is not None and not mass_windows(burn_in)[1]:
+        raise ValueError("mass='diag' needs burn_in >= %d (no estimation window fits); got burn_in = %r" % (MASS_MIN_BURN_IN, burn_in))
+    return "diag"
+
+
+def mass_windows(burn_in):
+    """(start, [end_1, ..., end_k]): the metric is estimated from the draws of [start, end_1), [end_1, end_2), ... and updated at
+    every end.  An initial buffer of 75 iterations, windows of 25, 50, 100, ... and a terminal buffer of 50; a window whose successor
+    would not fit before the terminal buffer is stretched to it.  When 75 + 25 + 50 > burn_in: 15 % / 75 % / 10 % of burn_in with one
+    window.  burn_in < 20: no windows."""
+    burn_in = int(burn_in)
+    if burn_in < MASS_MIN_BURN_IN:
+        return max(burn_in, 0), []
+    if MASS_INIT_BUFFER + MASS_BASE_WINDOW + MASS_TERM_BUFFER > burn_in:
+        return burn_in * 15 // 100, [burn_in - burn_in * 10 // 100]
+    start, last = MASS_INIT_BUFFER, burn_in - MASS_TERM_BUFFER
+    ends, size, end = [], MASS_BASE_WINDOW, MASS_INIT_BUFFER
+    while end < last:
+        end += size
+        size *= 2
+        if end + size > last:
+            end = last
+        ends.append(end)
+    return start, ends
+
+
+def check_windows(windows, burn_in):
+    """(start, ends) -> (int, [int]) with 1 <= start < end_1 < ... < end_k <= burn_in; ValueError otherwise."""
+    try:
+        start, ends = int(windows[0]), [int(e) for e in windows[1]]
+    except (TypeError, ValueError, IndexError):
+        raise ValueError("mass_windows must be (start, [end_1, ..., end_k]); got %r" % (windows,))
+    marks = [start] + ends
+    if not ends or start < 1 or ends[-1] > int(burn_in) or any(b <= a for a, b in zip(marks[:-1], marks[1:])):
+        raise ValueError("mass_windows needs 1 <= start < end_1 < ... < end_k <= burn_in (= %d); got %r" % (int(burn_in), windows))
+    return start, ends
+
+
+def mass_schedule(burn_in, target, windows=None):
+    """((start, ends), (up, dn)): the windows (``windows`` or mass_windows(burn_in)) and the step table of the whole burn-in, the
+    concatenation of row_adapt_factors(len, target) over [0, start), every window and [end_k, burn_in): the Robbins-Monro gain
+    restarts whenever the metric changes.  ValueError naming burn_in when no window fits."""
+    burn_in = int(burn_in)
+    if windows is None:
+        windows = mass_windows(burn_in)
+        if not windows[1]:
+            raise ValueError("mass='diag' needs burn_in >= %d (no estimation window fits); got burn_in = %r" % (MASS_MIN_BURN_IN, burn_in))
+    start, ends = check_windows(windows, burn_in)
+    marks = [0, start] + ends + [burn_in]
+    parts = [RA.row_adapt_factors(b - a, target) for a, b in zip(marks[:-1], marks[1:])]
+    return (start, ends), (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
+
+
+def mass_update(W, state, scale, ref, s1, s2):
+    """The update of a chain's metric at the end of a window of W draws, as the device does it (csrc/causal_hmc_kernels.h,
+    causal_hmc_mass_update_kernel), in NumPy float64 on [n x q] arrays -> (scale float32, ref, s1, s2).  With d = z - ref summed
+    into s1 and d^2 into s2: var_i = max(s2_i / W - (s1_i / W)^2, 0), shrunk towards 1e-3 of the chain's mean variance vbar with the
+    weight of 5 draws, var_r_i = (W var_i + 5e-3 vbar) / (W + 5); s_i = sqrt(var_i) over the geometric mean of the chain, clamped to [0.05, 20]: only the shape, the step keeps the
+    scale.  A chain whose vbar is zero or not finite keeps its scales; W = 0 only resets.  Then ref = state, s1 = s2 = 0."""
+    scale = np.array(scale, np.float32)
+    if W > 0:
+        with np.errstate(all="ignore"):
+            mean = np.asarray(s1, np.float64) / W
+            var = np.maximum(np.asarray(s2, np.float64) / W - mean * mean, 0.0)
+            vbar = var.mean(axis=1, keepdims=True)
+            t = np.sqrt((W * var + MASS_SHRINK * MASS_SHRINK_TARGET * vbar) / (W + MASS_SHRINK))
+            new = np.clip(t / np.exp(np.log(t).mean(axis=1, keepdims=True)), MASS_S_MIN, MASS_S_MAX).astype(np.float32)
+        ok = (np.isfinite(vbar) & (vbar > 0))[:, 0]
+        scale[ok] = new[ok]
+    return scale, np.array(state, np.float32), np.zeros_like(scale), np.zeros_like(scale)

@@ -8,17 +8,11 @@
 #include <vector>
 
 #include "causal_launch.h"
-#include "causal_hmc_kernels.h"
+#include "causal_hmc_host.h"
 #include "bnf_det_host.h"
 #include "gx_host.h"
 
 namespace {
-
-struct HmcState {
-  float *blob_dev = nullptr;
-  size_t blob_cap = 0;
-  CausalHmcMeta m{};
-};
 
 // element (input row rho, output column o) of a layer packed by pack_layer (bgm_host.h) with K_ROWS input rows and NT output tiles
 float packed_at(const std::vector<float> &b, int off, int K_ROWS, int NT, int rho, int o) {
@@ -46,8 +40,7 @@ const char *refused_path(const bgm_handle *h) {
 // the Gram blob of the handle and this panel's 2 u, c; then the dual-access copy, rebuilt whenever the Gram copy was
 int hmc_prepare(bgm_handle *h, const float *v, int64_t n, hipStream_t stream, HmcState *&st) {
   if (int rc = bgm_causal_gram_prepare(h, v, n, stream)) return rc;
-  if (!h->hmc_state) h->hmc_state = new HmcState();
-  st = static_cast<HmcState *>(h->hmc_state);
+  st = bgm_causal_hmc_state(h);
   if (h->hmc_valid) return BGM_OK;
   const CausalMeta &gm = h->gmeta;
   const int KT1 = h->KT1, KR1 = 16 * KT1;
@@ -90,13 +83,13 @@ int hmc_prepare(bgm_handle *h, const float *v, int64_t n, hipStream_t stream, Hm
   return BGM_OK;
 }
 
-int check_handle(bgm_handle *h, const char *who) {
+}  // namespace
+
+int bgm_causal_hmc_check(bgm_handle *h, const char *who) {
   if (!h || !h->configured) { bgm_set_error(std::string(who) + ": handle not configured"); return BGM_E_STATE; }
   if (const char *path = refused_path(h)) { bgm_set_error(std::string(who) + ": the gradient / HMC kernels do not exist for " + path); return BGM_E_UNSUPPORTED; }
   return BGM_OK;
 }
-
-}  // namespace
 
 void bgm_causal_hmc_free(bgm_handle *h) {
   HmcState *st = static_cast<HmcState *>(h->hmc_state);
@@ -109,7 +102,7 @@ void bgm_causal_hmc_free(bgm_handle *h) {
 
 extern "C" int bgm_causal_logpost_grad(bgm_handle *h, const float *x, const float *y, const float *v, const float *z, int64_t n,
                                        float *out_logp, float *out_grad, void *stream_) {
-  if (int rc = check_handle(h, "bgm_causal_logpost_grad")) return rc;
+  if (int rc = bgm_causal_hmc_check(h, "bgm_causal_logpost_grad")) return rc;
   if (n <= 0) return BGM_OK;
   if (!x || !y || !v || !z || !out_logp || !out_grad) { bgm_set_error("bgm_causal_logpost_grad: NULL pointer"); return BGM_E_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
@@ -128,7 +121,7 @@ extern "C" int bgm_causal_hmc_run(bgm_handle *h, const float *x, const float *y,
                                   float *logp, float *grad, float *step, const float *up, const float *dn, int32_t n_table, float s_min,
                                   float s_max, int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog,
                                   uint64_t seed, uint32_t *acc_count, float *draws, int32_t n_keep, void *stream_) {
-  if (int rc = check_handle(h, "bgm_causal_hmc_run")) return rc;
+  if (int rc = bgm_causal_hmc_check(h, "bgm_causal_hmc_run")) return rc;
   if (n <= 0 || n_iters <= 0) return BGM_OK;
   if (!x || !y || !v || !state || !logp || !grad || !step) { bgm_set_error("bgm_causal_hmc_run: NULL data pointer"); return BGM_E_INVALID; }
   if (n_leapfrog < 1) { bgm_set_error("bgm_causal_hmc_run: n_leapfrog must be >= 1"); return BGM_E_INVALID; }
@@ -151,6 +144,7 @@ extern "C" int bgm_causal_hmc_run(bgm_handle *h, const float *x, const float *y,
   ka.k0 = (unsigned)(seed & 0xFFFFFFFFull); ka.k1 = (unsigned)(seed >> 32);
   ka.acc_count = acc_count; ka.draws = draws; ka.m = st->m;
   const int grid = bgm_causal_grid(h, n, 1);
+  if (st->mass.scale) return bgm_causal_hmc_mass_launch(h, ka, st->mass, grid, st->m.total * 4, stream);      // bgm_causal_hmc_set_mass
   return bgm_causal_dispatch(h, "HMC kernel", [&](auto s) {
     using S = decltype(s);
     return bgm_causal_launch(causal_hmc_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, st->m.total * 4, stream, ka);

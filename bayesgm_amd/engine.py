@@ -136,15 +136,43 @@ class CausalEngine(object):
                                                int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws),
                                                int(n_keep), self._stream()), "bgm_causal_hmc_run")
 
+    def set_hmc_mass(self, scale=None, ref=None, s1=None, s2=None, accumulate=False):
+        """Diagonal metric of the hmc_run calls made afterwards (bgm_causal_hmc_set_mass): scale float32 [n x q] (device), the
+        per-coordinate factors of every chain's step, aligned with the rows of the call.  accumulate: those calls also add
+        z - ref and its square into s1 / s2 [n x q] after every decision (the moments hmc_mass_update turns into scales).
+        scale = None: back to identity mass."""
+        self._hmc_mass_keep = (scale, ref, s1, s2)          # keep the buffers alive while set
+        _lib.check(self.lib.bgm_causal_hmc_set_mass(self.h, _ptr(scale), _ptr(ref), _ptr(s1), _ptr(s2), int(bool(accumulate))),
+                   "bgm_causal_hmc_set_mass")
+
+    def hmc_mass_update(self, n_draws, state, scale, ref, s1, s2):
+        """End of an estimation window of n_draws iterations (bgm_causal_hmc_mass_update): scale from the moments (causal_hmc.py,
+        mass_update), then ref = state and s1 = s2 = 0.  n_draws = 0 only resets."""
+        _lib.check(self.lib.bgm_causal_hmc_mass_update(self.h, state.shape[0], int(n_draws), _ptr(state), _ptr(scale), _ptr(ref), _ptr(s1),
+                                                       _ptr(s2), self._stream()), "bgm_causal_hmc_mass_update")
+
     def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
-                   adapt=HM.DEFAULT_TARGET, adapt_table=None):
+                   adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None):
         """HMC over the latent posterior of every row, one chain per row with a step size of its own.
 
         adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
         step by the factor of row_adapt.row_adapt_factors(burn_in, adapt) for "moved" / "did not" and clamps it; the retained chain
         is plain HMC.  adapt_table = (up, dn) replaces that schedule.  One launch per chunk of iterations (None: one launch).
-        Returns dict(draws [n_keep, n, q] | None, state, logp, grad, acc_count [burn_in + n_keep], row_step [n])."""
+
+        mass = 'diag': every chain estimates a scale per coordinate from its own burn-in draws in the windows of
+        causal_hmc.mass_windows(burn_in) (mass_windows = (start, ends) replaces them) and keeps it afterwards; the step table is
+        causal_hmc.mass_schedule's.  mass_scale = tensor [n x q]: that metric, frozen, no estimation.  Windows are launch
+        boundaries; cuts by chunk inside them change nothing.
+        Returns dict(draws [n_keep, n, q] | None, state, logp, grad, acc_count [burn_in + n_keep], row_step [n]) and, with a metric,
+        mass_scale [n x q]."""
         HM.check_args(step_size, n_leapfrog, adapt)
+        diag = HM.check_mass(mass, True, adapt if adapt_table is None else True) is not None
+        if diag and mass_scale is not None:
+            raise ValueError("hmc_sample: mass='diag' estimates the metric; mass_scale gives a frozen one")
+        start, ends = None, []
+        if diag:
+            (start, ends), table = HM.mass_schedule(burn_in, float(adapt) if adapt is not None else HM.DEFAULT_TARGET, mass_windows)
+            adapt_table = table if adapt_table is None else adapt_table
         dev = self.device
         x, y, v = (_f32(t, dev) for t in (x, y, v))
         x, y = x.reshape(-1), y.reshape(-1)
@@ -164,10 +192,35 @@ class CausalEngine(object):
         acc = torch.zeros(total, device=dev, dtype=torch.int32)
         draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
         chunk = total if chunk is None else max(1, int(chunk))
-        for it in range(0, total, chunk):
-            self.hmc_run(x, y, v, state, logp, grad, step, it, min(chunk, total - it), burn_in, n_leapfrog, seed, init=(it == 0),
-                         row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep)
-        return dict(draws=draws, state=state, logp=logp, grad=grad, acc_count=acc, row_step=step)
+        scale = moments = None
+        if diag:
+            scale = torch.ones((n, self.q), device=dev, dtype=torch.float32)
+            moments = [torch.zeros((n, self.q), device=dev, dtype=torch.float32) for _ in range(3)]      # ref, s1, s2
+        elif mass_scale is not None:
+            scale = _f32(mass_scale, dev).clone()
+            if tuple(scale.shape) != (n, self.q):
+                raise ValueError("hmc_sample: mass_scale must be [n x q] = %r; got %r" % ((n, self.q), tuple(scale.shape)))
+        marks = [start] + ends if diag else []
+        try:
+            if scale is not None:
+                self.set_hmc_mass(scale)
+            it = 0
+            while it < total:
+                stop = min([it + chunk, total] + [b for b in marks if b > it])
+                self.hmc_run(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0),
+                             row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep)
+                if stop in marks:      # a window's edge: the first one only sets the reference point and turns the moments on
+                    k = marks.index(stop)
+                    self.hmc_mass_update(0 if k == 0 else stop - marks[k - 1], state, scale, *moments)
+                    self.set_hmc_mass(scale, *moments, accumulate=(k < len(marks) - 1))
+                it = stop
+        finally:
+            if scale is not None:
+                self.set_hmc_mass(None)
+        out = dict(draws=draws, state=state, logp=logp, grad=grad, acc_count=acc, row_step=step)
+        if scale is not None:
+            out["mass_scale"] = scale
+        return out
 
     def encode(self, v):
         v = _f32(v, self.device)

@@ -60,6 +60,7 @@ def _disc_norm(p):
 class CausalBGM(object):
     mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last sampler call that asked for them
     hmc_row_step_ = None             # per-row HMC step sizes (NumPy, global row order) of the last predict(sampler='hmc') / hmc_sampler call
+    hmc_row_mass_ = None             # per-row, per-coordinate HMC metric scales [n, q] (NumPy, global row order) of the last mass='diag' call; None otherwise
     mh_row_scale_ = None             # per-row proposal scales (NumPy, global row order) of the last predict / sampler call; None when it ran without row adaptation
 
     def __new__(cls, params, *args, **kwargs):
@@ -523,7 +524,7 @@ class CausalBGM(object):
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
                 bs=10000, verbose=1, diagnose_rows=0, row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None,
-                draw_budget_bytes=None):
+                draw_budget_bytes=None, mass='identity'):
         """Causal effects with posterior intervals from latent MCMC samples (base.py:573-668).
 
         ``sampler='hmc'`` (opt-in; ``'mh'`` is the reference's sampler and the default): the latents are sampled by Hamiltonian Monte
@@ -532,7 +533,9 @@ class CausalBGM(object):
         blocks whose retained draws fit ``draw_budget_bytes`` (default 2 GiB) and the effects are computed from each block's draws
         on the device; a chain depends on its own row only, so the block size does not change a row's draws.  ``q_sd`` is not
         used, ``row_adapt`` and a non-positive ``q_sd`` are refused, ``diagnose_rows`` works.  The steps are left in
-        ``self.hmc_row_step_``.
+        ``self.hmc_row_step_``.  ``mass='diag'`` (with ``sampler='hmc'``): every chain also estimates a scale per latent coordinate
+        from its own burn-in draws (a diagonal metric, causal_hmc.py) and keeps it for the retained draws; the scales are left in
+        ``self.hmc_row_mass_`` [n, q].
 
         ``bs`` bounded the host memory of the reference; here all rows are sampled in one launch per
         segment (row-blocked only if the ITE draw matrix would exceed device memory) and the result does
@@ -549,9 +552,13 @@ class CausalBGM(object):
         ra_target = self._row_adapt_target(row_adapt)
         self.mh_row_scale_ = None
         self.hmc_row_step_ = None
-        hmc = None                       # (step size, leapfrog steps, target acceptance rate) of sampler='hmc'
+        self.hmc_row_mass_ = None
+        hmc = None                       # (step size, leapfrog steps, target acceptance rate, mass) of sampler='hmc'
         if hmc_mod.check_predict_options(sampler, q_sd, row_adapt):
             hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
+        mass = hmc_mod.check_mass(mass, hmc is not None, True, burn_in)
+        if hmc is not None:
+            hmc = hmc + (mass,)
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         binary = bool(self._p['binary_treatment'])
@@ -594,6 +601,7 @@ class CausalBGM(object):
             blocks = [(s0, min(s0 + rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, rows)]
         acc_tail = 0.0
         row_scale = torch.zeros(n_test, device=dev, dtype=torch.float32) if (ra_target is not None or hmc is not None) else None
+        row_mass = torch.zeros((n_test, eng.q), device=dev, dtype=torch.float32) if mass is not None else None
         if binary:
             res = torch.zeros((3, n_test), device=dev, dtype=torch.float32)     # mean, lower, upper (this rank's rows filled)
         else:
@@ -603,7 +611,9 @@ class CausalBGM(object):
             y = self._dev(data_y[s0:e0]).reshape(-1)
             v = self._dev(data_v[s0:e0])
             if hmc is not None:          # draws kept, effects from the draws (engine.effects), accumulated as below
-                out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2])
+                out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2], mass=hmc[3])
+                if row_mass is not None:
+                    row_mass[s0:e0] = out["mass_scale"]
                 if binary:
                     ite = eng.effects(x, out["draws"], burn_in, seed, sample_y=sample_y, row_base=s0)          # [n_mcmc, rows]
                     mean, lo, hi = eng.row_mean_quantiles(ite.t().contiguous(), alpha / 2, 1 - alpha / 2)
@@ -630,6 +640,8 @@ class CausalBGM(object):
             gathered = parallel.all_reduce_sum_(row_scale).cpu().numpy()      # disjoint row sets: the sum is the gather
             if hmc is not None:
                 self.hmc_row_step_ = gathered
+                if row_mass is not None:
+                    self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
             else:
                 self.mh_row_scale_ = gathered
         if diagnose_rows > 0:
@@ -672,11 +684,13 @@ class CausalBGM(object):
             row_adapt_mod.check_supported(type(self).__name__, self._p)
         return target
 
-    def _refuse_hmc(self, sampler, q_sd, row_adapt, step_size, n_leapfrog):
-        """predict of the subclasses without an HMC path: sampler='hmc' raises the ValueError that names what is in the way."""
+    def _refuse_hmc(self, sampler, q_sd, row_adapt, step_size, n_leapfrog, mass='identity'):
+        """predict of the subclasses without an HMC path: sampler='hmc' raises the ValueError that names what is in the way (and so
+        does a mass that belongs to it)."""
         if hmc_mod.check_predict_options(sampler, q_sd, row_adapt):
             hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
             raise ValueError("sampler='hmc' is not available for %s" % type(self).__name__)
+        hmc_mod.check_mass(mass, False)
 
     def _adaptive_sd_target(self, adaptive_sd, target_acceptance_rate):
         """adaptive_sd of metropolis_hastings_sampler -> None (None / bool: the fixed or the block-wide scale) or, for 'row', the
@@ -698,7 +712,7 @@ class CausalBGM(object):
         for (s0, e0) in self._diagnose_windows(len(data_x), k):
             xyv = (self._dev(data_x[s0:e0]).reshape(-1), self._dev(data_y[s0:e0]).reshape(-1), self._dev(data_v[s0:e0]))
             if hmc is not None:
-                out = eng.hmc_sample(*xyv, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2])
+                out = eng.hmc_sample(*xyv, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2], mass=hmc[3])
             else:
                 out = eng.mh_sample(*xyv, burn_in, n_mcmc, q_sd, seed, want_draws=True, row_base=s0, row_adapt=row_adapt)
             parts.append(out["draws"])
@@ -745,17 +759,23 @@ class CausalBGM(object):
         return out["draws"].cpu().numpy()
 
     def hmc_sampler(self, data, n_keep=3000, burn_in=5000, step_size=hmc_mod.DEFAULT_STEP_SIZE, n_leapfrog=hmc_mod.DEFAULT_N_LEAPFROG,
-                    target_acceptance_rate=hmc_mod.DEFAULT_TARGET, adapt=True, diagnostics=False):
+                    target_acceptance_rate=hmc_mod.DEFAULT_TARGET, adapt=True, diagnostics=False, mass='identity'):
         """Posterior samples of Z, shape (n_keep, n, q), by Hamiltonian Monte Carlo on get_log_posterior: ``n_leapfrog`` steps per
         transition, identity mass, one chain per row.  ``adapt=True``: every chain adapts a step size of its own during burn-in
         towards ``target_acceptance_rate``, starting from ``step_size`` (causal_hmc.py); the retained chain is plain HMC.  The steps
-        are left in ``self.hmc_row_step_``.  diagnostics=True: as in metropolis_hastings_sampler."""
+        are left in ``self.hmc_row_step_``.  ``mass='diag'`` (needs ``adapt=True``): every chain also estimates a scale per latent
+        coordinate from its own burn-in draws, in windows, and keeps it afterwards (a diagonal metric, causal_hmc.py); the scales
+        are left in ``self.hmc_row_mass_`` [n, q].  diagnostics=True: as in metropolis_hastings_sampler."""
         step_size, n_leapfrog, target = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, target_acceptance_rate, adapt)
+        mass = hmc_mod.check_mass(mass, True, adapt, burn_in)
         self.hmc_row_step_ = None
+        self.hmc_row_mass_ = None
         data_x, data_y, data_v = data
         out = self.engine.hmc_sample(self._dev(data_x).reshape(-1), self._dev(data_y).reshape(-1), self._dev(data_v), burn_in, n_keep,
-                                     step_size, n_leapfrog, self._next_seed(), want_draws=True, adapt=target)
+                                     step_size, n_leapfrog, self._next_seed(), want_draws=True, adapt=target, mass=mass)
         self.hmc_row_step_ = out["row_step"].cpu().numpy()
+        if mass is not None:
+            self.hmc_row_mass_ = out["mass_scale"].cpu().numpy()
         tot = burn_in + n_keep
         w = min(100, tot)
         self.last_acceptance_rate = float(out["acc_count"][tot - w:].sum().item()) / (max(1, w) * len(data_x))

@@ -388,6 +388,24 @@ BGM_API int bgm_causal_hmc_run(bgm_handle *h, const float *x_dev, const float *y
                                int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed, uint32_t *acc_count_dev,
                                float *draws_dev, int32_t n_keep, void *stream);
 
+/* Diagonal metric per chain for the bgm_causal_hmc_run calls made afterwards (opt-in; NULL = identity mass, today's kernels).
+ * scale_dev [n x q], aligned with the rows of the call like state_dev: chain r carries s = scale_dev[r], M^-1 = diag(s^2), in the
+ * scaled form -- momentum and kinetic energy as with identity mass, the step of coordinate i is step * s_i in the position step and
+ * in the kicks.  With s = 1 the run is bit-identical to identity mass.  accumulate != 0: after the accept decision of every
+ * iteration the calls add d = state - ref_dev into s1_dev and d^2 into s2_dev (all [n x q], float32; ref_dev / s1_dev / s2_dev may
+ * be NULL otherwise).  The buffers must stay valid while set.  Refuses what bgm_causal_logpost_grad refuses.
+ * replaces: nothing in causalbgm/base.py (tfp's HamiltonianMonteCarlo of bgm/base.py:709-830 has identity mass only); the windowed
+ * per-chain estimate follows the diagonal adaptation of Stan's warm-up (opt-in). */
+BGM_API int bgm_causal_hmc_set_mass(bgm_handle *h, const float *scale_dev, const float *ref_dev, float *s1_dev, float *s2_dev,
+                                    int32_t accumulate);
+/* End of an estimation window of n_draws iterations, for n chains: with mean_i = s1_i / W and var_i = max(s2_i / W - mean_i^2, 0)
+ * (float64), vbar = mean_i var_i and var_r_i = (W var_i + 5e-3 vbar) / (W + 5), scale_dev_i = clamp(sqrt(var_r_i) / geomean_j
+ * sqrt(var_r_j), 0.05, 20) rounded once to float32 -- the shape only, the step keeps the scale; a chain whose vbar is zero or not
+ * finite keeps its scales.  Then ref_dev = state_dev and s1_dev = s2_dev = 0.  n_draws = 0 only resets.
+ * replaces: nothing in causalbgm/base.py (see bgm_causal_hmc_set_mass). */
+BGM_API int bgm_causal_hmc_mass_update(bgm_handle *h, int64_t n, int32_t n_draws, const float *state_dev, float *scale_dev,
+                                       float *ref_dev, float *s1_dev, float *s2_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * CausalBGM.fit step functions (iterative theta / Z updates).
  * replaces: update_g_net :156-180, update_h_net :183-214, update_f_net :217-243,
