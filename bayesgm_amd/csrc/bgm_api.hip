@@ -7,7 +7,7 @@
 
 #include "bgm_host.h"
 #include "bgm_kernels.h"
-#include "bgm_state.h"
+#include "bgm_launch.h"
 #include "gx_bgm_host.h"
 
 static constexpr int BGM_WAVES = 8;
@@ -69,12 +69,117 @@ extern "C" int bgm_bgm_set_weights(bgm_handle *h, const float *theta, int64_t co
   return BGM_OK;
 }
 
+// Split precision (bgm_kernels.h PREC 2): the fp16 fragment stream and the bias block of the generator whose fp32 blob (BatchNorm folded in,
+// scale [q] being the fold's factor per latent) has just been packed
+static int bgm_build_sx3(BgmState *s, const std::vector<float> &blob, const float *scale) {
+  const BgmMeta &m = s->meta;
+  const int q = m.q, p = m.p, NH = s->NH, NTX = m.ntx;
+  if (s->KTQ != 1) { bgm_set_error("BGM generator: split precision serves z_dim <= 16"); return BGM_E_UNSUPPORTED; }
+  const float *Wh = s->theta.data() + 4 * (size_t)q + (size_t)q * 64 + 64;                                 // hidden layer l (1-based) at Wh + (l - 1) * (4096 + 64)
+  const float *Wm = Wh + (size_t)(NH - 1) * (4096 + 64), *Wv = Wm + (size_t)64 * p + p;
+  std::vector<float> W1(Wh - 64 - (size_t)q * 64, Wh - 64);                     // first Dense [q][64] with the BatchNorm folded in, as in the fp32 blob
+  for (int i = 0; i < q; ++i) for (int k = 0; k < 64; ++k) W1[(size_t)i * 64 + k] *= scale[i];
+  // head fragments (bgm_kernels.h): per 16-feature block 16 fragments of 64 lanes x 8 halves --
+  //   forward f = 2 (2 head + b) + (lo): lane (i, gA), slot u <-> W_head[unit 16 (2 b + (u >> 2)) + 4 gA + (u & 3)][column 16 tx + i]
+  //   backward f = 8 + 2 ti + (lo):     lane (i, gA), slot u <-> (u < 4 ? W_mean : W_var)[unit 16 ti + i][column 16 tx + 4 gA + (u & 3)]
+  std::vector<unsigned short> hx3((size_t)((NTX + BGM_X3_STEP - 1) / BGM_X3_STEP * BGM_X3_STEP) * (BGM_X3_BLOCK_BYTES / 2), 0);       // (whole steps of the stream; padding = zero fragments)
+  auto put = [&](size_t base, float w) {      // hi at base, lo one fragment (512 halves) further
+    const unsigned short hi = bgm_f2h(w);
+    hx3[base] = hi;
+    hx3[base + 512] = bgm_f2h(w - bgm_h2f(hi));
+  };
+  for (int tx = 0; tx < NTX; ++tx) {
+    const size_t blk = (size_t)tx * (BGM_X3_BLOCK_BYTES / 2);
+    for (int lane = 0; lane < 64; ++lane) {
+      const int i = lane & 15, gA = lane >> 4;
+      for (int u = 0; u < 8; ++u) {
+        for (int head = 0; head < 2; ++head)
+          for (int b = 0; b < 2; ++b) {
+            const int unit = 16 * (2 * b + (u >> 2)) + 4 * gA + (u & 3), col = 16 * tx + i;
+            const float w = col < p ? (head ? Wv : Wm)[(size_t)unit * p + col] : 0.0f;
+            put(blk + (size_t)(2 * (2 * head + b)) * 512 + (size_t)lane * 8 + u, w);
+          }
+        for (int ti = 0; ti < 4; ++ti) {
+          const int unit = 16 * ti + i, col = 16 * tx + 4 * gA + (u & 3);
+          const float w = col < p ? (u < 4 ? Wm : Wv)[(size_t)unit * p + col] : 0.0f;
+          put(blk + (size_t)(8 + 2 * ti) * 512 + (size_t)lane * 8 + u, w);
+        }
+      }
+    }
+  }
+  // ---- the stream: steps of BGM_X3_STEP units of 16 KiB, the head blocks above in the middle; unit layouts (64 lanes x 8 halves per fragment, hi at an
+  //      even fragment index, lo behind it):
+  //   L1      f = 2 mt (+1): lane (i, gA), slot u < 4 <-> W1'[latent 4 u + gA][unit 16 mt + i] (BatchNorm folded in, as in the fp32 blob), u >= 4: 0;
+  //           f = 8 + 2 b (+1), the transposed copy: lane (i, gA), slot u <-> W1'[latent 4 (i % 4) + i / 4][unit 16 (2 b + (u >> 2)) + 4 gA + (u & 3)]
+  //   hidden  forward  f = 2 (2 mt + b) (+1): lane (i, gA), slot u <-> W[unit 16 (2 b + (u >> 2)) + 4 gA + (u & 3)][unit 16 mt + i]
+  //           backward f = 2 (2 ti + b) (+1): lane (i, gA), slot u <-> W[unit 16 ti + i][unit 16 (2 b + (u >> 2)) + 4 gA + (u & 3)]
+  //   heads   the 16 KiB blocks above, BGM_X3_STEP per step
+  const int S = (NTX + BGM_X3_STEP - 1) / BGM_X3_STEP, U = BGM_X3_STEP, FT = (NH + U - 1) / U, n_steps = 2 * FT + S;
+  // trunk layer l forward: unit l % U of step l / U; backward unit i = NH - 1 - l (hidden NH - 1 first, L1 last): unit i % U of step FT + S + i / U
+  auto fpos = [&](int l) { return std::pair<size_t, int>((size_t)(l / U), (l % U) * 16); };
+  auto bpos = [&](int l) { const int i = NH - 1 - l; return std::pair<size_t, int>((size_t)(FT + S + i / U), (i % U) * 16); };
+  const size_t step_h = (size_t)BGM_X3_STEP * (BGM_X3_BLOCK_BYTES / 2);      // halves per step
+  std::vector<unsigned short> sx((size_t)n_steps * step_h, 0);
+  auto put2 = [&](size_t step, int frag, int lane, int u, float w) {
+    const size_t base = step * step_h + (size_t)frag * 512 + (size_t)lane * 8 + u;
+    const unsigned short hi = bgm_f2h(w);
+    sx[base] = hi;
+    sx[base + 512] = bgm_f2h(w - bgm_h2f(hi));
+  };
+  for (int lane = 0; lane < 64; ++lane) {
+    const int i = lane & 15, gA = lane >> 4;
+    for (int u = 0; u < 8; ++u) {
+      const int ku = 4 * gA + (u & 3);      // + 16 (2 b + (u >> 2))
+      for (int first = 0; first < 2; ++first) {      // L1 sits at its forward position and at its backward position (the last unit)
+        const auto pos = first ? fpos(0) : bpos(0);
+        for (int mt = 0; mt < 4; ++mt) {
+          const int f = 4 * u + gA;
+          put2(pos.first, pos.second + 2 * mt, lane, u, (u < 4 && f < q) ? W1[(size_t)f * 64 + 16 * mt + i] : 0.0f);
+        }
+        for (int b = 0; b < 2; ++b) {
+          const int f = 4 * (i & 3) + (i >> 2);
+          put2(pos.first, pos.second + 8 + 2 * b, lane, u, f < q ? W1[(size_t)f * 64 + 16 * (2 * b + (u >> 2)) + ku] : 0.0f);
+        }
+      }
+      for (int l = 1; l < NH; ++l) {
+        const float *W = Wh + (size_t)(l - 1) * (4096 + 64);
+        const auto pf = fpos(l), pb = bpos(l);
+        for (int t = 0; t < 4; ++t)
+          for (int b = 0; b < 2; ++b) {
+            const int k = 16 * (2 * b + (u >> 2)) + ku;
+            put2(pf.first, pf.second + 2 * (2 * t + b), lane, u, W[(size_t)k * 64 + 16 * t + i]);              // forward: out tile t
+            put2(pb.first, pb.second + 2 * (2 * t + b), lane, u, W[(size_t)(16 * t + i) * 64 + k]);            // backward: in tile t
+          }
+      }
+    }
+  }
+  for (int tx = 0; tx < NTX; ++tx)      // the head blocks as packed above
+    std::memcpy(&sx[(size_t)(FT + tx / BGM_X3_STEP) * step_h + (size_t)(tx % BGM_X3_STEP) * (BGM_X3_BLOCK_BYTES / 2)],
+                &hx3[(size_t)tx * (BGM_X3_BLOCK_BYTES / 2)], BGM_X3_BLOCK_BYTES);
+  if (int rc = bgm_reserve(s->sx3_dev, s->sx3_cap, sx.size() * 2)) return rc;
+  BGM_HIP_CHECK(hipMemcpy(s->sx3_dev, sx.data(), sx.size() * 2, hipMemcpyHostToDevice));
+  // biases: [b1' (64) | hidden (NH - 1) x 64 | heads 2 x 16 NTX] in the posterior blob's own order, the stage behind them
+  BgmMeta &xm = s->sx3_meta;
+  xm = m;
+  xm.b1 = 0; xm.bh = 64; xm.bhd = 64 + 64 * m.n_hh;
+  const int nb = xm.bhd + 2 * 16 * NTX;
+  xm.w1 = xm.wh = xm.whd = 0;
+  xm.lds_resident = (nb + 3) / 4 * 4; xm.stage = xm.lds_resident; xm.total = xm.lds_resident;
+  std::vector<float> xb(xm.lds_resident, 0.0f);
+  for (int k = 0; k < 64; ++k) xb[xm.b1 + k] = blob[m.b1 + k];
+  for (int k = 0; k < 64 * m.n_hh; ++k) xb[xm.bh + k] = blob[m.bh + k];
+  for (int k = 0; k < 2 * 16 * NTX; ++k) xb[xm.bhd + k] = blob[m.bhd + k];
+  if (int rc = bgm_reserve(s->sx3_bias_dev, s->sx3_bias_cap, xb.size())) return rc;
+  BGM_HIP_CHECK(hipMemcpy(s->sx3_bias_dev, xb.data(), xb.size() * sizeof(float), hipMemcpyHostToDevice));
+  s->lds_bytes_sx3 = (xm.stage + 2 * BGM_X3_STEP * (BGM_X3_BLOCK_BYTES / 4)) * 4;
+  return BGM_OK;
+}
+
 static int bgm_build_blob(bgm_handle *h, hipStream_t stream) {
   BgmState *s = bst(h);
   if (s->blob_valid) return BGM_OK;
   if (!s->set) { bgm_set_error("BGM weights not set"); return BGM_E_STATE; }
   const int q = s->cfg.z_dim, p = s->cfg.x_dim, NH = s->cfg.n_hidden_g;
-  const int KTQ = (q + 15) / 16;
   BgmMeta &m = s->meta;
   int ntx_variant = 0;
   const int lds_bytes = bgm_layout(q, p, NH, m, ntx_variant, s->precision != 0);      // (split-precision heads: the streamed variant)
@@ -82,138 +187,18 @@ static int bgm_build_blob(bgm_handle *h, hipStream_t stream) {
     bgm_set_error("BGM generator: trunk + head biases + stage exceed the 160 KiB LDS (x_dim too large)");
     return BGM_E_UNSUPPORTED;
   }
-  s->KTQ = KTQ; s->NTX = ntx_variant; s->NH = NH; s->lds_bytes = lds_bytes;
-  const int NTX = m.ntx;
-  std::vector<float> blob(m.total, 0.0f);
-  const float *th = s->theta.data();
-  const float *gamma = th, *beta = th + q, *mmean = th + 2 * q, *mvar = th + 3 * q;
-  size_t o = 4 * (size_t)q;
-  // first Dense with the inference-mode BatchNorm folded in:  zn = z*scale + shift
+  s->KTQ = (q + 15) / 16; s->NTX = ntx_variant; s->NH = NH; s->lds_bytes = lds_bytes;
+  // the inference-mode BatchNorm, folded into the first Dense by the packer:  zn = z*scale + shift
+  const float *gamma = s->theta.data(), *beta = gamma + q, *mmean = gamma + 2 * q, *mvar = gamma + 3 * q;
   std::vector<float> scale(q), shift(q);
   for (int i = 0; i < q; ++i) { scale[i] = gamma[i] / std::sqrt(mvar[i] + BN_EPS_F); shift[i] = beta[i] - mmean[i] * scale[i]; }
-  std::vector<float> W1(th + o, th + o + (size_t)q * 64); o += (size_t)q * 64;
-  std::vector<float> b1(th + o, th + o + 64); o += 64;
-  for (int k = 0; k < 64; ++k) { double acc = b1[k]; for (int i = 0; i < q; ++i) acc += (double)shift[i] * W1[(size_t)i * 64 + k]; b1[k] = (float)acc; }
-  for (int i = 0; i < q; ++i) for (int k = 0; k < 64; ++k) W1[(size_t)i * 64 + k] *= scale[i];
-  pack17(blob, m.w1, W1, q, 64, 16 * KTQ, 4, [&](int slot) { int f = l1_feature(slot); return f < q ? f : -1; });
-  for (int k = 0; k < 64; ++k) blob[m.b1 + k] = b1[k];
-  auto ident = [](int r) { return r; };
-  for (int l = 0; l < m.n_hh; ++l) {
-    std::vector<float> W(th + o, th + o + 4096); o += 4096;
-    pack17(blob, m.wh + l * 4 * 64 * 17, W, 64, 64, 64, 4, ident);
-    for (int k = 0; k < 64; ++k) blob[m.bh + l * 64 + k] = th[o + k];
-    o += 64;
-  }
-  for (int head = 0; head < 2; ++head) {   // mean, var
-    std::vector<float> W(th + o, th + o + (size_t)64 * p); o += (size_t)64 * p;
-    pack17_heads(blob, m.whd, W.data(), p, NTX, head);
-    for (int k = 0; k < p; ++k) blob[m.bhd + head * 16 * NTX + k] = th[o + k];
-    o += p;
-  }
+  std::vector<float> blob;
+  bgm_pack_blob(m, s->theta.data(), scale.data(), shift.data(), blob);
   BGM_HIP_CHECK(hipSetDevice(h->device));
   if (int rc = bgm_reserve(s->blob_dev, s->blob_cap, blob.size())) return rc;
   BGM_HIP_CHECK(hipMemcpyAsync(s->blob_dev, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-  std::vector<unsigned short> hx3;
-  if (s->precision != 0) {
-    // split-precision head fragments (bgm_kernels.h): per 16-feature block 16 fragments of 64 lanes x 8 halves --
-    //   forward f = 2 (2 head + b) + (lo): lane (i, gA), slot u <-> W_head[unit 16 (2 b + (u >> 2)) + 4 gA + (u & 3)][column 16 tx + i]
-    //   backward f = 8 + 2 ti + (lo):     lane (i, gA), slot u <-> (u < 4 ? W_mean : W_var)[unit 16 ti + i][column 16 tx + 4 gA + (u & 3)]
-    const float *Wm = th + (o - 2 * ((size_t)64 * p + p)), *Wv = Wm + (size_t)64 * p + p;
-    hx3.assign((size_t)((NTX + BGM_X3_STEP - 1) / BGM_X3_STEP * BGM_X3_STEP) * (BGM_X3_BLOCK_BYTES / 2), 0);      // (whole steps of the stream; padding = zero fragments)
-    auto put = [&](size_t base, float w) {      // hi at base, lo one fragment (512 halves) further
-      const unsigned short hi = bgm_f2h(w);
-      hx3[base] = hi;
-      hx3[base + 512] = bgm_f2h(w - bgm_h2f(hi));
-    };
-    for (int tx = 0; tx < NTX; ++tx) {
-      const size_t blk = (size_t)tx * (BGM_X3_BLOCK_BYTES / 2);
-      for (int lane = 0; lane < 64; ++lane) {
-        const int i = lane & 15, gA = lane >> 4;
-        for (int u = 0; u < 8; ++u) {
-          for (int head = 0; head < 2; ++head)
-            for (int b = 0; b < 2; ++b) {
-              const int unit = 16 * (2 * b + (u >> 2)) + 4 * gA + (u & 3), col = 16 * tx + i;
-              const float w = col < p ? (head ? Wv : Wm)[(size_t)unit * p + col] : 0.0f;
-              put(blk + (size_t)(2 * (2 * head + b)) * 512 + (size_t)lane * 8 + u, w);
-            }
-          for (int ti = 0; ti < 4; ++ti) {
-            const int unit = 16 * ti + i, col = 16 * tx + 4 * gA + (u & 3);
-            const float w = col < p ? (u < 4 ? Wm : Wv)[(size_t)unit * p + col] : 0.0f;
-            put(blk + (size_t)(8 + 2 * ti) * 512 + (size_t)lane * 8 + u, w);
-          }
-        }
-      }
-    }
-    // ---- the stream: steps of BGM_X3_STEP units of 16 KiB, the head blocks above in the middle; unit layouts (64 lanes x 8 halves per fragment, hi at an
-    //      even fragment index, lo behind it):
-    //   L1      f = 2 mt (+1): lane (i, gA), slot u < 4 <-> W1'[latent 4 u + gA][unit 16 mt + i] (BatchNorm folded in, as in the fp32 blob), u >= 4: 0;
-    //           f = 8 + 2 b (+1), the transposed copy: lane (i, gA), slot u <-> W1'[latent 4 (i % 4) + i / 4][unit 16 (2 b + (u >> 2)) + 4 gA + (u & 3)]
-    //   hidden  forward  f = 2 (2 mt + b) (+1): lane (i, gA), slot u <-> W[unit 16 (2 b + (u >> 2)) + 4 gA + (u & 3)][unit 16 mt + i]
-    //           backward f = 2 (2 ti + b) (+1): lane (i, gA), slot u <-> W[unit 16 ti + i][unit 16 (2 b + (u >> 2)) + 4 gA + (u & 3)]
-    //   heads   the 16 KiB blocks above, BGM_X3_STEP per step
-    if (KTQ != 1) { bgm_set_error("BGM generator: split precision serves z_dim <= 16"); return BGM_E_UNSUPPORTED; }
-    {
-      const int S = (NTX + BGM_X3_STEP - 1) / BGM_X3_STEP, U = BGM_X3_STEP, FT = (NH + U - 1) / U, n_steps = 2 * FT + S;
-      // trunk layer l forward: unit l % U of step l / U; backward unit i = NH - 1 - l (hidden NH - 1 first, L1 last): unit i % U of step FT + S + i / U
-      auto fpos = [&](int l) { return std::pair<size_t, int>((size_t)(l / U), (l % U) * 16); };
-      auto bpos = [&](int l) { const int i = NH - 1 - l; return std::pair<size_t, int>((size_t)(FT + S + i / U), (i % U) * 16); };
-      const size_t step_h = (size_t)BGM_X3_STEP * (BGM_X3_BLOCK_BYTES / 2);      // halves per step
-      std::vector<unsigned short> sx((size_t)n_steps * step_h, 0);
-      auto put2 = [&](size_t step, int frag, int lane, int u, float w) {
-        const size_t base = step * step_h + (size_t)frag * 512 + (size_t)lane * 8 + u;
-        const unsigned short hi = bgm_f2h(w);
-        sx[base] = hi;
-        sx[base + 512] = bgm_f2h(w - bgm_h2f(hi));
-      };
-      const float *Wh = th + 4 * (size_t)q + (size_t)q * 64 + 64;      // hidden layer l (1-based) at Wh + (l - 1) * (4096 + 64)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int i = lane & 15, gA = lane >> 4;
-        for (int u = 0; u < 8; ++u) {
-          const int ku = 4 * gA + (u & 3);      // + 16 (2 b + (u >> 2))
-          for (int first = 0; first < 2; ++first) {      // L1 sits at its forward position and at its backward position (the last unit)
-            const auto pos = first ? fpos(0) : bpos(0);
-            for (int mt = 0; mt < 4; ++mt) {
-              const int f = 4 * u + gA;
-              put2(pos.first, pos.second + 2 * mt, lane, u, (u < 4 && f < q) ? W1[(size_t)f * 64 + 16 * mt + i] : 0.0f);
-            }
-            for (int b = 0; b < 2; ++b) {
-              const int f = 4 * (i & 3) + (i >> 2);
-              put2(pos.first, pos.second + 8 + 2 * b, lane, u, f < q ? W1[(size_t)f * 64 + 16 * (2 * b + (u >> 2)) + ku] : 0.0f);
-            }
-          }
-          for (int l = 1; l < NH; ++l) {
-            const float *W = Wh + (size_t)(l - 1) * (4096 + 64);
-            const auto pf = fpos(l), pb = bpos(l);
-            for (int t = 0; t < 4; ++t)
-              for (int b = 0; b < 2; ++b) {
-                const int k = 16 * (2 * b + (u >> 2)) + ku;
-                put2(pf.first, pf.second + 2 * (2 * t + b), lane, u, W[(size_t)k * 64 + 16 * t + i]);              // forward: out tile t
-                put2(pb.first, pb.second + 2 * (2 * t + b), lane, u, W[(size_t)(16 * t + i) * 64 + k]);            // backward: in tile t
-              }
-          }
-        }
-      }
-      for (int tx = 0; tx < NTX; ++tx)      // the head blocks as packed above
-        std::memcpy(&sx[(size_t)(FT + tx / BGM_X3_STEP) * step_h + (size_t)(tx % BGM_X3_STEP) * (BGM_X3_BLOCK_BYTES / 2)],
-                    &hx3[(size_t)tx * (BGM_X3_BLOCK_BYTES / 2)], BGM_X3_BLOCK_BYTES);
-      if (int rc = bgm_reserve(s->sx3_dev, s->sx3_cap, sx.size() * 2)) return rc;
-      BGM_HIP_CHECK(hipMemcpy(s->sx3_dev, sx.data(), sx.size() * 2, hipMemcpyHostToDevice));
-      // biases: [b1' (64) | hidden (NH - 1) x 64 | heads 2 x 16 NTX] in the posterior blob's own order, the stage behind them
-      BgmMeta &xm = s->sx3_meta;
-      xm = m;
-      xm.b1 = 0; xm.bh = 64; xm.bhd = 64 + 64 * m.n_hh;
-      const int nb = xm.bhd + 2 * 16 * NTX;
-      xm.w1 = xm.wh = xm.whd = 0;
-      xm.lds_resident = (nb + 3) / 4 * 4; xm.stage = xm.lds_resident; xm.total = xm.lds_resident;
-      std::vector<float> xb(xm.lds_resident, 0.0f);
-      for (int k = 0; k < 64; ++k) xb[xm.b1 + k] = blob[m.b1 + k];
-      for (int k = 0; k < 64 * m.n_hh; ++k) xb[xm.bh + k] = blob[m.bh + k];
-      for (int k = 0; k < 2 * 16 * NTX; ++k) xb[xm.bhd + k] = blob[m.bhd + k];
-      if (int rc = bgm_reserve(s->sx3_bias_dev, s->sx3_bias_cap, xb.size())) return rc;
-      BGM_HIP_CHECK(hipMemcpy(s->sx3_bias_dev, xb.data(), xb.size() * sizeof(float), hipMemcpyHostToDevice));
-      s->lds_bytes_sx3 = (xm.stage + 2 * BGM_X3_STEP * (BGM_X3_BLOCK_BYTES / 4)) * 4;
-    }
-  }
+  if (s->precision != 0)
+    if (int rc = bgm_build_sx3(s, blob, scale.data())) return rc;
   BGM_HIP_CHECK(hipStreamSynchronize(stream));
   s->blob_valid = true;
   return BGM_OK;
@@ -232,18 +217,6 @@ extern "C" int bgm_bgm_set_precision(bgm_handle *h, int32_t mode) {
   return BGM_OK;
 }
 
-// (KTQ, NTX, NH) variants: z_dim <= 16; x_dim in (16,32] / (96,112] LDS-resident, NTX = 0 = wide (any x_dim,
-// head weights streamed through an LDS stage); 5 hidden layers (configs/*.yaml) or 3
-#define BGM_BGM_VARIANTS(X) X(1, 2, 5) X(1, 7, 5) X(1, 0, 5) X(1, 2, 3) X(1, 7, 3) X(1, 0, 3)
-
-static int bgm_grid(const bgm_handle *h, long long tiles) {
-  return (int)std::max<long long>(1, std::min<long long>((tiles + BGM_WAVES - 1) / BGM_WAVES, h->n_cus));
-}
-#define BGM_NO_VARIANT(s)                                                                               \
-  bgm_set_error("no compiled BGM kernel variant for (KTQ,NTX,NH)=(" + std::to_string((s)->KTQ) + "," +  \
-                std::to_string((s)->NTX) + "," + std::to_string((s)->NH) + ")");                        \
-  return BGM_E_UNSUPPORTED;
-
 extern "C" int bgm_bgm_logpost(bgm_handle *h, const float *z, const float *x, int64_t n, float *out, float *grad,
                                void *stream_) {
   if (!h || !h->bgm_state || !bst(h)->configured) { bgm_set_error("bgm_bgm_logpost: not configured"); return BGM_E_STATE; }
@@ -255,34 +228,19 @@ extern "C" int bgm_bgm_logpost(bgm_handle *h, const float *z, const float *x, in
   int rc = bgm_build_blob(h, stream);
   if (rc) return rc;
   BgmState *s = bst(h);
-  const int grid = bgm_grid(h, (n + 15) / 16), lds = s->lds_bytes;
-  if (s->precision != 0) {      // split precision: the whole generator as one fp16 fragment stream (bgm_kernels.h, PREC 2)
-    const int ldx = s->lds_bytes_sx3;
-#define X(KTQ_, NH_)                                                                                                \
-    if (s->KTQ == KTQ_ && s->NH == NH_) {                                                                           \
-      auto k = (s->sx3_meta.p & 3) == 0 ? bgm_logpost_kernel<KTQ_, 0, NH_, BGM_WAVES, 2, true> : bgm_logpost_kernel<KTQ_, 0, NH_, BGM_WAVES, 2, false>; \
-      BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, ldx)); \
-      hipLaunchKernelGGL(k, dim3(grid), dim3(64 * BGM_WAVES), ldx, stream, s->sx3_bias_dev, s->sx3_meta, z, x, (long long)n, out, grad, \
-                         (const unsigned char *)s->sx3_dev);                                                        \
-      BGM_HIP_CHECK(hipGetLastError());                                                                             \
-      return BGM_OK;                                                                                                \
-    }
-    X(1, 5) X(1, 3)
-#undef X
-    BGM_NO_VARIANT(s)
-  }
-#define X(KTQ_, NTX_, NH_)                                                                                          \
-  if (s->KTQ == KTQ_ && s->NTX == NTX_ && s->NH == NH_) {                                                           \
-    auto k = bgm_logpost_kernel<KTQ_, NTX_, NH_, BGM_WAVES>;                                                        \
-    BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * BGM_WAVES), lds, stream, s->blob_dev, s->meta, z, x, (long long)n, out, grad, \
-                       (const unsigned char *)nullptr);                                                             \
-    BGM_HIP_CHECK(hipGetLastError());                                                                               \
-    return BGM_OK;                                                                                                  \
-  }
-  BGM_BGM_VARIANTS(X)
-#undef X
-  BGM_NO_VARIANT(s)
+  const int grid = bgm_tile_grid(h, (n + 15) / 16, BGM_WAVES);
+  if (s->precision != 0)      // split precision: the whole generator as one fp16 fragment stream (bgm_kernels.h, PREC 2)
+    return bgm_bgm_dispatch(BgmSx3Variants{}, s->KTQ, s->NTX, s->NH, "BGM log-posterior (split precision)", [&](auto v) {
+      using V = decltype(v);
+      return bgm_launch((s->sx3_meta.p & 3) == 0 ? bgm_logpost_kernel<V::KTQ, 0, V::NH, BGM_WAVES, 2, true>
+                                                 : bgm_logpost_kernel<V::KTQ, 0, V::NH, BGM_WAVES, 2, false>,
+                        grid, BGM_WAVES, s->lds_bytes_sx3, stream, s->sx3_bias_dev, s->sx3_meta, z, x, n, out, grad, s->sx3_dev);
+    });
+  return bgm_bgm_dispatch(s, "BGM log-posterior", [&](auto v) {
+    using V = decltype(v);
+    return bgm_launch(bgm_logpost_kernel<V::KTQ, V::NTX, V::NH, BGM_WAVES>, grid, BGM_WAVES, s->lds_bytes, stream, s->blob_dev, s->meta, z, x, n,
+                      out, grad, nullptr);
+  });
 }
 
 extern "C" int bgm_bgm_hmc_run(bgm_handle *h, const bgm_hmc_args *a, void *stream_) {
@@ -299,61 +257,26 @@ extern "C" int bgm_bgm_hmc_run(bgm_handle *h, const bgm_hmc_args *a, void *strea
   if (rc) return rc;
   BgmState *s = bst(h);
   BgmHmcKArgs ka{};
-  ka.blob = s->blob_dev; ka.x = a->x_dev; ka.n = a->n; ka.row_base = a->row_base;
-  ka.state = a->state_dev; ka.logp = a->logp_dev; ka.grad = a->grad_dev; ka.init = a->init;
-  ka.it_begin = a->it_begin; ka.n_iters = a->n_iters; ka.burn_in = a->burn_in; ka.n_leapfrog = a->n_leapfrog;
-  ka.step = a->step_dev; ka.k0 = (unsigned)(a->seed & 0xFFFFFFFFull); ka.k1 = (unsigned)(a->seed >> 32);
-  ka.acc_prob_sum = a->acc_prob_sum_dev; ka.acc_count = a->acc_count_dev; ka.draws = a->draws_dev; ka.m = s->meta;
-  const int lds = s->lds_bytes;
+  bgm_hmc_fill(ka, a);
+  ka.blob = s->blob_dev; ka.m = s->meta;
   const long long tiles = (a->n + 15) / 16;
+  if (s->precision != 0) {      // split precision (bgm_kernels.h, PREC 2): the biases are the only LDS-resident data, everything else streams
+    ka.blob = s->sx3_bias_dev; ka.m = s->sx3_meta; ka.hx3 = s->sx3_dev;
+    return bgm_bgm_dispatch(BgmSx3Variants{}, s->KTQ, s->NTX, s->NH, "BGM HMC (split precision)", [&](auto v) {
+      using V = decltype(v);
+      constexpr int W = BGM_SX3_WAVES_DEFAULT;      // (12 waves: three per SIMD inside the 168-register line; 8 measured slower, round 6)
+      return bgm_launch((s->sx3_meta.p & 3) == 0 ? bgm_hmc_kernel<V::KTQ, 0, V::NH, W, 2, true> : bgm_hmc_kernel<V::KTQ, 0, V::NH, W, 2, false>,
+                        bgm_tile_grid(h, tiles, W), W, s->lds_bytes_sx3, stream, ka);
+    });
+  }
   // The wide variant's unit of work is a block pass (W row tiles x all iterations of the launch) and every block makes the same
   // number of passes.  Tiles are dealt wave-major and tile-less waves skip the matrix work (bgm_hmc_kernel), so a partly filled
   // last round costs its ceil(active waves / 4) waves per SIMD: 12 waves (3 per SIMD, the fastest per tile by ~4 %) always.
-  auto wide_waves = [&](void) { return std::getenv("BGM_WIDE_W8") ? 8 : BGM_WAVES_WIDE_HMC; };
-  const int ww = wide_waves();
-#define LAUNCH_HMC(KTQ_, NTX_, NH_, W)                                                                              \
-  {                                                                                                                 \
-    const int grid = (int)std::max<long long>(1, std::min<long long>((tiles + W - 1) / W, h->n_cus));               \
-    auto k = bgm_hmc_kernel<KTQ_, NTX_, NH_, W>;                                                                    \
-    BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * W), lds, stream, ka);                                               \
-    BGM_HIP_CHECK(hipGetLastError());                                                                               \
-    return BGM_OK;                                                                                                  \
-  }
-  if (s->precision != 0) {      // split precision (bgm_kernels.h, PREC 2): the biases are the only LDS-resident data, everything else streams
-    ka.blob = s->sx3_bias_dev; ka.m = s->sx3_meta; ka.hx3 = s->sx3_dev;
-    const int ldx = s->lds_bytes_sx3;
-    constexpr int W = BGM_SX3_WAVES_DEFAULT;      // (12 waves: three per SIMD inside the 168-register line; 8 measured slower, round 6)
-#define LAUNCH_SX3(KTQ_, NH_, X4_)                                                                                  \
-    {                                                                                                               \
-      const int grid = (int)std::max<long long>(1, std::min<long long>((tiles + W - 1) / W, h->n_cus));             \
-      auto k = bgm_hmc_kernel<KTQ_, 0, NH_, W, 2, X4_>;                                                             \
-      BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, ldx)); \
-      hipLaunchKernelGGL(k, dim3(grid), dim3(64 * W), ldx, stream, ka);                                             \
-      BGM_HIP_CHECK(hipGetLastError());                                                                             \
-      return BGM_OK;                                                                                                \
-    }
-#define X(KTQ_, NH_)                                                                                                \
-    if (s->KTQ == KTQ_ && s->NH == NH_) {                                                                           \
-      if ((s->sx3_meta.p & 3) == 0) LAUNCH_SX3(KTQ_, NH_, true)                                                              \
-      LAUNCH_SX3(KTQ_, NH_, false)                                                                                  \
-    }
-    X(1, 5) X(1, 3)
-#undef X
-#undef LAUNCH_SX3
-    BGM_NO_VARIANT(s)
-  }
-#define X(KTQ_, NTX_, NH_)                                                                                          \
-  if (s->KTQ == KTQ_ && s->NTX == NTX_ && s->NH == NH_) {                                                           \
-    if constexpr (NTX_ == 0) {                                                                                      \
-      if (ww == 8) LAUNCH_HMC(KTQ_, NTX_, NH_, 8)                                                                   \
-      LAUNCH_HMC(KTQ_, NTX_, NH_, BGM_WAVES_WIDE_HMC)                                                               \
-    } else LAUNCH_HMC(KTQ_, NTX_, NH_, BGM_WAVES)                                                                   \
-  }
-  BGM_BGM_VARIANTS(X)
-#undef X
-#undef LAUNCH_HMC
-  BGM_NO_VARIANT(s)
+  return bgm_bgm_dispatch(s, "BGM HMC", [&](auto v) {
+    using V = decltype(v);
+    constexpr int W = V::NTX == 0 ? BGM_WAVES_WIDE_HMC : BGM_WAVES;
+    return bgm_launch(bgm_hmc_kernel<V::KTQ, V::NTX, V::NH, W>, bgm_tile_grid(h, tiles, W), W, s->lds_bytes, stream, ka);
+  });
 }
 
 extern "C" int bgm_bgm_hmc_adapt(bgm_handle *h, float *step, const double *acc_prob_sum, int32_t it, double n_chains,
@@ -382,17 +305,8 @@ extern "C" int bgm_bgm_predict_draws(bgm_handle *h, const float *draws, int64_t 
   ka.k_slots = k_slots; ka.slot = slot; ka.cells = cells; ka.full = full; ka.var_full = var_full; ka.add_noise = add_noise;
   ka.k0 = (unsigned)(seed & 0xFFFFFFFFull); ka.k1 = (unsigned)(seed >> 32); ka.m = s->meta;
   const long long work = ((n + 15) / 16) * (long long)n_draws;
-  const int grid = (int)std::max<long long>(1, std::min<long long>((work + BGM_WAVES - 1) / BGM_WAVES, (long long)h->n_cus));
-  const int lds = s->lds_bytes;
-#define X(KTQ_, NTX_, NH_)                                                                                          \
-  if (s->KTQ == KTQ_ && s->NTX == NTX_ && s->NH == NH_) {                                                           \
-    auto k = bgm_predict_kernel<KTQ_, NTX_, NH_, BGM_WAVES>;                                                        \
-    BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * BGM_WAVES), lds, stream, ka);                                       \
-    BGM_HIP_CHECK(hipGetLastError());                                                                               \
-    return BGM_OK;                                                                                                  \
-  }
-  BGM_BGM_VARIANTS(X)
-#undef X
-  BGM_NO_VARIANT(s)
+  return bgm_bgm_dispatch(s, "BGM predict", [&](auto v) {
+    using V = decltype(v);
+    return bgm_launch(bgm_predict_kernel<V::KTQ, V::NTX, V::NH, BGM_WAVES>, bgm_tile_grid(h, work, BGM_WAVES), BGM_WAVES, s->lds_bytes, stream, ka);
+  });
 }

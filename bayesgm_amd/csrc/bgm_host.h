@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -31,6 +32,26 @@ static int bgm_reserve(T *&ptr, size_t &cap, size_t count) {
   BGM_HIP_CHECK(hipMalloc((void **)&ptr, count * sizeof(T)));
   cap = count;
   return BGM_OK;
+}
+
+// One launch of `waves` waves per workgroup with `lds` bytes of dynamic LDS (beyond the 64 KiB a kernel gets without asking): the one
+// place that raises the dynamic-LDS limit, launches and checks, for every kernel family of the library
+template <class... KA, class... A>
+static int bgm_launch(void (*kernel)(KA...), int grid, int waves, int lds, hipStream_t stream, A &&...args) {
+  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, stream, static_cast<KA>(args)...);
+  BGM_HIP_CHECK(hipGetLastError());
+  return BGM_OK;
+}
+
+// The common fields of a *HmcKArgs struct (BgmHmcKArgs, BgmfHmcKArgs, GxHmcArgs, GxfHmcArgs) from the C ABI's bgm_hmc_args; the caller
+// sets its own blob / meta / stream pointers, and overrides init / it_begin / n_iters where a call is split into several launches
+template <class K>
+static void bgm_hmc_fill(K &k, const bgm_hmc_args *a) {
+  k.x = a->x_dev; k.n = a->n; k.row_base = a->row_base; k.state = a->state_dev; k.logp = a->logp_dev; k.grad = a->grad_dev;
+  k.init = a->init; k.it_begin = a->it_begin; k.n_iters = a->n_iters; k.burn_in = a->burn_in; k.n_leapfrog = a->n_leapfrog; k.step = a->step_dev;
+  k.k0 = (unsigned)(a->seed & 0xFFFFFFFFull); k.k1 = (unsigned)(a->seed >> 32);
+  k.acc_prob_sum = a->acc_prob_sum_dev; k.acc_count = a->acc_count_dev; k.draws = a->draws_dev;
 }
 
 struct HostNet {
@@ -154,6 +175,11 @@ struct bgm_handle {
   long long timed_launches[3] = {0, 0, 0};
   double timed_ms[3] = {0.0, 0.0, 0.0};
 };
+
+// workgroups over `tiles` units of work at one per wave, `waves` waves per workgroup, at most one workgroup per CU (the waves loop over the rest)
+static inline int bgm_tile_grid(const bgm_handle *h, long long tiles, int waves) {
+  return (int)std::max<long long>(1, std::min<long long>((tiles + waves - 1) / waves, h->n_cus));
+}
 
 // Compiled kernel shapes.  A model runs on the smallest compiled shape that contains it; the extra K rows / output
 // tiles are zero weights (and zero-padded data), so results are unchanged and only some MFMAs are wasted.

@@ -83,8 +83,9 @@ inline void pack17_heads(std::vector<float> &blob, int off, const float *W, int 
 
 // Blob layout shared by the inference and the training blob.  Chooses the LDS-resident variant when the
 // whole generator fits the 160 KiB LDS AND a kernel is compiled for ceil(p/16); otherwise the wide variant.
-// Returns the dynamic LDS bytes, or -1 if not even the trunk + stage fits.
-inline int bgm_layout(int q, int p, int NH, BgmMeta &m, int &ntx_variant, bool force_wide = false) {
+// Returns the dynamic LDS bytes, or -1 if not even the trunk + stage fits.  bgm_launch.h holds the table of compiled
+// variants and proves at build time that it lists every (KTQ, ntx_variant, NH) this function can return.
+constexpr int bgm_layout_at(int q, int p, int NH, bool force_wide, BgmMeta &m, int &ntx_variant) {
   const int KTQ = (q + 15) / 16, NTX = (p + 15) / 16;
   m = BgmMeta{};
   m.q = q; m.p = p; m.n_hh = NH - 1; m.ntx = NTX;
@@ -95,8 +96,7 @@ inline int bgm_layout(int q, int p, int NH, BgmMeta &m, int &ntx_variant, bool f
   m.bhd = take(2 * 16 * NTX);
   m.whd = take(NTX * BGM_PAIR);
   m.total = off;
-  const char *force = std::getenv("BGM_FORCE_WIDE");   // test hook: run the wide variant on small shapes too
-  const bool resident = (size_t)m.total * 4 <= 160 * 1024 && (NTX == 2 || NTX == 7) && !(force && force[0] == '1') && !force_wide;
+  const bool resident = (size_t)m.total * 4 <= 160 * 1024 && (NTX == 2 || NTX == 7) && !force_wide;
   if (resident) {
     ntx_variant = NTX; m.lds_resident = m.total; m.stage = 0;
     return m.total * 4;
@@ -104,6 +104,40 @@ inline int bgm_layout(int q, int p, int NH, BgmMeta &m, int &ntx_variant, bool f
   ntx_variant = 0; m.lds_resident = m.whd; m.stage = m.whd;
   const size_t bytes = ((size_t)m.whd + 2 * BGM_PAIR) * 4;
   return bytes <= 160 * 1024 ? (int)bytes : -1;
+}
+inline int bgm_layout(int q, int p, int NH, BgmMeta &m, int &ntx_variant, bool force_wide = false) {
+  const char *force = std::getenv("BGM_FORCE_WIDE");   // test hook: run the wide variant on small shapes too
+  return bgm_layout_at(q, p, NH, force_wide || (force && force[0] == '1'), m, ntx_variant);
+}
+
+// theta (bgm_bgm_set_weights order: gamma, beta, moving mean, moving var [q each] | trunk W, b ... | mean W, b | var W, b) packed into a
+// blob of layout m.  scale / shift [q]: the inference-mode input BatchNorm zn = z * scale + shift, folded into the first Dense (the
+// posterior kernels' blob); NULL: layer 1 as it is (the training blob, whose kernels normalise with the batch statistics).
+inline void bgm_pack_blob(const BgmMeta &m, const float *th, const float *scale, const float *shift, std::vector<float> &blob) {
+  const int q = m.q, p = m.p, KTQ = (q + 15) / 16, NTX = m.ntx;
+  blob.assign(m.total, 0.0f);
+  size_t o = 4 * (size_t)q;
+  std::vector<float> W1(th + o, th + o + (size_t)q * 64); o += (size_t)q * 64;
+  std::vector<float> b1(th + o, th + o + 64); o += 64;
+  if (scale) {
+    for (int k = 0; k < 64; ++k) { double acc = b1[k]; for (int i = 0; i < q; ++i) acc += (double)shift[i] * W1[(size_t)i * 64 + k]; b1[k] = (float)acc; }
+    for (int i = 0; i < q; ++i) for (int k = 0; k < 64; ++k) W1[(size_t)i * 64 + k] *= scale[i];
+  }
+  pack17(blob, m.w1, W1, q, 64, 16 * KTQ, 4, [&](int slot) { int f = l1_feature(slot); return f < q ? f : -1; });
+  for (int k = 0; k < 64; ++k) blob[m.b1 + k] = b1[k];
+  auto ident = [](int r) { return r; };
+  for (int l = 0; l < m.n_hh; ++l) {
+    std::vector<float> W(th + o, th + o + 4096); o += 4096;
+    pack17(blob, m.wh + l * 4 * 64 * 17, W, 64, 64, 64, 4, ident);
+    for (int k = 0; k < 64; ++k) blob[m.bh + l * 64 + k] = th[o + k];
+    o += 64;
+  }
+  for (int head = 0; head < 2; ++head) {   // mean, var
+    pack17_heads(blob, m.whd, th + o, p, NTX, head);
+    o += (size_t)64 * p;
+    for (int k = 0; k < p; ++k) blob[m.bhd + head * 16 * NTX + k] = th[o + k];
+    o += p;
+  }
 }
 
 // fp32 -> fp16 bits, round to nearest even, clamped to the largest finite value (host-side packing of the split-precision fragments)

@@ -384,9 +384,7 @@ extern "C" int bgm_bvn_hmc_run(bgm_handle *h, const bgm_hmc_args *g, void *strea
       hipLaunchKernelGGL(gxf_pack_kernel, dim3(64, pk.n_flip), dim3(256), 0, st, pk);       // packs of the CURRENT parameters (they may have been trained since)
       GxfHmcArgs k{};
       k.f = gx->f; k.f.m.bnp = s->theta_dev + s->net.off;
-      k.x = g->x_dev; k.n = g->n; k.row_base = g->row_base; k.state = g->state_dev; k.logp = g->logp_dev; k.grad = g->grad_dev;
-      k.init = g->init; k.it_begin = g->it_begin; k.n_iters = g->n_iters; k.burn_in = g->burn_in; k.n_leapfrog = g->n_leapfrog; k.step = g->step_dev;
-      k.k0 = (uint32_t)(g->seed & 0xFFFFFFFFull); k.k1 = (uint32_t)(g->seed >> 32); k.acc_prob_sum = g->acc_prob_sum_dev; k.acc_count = g->acc_count_dev; k.draws = g->draws_dev;
+      bgm_hmc_fill(k, g);
       BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(gxf_bgm_hmc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, gx->lds_bytes));
       const long long tiles32 = (g->n + GX_ROWS - 1) / GX_ROWS;
       const int occ = std::max(1, std::min(4, (160 * 1024) / gx->lds_bytes));

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "bgm_host.h"
 #include "bgmb_state.h"
@@ -21,6 +22,14 @@ struct BgmfState {
   float *xres = nullptr;
   int lds_bytes_x = 0;
 };
+
+// A two-valued run-time choice as a template argument: f(std::integral_constant<int, A>) when `first`, else f(std::integral_constant<int, B>).
+// The compiled chains are the products of two such choices (bgmf_session / bgmfx_session admit nothing else): first layer K tiles 1 | 2
+// and 5 | 3 hidden layers (bgmf_hmc_kernel), x_dim % 4 == 0 | not and 5 | 3 hidden layers (bgmfx_hmc_kernel).
+template <int A, int B, class F>
+static int bgmf_pick(bool first, F &&f) {
+  return first ? f(std::integral_constant<int, A>{}) : f(std::integral_constant<int, B>{});
+}
 
 void bgmf_free(BgmbState *s) {
   BgmfState *f = static_cast<BgmfState *>(s->bgmf);
@@ -127,24 +136,26 @@ static int bgmfx_hmc(bgm_handle *h, BgmbState *s, BgmfState *f, const bgm_hmc_ar
   hipLaunchKernelGGL(bgmfx_pack_kernel, dim3((unsigned)n_steps + 1, 16), dim3(512), 0, st, pk);      // fragments of the CURRENT parameters and of this run's perturbation
   BGM_HIP_CHECK(hipGetLastError());
   BgmfxHmcKArgs x{};
-  BgmfHmcKArgs &k = x.k;
-  k.blob = f->xres; k.x = g->x_dev; k.n = g->n; k.row_base = g->row_base; k.state = g->state_dev; k.logp = g->logp_dev; k.grad = g->grad_dev;
-  k.init = g->init; k.it_begin = g->it_begin; k.n_iters = g->n_iters; k.burn_in = g->burn_in; k.n_leapfrog = g->n_leapfrog; k.step = g->step_dev;
-  k.k0 = (uint32_t)(g->seed & 0xFFFFFFFFull); k.k1 = (uint32_t)(g->seed >> 32);
-  k.acc_prob_sum = g->acc_prob_sum_dev; k.acc_count = g->acc_count_dev; k.draws = g->draws_dev;
-  k.m = f->xm;
+  bgm_hmc_fill(x.k, g);
+  x.k.blob = f->xres; x.k.m = f->xm;
   x.sx = f->sx;
-  const long long tiles = (g->n + 15) / 16;
-  const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((tiles + BGMFX_WAVES - 1) / BGMFX_WAVES, h->n_cus));
-  auto launch = [&](auto kern) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, f->lds_bytes_x) != hipSuccess) return BGM_E_HIP;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * BGMFX_WAVES), f->lds_bytes_x, st, x);
-    return hipGetLastError() == hipSuccess ? BGM_OK : BGM_E_HIP;
-  };
-  if ((f->xm.p & 3) == 0) rc = f->xm.nh == 5 ? launch(bgmfx_hmc_kernel<5, BGMFX_WAVES, true>) : launch(bgmfx_hmc_kernel<3, BGMFX_WAVES, true>);
-  else rc = f->xm.nh == 5 ? launch(bgmfx_hmc_kernel<5, BGMFX_WAVES, false>) : launch(bgmfx_hmc_kernel<3, BGMFX_WAVES, false>);
-  if (rc) bgm_set_error("frozen-noise HMC (bgmfx_hmc_kernel): launch failed");
-  return rc;
+  const int grid = bgm_tile_grid(h, (g->n + 15) / 16, BGMFX_WAVES);
+  return bgmf_pick<1, 0>((f->xm.p & 3) == 0, [&](auto x4) {
+    return bgmf_pick<5, 3>(f->xm.nh == 5, [&](auto nh) {
+      return bgm_launch(bgmfx_hmc_kernel<decltype(nh)::value, BGMFX_WAVES, decltype(x4)::value != 0>, grid, BGMFX_WAVES, f->lds_bytes_x, st, x);
+    });
+  });
+}
+
+// bgmf_hmc_kernel<KTQ, NH, FRESH> of the session's shape over the rows of k
+template <bool FRESH>
+static int bgmf_launch_chain(bgm_handle *h, const BgmfState *f, const BgmfHmcKArgs &k, hipStream_t st) {
+  const int grid = bgm_tile_grid(h, (k.n + 15) / 16, BGMF_WAVES);
+  return bgmf_pick<1, 2>(f->ktq == 1, [&](auto ktq) {
+    return bgmf_pick<5, 3>(f->m.nh == 5, [&](auto nh) {
+      return bgm_launch(bgmf_hmc_kernel<decltype(ktq)::value, decltype(nh)::value, FRESH>, grid, BGMF_WAVES, f->lds_bytes, st, k);
+    });
+  });
 }
 
 // 0: launched; 1: not this kernel's shape; < 0: error
@@ -158,22 +169,9 @@ int bgmf_hmc_try(bgm_handle *h, BgmbState *s, const bgm_hmc_args *g, hipStream_t
   hipLaunchKernelGGL(bgmf_pack_kernel, dim3(32, f->m.nh + 1, 1), dim3(256), 0, st, pk);        // blob of the CURRENT parameters and of this run's perturbation
   BGM_HIP_CHECK(hipGetLastError());
   BgmfHmcKArgs k{};
-  k.blob = f->blob; k.x = g->x_dev; k.n = g->n; k.row_base = g->row_base; k.state = g->state_dev; k.logp = g->logp_dev; k.grad = g->grad_dev;
-  k.init = g->init; k.it_begin = g->it_begin; k.n_iters = g->n_iters; k.burn_in = g->burn_in; k.n_leapfrog = g->n_leapfrog; k.step = g->step_dev;
-  k.k0 = (uint32_t)(g->seed & 0xFFFFFFFFull); k.k1 = (uint32_t)(g->seed >> 32);
-  k.acc_prob_sum = g->acc_prob_sum_dev; k.acc_count = g->acc_count_dev; k.draws = g->draws_dev;
-  k.m = f->m;
-  const long long tiles = (g->n + 15) / 16;
-  const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((tiles + BGMF_WAVES - 1) / BGMF_WAVES, h->n_cus));
-  auto launch = [&](auto kern) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, f->lds_bytes) != hipSuccess) return BGM_E_HIP;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * BGMF_WAVES), f->lds_bytes, st, k);
-    return hipGetLastError() == hipSuccess ? BGM_OK : BGM_E_HIP;
-  };
-  if (f->ktq == 1) rc = f->m.nh == 5 ? launch(bgmf_hmc_kernel<1, 5, false>) : launch(bgmf_hmc_kernel<1, 3, false>);
-  else rc = f->m.nh == 5 ? launch(bgmf_hmc_kernel<2, 5, false>) : launch(bgmf_hmc_kernel<2, 3, false>);
-  if (rc) bgm_set_error("frozen-noise HMC (bgmf_hmc_kernel): launch failed");
-  return rc;
+  bgm_hmc_fill(k, g);
+  k.blob = f->blob; k.m = f->m;
+  return bgmf_launch_chain<false>(h, f, k, st);
 }
 
 
@@ -199,20 +197,8 @@ int bgmf_hmc_fresh(bgm_handle *h, BgmbState *s, const bgm_hmc_args *g, int it_be
   hipLaunchKernelGGL(bgmf_pack_kernel, dim3(16, f->m.nh + 1, (unsigned)slots), dim3(256), 0, st, pk);
   BGM_HIP_CHECK(hipGetLastError());
   BgmfHmcKArgs k{};
-  k.blob = f->blob_fresh; k.x = g->x_dev; k.n = g->n; k.row_base = g->row_base; k.state = g->state_dev; k.logp = g->logp_dev; k.grad = g->grad_dev;
-  k.init = init; k.it_begin = it_begin; k.n_iters = n_iters; k.burn_in = g->burn_in; k.n_leapfrog = g->n_leapfrog; k.step = g->step_dev;
-  k.k0 = (uint32_t)(g->seed & 0xFFFFFFFFull); k.k1 = (uint32_t)(g->seed >> 32);
-  k.acc_prob_sum = g->acc_prob_sum_dev; k.acc_count = g->acc_count_dev; k.draws = g->draws_dev;
-  k.m = f->m;
-  const long long tiles = (g->n + 15) / 16;
-  const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((tiles + BGMF_WAVES - 1) / BGMF_WAVES, h->n_cus));
-  auto launch = [&](auto kern) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, f->lds_bytes) != hipSuccess) return BGM_E_HIP;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * BGMF_WAVES), f->lds_bytes, st, k);
-    return hipGetLastError() == hipSuccess ? BGM_OK : BGM_E_HIP;
-  };
-  if (f->ktq == 1) rc = f->m.nh == 5 ? launch(bgmf_hmc_kernel<1, 5, true>) : launch(bgmf_hmc_kernel<1, 3, true>);
-  else rc = f->m.nh == 5 ? launch(bgmf_hmc_kernel<2, 5, true>) : launch(bgmf_hmc_kernel<2, 3, true>);
-  if (rc) bgm_set_error("fresh-noise HMC (bgmf_hmc_kernel): launch failed");
-  return rc;
+  bgm_hmc_fill(k, g);
+  k.blob = f->blob_fresh; k.m = f->m;
+  k.init = init; k.it_begin = it_begin; k.n_iters = n_iters;
+  return bgmf_launch_chain<true>(h, f, k, st);
 }

@@ -450,8 +450,8 @@ extern "C" int bgm_causal_logpost(bgm_handle *h, const float *x, const float *y,
   if (h->prior_seg) return bgm_causal_prior_logpost(h, x, y, v, z, n, out, grid, stream);
   return bgm_causal_dispatch(h, "kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_causal_launch(causal_logpost_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES>, grid, MH_WAVES, h->meta.total * 4, stream,
-                             h->sblob_dev, h->meta, x, y, v, z, n, out, nullptr, nullptr);
+    return bgm_launch(causal_logpost_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES>, grid, MH_WAVES, h->meta.total * 4, stream,
+                      h->sblob_dev, h->meta, x, y, v, z, n, out, nullptr, nullptr);
   });
 }
 
@@ -459,9 +459,9 @@ template <int EFFECT>
 static int launch_mh(bgm_handle *h, const CausalMhKArgs &ka, int grid, int lds, hipStream_t stream) {
   return bgm_causal_dispatch(h, "MH kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_causal_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2)>
-                                   : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT>,
-                             grid, MH_WAVES, lds, stream, ka);
+    return bgm_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2)>
+                            : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT>,
+                      grid, MH_WAVES, lds, stream, ka);
   });
 }
 
@@ -596,7 +596,7 @@ template <int EFFECT>
 static int launch_eval(bgm_handle *h, const CausalEvalKArgs &ka, int grid, int lds, hipStream_t stream) {
   return bgm_causal_dispatch(h, "evaluate kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_causal_launch(causal_eval_kernel<S::KT1, S::KSL1, S::NTL, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka);
+    return bgm_launch(causal_eval_kernel<S::KT1, S::KSL1, S::NTL, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka);
   });
 }
 
@@ -627,7 +627,7 @@ template <int EFFECT>
 static int launch_effects(bgm_handle *h, const CausalEffKArgs &ka, int grid, int lds, hipStream_t stream) {
   return bgm_causal_dispatch(h, "effects kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_causal_launch(causal_effects_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka);
+    return bgm_launch(causal_effects_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka);
   });
 }
 

@@ -207,8 +207,8 @@ int bgm_causal_bx3_logpost(bgm_handle *h, const float *x, const float *y, const 
   std::memcpy(&m, h->bx_meta_store, sizeof(m));
   return bgm_causal_dispatch(h, "bf16x3: kernel", [&](auto s) {
     constexpr int KT1 = decltype(s)::KT1, NTL = decltype(s)::NTL;
-    return bgm_causal_launch(h->precision == 2 ? bxh::causal_logpost_bx3_kernel<KT1, NTL, MH_WAVES> : bxb::causal_logpost_bx3_kernel<KT1, NTL, MH_WAVES>,
-                             grid, MH_WAVES, m.total_bytes, stream, h->bx_blob_dev, m, x, y, v, z, n, out, h->prior_seg, h->prior_tab);
+    return bgm_launch(h->precision == 2 ? bxh::causal_logpost_bx3_kernel<KT1, NTL, MH_WAVES> : bxb::causal_logpost_bx3_kernel<KT1, NTL, MH_WAVES>,
+                      grid, MH_WAVES, m.total_bytes, stream, h->bx_blob_dev, m, x, y, v, z, n, out, h->prior_seg, h->prior_tab);
   });
 }
 
@@ -226,8 +226,8 @@ int bgm_causal_bx3_mh_launch(bgm_handle *h, const CausalMhKArgs &a, int effect, 
   return bgm_causal_with_effect(effect, [&](auto e) {
     return bgm_causal_dispatch(h, "bf16x3: MH kernel", [&](auto s) {
       constexpr int KT1 = decltype(s)::KT1, NTL = decltype(s)::NTL, EFFECT = decltype(e)::value;
-      return bgm_causal_launch(h->precision == 2 ? bxh::causal_mh_bx3_kernel<KT1, NTL, MH_WAVES, EFFECT> : bxb::causal_mh_bx3_kernel<KT1, NTL, MH_WAVES, EFFECT>,
-                               grid, MH_WAVES, lds, stream, ka);
+      return bgm_launch(h->precision == 2 ? bxh::causal_mh_bx3_kernel<KT1, NTL, MH_WAVES, EFFECT> : bxb::causal_mh_bx3_kernel<KT1, NTL, MH_WAVES, EFFECT>,
+                        grid, MH_WAVES, lds, stream, ka);
     });
   });
 }

@@ -100,9 +100,9 @@ int bgm_causal_event_mh_launch(bgm_handle *h, CausalMhKArgs &ka, int grid, int l
   if (ka.row_scale) return bgm_causal_rowadapt_mh_launch(h, ka, 3, grid, lds, stream);
   return bgm_causal_dispatch(h, "event-form MH kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_causal_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, 3, 0, (S::NTL > 2)>
-                                   : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, 3>,
-                             grid, MH_WAVES, lds, stream, ka);
+    return bgm_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, 3, 0, (S::NTL > 2)>
+                            : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, 3>,
+                      grid, MH_WAVES, lds, stream, ka);
   });
 }
 
@@ -116,9 +116,9 @@ int bgm_causal_event_finish(bgm_handle *h, const CausalMhKArgs &ka, int grid, in
   const int rc = bgm_causal_dispatch(h, "event-form outcome-net kernel", [&](auto s) {
     using S = decltype(s);
     const int lds = 4 * (16 * S::KT1 * 64 + 64 + 64 * 32 + 32 + 32 * 16 + 16 + 16 * 16 + 16 + 64);
-    return bgm_causal_launch(effect == BGM_EFFECT_ITE ? causal_event_f_ite_kernel<S::KT1, S::KSL1, FW, WPS>
-                                                      : causal_event_f_kernel<S::KT1, S::KSL1, FW, WPS>,
-                             grid * MH_WAVES * WPS / FW, FW, lds, stream, fa);
+    return bgm_launch(effect == BGM_EFFECT_ITE ? causal_event_f_ite_kernel<S::KT1, S::KSL1, FW, WPS>
+                                               : causal_event_f_kernel<S::KT1, S::KSL1, FW, WPS>,
+                      grid * MH_WAVES * WPS / FW, FW, lds, stream, fa);
   });
   if (rc) return rc;
   if (effect == BGM_EFFECT_ITE) {      // binary treatment: the two arms per event, then one thread per chain (causal_event_kernels.h)

@@ -112,8 +112,8 @@ extern "C" int bgm_causal_logpost_grad(bgm_handle *h, const float *x, const floa
   const int grid = bgm_causal_grid(h, n, 1);
   return bgm_causal_dispatch(h, "log-posterior gradient kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_causal_launch(causal_hmc_logpost_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, st->m.total * 4, stream, st->blob_dev, st->m, x, y,
-                             h->uc_dev, z, (long long)n, out_logp, out_grad);
+    return bgm_launch(causal_hmc_logpost_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, st->m.total * 4, stream, st->blob_dev, st->m, x, y,
+                      h->uc_dev, z, (long long)n, out_logp, out_grad);
   });
 }
 
@@ -147,6 +147,6 @@ extern "C" int bgm_causal_hmc_run(bgm_handle *h, const float *x, const float *y,
   if (st->mass.scale) return bgm_causal_hmc_mass_launch(h, ka, st->mass, grid, st->m.total * 4, stream);      // bgm_causal_hmc_set_mass
   return bgm_causal_dispatch(h, "HMC kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_causal_launch(causal_hmc_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, st->m.total * 4, stream, ka);
+    return bgm_launch(causal_hmc_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, st->m.total * 4, stream, ka);
   });
 }

@@ -75,6 +75,6 @@ int bgm_causal_hmc_mass_launch(bgm_handle *h, const CausalHmcKArgs &ka, const Ca
   if (!ma.scale || (ma.accumulate && (!ma.ref || !ma.s1 || !ma.s2))) { bgm_set_error("HMC metric: launched without its buffers"); return BGM_E_STATE; }
   return bgm_causal_dispatch(h, "HMC kernel with a diagonal metric", [&](auto s) {
     using S = decltype(s);
-    return bgm_causal_launch(causal_hmc_mass_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, ma);
+    return bgm_launch(causal_hmc_mass_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, ma);
   });
 }

@@ -1,7 +1,7 @@
 // causal_launch.h -- host-side dispatch of the LDS-resident CausalBGM kernels, shared by the translation units that instantiate them
 // (causal_api.hip, causal_event_api.hip, causal_prior_api.hip, causal_rowadapt_api.hip, causal_bx3_api.hip, fit_api.hip): the launch
-// geometry, the table of compiled shapes, the dispatch from a handle's shape to a template instantiation, and the launch itself.
-// Host only: no kernel lives here, and which kernels a unit instantiates is decided by the lambdas it passes to bgm_causal_dispatch.
+// geometry, the table of compiled shapes and the dispatch from a handle's shape to a template instantiation.  The launch itself is
+// bgm_launch (bgm_host.h), shared with the BGM kernels (bgm_launch.h).  Host only: no kernel lives here, and which kernels a unit instantiates is decided by the lambdas it passes to bgm_causal_dispatch.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -24,9 +24,7 @@ static_assert(MH_R == 1, "BGM_MH_R != 1: the conditional-prior, per-chain-scale,
 
 // workgroups over n rows at `row_tiles` 16-row tiles per wave, at most one per CU; a wave slot (grid * MH_WAVES of them) loops over the rest
 static inline int bgm_causal_grid(const bgm_handle *h, int64_t n, int row_tiles) {
-  const int64_t tiles = (n + 16 * row_tiles - 1) / (16 * row_tiles);
-  const int64_t blocks = (tiles + MH_WAVES - 1) / MH_WAVES;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(blocks, h->n_cus));
+  return bgm_tile_grid(h, (n + 16 * row_tiles - 1) / (16 * row_tiles), MH_WAVES);
 }
 
 // ---- compiled shapes.  (KT1, KSL1, NTL): first-layer K tiling and number of 16-wide output tiles of g's last layer.
@@ -82,13 +80,4 @@ static int bgm_causal_with_effect(int effect, F &&f) {
   if (effect == BGM_EFFECT_ADRF) return f(std::integral_constant<int, 1>{});
   if (effect == BGM_EFFECT_ITE) return f(std::integral_constant<int, 2>{});
   return f(std::integral_constant<int, 0>{});
-}
-
-// One launch of `waves` waves per workgroup with `lds` bytes of dynamic LDS (beyond the 64 KiB a kernel gets without asking)
-template <class... KA, class... A>
-static int bgm_causal_launch(void (*kernel)(KA...), int grid, int waves, int lds, hipStream_t stream, A &&...args) {
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, stream, static_cast<KA>(args)...);
-  BGM_HIP_CHECK(hipGetLastError());
-  return BGM_OK;
 }

@@ -20,8 +20,8 @@ int bgm_causal_prior_logpost(bgm_handle *h, const float *x, const float *y, cons
                              int grid, hipStream_t stream) {
   return bgm_causal_dispatch(h, "conditional prior: kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_causal_launch(causal_logpost_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, 1>, grid, MH_WAVES, h->meta.total * 4, stream,
-                             h->sblob_dev, h->meta, x, y, v, z, n, out, h->prior_seg, h->prior_tab);
+    return bgm_launch(causal_logpost_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, 1>, grid, MH_WAVES, h->meta.total * 4, stream,
+                      h->sblob_dev, h->meta, x, y, v, z, n, out, h->prior_seg, h->prior_tab);
   });
 }
 
@@ -33,9 +33,9 @@ int bgm_causal_prior_mh_launch(bgm_handle *h, const CausalMhKArgs &a, int effect
     return bgm_causal_dispatch(h, "conditional prior: MH kernel", [&](auto s) {
       using S = decltype(s);
       constexpr int EFFECT = decltype(e)::value;
-      return bgm_causal_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 1, (S::NTL > 2)>
-                                     : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 1>,
-                               grid, MH_WAVES, lds, stream, ka);
+      return bgm_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 1, (S::NTL > 2)>
+                              : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 1>,
+                        grid, MH_WAVES, lds, stream, ka);
     });
   });
 }
@@ -80,7 +80,7 @@ extern "C" int bgm_prior_table(bgm_handle *h, const bgm_prior_config *cfg, const
   if (n.dims[n.n_layers] != h->q + 1) { bgm_set_error("bgm_prior_table: the prior net must end in q + 1 outputs"); return BGM_E_INVALID; }
   if ((size_t)lf * 4 > 150 * 1024) { bgm_set_error("bgm_prior_table: prior net too wide for one workgroup's LDS"); return BGM_E_UNSUPPORTED; }
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  return bgm_causal_launch(prior_table_kernel, 1, PRIOR_THREADS / 64, lf * 4, (hipStream_t)stream_, n, theta_dev, table_dev, h->q);
+  return bgm_launch(prior_table_kernel, 1, PRIOR_THREADS / 64, lf * 4, (hipStream_t)stream_, n, theta_dev, table_dev, h->q);
 }
 
 static int prior_step_impl(bgm_handle *h, const bgm_prior_config *cfg, float *theta_dev, float *m_dev, float *v_dev, const int32_t *seg_dev,
@@ -104,7 +104,7 @@ static int prior_step_impl(bgm_handle *h, const bgm_prior_config *cfg, float *th
   a.b1 = 0.9f; a.b2 = 0.99f; a.eps = 1e-7f;        // tf.keras.optimizers.Adam(lr, beta_1=0.9, beta_2=0.99), identifiable.py:88-95
   a.out = out_dev; a.inv_B = 1.0f / (float)batch_global; a.grad = grad_dev; a.apply = apply;
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  return bgm_causal_launch(prior_step_kernel, 1, PRIOR_THREADS / 64, (int)bytes, (hipStream_t)stream_, a);
+  return bgm_launch(prior_step_kernel, 1, PRIOR_THREADS / 64, (int)bytes, (hipStream_t)stream_, a);
 }
 
 extern "C" int bgm_prior_step(bgm_handle *h, const bgm_prior_config *cfg, float *theta_dev, float *m_dev, float *v_dev, const int32_t *seg_dev,

@@ -27,9 +27,9 @@ int bgm_causal_rowadapt_mh_launch(bgm_handle *h, const CausalMhKArgs &ka, int ef
     return bgm_causal_dispatch(h, "per-chain proposal scale: MH kernel", [&](auto s) {
       using S = decltype(s);
       constexpr int EFFECT = decltype(e)::value;
-      return bgm_causal_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2), true>
-                                     : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, false, true>,
-                               grid, MH_WAVES, lds, stream, ka);
+      return bgm_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2), true>
+                              : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, false, true>,
+                        grid, MH_WAVES, lds, stream, ka);
     });
   });
 }

@@ -491,10 +491,10 @@ static int launch_fwd_bwd(bgm_handle *h, FitKArgs &ka, hipStream_t stream) {
   return bgm_causal_dispatch(h, "fit kernel", [&](auto s) {
     using S = decltype(s);
     ka.blob = h->blob_dev;
-    if (int rc = bgm_causal_launch(fit_fwd_kernel<S::KT1, S::KSL1, S::NTL, FIT_WAVES>, grid, FIT_WAVES, h->meta.total * 4, stream, ka)) return rc;
+    if (int rc = bgm_launch(fit_fwd_kernel<S::KT1, S::KSL1, S::NTL, FIT_WAVES>, grid, FIT_WAVES, h->meta.total * 4, stream, ka)) return rc;
     ka.blob = h->bblob_dev;
     ka.loss = nullptr;
-    return bgm_causal_launch(fit_bwd_kernel<S::KT1, S::KSL1, S::NTL, FIT_WAVES>, grid, FIT_WAVES, h->fit_meta.total * 4, stream, ka);
+    return bgm_launch(fit_bwd_kernel<S::KT1, S::KSL1, S::NTL, FIT_WAVES>, grid, FIT_WAVES, h->fit_meta.total * 4, stream, ka);
   });
 }
 
@@ -989,7 +989,7 @@ extern "C" int bgm_causal_fit_end(bgm_handle *h, void *stream_) {
 // ===========================================================================================
 // BGM.fit step functions (bgm/base.py:145-187, 399-413) -- see bgm_fit_kernels.h
 // ===========================================================================================
-#include "bgm_state.h"
+#include "bgm_launch.h"
 #include "gx_bgm_host.h"
 
 static constexpr int BGM_FIT_WAVES = 8;
@@ -1005,31 +1005,6 @@ void bgm_bgm_fit_free(bgm_handle *h) {
   s->theta_dev = s->m1_dev = s->m2_dev = s->tblob_dev = s->ws_dev = s->partial_dev = s->bn_dev = s->split_part_dev = s->epoch_grad_dev = nullptr;
   s->tables_dev = nullptr;
   s->fit_active = false; s->gx_fit = false;
-}
-
-// training blob: same layout as the inference blob but WITHOUT folding the BatchNorm into layer 1
-static void bgm_pack_training(const BgmState *s, const std::vector<float> &theta, std::vector<float> &blob) {
-  const BgmMeta &m = s->tmeta;
-  const int q = m.q, p = m.p, KTQ = s->KTQ, NTX = m.ntx;
-  blob.assign(m.total, 0.0f);
-  size_t o = 4 * (size_t)q;
-  std::vector<float> W1(theta.begin() + o, theta.begin() + o + (size_t)q * 64); o += (size_t)q * 64;
-  pack17(blob, m.w1, W1, q, 64, 16 * KTQ, 4, [&](int slot) { int f = l1_feature(slot); return f < q ? f : -1; });
-  for (int k = 0; k < 64; ++k) blob[m.b1 + k] = theta[o + k];
-  o += 64;
-  auto ident = [](int r) { return r; };
-  for (int l = 0; l < m.n_hh; ++l) {
-    std::vector<float> W(theta.begin() + o, theta.begin() + o + 4096); o += 4096;
-    pack17(blob, m.wh + l * 4 * 64 * 17, W, 64, 64, 64, 4, ident);
-    for (int k = 0; k < 64; ++k) blob[m.bh + l * 64 + k] = theta[o + k];
-    o += 64;
-  }
-  for (int head = 0; head < 2; ++head) {
-    std::vector<float> W(theta.begin() + o, theta.begin() + o + (size_t)64 * p); o += (size_t)64 * p;
-    pack17_heads(blob, m.whd, W.data(), p, NTX, head);
-    for (int k = 0; k < p; ++k) blob[m.bhd + head * 16 * NTX + k] = theta[o + k];
-    o += p;
-  }
 }
 
 extern "C" int bgm_bgm_fit_n_params(bgm_handle *h, int64_t *n) {
@@ -1068,14 +1043,14 @@ extern "C" int bgm_bgm_fit_begin(bgm_handle *h, int64_t n_rows, int32_t max_batc
   BGM_HIP_CHECK(hipMemset(s->m2_dev, 0, sizeof(float) * np));
   s->t_theta = 0; s->t_z = 0; s->batch_global = 0;
   std::vector<float> blob;
-  bgm_pack_training(s, s->theta, blob);
+  bgm_pack_blob(m, s->theta.data(), nullptr, nullptr, blob);      // the training blob: the BatchNorm is NOT folded into layer 1
   BGM_HIP_CHECK(hipMalloc(&s->tblob_dev, sizeof(float) * blob.size()));
   BGM_HIP_CHECK(hipMemcpy(s->tblob_dev, blob.data(), sizeof(float) * blob.size(), hipMemcpyHostToDevice));
   // canonical parameter -> training-blob position (pack an iota vector through the same packer)
   std::vector<float> iota(np);
   for (int i = 0; i < np; ++i) iota[i] = (float)(i + 1);
   std::vector<float> bidx;
-  bgm_pack_training(s, iota, bidx);
+  bgm_pack_blob(m, iota.data(), nullptr, nullptr, bidx);
   std::vector<int> tables(4 * (size_t)np, -1);
   int *dst = tables.data(), *grad_src = dst + 3 * (size_t)np;
   for (size_t d = 0; d < bidx.size(); ++d) { const int c = (int)bidx[d] - 1; if (c >= 0) dst[c] = (int)d; }
@@ -1129,8 +1104,6 @@ extern "C" int bgm_bgm_fit_begin(bgm_handle *h, int64_t n_rows, int32_t max_batc
   return BGM_OK;
 }
 
-#define BGM_BGM_FIT_VARIANTS(X) X(1, 2, 5) X(1, 7, 5) X(1, 0, 5) X(1, 2, 3) X(1, 7, 3) X(1, 0, 3)
-
 static int bgm_fit_fwd_bwd(bgm_handle *h, BgmState *s, const float *x, const float *data_z, const int32_t *idx, int batch,
                            double *loss, int update_moving, hipStream_t stream) {
   const int q = s->cfg.z_dim, KQ = 16 * s->KTQ;
@@ -1148,7 +1121,7 @@ static int bgm_fit_fwd_bwd(bgm_handle *h, BgmState *s, const float *x, const flo
   BgmFitKArgs ka{};
   ka.blob = s->tblob_dev; ka.m = s->tmeta; ka.ws = s->fit_ws; ka.wsp = s->ws_dev; ka.x = x; ka.data_z = data_z;
   ka.idx = idx; ka.B = batch; ka.inv_B = 1.0f / (float)(s->batch_global > 0 ? s->batch_global : batch); ka.bn = s->bn_dev; ka.loss = loss;
-  int grid = std::max(1, std::min((tiles + BGM_FIT_WAVES - 1) / BGM_FIT_WAVES, h->n_cus));
+  int grid = bgm_tile_grid(h, tiles, BGM_FIT_WAVES);
   int lds = s->fit_lds_bytes;
   if (split) {
     const int ntx = s->tmeta.ntx, rounds = (ntx + BGM_FIT_S - 1) / BGM_FIT_S;
@@ -1159,22 +1132,11 @@ static int bgm_fit_fwd_bwd(bgm_handle *h, BgmState *s, const float *x, const flo
     grid = std::max(1, std::min(BGM_SPLIT_MAX_WG, s->fit_NTX == 0 ? rounds : (rounds + 1) / 2));
     if (s->fit_NTX == 0) lds += (BGM_FIT_S - 2) * BGM_PAIR * (int)sizeof(float);      // the stage holds BGM_FIT_S tile pairs
   }
-#define X(KTQ_, NTX_, NH_)                                                                                          \
-  if (s->KTQ == KTQ_ && s->fit_NTX == NTX_ && s->NH == NH_) {                                                           \
-    auto kf = bgm_fit_fwd_kernel<KTQ_, NTX_, NH_, BGM_FIT_WAVES>;                                                   \
-    auto kb = bgm_fit_bwd_kernel<KTQ_, NTX_, NH_, BGM_FIT_WAVES>;                                                   \
-    BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-    BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-    hipLaunchKernelGGL(kf, dim3(grid), dim3(64 * BGM_FIT_WAVES), lds, stream, ka);                                  \
-    BGM_HIP_CHECK(hipGetLastError());                                                                               \
-    hipLaunchKernelGGL(kb, dim3(grid), dim3(64 * BGM_FIT_WAVES), lds, stream, ka);                                  \
-    BGM_HIP_CHECK(hipGetLastError());                                                                               \
-    return BGM_OK;                                                                                                  \
-  }
-  BGM_BGM_FIT_VARIANTS(X)
-#undef X
-  bgm_set_error("no compiled BGM fit kernel variant for this shape");
-  return BGM_E_UNSUPPORTED;
+  return bgm_bgm_dispatch(BgmVariants{}, s->KTQ, s->fit_NTX, s->NH, "BGM fit", [&](auto v) {
+    using V = decltype(v);
+    if (int rc = bgm_launch(bgm_fit_fwd_kernel<V::KTQ, V::NTX, V::NH, BGM_FIT_WAVES>, grid, BGM_FIT_WAVES, lds, stream, ka)) return rc;
+    return bgm_launch(bgm_fit_bwd_kernel<V::KTQ, V::NTX, V::NH, BGM_FIT_WAVES>, grid, BGM_FIT_WAVES, lds, stream, ka);
+  });
 }
 
 static int bgm_fit_check(bgm_handle *h, const void *x, const void *z, const void *idx, int batch, const char *who) {

@@ -140,10 +140,8 @@ int gxb_hmc_run(bgm_handle *h, BgmState *s, const bgm_hmc_args *a, hipStream_t s
   int rc = session(h, s, g, stream);
   if (rc) return rc;
   GxHmcArgs k{};
-  k.m = g->m; k.x = a->x_dev; k.n = a->n; k.row_base = a->row_base; k.state = a->state_dev; k.logp = a->logp_dev; k.grad = a->grad_dev;
-  k.init = a->init; k.it_begin = a->it_begin; k.n_iters = a->n_iters; k.burn_in = a->burn_in; k.n_leapfrog = a->n_leapfrog; k.step = a->step_dev;
-  k.k0 = (unsigned)(a->seed & 0xFFFFFFFFull); k.k1 = (unsigned)(a->seed >> 32);
-  k.acc_prob_sum = a->acc_prob_sum_dev; k.acc_count = a->acc_count_dev; k.draws = a->draws_dev;
+  bgm_hmc_fill(k, a);
+  k.m = g->m;
   rc = set_lds(gx_bgm_hmc_kernel, g->lds_bytes);
   if (rc) return rc;
   hipLaunchKernelGGL(gx_bgm_hmc_kernel, dim3(grid_for(h, (a->n + GX_ROWS - 1) / GX_ROWS, g->lds_bytes)), dim3(GX_THREADS), g->lds_bytes, stream, k);
