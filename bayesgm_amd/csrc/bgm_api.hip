@@ -10,13 +10,6 @@
 #include "bgm_launch.h"
 #include "gx_bgm_host.h"
 
-static constexpr int BGM_WAVES = 8;
-#ifndef BGM_WAVES_WIDE_HMC
-#define BGM_WAVES_WIDE_HMC 12   // 148 VGPRs -> 3 waves/SIMD; measured 89 vs 86 (8) vs 86 (16) TF at p=500
-#endif
-#ifndef BGM_SX3_WAVES_DEFAULT
-#define BGM_SX3_WAVES_DEFAULT 12      // ms per transition at N = 2e5, p = 500: 3.43 (8 waves, no spill) / 3.19 (12 waves, 168 registers); two 6-wave workgroups per CU: 4.0; two / three / four units per stream step: 3.12 / 3.24 / 3.34
-#endif
 static constexpr float BN_EPS_F = 1e-3f;   // keras BatchNormalization default epsilon
 
 void bgm_bgm_free_state(bgm_handle *h) {
@@ -175,7 +168,7 @@ static int bgm_build_sx3(BgmState *s, const std::vector<float> &blob, const floa
   return BGM_OK;
 }
 
-static int bgm_build_blob(bgm_handle *h, hipStream_t stream) {
+int bgm_bgm_build_blob(bgm_handle *h, hipStream_t stream) {
   BgmState *s = bst(h);
   if (s->blob_valid) return BGM_OK;
   if (!s->set) { bgm_set_error("BGM weights not set"); return BGM_E_STATE; }
@@ -225,7 +218,7 @@ extern "C" int bgm_bgm_logpost(bgm_handle *h, const float *z, const float *x, in
   hipStream_t stream = (hipStream_t)stream_;
   BGM_HIP_CHECK(hipSetDevice(h->device));
   if (gxb_wanted(bst(h))) return gxb_logpost(h, bst(h), z, x, n, out, grad, stream);
-  int rc = bgm_build_blob(h, stream);
+  int rc = bgm_bgm_build_blob(h, stream);
   if (rc) return rc;
   BgmState *s = bst(h);
   const int grid = bgm_tile_grid(h, (n + 15) / 16, BGM_WAVES);
@@ -253,7 +246,7 @@ extern "C" int bgm_bgm_hmc_run(bgm_handle *h, const bgm_hmc_args *a, void *strea
   hipStream_t stream = (hipStream_t)stream_;
   BGM_HIP_CHECK(hipSetDevice(h->device));
   if (gxb_wanted(bst(h))) return gxb_hmc_run(h, bst(h), a, stream);
-  int rc = bgm_build_blob(h, stream);
+  int rc = bgm_bgm_build_blob(h, stream);
   if (rc) return rc;
   BgmState *s = bst(h);
   BgmHmcKArgs ka{};
@@ -297,7 +290,7 @@ extern "C" int bgm_bgm_predict_draws(bgm_handle *h, const float *draws, int64_t 
   hipStream_t stream = (hipStream_t)stream_;
   BGM_HIP_CHECK(hipSetDevice(h->device));
   if (gxb_wanted(bst(h))) return gxb_predict_draws(h, bst(h), draws, n, row_base, n_draws, burn_in, seed, slot, k_slots, cells, full, var_full, add_noise, stream);
-  int rc = bgm_build_blob(h, stream);
+  int rc = bgm_bgm_build_blob(h, stream);
   if (rc) return rc;
   BgmState *s = bst(h);
   BgmPredKArgs ka{};

@@ -8,6 +8,17 @@
 
 #include "bgm_state.h"
 
+// ---- waves per workgroup of the posterior kernels, shared by the units that instantiate them (bgm_api.hip, bgm_rowstep_api.hip)
+static constexpr int BGM_WAVES = 8;
+#ifndef BGM_WAVES_WIDE_HMC
+#define BGM_WAVES_WIDE_HMC 12   // 148 VGPRs -> 3 waves/SIMD; measured 89 vs 86 (8) vs 86 (16) TF at p=500
+#endif
+#ifndef BGM_SX3_WAVES_DEFAULT
+#define BGM_SX3_WAVES_DEFAULT 12      // ms per transition at N = 2e5, p = 500: 3.43 (8 waves, no spill) / 3.19 (12 waves, 168 registers); two 6-wave workgroups per CU: 4.0; two / three / four units per stream step: 3.12 / 3.24 / 3.34
+#endif
+// the posterior blob of the handle's current weights and precision, packed and uploaded when it is not current (bgm_api.hip)
+int bgm_bgm_build_blob(bgm_handle *h, hipStream_t stream);
+
 // ---- compiled variants.  (KTQ, NTX, NH): z_dim <= 16; x_dim in (16, 32] / (96, 112] LDS-resident, NTX = 0 = wide (any x_dim, head weights
 // streamed through an LDS stage); 5 hidden layers (configs/*.yaml) or 3.  Split precision is always the streamed variant.
 template <int KTQ_, int NTX_, int NH_>

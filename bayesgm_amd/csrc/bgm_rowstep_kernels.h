@@ -1,0 +1,142 @@
+// bgm_rowstep_kernels.h -- BGM Hamiltonian Monte Carlo with a step size per chain, adapted by that chain alone during burn-in (gfx950).
+//
+// replaces: the one scalar step of tfp.mcmc.SimpleStepSizeAdaptation in tfp_mcmc_sampler (bgm/base.py:798-821), opt-in; the transition
+//   is bgm_hmc_kernel's (bgm_kernels.h) and the rule is causal_hmc_kernel's (causal_hmc_kernels.h): the Robbins-Monro table of
+//   row_adapt.py, ONE fp32 multiply and a clamp after the accept decision.
+//
+// A sibling of bgm_hmc_kernel rather than a flag on it: the scalar-step instantiations keep their names and their code.  Momentum,
+// accept uniform, initial state, leapfrog order, the non-finite-ratio rule, the tile deal of the streamed variant and the statistics
+// are those of bgm_hmc_kernel line for line; with every step equal and no table the two kernels give the same bits.  What differs:
+// eps is read from step[row] when a wave takes up a row tile (so a second pass reloads it), lives in a VGPR, is updated after the
+// decision of iteration it < n_table and written back with the state.  state, logp, grad and step travel between launches, so a
+// run cut at any iteration is the same run.
+#pragma once
+#include "bgm_kernels.h"
+
+struct BgmRowHmcKArgs : BgmHmcKArgs {      // (BgmHmcKArgs::step is not read)
+  float *row_step;           // [n] step size of every chain, in / out
+  const float *up, *dn;      // [n_table] factor after the decision of iteration it < n_table (moved / did not), or NULL: fixed steps
+  int n_table;
+  float s_min, s_max;
+};
+
+template <int KTQ, int NTX, int NH, int WAVES, int PREC = 0, bool X4 = false>
+__global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_kernel(BgmRowHmcKArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const BgmMeta &m = a.m;
+  lds_fill(lds, a.blob, m.lds_resident);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+  using HS = typename bgm_stream_of<PREC, WAVES, X4>::type;
+  HS hs;
+  if constexpr (PREC >= 1) hs.begin(a.hx3, m, lds);
+  else if constexpr (NTX == 0) hs.begin(a.blob, m, lds);
+  const long long n = a.n, n_tiles = (n + 15) / 16, passes = bgm_block_passes(n_tiles, WAVES);
+  for (long long ps = 0; ps < passes; ++ps) {
+    // (the tile deal of bgm_hmc_kernel: wave-major in the streamed variant, whose tile-less waves only keep the head stream moving)
+    long long tile = NTX == 0 ? (ps * WAVES + wave) * gridDim.x + blockIdx.x : (ps * gridDim.x + blockIdx.x) * WAVES + wave;
+    const bool tile_ok = tile < n_tiles;
+    if (NTX > 0 && !tile_ok) break;
+    if constexpr (NTX == 0) {
+      if (!tile_ok) {
+        const int evals = (a.init ? 1 : 0) + a.n_iters * a.n_leapfrog;
+        const int n_steps = PREC == 0 ? m.ntx : (m.ntx + BGM_X3_STEP - 1) / BGM_X3_STEP + (PREC == 2 ? 2 * ((NH + BGM_X3_STEP - 1) / BGM_X3_STEP) : 0);      // (steps of the stream per evaluation)
+        for (int e = 0; e < evals; ++e)
+          for (int tx = 0; tx < n_steps; ++tx) { hs.fetch(tx + 1 < n_steps ? tx + 1 : 0); hs.commit(); }
+        continue;
+      }
+    }
+    tile = tile_ok ? tile : n_tiles - 1;
+    long long row = tile * 16 + j;
+    const bool ok = tile_ok && row < n;
+    row = row < n ? row : n - 1;
+    const unsigned rowid = (unsigned)(a.row_base + row);
+    BgmX<NTX> xr;
+    f32x4 z[KTQ], gr[KTQ];
+    bgm_load_x<NTX>(a.x, n, m.p, row, g, xr);
+    if constexpr (PREC >= 1) hs.x_valid = false;       // (a new row: nothing of it has been requested ahead)
+    float eps = a.row_step[row];      // (every pass: the rows are new)
+    float lp;
+    if (a.init) {   // initial_state ~ N(0,1)  (bgm/base.py:778), RNG tag 0
+#pragma unroll
+      for (int t = 0; t < KTQ; ++t) {
+        const f32x4 e = box_muller4(philox4x32_10(rowid, 0u, (unsigned)(g + 4 * t), TAG_INIT, a.k0, a.k1));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) z[t][r] = (16 * t + 4 * r + g < m.q) ? e[r] : 0.0f;
+      }
+      bgm_logp_grad<KTQ, NTX, NH, true, PREC, HS>(lds, m, j, g, z, xr, hs, lp, gr);
+    } else {
+      bgm_load_z<KTQ>(a.state, m.q, row, g, z);
+      bgm_load_z<KTQ>(a.grad, m.q, row, g, gr);
+      lp = a.logp[row];
+    }
+    for (int it = a.it_begin; it < a.it_begin + a.n_iters; ++it) {
+      BGM_NO_HOIST();
+      f32x4 mom[KTQ], zc[KTQ], gc[KTQ];
+      float ke0 = 0.0f;
+#pragma unroll
+      for (int t = 0; t < KTQ; ++t) {
+        const f32x4 e = box_muller4(philox4x32_10(rowid, (unsigned)it, (unsigned)(g + 4 * t), TAG_MOM, a.k0, a.k1));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pm = (16 * t + 4 * r + g < m.q) ? e[r] : 0.0f;
+          ke0 = fmaf(pm, pm, ke0);
+          mom[t][r] = fmaf(0.5f * eps, gr[t][r], pm);   // first half kick
+          zc[t][r] = z[t][r];
+        }
+      }
+      ke0 = sum_over_g(ke0);
+      float lpc = lp;
+      for (int l = 0; l < a.n_leapfrog; ++l) {
+        BGM_NO_HOIST();
+#pragma unroll
+        for (int t = 0; t < KTQ; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) zc[t][r] = fmaf(eps, mom[t][r], zc[t][r]);
+        bgm_logp_grad<KTQ, NTX, NH, true, PREC, HS>(lds, m, j, g, zc, xr, hs, lpc, gc, PREC == 0 || l == a.n_leapfrog - 1);
+        const float kick = (l < a.n_leapfrog - 1) ? eps : 0.5f * eps;
+#pragma unroll
+        for (int t = 0; t < KTQ; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) mom[t][r] = fmaf(kick, gc[t][r], mom[t][r]);
+      }
+      float ke1 = 0.0f;
+#pragma unroll
+      for (int t = 0; t < KTQ; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ke1 = fmaf(mom[t][r], mom[t][r], ke1);
+      ke1 = sum_over_g(ke1);
+      float log_ratio = -((-lpc + 0.5f * ke1) - (-lp + 0.5f * ke0));
+      log_ratio = (log_ratio == log_ratio && fabsf(log_ratio) != INFINITY) ? log_ratio : -INFINITY;
+      const uint4 w4 = philox4x32_10(rowid, (unsigned)it >> 2, 0u, TAG_HACC, a.k0, a.k1);
+      const unsigned w_ = (it & 2) ? ((it & 1) ? w4.w : w4.z) : ((it & 1) ? w4.y : w4.x);
+      const float u = u01_open(w_);
+      const bool acc = logf(u) < log_ratio;
+#pragma unroll
+      for (int t = 0; t < KTQ; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          z[t][r] = acc ? zc[t][r] : z[t][r];
+          gr[t][r] = acc ? gc[t][r] : gr[t][r];
+        }
+      lp = acc ? lpc : lp;
+      if (a.up != nullptr && it < a.n_table) eps = fminf(fmaxf(eps * (acc ? a.up : a.dn)[it], a.s_min), a.s_max);
+      // per-iteration statistics of the acceptance report
+      {
+        float pa = (ok && g == 0) ? expf(fminf(log_ratio, 0.0f)) : 0.0f;
+        for (int off = 8; off > 0; off >>= 1) pa += __shfl_xor(pa, off);
+        const unsigned cnt = (unsigned)__popcll(__ballot(acc && ok && g == 0));
+        if (lane == 0) {
+          if (a.acc_prob_sum) atomicAdd(a.acc_prob_sum + it, (double)pa);
+          if (a.acc_count) atomicAdd(a.acc_count + it, cnt);
+        }
+      }
+      if (a.draws != nullptr && it >= a.burn_in && ok)
+        bgm_store_z<KTQ>(a.draws + (long long)(it - a.burn_in) * n * m.q, m.q, row, g, z);
+    }
+    if (ok) {
+      bgm_store_z<KTQ>(a.state, m.q, row, g, z);
+      bgm_store_z<KTQ>(a.grad, m.q, row, g, gr);
+      if (g == 0) { a.logp[row] = lp; a.row_step[row] = eps; }
+    }
+  }
+}

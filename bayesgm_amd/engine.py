@@ -682,8 +682,8 @@ class BgmEngine(object):
                    "bgm_bgm_logpost")
         return (out, grad) if want_grad else out
 
-    def hmc_run(self, x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
-                row_base=0, acc_prob=None, acc_count=None, draws=None):
+    @staticmethod
+    def _hmc_args(x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, acc_prob, acc_count, draws):
         a = _lib.HmcArgs()
         a.x_dev = x.data_ptr(); a.n = x.shape[0]; a.row_base = int(row_base)
         a.state_dev, a.logp_dev, a.grad_dev = state.data_ptr(), logp.data_ptr(), grad.data_ptr()
@@ -692,17 +692,37 @@ class BgmEngine(object):
         a.acc_prob_sum_dev = acc_prob.data_ptr() if acc_prob is not None else None
         a.acc_count_dev = acc_count.data_ptr() if acc_count is not None else None
         a.draws_dev = draws.data_ptr() if draws is not None else None
+        return a
+
+    def hmc_run(self, x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
+                row_base=0, acc_prob=None, acc_count=None, draws=None):
+        a = self._hmc_args(x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, acc_prob, acc_count,
+                           draws)
         _lib.check(self.lib.bgm_bgm_hmc_run(self.h, C.byref(a), self._stream()), "bgm_bgm_hmc_run")
+
+    def hmc_run_rows(self, x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False, row_base=0, up=None,
+                     dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_prob=None, acc_count=None, draws=None):
+        """hmc_run with a step size per chain (bgm_bgm_hmc_run_rows): step float32 [n], in / out; up / dn: the factor tables of
+        row_adapt.row_adapt_factors on the device (None: the steps stay as given)."""
+        a = self._hmc_args(x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, acc_prob, acc_count,
+                           draws)
+        _lib.check(self.lib.bgm_bgm_hmc_run_rows(self.h, C.byref(a), _ptr(up), _ptr(dn), 0 if up is None else int(up.numel()), float(s_min),
+                                                 float(s_max), self._stream()), "bgm_bgm_hmc_run_rows")
 
     def hmc_adapt(self, step, acc_prob, it, n_chains, target=0.75, rate=0.01):
         _lib.check(self.lib.bgm_bgm_hmc_adapt(self.h, _ptr(step), _ptr(acc_prob), int(it), float(n_chains),
                                               float(target), float(rate), self._stream()), "bgm_bgm_hmc_adapt")
 
     def hmc_sample(self, x, n_mcmc, burn_in, step_size=0.01, n_leapfrog=10, seed=42, row_base=0, want_draws=True,
-                   n_chains_global=None, reduce_fn=None):
+                   n_chains_global=None, reduce_fn=None, row_adapt=None):
         """tfp_mcmc_sampler (bgm/base.py:709-830): HMC + SimpleStepSizeAdaptation over int(0.8*burn_in)
         steps, all rows one chain each.  `reduce_fn(tensor)` all-reduces the per-iteration acceptance
-        statistic across ranks (the step size is shared by ALL chains)."""
+        statistic across ranks (the step size is shared by ALL chains).
+
+        row_adapt = target acceptance rate in (0, 1) (opt-in): every chain carries a step of its own instead, starting at step_size and
+        multiplied after each of the burn_in decisions by the factor of row_adapt.row_adapt_factors(burn_in, row_adapt) for "moved" /
+        "did not"; burn-in and retained draws run in ONE launch, reduce_fn is not called, and the result holds row_step [n] instead
+        of step."""
         dev = self.device
         x = _f32(x, dev)
         n = x.shape[0]
@@ -714,6 +734,13 @@ class BgmEngine(object):
         acc_prob = torch.zeros(total, device=dev, dtype=torch.float64)
         acc_count = torch.zeros(total, device=dev, dtype=torch.int32)
         draws = torch.empty((n_mcmc, n, self.q), device=dev) if want_draws else None
+        if row_adapt is not None:
+            up, dn = self.row_step_table(burn_in, row_adapt)
+            step = torch.full((n,), float(step_size), device=dev, dtype=torch.float32)
+            if total > 0:
+                self.hmc_run_rows(x, state, logp, grad, step, 0, total, burn_in, n_leapfrog, seed, init=True, row_base=row_base, up=up,
+                                  dn=dn, acc_prob=acc_prob, acc_count=acc_count, draws=draws)
+            return dict(state=state, logp=logp, grad=grad, row_step=step, acc_prob=acc_prob, acc_count=acc_count, draws=draws)
         n_adapt = int(burn_in * 0.8)
         n_all = float(n_chains_global if n_chains_global is not None else n)
         it = 0
@@ -728,6 +755,13 @@ class BgmEngine(object):
             self.hmc_run(x, state, logp, grad, step, it, total - it, burn_in, n_leapfrog, seed, init=(it == 0),
                          row_base=row_base, acc_prob=acc_prob, acc_count=acc_count, draws=draws)
         return dict(state=state, logp=logp, grad=grad, step=step, acc_prob=acc_prob, acc_count=acc_count, draws=draws)
+
+    def row_step_table(self, burn_in, target):
+        """(up, dn) of row_adapt.row_adapt_factors(burn_in, target) on the device, or (None, None) when burn_in = 0 (nothing adapts)."""
+        up, dn = RA.row_adapt_factors(burn_in, target)      # (refuses a target outside (0, 1))
+        if up.size == 0:
+            return None, None
+        return _f32(up, self.device), _f32(dn, self.device)
 
     def predict_draws(self, draws, burn_in, seed, slot=None, k_slots=0, want_full=False, row_base=0, want_var=False,
                       add_noise=True):

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import parallel
+from .. import row_adapt as row_adapt_mod
 from ..engine import BgmEngine
 from ..datasets import Gaussian_sampler
 
@@ -29,6 +30,7 @@ def _glorot(rs, fan_in, fan_out):
 
 class BGM(object):
     mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last tfp_mcmc_sampler(diagnostics=True)
+    hmc_row_step_ = None             # per-row HMC step sizes (NumPy, global row order) of the last predict / tfp_mcmc_sampler call with row_adapt; None when it ran without
 
     def __new__(cls, params=None, *args, **kwargs):
         if cls is BGM and isinstance(params, dict) and params.get("use_bnn", _DEFAULTS["use_bnn"]):
@@ -341,9 +343,14 @@ class BGM(object):
         return self.engine.logpost(self._dev(data_z), self._dev(x)).cpu().numpy()
 
     def tfp_mcmc_sampler(self, data, ind_x1=None, n_mcmc=3000, burn_in=5000, step_size=0.01, num_leapfrog_steps=10,
-                         seed=42, diagnostics=False):
+                         seed=42, diagnostics=False, row_adapt=False):
         """Posterior samples of Z, shape (n_mcmc, n, z_dim) (bgm/base.py:709-830).  diagnostics=True: split R-hat / effective
-        sample size of every chain, computed on the device before the copy to the host, in ``self.mcmc_diagnostics_``."""
+        sample size of every chain, computed on the device before the copy to the host, in ``self.mcmc_diagnostics_``.
+        row_adapt (opt-in; True = target acceptance 0.75, or a target in (0, 1)): every chain adapts a step size of its own over the
+        whole burn-in, starting from ``step_size``, instead of the one step shared by all chains (row_adapt.py); the steps are left
+        in ``self.hmc_row_step_``."""
+        target = row_adapt_mod.resolve_step_target(row_adapt)
+        self.hmc_row_step_ = None
         x = np.array(data, dtype=np.float32, copy=True)
         if ind_x1 is not None:
             keep = np.zeros(x.shape, bool)
@@ -355,7 +362,9 @@ class BGM(object):
             else:
                 keep[:, list(ind_x1)] = True
             x[~keep] = np.nan
-        out = self.engine.hmc_sample(self._dev(x), n_mcmc, burn_in, step_size, num_leapfrog_steps, seed)
+        out = self.engine.hmc_sample(self._dev(x), n_mcmc, burn_in, step_size, num_leapfrog_steps, seed, row_adapt=target)
+        if target is not None:
+            self.hmc_row_step_ = out["row_step"].cpu().numpy()
         self.last_acceptance_rate = float(out["acc_count"][burn_in:].sum().item()) / max(1, n_mcmc * x.shape[0])
         print(f"TFP MCMC Acceptance Rate: {self.last_acceptance_rate:.4f}")
         if diagnostics:
@@ -397,13 +406,19 @@ class BGM(object):
 
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.05, return_samples=False, bs=100, n_mcmc=5000, burn_in=5000, step_size=0.01,
-                num_leapfrog_steps=10, seed=42, max_draw_bytes=64 << 30):
+                num_leapfrog_steps=10, seed=42, max_draw_bytes=64 << 30, row_adapt=False):
         """Posterior-predictive imputation of the NaN cells (bgm/base.py:527-663).
 
         HMC burn-in (with the shared step-size adaptation) runs over ALL rows at once as in the reference;
         the sampling phase then runs in row blocks sized so that the latent draws and the predictive cells of
-        a block stay below ``max_draw_bytes`` (the reference materialises [n_mcmc, n, x_dim] on the host)."""
+        a block stay below ``max_draw_bytes`` (the reference materialises [n_mcmc, n, x_dim] on the host).
+
+        ``row_adapt`` (opt-in; True = target acceptance 0.75, or a target in (0, 1)): every chain adapts a step size of its own over
+        the whole burn-in, starting from ``step_size`` (row_adapt.py).  Burn-in is then one launch per rank with no all-reduce, a
+        chain depends on (seed, global row, the row's data) only, and the steps are left in ``self.hmc_row_step_`` [n]."""
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
+        target = row_adapt_mod.resolve_step_target(row_adapt)
+        self.hmc_row_step_ = None
         parallel.check_n_mcmc(n_mcmc)
         import time as _time
         _t = {"_last": _time.perf_counter()}
@@ -432,15 +447,23 @@ class BGM(object):
         acc_prob = torch.zeros(total, device=dev, dtype=torch.float64)
         acc_count = torch.zeros(total, device=dev, dtype=torch.int32)
         n_adapt = int(burn_in * 0.8)
+        if target is not None:      # a step per chain: the whole burn-in adapts, in one launch, and no statistic crosses rows or ranks
+            step = torch.full((n_loc,), float(step_size), device=dev)
+            up, dn = eng.row_step_table(burn_in, target)
         _mark("setup_h2d")
-        for it in range(n_adapt):
-            eng.hmc_run(x, state, logp, grad, step, it, 1, burn_in, num_leapfrog_steps, seed, init=(it == 0),
-                        row_base=lo_r, acc_prob=acc_prob, acc_count=acc_count)
-            parallel.all_reduce_sum_(acc_prob[it:it + 1])
-            eng.hmc_adapt(step, acc_prob, it, n)
-        if burn_in > n_adapt:
-            eng.hmc_run(x, state, logp, grad, step, n_adapt, burn_in - n_adapt, burn_in, num_leapfrog_steps, seed,
-                        init=(n_adapt == 0), row_base=lo_r, acc_prob=acc_prob, acc_count=acc_count)
+        if target is not None:
+            if burn_in > 0:
+                eng.hmc_run_rows(x, state, logp, grad, step, 0, burn_in, burn_in, num_leapfrog_steps, seed, init=True, row_base=lo_r,
+                                 up=up, dn=dn, acc_prob=acc_prob, acc_count=acc_count)
+        else:
+            for it in range(n_adapt):
+                eng.hmc_run(x, state, logp, grad, step, it, 1, burn_in, num_leapfrog_steps, seed, init=(it == 0),
+                            row_base=lo_r, acc_prob=acc_prob, acc_count=acc_count)
+                parallel.all_reduce_sum_(acc_prob[it:it + 1])
+                eng.hmc_adapt(step, acc_prob, it, n)
+            if burn_in > n_adapt:
+                eng.hmc_run(x, state, logp, grad, step, n_adapt, burn_in - n_adapt, burn_in, num_leapfrog_steps, seed,
+                            init=(n_adapt == 0), row_base=lo_r, acc_prob=acc_prob, acc_count=acc_count)
         _mark("burn_in")
         # ---- sampling + predictive draws per row block (slot maps, moments and the imputation stay in HBM)
         miss_dev = torch.isnan(x)
@@ -462,8 +485,12 @@ class BGM(object):
         for s in range(0, n_loc, rows_blk):
             e = min(s + rows_blk, n_loc)
             draws = torch.empty((n_mcmc, e - s, q), device=dev)
-            eng.hmc_run(x[s:e], state[s:e], logp[s:e], grad[s:e], step, burn_in, n_mcmc, burn_in, num_leapfrog_steps,
-                        seed, init=(burn_in == 0), row_base=lo_r + s, acc_count=acc_count, draws=draws)
+            if target is not None:      # (frozen from here on: every iteration lies behind the table)
+                eng.hmc_run_rows(x[s:e], state[s:e], logp[s:e], grad[s:e], step[s:e], burn_in, n_mcmc, burn_in, num_leapfrog_steps,
+                                 seed, init=(burn_in == 0), row_base=lo_r + s, acc_count=acc_count, draws=draws)
+            else:
+                eng.hmc_run(x[s:e], state[s:e], logp[s:e], grad[s:e], step, burn_in, n_mcmc, burn_in, num_leapfrog_steps,
+                            seed, init=(burn_in == 0), row_base=lo_r + s, acc_count=acc_count, draws=draws)
             cells = full = None
             if k_slots > 0 or return_samples:
                 cells, full = eng.predict_draws(draws, burn_in, seed, slot=slot_dev[s:e] if k_slots > 0 else None,
@@ -484,6 +511,8 @@ class BGM(object):
         # imputation: observed cells as given, missing cells = posterior-predictive mean
         imputed_dev = torch.where(miss_dev, means.gather(1, slot_dev.clamp(min=0).long()), torch.nan_to_num(x, nan=0.0)) \
             if k_slots > 0 else x.clone()
+        if target is not None:
+            self.hmc_row_step_ = parallel.all_gather_rows(step, n).cpu().numpy()
         if parallel.is_dist():
             means, los, his = (parallel.all_gather_rows(a_, n) for a_ in (means, los, his))
             imputed_dev = parallel.all_gather_rows(imputed_dev, n)

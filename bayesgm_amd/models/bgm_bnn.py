@@ -62,6 +62,13 @@ def block_plan(lo_r, n_loc, bs, rows_chunk):
     return plan
 
 
+def _refuse_row_adapt(row_adapt):
+    """The HMC step per chain (BGM.predict / tfp_mcmc_sampler, row_adapt) exists for the deterministic generator only."""
+    if not (row_adapt is None or (isinstance(row_adapt, (bool, np.bool_)) and not row_adapt)):
+        raise ValueError("row_adapt is not available with params['use_bnn'] = True: the Bayesian generator's HMC kernels have the shared "
+                         "step size only; got row_adapt=%r" % (row_adapt,))
+
+
 class BGMBayes(BGM):
     def __init__(self, params, timestamp=None, random_seed=None, device=None):
         self.params = params
@@ -367,9 +374,10 @@ class BGMBayes(BGM):
         return self.engine.logpost(self._dev(data_z), self._dev(x), self._new_seed() if seed is None else seed, 0).cpu().numpy()
 
     def tfp_mcmc_sampler(self, data, ind_x1=None, n_mcmc=3000, burn_in=5000, step_size=0.01, num_leapfrog_steps=10, seed=42,
-                         diagnostics=False):
+                         diagnostics=False, row_adapt=False):
         """Posterior samples of Z, shape (n_mcmc, n, z_dim) (bgm/base.py:709-830), stochastic target.  diagnostics=True: as
-        BGM.tfp_mcmc_sampler."""
+        BGM.tfp_mcmc_sampler.  row_adapt: BGM's keyword, refused here for anything but False."""
+        _refuse_row_adapt(row_adapt)
         x = np.array(data, dtype=np.float32, copy=True)
         if ind_x1 is not None:
             keep = np.zeros(x.shape, bool)
@@ -404,9 +412,11 @@ class BGMBayes(BGM):
 
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.05, return_samples=False, bs=100, n_mcmc=5000, burn_in=5000, step_size=0.01,
-                num_leapfrog_steps=10, seed=42, max_draw_bytes=16 << 30):
+                num_leapfrog_steps=10, seed=42, max_draw_bytes=16 << 30, row_adapt=False):
         """Posterior-predictive imputation of the NaN cells (bgm/base.py:527-663).  HMC over ALL rows as in the reference
-        (one generator call per gradient evaluation), then one predictive generator call per block of `bs` rows."""
+        (one generator call per gradient evaluation), then one predictive generator call per block of `bs` rows.  row_adapt: BGM's
+        keyword, refused here for anything but False."""
+        _refuse_row_adapt(row_adapt)
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         self._warn_fresh_noise()

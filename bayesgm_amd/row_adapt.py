@@ -49,6 +49,23 @@ def resolve_target(row_adapt):
     return t
 
 
+STEP_DEFAULT_TARGET = 0.75        # BGM's HMC step per chain: the target of the shared rule (bgm/base.py:805-809) and causal_hmc.DEFAULT_TARGET
+
+
+def resolve_step_target(row_adapt):
+    """``row_adapt`` of BGM.predict / tfp_mcmc_sampler / BgmEngine.hmc_sample (an HMC step size per chain) -> None (off) or the target
+    acceptance rate: False / None = off, True = 0.75, a number in (0, 1) = that target."""
+    if row_adapt is None or (isinstance(row_adapt, (bool, np.bool_)) and not row_adapt):
+        return None
+    if isinstance(row_adapt, (bool, np.bool_)):
+        return STEP_DEFAULT_TARGET
+    t = float(row_adapt) if isinstance(row_adapt, (int, float, np.integer, np.floating)) else float("nan")
+    if not (0.0 < t < 1.0):
+        raise ValueError("row_adapt must be False, True (target acceptance %.2f) or a target acceptance rate in (0, 1); got %r"
+                         % (STEP_DEFAULT_TARGET, row_adapt))
+    return t
+
+
 def start_scale(q_sd, initial_q_sd=1.0):
     """Scale every chain starts from: ``q_sd`` if positive, else ``initial_q_sd``, else 1."""
     for s in (q_sd, initial_q_sd):

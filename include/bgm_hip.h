@@ -613,6 +613,22 @@ BGM_API int bgm_bgm_set_precision(bgm_handle *h, int32_t mode);
 BGM_API int bgm_bgm_hmc_adapt(bgm_handle *h, float *step_dev, const double *acc_prob_sum_dev, int32_t it,
                       double n_chains, float target, float rate, void *stream);
 
+/* bgm_bgm_hmc_run with a step size per chain (opt-in): the same transition, argument struct and Philox streams, but
+ * args->step_dev holds args->n floats, in and out -- chain r reads its step from step_dev[r] at the start of the launch and the
+ * launch writes it back, so state_dev, logp_dev, grad_dev and step_dev carry a run from one call to the next and a run cut into
+ * segments at any iteration is bit-identical to one call.  up_dev / dn_dev [n_table]: after the accept decision of iteration
+ * it < n_table a chain's step is multiplied by up_dev[it] (it moved) or dn_dev[it] (it did not) and clamped to [s_min, s_max]: one
+ * fp32 multiply, the table of bgm_causal_hmc_run (row_adapt.py).  up_dev = dn_dev = NULL: the steps stay as given, and with every
+ * step equal the call is bit-identical to bgm_bgm_hmc_run with that scalar.  A chain depends on (seed, row_base + r, its row of
+ * x_dev) only, not on the other rows, blocks or ranks.  acc_prob_sum_dev / acc_count_dev / draws_dev as in bgm_bgm_hmc_run.
+ * BGM_E_INVALID: one of up_dev / dn_dev alone, n_table < 0, a clamp outside 0 < s_min <= s_max < inf, a NULL data pointer,
+ * n_leapfrog < 1, a row index beyond the 32-bit RNG counter.  BGM_E_UNSUPPORTED (the handle stays usable): trunks other than
+ * [64] x 3 / [64] x 5 or z_dim > 16, which run on the general-width engine; that engine and the Bayesian generator (bgm_bvn_*) have
+ * the shared step only.  Both precisions of bgm_bgm_set_precision are served.
+ * replaces: tfp.mcmc.SimpleStepSizeAdaptation's one step for all chains in tfp_mcmc_sampler, bgm/base.py:798-821 (opt-in). */
+BGM_API int bgm_bgm_hmc_run_rows(bgm_handle *h, const bgm_hmc_args *args, const float *up_dev, const float *dn_dev, int32_t n_table,
+                                 float s_min, float s_max, void *stream);
+
 /* Posterior-predictive draws x ~ N(mu(z_d), sigma^2(z_d)) for draws_dev [n_draws x n x q]:
  * full_dev [n_draws x n x p] (or NULL) and / or cells_dev [(row*k_slots + slot)*n_draws + d] for
  * the cells with slot_dev[row*p + c] >= 0 (or NULL); var_full_dev [n_draws x n x p] receives sigma^2
