@@ -120,6 +120,17 @@ __device__ __forceinline__ float softplus_f(float x) {
   return vmax(x, 0.0f) + l;
 }
 
+// softplus to the relative accuracy of its argument at every x (the general-width engine's variance heads): log(1 + e) from the ROUNDED
+// u = 1 + e is log(u) * e / (u - 1) -- u - 1 is exact and the quotient undoes the rounding of the sum.  softplus_f's plain log(1 + e)
+// is off by up to 2^-24 / e relative (2e-5 at x = -6), and a learned variance softplus(x) + eps divides a squared residual: a row with
+// |log p| ~ 500 from a treatment head at raw = -5.9 missed the log-posterior bar 1e-5 |log p| + 1e-3 (tests/test_gpu_gx_edges.py, part B).
+__device__ __forceinline__ float softplus_rel(float x) {
+  const float e = fast_exp(-fabsf(x));
+  const float u = 1.0f + e;
+  const float l = (e < 2.44140625e-4f) ? e * (1.0f - 0.5f * e) : fast_log(u) * (e * fast_rcp(u - 1.0f));
+  return vmax(x, 0.0f) + l;
+}
+
 // accurate (libm) forms, used where a value is reported or differentiated in the fit path
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float softplus_acc(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }

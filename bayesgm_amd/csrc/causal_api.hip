@@ -95,6 +95,11 @@ extern "C" int bgm_causal_configure(bgm_handle *h, const bgm_causal_config *cfg)
   if (p < 1 || q < 1 || cfg->z_dims[0] < 0 || cfg->z_dims[1] < 0 || cfg->z_dims[2] < 0 || cfg->z_dims[3] < 0) {
     bgm_set_error("bgm_causal_configure: bad v_dim / z_dims"); return BGM_E_INVALID;
   }
+  // h maps (z0, z2) to the treatment: with both empty its first layer has no input, and no kernel family contracts a zero-wide layer
+  // (gx_dense_ld always issues one K block: it would read the next parameters of the pack as weights)
+  if (cfg->z_dims[0] + cfg->z_dims[2] < 1) {
+    bgm_set_error("bgm_causal_configure: z_dims[0] + z_dims[2] = 0 leaves the treatment network h without an input"); return BGM_E_INVALID;
+  }
   for (int n : {cfg->n_hidden_g, cfg->n_hidden_f, cfg->n_hidden_h, cfg->n_hidden_e})
     if (n < 1 || n > BGM_MAX_LAYERS) { bgm_set_error("bgm_causal_configure: hidden layer count out of range"); return BGM_E_INVALID; }
   // Any hidden widths / depths (networks/base.py:7-28 takes any nb_units): the reference defaults (g_units [64]*k, f_units = h_units =

@@ -211,18 +211,18 @@ __device__ __forceinline__ float gw_causal_logp(const GxCausalModel &m, const Gw
     const int r = lane;
     long long gr = row0 + r; gr = gr < n ? gr : n - 1;
     const float sse = L.ssq[r];
-    const float s2v = (m.sig2_v > 0.0f) ? m.sig2_v : softplus_f(L.sraw[r]) + BGM_EPS;
+    const float s2v = (m.sig2_v > 0.0f) ? m.sig2_v : softplus_rel(L.sraw[r]) + BGM_EPS;
     const float xr = x[gr], yr = y[gr];
     float loss_x;
     if (m.binary) {
       const float l = mu_x, e = fast_exp(-fabsf(l));
       loss_x = vmax(l, 0.0f) - l * xr + ((e < 2.44140625e-4f) ? e * (1.0f - 0.5f * e) : fast_log(1.0f + e));
     } else {
-      const float s2x = (m.sig2_x > 0.0f) ? m.sig2_x : softplus_f(raw_x) + BGM_EPS;
+      const float s2x = (m.sig2_x > 0.0f) ? m.sig2_x : softplus_rel(raw_x) + BGM_EPS;
       const float dx = xr - mu_x;
       loss_x = 0.5f * (dx * dx * fast_rcp(s2x) + fast_log(s2x));
     }
-    const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_f(raw_y) + BGM_EPS;
+    const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_rel(raw_y) + BGM_EPS;
     const float dy = yr - mu_y;
     const float loss_y = 0.5f * (dy * dy * fast_rcp(s2y) + fast_log(s2y));
     float prior;
@@ -293,7 +293,7 @@ __device__ __forceinline__ void gw_causal_effects(const GxCausalModel &m, const 
         const float *fo = gw_f_rows<X3>(m, L, z, [&](int) { return ch; }, [&](int) { return xval(k); }, 1);
         if (lane < GW_ROWS && okp) {
           const float mean = fo[lane * m.ldf];
-          const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_f(fo[lane * m.ldf + 1]) + BGM_EPS;
+          const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_rel(fo[lane * m.ldf + 1]) + BGM_EPS;
           e.cache[k * GW_ROWS + ch] = make_float2(mean, __builtin_sqrtf(s2y));
         }
       }
@@ -310,7 +310,7 @@ __device__ __forceinline__ void gw_causal_effects(const GxCausalModel &m, const 
       if (lane < GW_ROWS) {
         if (!cached) {
           mean = fo[(GW_ROWS * dd + lane) * m.ldf];
-          const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_f(fo[(GW_ROWS * dd + lane) * m.ldf + 1]) + BGM_EPS;
+          const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_rel(fo[(GW_ROWS * dd + lane) * m.ldf + 1]) + BGM_EPS;
           sd = __builtin_sqrtf(s2y);
         } else {
           const float *cp = reinterpret_cast<const float *>(e.cache + k * GW_ROWS + lane);

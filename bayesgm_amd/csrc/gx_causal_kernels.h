@@ -190,7 +190,7 @@ __device__ __forceinline__ void gx_causal_logp(const GxCausalModel &m, const GxL
     long long gr = row0 + r; gr = gr < n ? gr : n - 1;
     float sse = 0.0f;
     for (int c = 0; c < m.ncg; ++c) sse += L.ssep[c * GX_ROWS + r];
-    const float s2v = (m.sig2_v > 0.0f) ? m.sig2_v : softplus_f(L.sraw[r]) + BGM_EPS;
+    const float s2v = (m.sig2_v > 0.0f) ? m.sig2_v : softplus_rel(L.sraw[r]) + BGM_EPS;
     const float xr = x[gr], yr = y[gr];
     const float mu_x = L.ho[2 * r], mu_y = L.fo[2 * r];
     float loss_x;
@@ -198,11 +198,11 @@ __device__ __forceinline__ void gx_causal_logp(const GxCausalModel &m, const GxL
       const float l = mu_x, e = fast_exp(-fabsf(l));
       loss_x = vmax(l, 0.0f) - l * xr + ((e < 2.44140625e-4f) ? e * (1.0f - 0.5f * e) : fast_log(1.0f + e));
     } else {
-      const float s2x = (m.sig2_x > 0.0f) ? m.sig2_x : softplus_f(L.ho[2 * r + 1]) + BGM_EPS;
+      const float s2x = (m.sig2_x > 0.0f) ? m.sig2_x : softplus_rel(L.ho[2 * r + 1]) + BGM_EPS;
       const float dx = xr - mu_x;
       loss_x = 0.5f * (dx * dx * fast_rcp(s2x) + fast_log(s2x));
     }
-    const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_f(L.fo[2 * r + 1]) + BGM_EPS;
+    const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_rel(L.fo[2 * r + 1]) + BGM_EPS;
     const float dy = yr - mu_y;
     const float loss_y = 0.5f * (dy * dy * fast_rcp(s2y) + fast_log(s2y));
     float prior;
@@ -285,7 +285,7 @@ __device__ __forceinline__ void gx_causal_effects(const GxCausalModel &m, const 
           const int pi = p0 + r;
           if (pi < npairs) {
             const int ci = pi / nd, k = pi - ci * nd;
-            const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_f(L.fo[2 * r + 1]) + BGM_EPS;
+            const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_rel(L.fo[2 * r + 1]) + BGM_EPS;
             e.cache[k * GX_ROWS + list[ci]] = make_float2(L.fo[2 * r], __builtin_sqrtf(s2y));
           }
         }
@@ -306,7 +306,7 @@ __device__ __forceinline__ void gx_causal_effects(const GxCausalModel &m, const 
         float mean, sd;
         if (!cached) {
           mean = L.fo[2 * (GX_ROWS * dd + r)];
-          const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_f(L.fo[2 * (GX_ROWS * dd + r) + 1]) + BGM_EPS;
+          const float s2y = (m.sig2_y > 0.0f) ? m.sig2_y : softplus_rel(L.fo[2 * (GX_ROWS * dd + r) + 1]) + BGM_EPS;
           sd = __builtin_sqrtf(s2y);
         } else {
           const float *cp = reinterpret_cast<const float *>(e.cache + k * GX_ROWS + r);
