@@ -1,6 +1,8 @@
 // bgm_rowstep_api.hip -- BGM HMC with a step size per chain, adapted by that chain alone during burn-in (bgm_bgm_hmc_run_rows,
 // include/bgm_hip.h): the instantiations of bgm_hmc_rows_kernel (bgm_rowstep_kernels.h) for every variant of bgm_launch.h, fp32 and
-// split precision, at the wave counts of their scalar-step twins -- kept in their own translation unit.  The default path
+// split precision, at the wave counts of their scalar-step twins -- kept in their own translation unit.  bgm_bgm_hmc_run_rows_traj
+// adds the number of leapfrog steps per chain: bgm_hmc_rows_traj_kernel for every variant, launched only when a cap, the jitter
+// or the step count is asked for, so the plain per-chain step runs the kernels it ran before.  The default path
 // (bgm_api.hip, bgm_bgm_hmc_run + bgm_bgm_hmc_adapt) is untouched.
 // replaces: the shared step of tfp.mcmc.SimpleStepSizeAdaptation in tfp_mcmc_sampler (bgm/base.py:798-821), opt-in.
 #include <cmath>
@@ -11,21 +13,29 @@
 #include "bgm_launch.h"
 #include "gx_bgm_host.h"
 
-extern "C" int bgm_bgm_hmc_run_rows(bgm_handle *h, const bgm_hmc_args *a, const float *up_dev, const float *dn_dev, int32_t n_table,
-                                    float s_min, float s_max, void *stream_) {
-  if (!h || !h->bgm_state || !bst(h)->configured) { bgm_set_error("bgm_bgm_hmc_run_rows: not configured"); return BGM_E_STATE; }
-  if (!a) { bgm_set_error("bgm_bgm_hmc_run_rows: NULL args"); return BGM_E_INVALID; }
-  if ((up_dev == nullptr) != (dn_dev == nullptr)) { bgm_set_error("bgm_bgm_hmc_run_rows: up_dev and dn_dev must both be given or both be NULL"); return BGM_E_INVALID; }
-  if (n_table < 0) { bgm_set_error("bgm_bgm_hmc_run_rows: n_table must be >= 0"); return BGM_E_INVALID; }
-  if (!(s_min > 0.0f) || !(s_max >= s_min) || !std::isfinite(s_max)) { bgm_set_error("bgm_bgm_hmc_run_rows: the clamp needs 0 < s_min <= s_max < inf"); return BGM_E_INVALID; }
+// the two entries' common body; traj = nullptr: bgm_bgm_hmc_run_rows
+struct BgmTrajOpts { float max_trajectory; int jitter; int *n_steps; };
+
+static int bgm_hmc_rows_run(const char *fn_, bgm_handle *h, const bgm_hmc_args *a, const float *up_dev, const float *dn_dev, int32_t n_table,
+                            float s_min, float s_max, const BgmTrajOpts *traj, void *stream_) {
+  const std::string fn = std::string(fn_) + ": ";
+  if (!h || !h->bgm_state || !bst(h)->configured) { bgm_set_error(fn + "not configured"); return BGM_E_STATE; }
+  if (!a) { bgm_set_error(fn + "NULL args"); return BGM_E_INVALID; }
+  if ((up_dev == nullptr) != (dn_dev == nullptr)) { bgm_set_error(fn + "up_dev and dn_dev must both be given or both be NULL"); return BGM_E_INVALID; }
+  if (n_table < 0) { bgm_set_error(fn + "n_table must be >= 0"); return BGM_E_INVALID; }
+  if (!(s_min > 0.0f) || !(s_max >= s_min) || !std::isfinite(s_max)) { bgm_set_error(fn + "the clamp needs 0 < s_min <= s_max < inf"); return BGM_E_INVALID; }
+  if (traj) {
+    if (!(traj->max_trajectory >= 0.0f) || !std::isfinite(traj->max_trajectory)) { bgm_set_error(fn + "max_trajectory must be 0 (no cap) or a finite number > 0"); return BGM_E_INVALID; }
+    if (traj->jitter != 0 && traj->jitter != 1) { bgm_set_error(fn + "jitter must be 0 or 1"); return BGM_E_INVALID; }
+  }
   if (a->n <= 0 || a->n_iters <= 0) return BGM_OK;
   const char *null_arg = !a->x_dev ? "x_dev" : !a->state_dev ? "state_dev" : !a->logp_dev ? "logp_dev" : !a->grad_dev ? "grad_dev" : !a->step_dev ? "step_dev" : nullptr;
-  if (null_arg) { bgm_set_error(std::string("bgm_bgm_hmc_run_rows: NULL pointer ") + null_arg); return BGM_E_INVALID; }
-  if (a->n_leapfrog < 1) { bgm_set_error("bgm_bgm_hmc_run_rows: n_leapfrog (num_leapfrog_steps) must be >= 1"); return BGM_E_INVALID; }
-  if (a->row_base < 0 || a->row_base + a->n > 0xFFFFFFFFll) { bgm_set_error("bgm_bgm_hmc_run_rows: row_base + n: row index exceeds the 32-bit RNG counter"); return BGM_E_INVALID; }
+  if (null_arg) { bgm_set_error(fn + "NULL pointer " + null_arg); return BGM_E_INVALID; }
+  if (a->n_leapfrog < 1) { bgm_set_error(fn + "n_leapfrog (num_leapfrog_steps) must be >= 1"); return BGM_E_INVALID; }
+  if (a->row_base < 0 || a->row_base + a->n > 0xFFFFFFFFll) { bgm_set_error(fn + "row_base + n: row index exceeds the 32-bit RNG counter"); return BGM_E_INVALID; }
   BgmState *s = bst(h);
   if (gxb_wanted(s)) {
-    bgm_set_error("bgm_bgm_hmc_run_rows: the per-chain step exists for trunks [64] x 3 / [64] x 5 with z_dim <= 16; this shape runs on the "
+    bgm_set_error(fn + "the per-chain step exists for trunks [64] x 3 / [64] x 5 with z_dim <= 16; this shape runs on the "
                   "general-width engine, which has the shared step only (bgm_bgm_hmc_run)");
     return BGM_E_UNSUPPORTED;
   }
@@ -33,25 +43,53 @@ extern "C" int bgm_bgm_hmc_run_rows(bgm_handle *h, const bgm_hmc_args *a, const 
   BGM_HIP_CHECK(hipSetDevice(h->device));
   int rc = bgm_bgm_build_blob(h, stream);
   if (rc) return rc;
-  BgmRowHmcKArgs ka{};
+  BgmTrajHmcKArgs ka{};
   bgm_hmc_fill(ka, a);
   ka.step = nullptr;
   ka.row_step = const_cast<float *>(a->step_dev);      // (in / out here: [n] steps)
   ka.up = up_dev; ka.dn = dn_dev; ka.n_table = up_dev ? n_table : 0; ka.s_min = s_min; ka.s_max = s_max;
   ka.blob = s->blob_dev; ka.m = s->meta;
+  // the kernels with a number of steps per chain run only when something of it is asked for
+  const bool want_traj = traj && (traj->max_trajectory > 0.0f || traj->jitter != 0 || traj->n_steps != nullptr);
+  if (want_traj) { ka.max_traj = traj->max_trajectory; ka.jitter = traj->jitter; ka.n_steps = traj->n_steps; }
+  const BgmRowHmcKArgs &kr = ka;      // (the argument block of the kernels without: the base, by value)
   const long long tiles = (a->n + 15) / 16;
   if (s->precision != 0) {      // split precision (bgm_kernels.h, PREC 2), as bgm_bgm_hmc_run
     ka.blob = s->sx3_bias_dev; ka.m = s->sx3_meta; ka.hx3 = s->sx3_dev;
-    return bgm_bgm_dispatch(BgmSx3Variants{}, s->KTQ, s->NTX, s->NH, "BGM HMC with per-chain steps (split precision)", [&](auto v) {
+    constexpr int W = BGM_SX3_WAVES_DEFAULT;
+    const bool x4 = (s->sx3_meta.p & 3) == 0;
+    if (!want_traj)
+      return bgm_bgm_dispatch(BgmSx3Variants{}, s->KTQ, s->NTX, s->NH, "BGM HMC with per-chain steps (split precision)", [&](auto v) {
+        using V = decltype(v);
+        return bgm_launch(x4 ? bgm_hmc_rows_kernel<V::KTQ, 0, V::NH, W, 2, true> : bgm_hmc_rows_kernel<V::KTQ, 0, V::NH, W, 2, false>,
+                          bgm_tile_grid(h, tiles, W), W, s->lds_bytes_sx3, stream, kr);
+      });
+    return bgm_bgm_dispatch(BgmSx3Variants{}, s->KTQ, s->NTX, s->NH, "BGM HMC with per-chain steps and trajectories (split precision)", [&](auto v) {
       using V = decltype(v);
-      constexpr int W = BGM_SX3_WAVES_DEFAULT;
-      return bgm_launch((s->sx3_meta.p & 3) == 0 ? bgm_hmc_rows_kernel<V::KTQ, 0, V::NH, W, 2, true> : bgm_hmc_rows_kernel<V::KTQ, 0, V::NH, W, 2, false>,
+      return bgm_launch(x4 ? bgm_hmc_rows_traj_kernel<V::KTQ, 0, V::NH, W, 2, true> : bgm_hmc_rows_traj_kernel<V::KTQ, 0, V::NH, W, 2, false>,
                         bgm_tile_grid(h, tiles, W), W, s->lds_bytes_sx3, stream, ka);
     });
   }
-  return bgm_bgm_dispatch(s, "BGM HMC with per-chain steps", [&](auto v) {
+  if (!want_traj)
+    return bgm_bgm_dispatch(s, "BGM HMC with per-chain steps", [&](auto v) {
+      using V = decltype(v);
+      constexpr int W = V::NTX == 0 ? BGM_WAVES_WIDE_HMC : BGM_WAVES;
+      return bgm_launch(bgm_hmc_rows_kernel<V::KTQ, V::NTX, V::NH, W>, bgm_tile_grid(h, tiles, W), W, s->lds_bytes, stream, kr);
+    });
+  return bgm_bgm_dispatch(s, "BGM HMC with per-chain steps and trajectories", [&](auto v) {
     using V = decltype(v);
     constexpr int W = V::NTX == 0 ? BGM_WAVES_WIDE_HMC : BGM_WAVES;
-    return bgm_launch(bgm_hmc_rows_kernel<V::KTQ, V::NTX, V::NH, W>, bgm_tile_grid(h, tiles, W), W, s->lds_bytes, stream, ka);
+    return bgm_launch(bgm_hmc_rows_traj_kernel<V::KTQ, V::NTX, V::NH, W>, bgm_tile_grid(h, tiles, W), W, s->lds_bytes, stream, ka);
   });
+}
+
+extern "C" int bgm_bgm_hmc_run_rows(bgm_handle *h, const bgm_hmc_args *a, const float *up_dev, const float *dn_dev, int32_t n_table,
+                                    float s_min, float s_max, void *stream_) {
+  return bgm_hmc_rows_run("bgm_bgm_hmc_run_rows", h, a, up_dev, dn_dev, n_table, s_min, s_max, nullptr, stream_);
+}
+
+extern "C" int bgm_bgm_hmc_run_rows_traj(bgm_handle *h, const bgm_hmc_args *a, const float *up_dev, const float *dn_dev, int32_t n_table,
+                                         float s_min, float s_max, float max_trajectory, int32_t jitter, int32_t *n_steps_dev, void *stream_) {
+  const BgmTrajOpts t{max_trajectory, jitter, n_steps_dev};
+  return bgm_hmc_rows_run("bgm_bgm_hmc_run_rows_traj", h, a, up_dev, dn_dev, n_table, s_min, s_max, &t, stream_);
 }

@@ -701,11 +701,28 @@ class BgmEngine(object):
         _lib.check(self.lib.bgm_bgm_hmc_run(self.h, C.byref(a), self._stream()), "bgm_bgm_hmc_run")
 
     def hmc_run_rows(self, x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False, row_base=0, up=None,
-                     dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_prob=None, acc_count=None, draws=None):
+                     dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_prob=None, acc_count=None, draws=None, max_trajectory=None, jitter=False,
+                     n_steps=None):
         """hmc_run with a step size per chain (bgm_bgm_hmc_run_rows): step float32 [n], in / out; up / dn: the factor tables of
-        row_adapt.row_adapt_factors on the device (None: the steps stay as given)."""
+        row_adapt.row_adapt_factors on the device (None: the steps stay as given).
+
+        max_trajectory / jitter / n_steps (opt-in, bgm_bgm_hmc_run_rows_traj): a number of leapfrog steps per chain, from the chain's
+        own step -- capped so that step x steps stays below max_trajectory (row_adapt.leapfrog_cap), drawn uniformly from 1 .. cap
+        per transition with jitter; n_steps int32 [n], in / out, gains the steps every chain took.  Every transition still costs
+        n_leapfrog evaluations: the option buys mixing, not time."""
         a = self._hmc_args(x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, acc_prob, acc_count,
                            draws)
+        if max_trajectory is not None or jitter is not False or n_steps is not None:
+            # (the C entry checks the two values itself, as it does s_min / s_max: what is not a number at all is refused here)
+            try:
+                T = 0.0 if max_trajectory is None else float(max_trajectory)
+                jit = int(jitter)
+            except (TypeError, ValueError):
+                raise ValueError("hmc_run_rows: max_trajectory must be None or a number and jitter a bool; got %r, %r" % (max_trajectory, jitter))
+            _lib.check(self.lib.bgm_bgm_hmc_run_rows_traj(self.h, C.byref(a), _ptr(up), _ptr(dn), 0 if up is None else int(up.numel()),
+                                                          float(s_min), float(s_max), T, jit, _ptr(n_steps), self._stream()),
+                       "bgm_bgm_hmc_run_rows_traj")
+            return
         _lib.check(self.lib.bgm_bgm_hmc_run_rows(self.h, C.byref(a), _ptr(up), _ptr(dn), 0 if up is None else int(up.numel()), float(s_min),
                                                  float(s_max), self._stream()), "bgm_bgm_hmc_run_rows")
 
@@ -714,7 +731,7 @@ class BgmEngine(object):
                                               float(target), float(rate), self._stream()), "bgm_bgm_hmc_adapt")
 
     def hmc_sample(self, x, n_mcmc, burn_in, step_size=0.01, n_leapfrog=10, seed=42, row_base=0, want_draws=True,
-                   n_chains_global=None, reduce_fn=None, row_adapt=None):
+                   n_chains_global=None, reduce_fn=None, row_adapt=None, max_trajectory=None, jitter=False):
         """tfp_mcmc_sampler (bgm/base.py:709-830): HMC + SimpleStepSizeAdaptation over int(0.8*burn_in)
         steps, all rows one chain each.  `reduce_fn(tensor)` all-reduces the per-iteration acceptance
         statistic across ranks (the step size is shared by ALL chains).
@@ -722,7 +739,9 @@ class BgmEngine(object):
         row_adapt = target acceptance rate in (0, 1) (opt-in): every chain carries a step of its own instead, starting at step_size and
         multiplied after each of the burn_in decisions by the factor of row_adapt.row_adapt_factors(burn_in, row_adapt) for "moved" /
         "did not"; burn-in and retained draws run in ONE launch, reduce_fn is not called, and the result holds row_step [n] instead
-        of step."""
+        of step.  max_trajectory / jitter (with row_adapt only): the number of leapfrog steps per chain of hmc_run_rows; the result
+        then holds n_steps int32 [n] as well, the steps every chain took over the n_mcmc retained transitions."""
+        T, jit = RA.resolve_trajectory(row_adapt, max_trajectory, jitter, what="hmc_sample: max_trajectory / jitter")
         dev = self.device
         x = _f32(x, dev)
         n = x.shape[0]
@@ -737,6 +756,18 @@ class BgmEngine(object):
         if row_adapt is not None:
             up, dn = self.row_step_table(burn_in, row_adapt)
             step = torch.full((n,), float(step_size), device=dev, dtype=torch.float32)
+            if T > 0.0 or jit:      # (two launches, so that n_steps counts the retained transitions alone: a cut changes nothing else)
+                n_steps = torch.zeros(n, device=dev, dtype=torch.int32)
+                tr = dict(max_trajectory=T if T > 0.0 else None, jitter=bool(jit))
+                if burn_in > 0:
+                    self.hmc_run_rows(x, state, logp, grad, step, 0, burn_in, burn_in, n_leapfrog, seed, init=True, row_base=row_base,
+                                      up=up, dn=dn, acc_prob=acc_prob, acc_count=acc_count, **tr)
+                if n_mcmc > 0:
+                    self.hmc_run_rows(x, state, logp, grad, step, burn_in, n_mcmc, burn_in, n_leapfrog, seed, init=(burn_in == 0),
+                                      row_base=row_base, up=up, dn=dn, acc_prob=acc_prob, acc_count=acc_count, draws=draws,
+                                      n_steps=n_steps, **tr)
+                return dict(state=state, logp=logp, grad=grad, row_step=step, n_steps=n_steps, acc_prob=acc_prob, acc_count=acc_count,
+                            draws=draws)
             if total > 0:
                 self.hmc_run_rows(x, state, logp, grad, step, 0, total, burn_in, n_leapfrog, seed, init=True, row_base=row_base, up=up,
                                   dn=dn, acc_prob=acc_prob, acc_count=acc_count, draws=draws)

@@ -30,6 +30,7 @@ def _glorot(rs, fan_in, fan_out):
 
 class BGM(object):
     mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last tfp_mcmc_sampler(diagnostics=True)
+    hmc_row_leapfrog_ = None         # per-row mean number of leapfrog steps per retained transition (NumPy float32, global row order) of the last call with max_trajectory / jitter_leapfrog; None otherwise
     hmc_row_step_ = None             # per-row HMC step sizes (NumPy, global row order) of the last predict / tfp_mcmc_sampler call with row_adapt; None when it ran without
 
     def __new__(cls, params=None, *args, **kwargs):
@@ -343,14 +344,15 @@ class BGM(object):
         return self.engine.logpost(self._dev(data_z), self._dev(x)).cpu().numpy()
 
     def tfp_mcmc_sampler(self, data, ind_x1=None, n_mcmc=3000, burn_in=5000, step_size=0.01, num_leapfrog_steps=10,
-                         seed=42, diagnostics=False, row_adapt=False):
+                         seed=42, diagnostics=False, row_adapt=False, max_trajectory=None, jitter_leapfrog=False):
         """Posterior samples of Z, shape (n_mcmc, n, z_dim) (bgm/base.py:709-830).  diagnostics=True: split R-hat / effective
         sample size of every chain, computed on the device before the copy to the host, in ``self.mcmc_diagnostics_``.
         row_adapt (opt-in; True = target acceptance 0.75, or a target in (0, 1)): every chain adapts a step size of its own over the
         whole burn-in, starting from ``step_size``, instead of the one step shared by all chains (row_adapt.py); the steps are left
-        in ``self.hmc_row_step_``."""
+        in ``self.hmc_row_step_``.  max_trajectory / jitter_leapfrog: as in predict."""
         target = row_adapt_mod.resolve_step_target(row_adapt)
-        self.hmc_row_step_ = None
+        max_traj, jit = row_adapt_mod.resolve_trajectory(target, max_trajectory, jitter_leapfrog, what="max_trajectory / jitter_leapfrog")
+        self.hmc_row_step_ = self.hmc_row_leapfrog_ = None
         x = np.array(data, dtype=np.float32, copy=True)
         if ind_x1 is not None:
             keep = np.zeros(x.shape, bool)
@@ -362,9 +364,12 @@ class BGM(object):
             else:
                 keep[:, list(ind_x1)] = True
             x[~keep] = np.nan
-        out = self.engine.hmc_sample(self._dev(x), n_mcmc, burn_in, step_size, num_leapfrog_steps, seed, row_adapt=target)
+        out = self.engine.hmc_sample(self._dev(x), n_mcmc, burn_in, step_size, num_leapfrog_steps, seed, row_adapt=target,
+                                     max_trajectory=max_traj if max_traj > 0.0 else None, jitter=bool(jit))
         if target is not None:
             self.hmc_row_step_ = out["row_step"].cpu().numpy()
+        if "n_steps" in out:
+            self.hmc_row_leapfrog_ = (out["n_steps"].cpu().numpy() / np.float32(max(1, n_mcmc))).astype(np.float32)
         self.last_acceptance_rate = float(out["acc_count"][burn_in:].sum().item()) / max(1, n_mcmc * x.shape[0])
         print(f"TFP MCMC Acceptance Rate: {self.last_acceptance_rate:.4f}")
         if diagnostics:
@@ -406,7 +411,7 @@ class BGM(object):
 
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.05, return_samples=False, bs=100, n_mcmc=5000, burn_in=5000, step_size=0.01,
-                num_leapfrog_steps=10, seed=42, max_draw_bytes=64 << 30, row_adapt=False):
+                num_leapfrog_steps=10, seed=42, max_draw_bytes=64 << 30, row_adapt=False, max_trajectory=None, jitter_leapfrog=False):
         """Posterior-predictive imputation of the NaN cells (bgm/base.py:527-663).
 
         HMC burn-in (with the shared step-size adaptation) runs over ALL rows at once as in the reference;
@@ -415,10 +420,19 @@ class BGM(object):
 
         ``row_adapt`` (opt-in; True = target acceptance 0.75, or a target in (0, 1)): every chain adapts a step size of its own over
         the whole burn-in, starting from ``step_size`` (row_adapt.py).  Burn-in is then one launch per rank with no all-reduce, a
-        chain depends on (seed, global row, the row's data) only, and the steps are left in ``self.hmc_row_step_`` [n]."""
+        chain depends on (seed, global row, the row's data) only, and the steps are left in ``self.hmc_row_step_`` [n].
+
+        ``max_trajectory`` / ``jitter_leapfrog`` (opt-in, with ``row_adapt`` only): a number of leapfrog steps per chain.  A chain
+        whose step has grown takes fewer than ``num_leapfrog_steps`` steps, so that step x steps stays below ``max_trajectory``
+        (pi / 2 is a quarter period of a unit-variance coordinate); with ``jitter_leapfrog`` the number is drawn uniformly from
+        1 .. that cap for every transition.  Without them a row with little observed ends up with step x steps near a full period
+        and returns to where it started.  A transition still costs ``num_leapfrog_steps`` gradient evaluations: the options buy
+        mixing, not time.  ``self.hmc_row_leapfrog_`` [n] holds every chain's mean steps per retained transition."""
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         target = row_adapt_mod.resolve_step_target(row_adapt)
-        self.hmc_row_step_ = None
+        max_traj, jit = row_adapt_mod.resolve_trajectory(target, max_trajectory, jitter_leapfrog, what="max_trajectory / jitter_leapfrog")
+        traj = dict(max_trajectory=max_traj if max_traj > 0.0 else None, jitter=bool(jit)) if (max_traj > 0.0 or jit) else {}
+        self.hmc_row_step_ = self.hmc_row_leapfrog_ = None
         parallel.check_n_mcmc(n_mcmc)
         import time as _time
         _t = {"_last": _time.perf_counter()}
@@ -450,11 +464,12 @@ class BGM(object):
         if target is not None:      # a step per chain: the whole burn-in adapts, in one launch, and no statistic crosses rows or ranks
             step = torch.full((n_loc,), float(step_size), device=dev)
             up, dn = eng.row_step_table(burn_in, target)
+            n_steps = torch.zeros(n_loc, device=dev, dtype=torch.int32) if traj else None
         _mark("setup_h2d")
         if target is not None:
             if burn_in > 0:
                 eng.hmc_run_rows(x, state, logp, grad, step, 0, burn_in, burn_in, num_leapfrog_steps, seed, init=True, row_base=lo_r,
-                                 up=up, dn=dn, acc_prob=acc_prob, acc_count=acc_count)
+                                 up=up, dn=dn, acc_prob=acc_prob, acc_count=acc_count, **traj)
         else:
             for it in range(n_adapt):
                 eng.hmc_run(x, state, logp, grad, step, it, 1, burn_in, num_leapfrog_steps, seed, init=(it == 0),
@@ -487,7 +502,8 @@ class BGM(object):
             draws = torch.empty((n_mcmc, e - s, q), device=dev)
             if target is not None:      # (frozen from here on: every iteration lies behind the table)
                 eng.hmc_run_rows(x[s:e], state[s:e], logp[s:e], grad[s:e], step[s:e], burn_in, n_mcmc, burn_in, num_leapfrog_steps,
-                                 seed, init=(burn_in == 0), row_base=lo_r + s, acc_count=acc_count, draws=draws)
+                                 seed, init=(burn_in == 0), row_base=lo_r + s, acc_count=acc_count, draws=draws,
+                                 n_steps=n_steps[s:e] if traj else None, **traj)
             else:
                 eng.hmc_run(x[s:e], state[s:e], logp[s:e], grad[s:e], step, burn_in, n_mcmc, burn_in, num_leapfrog_steps,
                             seed, init=(burn_in == 0), row_base=lo_r + s, acc_count=acc_count, draws=draws)
@@ -513,6 +529,8 @@ class BGM(object):
             if k_slots > 0 else x.clone()
         if target is not None:
             self.hmc_row_step_ = parallel.all_gather_rows(step, n).cpu().numpy()
+            if traj:
+                self.hmc_row_leapfrog_ = (parallel.all_gather_rows(n_steps, n).cpu().numpy() / np.float32(max(1, n_mcmc))).astype(np.float32)
         if parallel.is_dist():
             means, los, his = (parallel.all_gather_rows(a_, n) for a_ in (means, los, his))
             imputed_dev = parallel.all_gather_rows(imputed_dev, n)

@@ -69,6 +69,14 @@ def _refuse_row_adapt(row_adapt):
                          "step size only; got row_adapt=%r" % (row_adapt,))
 
 
+def _refuse_trajectory(max_trajectory, jitter_leapfrog):
+    """The leapfrog steps per chain (BGM.predict / tfp_mcmc_sampler, max_trajectory / jitter_leapfrog) come with the step per chain."""
+    if max_trajectory is not None or not (isinstance(jitter_leapfrog, (bool, np.bool_)) and not jitter_leapfrog):
+        raise ValueError("max_trajectory / jitter_leapfrog are not available with params['use_bnn'] = True: they need row_adapt, the HMC "
+                         "step per chain, which the Bayesian generator's kernels do not have; got max_trajectory=%r, jitter_leapfrog=%r"
+                         % (max_trajectory, jitter_leapfrog))
+
+
 class BGMBayes(BGM):
     def __init__(self, params, timestamp=None, random_seed=None, device=None):
         self.params = params
@@ -374,10 +382,11 @@ class BGMBayes(BGM):
         return self.engine.logpost(self._dev(data_z), self._dev(x), self._new_seed() if seed is None else seed, 0).cpu().numpy()
 
     def tfp_mcmc_sampler(self, data, ind_x1=None, n_mcmc=3000, burn_in=5000, step_size=0.01, num_leapfrog_steps=10, seed=42,
-                         diagnostics=False, row_adapt=False):
+                         diagnostics=False, row_adapt=False, max_trajectory=None, jitter_leapfrog=False):
         """Posterior samples of Z, shape (n_mcmc, n, z_dim) (bgm/base.py:709-830), stochastic target.  diagnostics=True: as
-        BGM.tfp_mcmc_sampler.  row_adapt: BGM's keyword, refused here for anything but False."""
+        BGM.tfp_mcmc_sampler.  row_adapt, max_trajectory, jitter_leapfrog: BGM's keywords, refused here for anything but their defaults."""
         _refuse_row_adapt(row_adapt)
+        _refuse_trajectory(max_trajectory, jitter_leapfrog)
         x = np.array(data, dtype=np.float32, copy=True)
         if ind_x1 is not None:
             keep = np.zeros(x.shape, bool)
@@ -412,11 +421,12 @@ class BGMBayes(BGM):
 
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.05, return_samples=False, bs=100, n_mcmc=5000, burn_in=5000, step_size=0.01,
-                num_leapfrog_steps=10, seed=42, max_draw_bytes=16 << 30, row_adapt=False):
+                num_leapfrog_steps=10, seed=42, max_draw_bytes=16 << 30, row_adapt=False, max_trajectory=None, jitter_leapfrog=False):
         """Posterior-predictive imputation of the NaN cells (bgm/base.py:527-663).  HMC over ALL rows as in the reference
-        (one generator call per gradient evaluation), then one predictive generator call per block of `bs` rows.  row_adapt: BGM's
-        keyword, refused here for anything but False."""
+        (one generator call per gradient evaluation), then one predictive generator call per block of `bs` rows.  row_adapt,
+        max_trajectory, jitter_leapfrog: BGM's keywords, refused here for anything but their defaults."""
         _refuse_row_adapt(row_adapt)
+        _refuse_trajectory(max_trajectory, jitter_leapfrog)
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         self._warn_fresh_noise()

@@ -66,6 +66,47 @@ def resolve_step_target(row_adapt):
     return t
 
 
+def leapfrog_cap(step, n_leapfrog, max_trajectory):
+    """Leapfrog steps a BGM chain with step size ``step`` takes under ``max_trajectory`` = T (``max_trajectory`` of BGM.predict,
+    bgm_bgm_hmc_run_rows_traj): the number of l in 0 .. n_leapfrog - 1 with ``l == 0 or float32(l) * step < T``, one float32 multiply
+    and one compare per l as in the kernel (csrc/bgm_rowstep_kernels.h) -- clamp(ceil(T / step), 1, n_leapfrog) without a quotient, so
+    NumPy reproduces every integer.  T = None or 0: no cap, n_leapfrog.  -> int32, the shape of ``step``."""
+    step = np.asarray(step, np.float32)
+    L = int(n_leapfrog)
+    if L < 1:
+        raise ValueError("leapfrog_cap: n_leapfrog must be >= 1; got %r" % (n_leapfrog,))
+    if max_trajectory is None or float(max_trajectory) == 0.0:
+        return np.full(step.shape, L, np.int32)
+    T = np.float32(max_trajectory)
+    cap = np.ones(step.shape, np.int32)
+    for l in range(1, L):
+        cap += (np.float32(l) * step < T).astype(np.int32)
+    return cap
+
+
+def resolve_trajectory(row_adapt_target, max_trajectory=None, jitter=False, what="max_trajectory / jitter"):
+    """The trajectory options of the HMC step per chain -> (max_trajectory as a float, 0.0 = no cap; jitter as 0 / 1).  ``max_trajectory``
+    is None or a finite number > 0, ``jitter`` a bool; either of them needs the step per chain (``row_adapt_target`` is what
+    resolve_step_target returned), since the cap is derived from the chain's own step."""
+    if isinstance(jitter, (bool, np.bool_)):
+        jit = int(bool(jitter))
+    elif isinstance(jitter, (int, np.integer)) and int(jitter) in (0, 1):
+        jit = int(jitter)
+    else:
+        raise ValueError("jitter must be False or True; got %r" % (jitter,))
+    T = 0.0
+    if max_trajectory is not None:
+        ok = isinstance(max_trajectory, (int, float, np.integer, np.floating)) and not isinstance(max_trajectory, (bool, np.bool_))
+        T = float(max_trajectory) if ok else float("nan")
+        if not (np.isfinite(T) and T > 0.0):
+            raise ValueError("max_trajectory must be None (no cap) or a finite number > 0 (the cap on step x leapfrog steps); got %r"
+                             % (max_trajectory,))
+    if (T > 0.0 or jit) and row_adapt_target is None:
+        raise ValueError("%s needs row_adapt (the HMC step per chain): the number of leapfrog steps is derived from the chain's own "
+                         "step; got row_adapt off" % (what,))
+    return T, jit
+
+
 def start_scale(q_sd, initial_q_sd=1.0):
     """Scale every chain starts from: ``q_sd`` if positive, else ``initial_q_sd``, else 1."""
     for s in (q_sd, initial_q_sd):

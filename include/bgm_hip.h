@@ -629,6 +629,22 @@ BGM_API int bgm_bgm_hmc_adapt(bgm_handle *h, float *step_dev, const double *acc_
 BGM_API int bgm_bgm_hmc_run_rows(bgm_handle *h, const bgm_hmc_args *args, const float *up_dev, const float *dn_dev, int32_t n_table,
                                  float s_min, float s_max, void *stream);
 
+/* bgm_bgm_hmc_run_rows with a number of leapfrog steps per chain (opt-in), derived from the chain's own step.  args->n_leapfrog = L
+ * stays the launch's count; from it and the chain's current fp32 step eps (the adapting one during burn-in), in fp32 and without a
+ * quotient:  cap = #{l in 0 .. L-1 : l == 0 or float(l) * eps < max_trajectory}, that is clamp(ceil(max_trajectory / eps), 1, L)
+ * (max_trajectory = 0: no cap, cap = L);  jitter = 1: at iteration it the chain takes L_i = 1 + min(cap - 1, int(u * float(cap)))
+ * steps, u = word it & 3 of Philox(row, it >> 2, 1, purpose 5) (the accept uniform is call 0 of that purpose); jitter = 0: L_i = cap.
+ * The proposal is the point after L_i steps, with the log posterior and gradient of that point.  L_i depends on (eps, row, it, seed)
+ * only, so with eps frozen after the table every transition is a valid HMC kernel, and a chain stays a function of (seed,
+ * row_base + r, its row of x_dev).  n_steps_dev [n] int32 (or NULL), in / out: chain r adds the steps it took over this launch's
+ * iterations.  Cost: a wave holds 16 chains on one matrix tile, so every transition still costs L gradient evaluations and a chain
+ * with L_i < L idles through the rest -- the option buys mixing, not time.
+ * (max_trajectory, jitter, n_steps_dev) = (0, 0, NULL) is bgm_bgm_hmc_run_rows, same kernels and same bits.
+ * BGM_E_INVALID, naming the argument: everything bgm_bgm_hmc_run_rows refuses, a negative or non-finite max_trajectory, a jitter
+ * other than 0 / 1.  BGM_E_UNSUPPORTED (the handle stays usable): the general-width engine.  There is no bgm_bvn_* twin. */
+BGM_API int bgm_bgm_hmc_run_rows_traj(bgm_handle *h, const bgm_hmc_args *args, const float *up_dev, const float *dn_dev, int32_t n_table,
+                                      float s_min, float s_max, float max_trajectory, int32_t jitter, int32_t *n_steps_dev, void *stream);
+
 /* Posterior-predictive draws x ~ N(mu(z_d), sigma^2(z_d)) for draws_dev [n_draws x n x q]:
  * full_dev [n_draws x n x p] (or NULL) and / or cells_dev [(row*k_slots + slot)*n_draws + d] for
  * the cells with slot_dev[row*p + c] >= 0 (or NULL); var_full_dev [n_draws x n x p] receives sigma^2
