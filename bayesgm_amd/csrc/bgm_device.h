@@ -35,6 +35,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // iteration loops and keeps dozens of them live.  Laundering the lane indices through an empty asm at
 // the entry of a layer makes the addresses be formed where they are used.
 #define BGM_OPAQUE2(a, b) asm volatile("" : "+v"(a), "+v"(b))
+// The same for a wave-uniform value in an SGPR: tests of it are made where they stand instead of once at kernel entry, where each
+// hoisted outcome would occupy an SGPR pair for the whole kernel.
+#define BGM_OPAQUE_S(a) asm volatile("" : "+s"(a))
 
 #define BGM_LEAK 0.2f
 #define BGM_EPS 1e-6f
@@ -1006,6 +1009,97 @@ __device__ __forceinline__ void dense_pair(const float *wlA, const float *blA, c
         for (int u = 0; u < GS; ++u) {
           accA[0][u] = BGM_MFMA(fa[i].get(u), inA[0][s >> 2][s & 3], accA[0][u]);
           accB[0][u] = BGM_MFMA(fb[i].get(u), inB[0][s >> 2][s & 3], accB[0][u]);
+        }
+      }
+    }
+  }
+}
+
+// First layers whose packed weights are zero over whole K-steps by construction (CausalBGM's f and h take only some of the latents:
+// CausalMeta::l1f / l1h / l1b): `dense` / `dense_pair` with K-step s issued only if bit s of `mask` is set.  The mask is a kernel
+// argument, so the test is one scalar compare-and-branch per step and no register is indexed dynamically.  A skipped step would
+// add 0 * b to its accumulators and the steps that run keep their order on every accumulator: results are bit for bit those of
+// the unmasked forms.  The fragments of the steps that run are still all requested before the first MFMA, but behind branches the
+// compiler no longer counts them: it waits for all of them (lgkmcnt(0)) before the first step that runs, where the unmasked
+// forms drain them one by one -- one LDS round trip either way.  (Requesting every fragment unconditionally and guarding only the
+// MFMAs left the register use and the spills where they are.)  dense_pair_masked issues a step's four MFMAs of net A, then the
+// four of net B -- a branch per net -- where dense_pair alternates A and B tile by tile; the four accumulators of one net are
+// independent, so no MFMA of a step waits for another.
+// (expected set: the steps that run fall through, a skipped step is one forward branch)
+#define BGM_KSTEP_ON(mask, s) __builtin_expect(((mask) >> (s)) & 1u, 1u)
+template <int KT, int KSL, int NT, int R>
+__device__ __forceinline__ void dense_masked(const float *wl, const float *bl, int lane_off, int g, const f32x4 (&in)[R][KT],
+                                             f32x4 (&acc)[R][NT], unsigned mask) {
+  static_assert(NT == 4 || NT == 2 || NT == 1, "dense_masked: one tile group per layer");
+  constexpr int GS = NT, NKS = 4 * (KT - 1) + KSL;
+  BGM_OPAQUE_S(mask);
+  bias_init<NT, R>(bl, g, acc);
+  const float *base = wl + lane_off * GS;
+  if constexpr (R == 1 && NKS * GS <= BGM_PREFETCH_ALL_MAX) {
+    AFrag<GS> a[NKS];
+#pragma unroll
+    for (int s = 0; s < NKS; ++s)
+      if (BGM_KSTEP_ON(mask, s)) a[s].load(base + (16 * (s >> 2) + (s & 3)) * 16 * GS);
+    BGM_NO_HOIST();
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+      if (BGM_KSTEP_ON(mask, s)) {
+#pragma unroll
+        for (int u = 0; u < GS; ++u) acc[0][u] = BGM_MFMA(a[s].get(u), in[0][s >> 2][s & 3], acc[0][u]);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+      if (BGM_KSTEP_ON(mask, s)) {
+        AFrag<GS> a;
+        a.load(base + (16 * (s >> 2) + (s & 3)) * 16 * GS);
+#pragma unroll
+        for (int u = 0; u < GS; ++u) {
+#pragma unroll
+          for (int rr = 0; rr < R; ++rr) acc[rr][u] = BGM_MFMA(a.get(u), in[rr][s >> 2][s & 3], acc[rr][u]);
+        }
+      }
+    }
+  }
+}
+
+template <int KT, int KSL, int NT>
+__device__ __forceinline__ void dense_pair_masked(const float *wlA, const float *blA, const float *wlB, const float *blB, int lane_off,
+                                                  int g, const f32x4 (&inA)[1][KT], const f32x4 (&inB)[1][KT], f32x4 (&accA)[1][NT],
+                                                  f32x4 (&accB)[1][NT], unsigned maskA, unsigned maskB) {
+  static_assert(NT == 4 || NT == 2 || NT == 1, "dense_pair_masked: one tile group per layer");
+  constexpr int GS = NT, NKS = 4 * (KT - 1) + KSL;
+  constexpr int CH = (NKS * GS <= 16) ? NKS : (16 / GS);
+  BGM_OPAQUE_S(maskA);
+  BGM_OPAQUE_S(maskB);
+  bias_init<NT, 1>(blA, g, accA);
+  bias_init<NT, 1>(blB, g, accB);
+  const float *baseA = wlA + lane_off * GS, *baseB = wlB + lane_off * GS;
+#pragma unroll
+  for (int c0 = 0; c0 < NKS; c0 += CH) {
+    AFrag<GS> fa[CH], fb[CH];
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int s = c0 + i;
+      if (s < NKS) {
+        if (BGM_KSTEP_ON(maskA, s)) fa[i].load(baseA + (16 * (s >> 2) + (s & 3)) * 16 * GS);
+        if (BGM_KSTEP_ON(maskB, s)) fb[i].load(baseB + (16 * (s >> 2) + (s & 3)) * 16 * GS);
+      }
+    }
+    BGM_NO_HOIST();
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int s = c0 + i;
+      if (s < NKS) {
+        // (a branch per net, not one per combination -- both / A only / B only: that form made Gram instantiations of the MH kernel spill)
+        if (BGM_KSTEP_ON(maskA, s)) {
+#pragma unroll
+          for (int u = 0; u < GS; ++u) accA[0][u] = BGM_MFMA(fa[i].get(u), inA[0][s >> 2][s & 3], accA[0][u]);
+        }
+        if (BGM_KSTEP_ON(maskB, s)) {
+#pragma unroll
+          for (int u = 0; u < GS; ++u) accB[0][u] = BGM_MFMA(fb[i].get(u), inB[0][s >> 2][s & 3], accB[0][u]);
         }
       }
     }

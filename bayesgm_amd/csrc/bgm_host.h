@@ -97,6 +97,7 @@ struct bgm_handle {
   size_t gblob_cap = 0, gram_w_cap = 0, uc_cap = 0;
   bool gram_valid = false;
   bool mh_direct = false;
+  bool mh_all_ksteps = false;  // BGM_MH_ALL_KSTEPS at bgm_create: the first layers of f and h issue every K-step (CausalMeta::l1f / l1h / l1b all ones)
   CausalMeta gmeta{};
   // split-precision (bf16 x 3) sampling blob (causal_bx3_api.hip); precision: 0 fp32 (default), 1 bf16x3, 2 f16x3 (bgm_causal_set_precision)
   int precision = 0;

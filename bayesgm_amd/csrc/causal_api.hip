@@ -34,6 +34,9 @@ extern "C" int bgm_create(bgm_handle **out, int device) {
   // BGM_MH_DIRECT_LIKELIHOOD=1: the fp32 MH kernels keep the direct form of g's likelihood on every shape (A/B runs, fallback)
   const char *direct = std::getenv("BGM_MH_DIRECT_LIKELIHOOD");
   h->mh_direct = direct != nullptr && std::strcmp(direct, "0") != 0;
+  // BGM_MH_ALL_KSTEPS=1: the first layers of f and h issue the K-steps that hold only structural zeros as well (A/B runs)
+  const char *all_ks = std::getenv("BGM_MH_ALL_KSTEPS");
+  h->mh_all_ksteps = all_ks != nullptr && std::strcmp(all_ks, "0") != 0;
   *out = h;
   return BGM_OK;
 }
@@ -158,6 +161,42 @@ extern "C" int bgm_causal_set_weights(bgm_handle *h, int net_id, const float *th
 // ---------------------------------------------------------------------------
 // packing (layout documented in bgm_device.h)
 // ---------------------------------------------------------------------------
+// First layers: packed K row rho (extended input feature l1_feature(rho): the q latents, then x at index q) -> input row of the net,
+// or -1 where the net does not take the feature (a zero row of the packed layer).
+struct L1RowMaps {
+  int z0, z1, z2, q;
+  explicit L1RowMaps(const bgm_handle *h) : z0(h->cfg.z_dims[0]), z1(h->cfg.z_dims[1]), z2(h->cfg.z_dims[2]), q(h->q) {}
+  int g(int rho) const { const int f = l1_feature(rho); return f < q ? f : -1; }
+  int f(int rho) const {
+    const int f = l1_feature(rho);
+    if (f < z0 + z1) return f;
+    if (f == q) return z0 + z1;  // treatment column
+    return -1;
+  }
+  int h(int rho) const {
+    const int f = l1_feature(rho);
+    if (f < z0) return f;
+    if (f >= z0 + z1 && f < z0 + z1 + z2) return z0 + (f - z0 - z1);
+    return -1;
+  }
+};
+
+// K-step masks of the first layers of f and h (CausalMeta::l1f / l1h / l1b): bit s is set iff one of the four K rows of step s maps
+// to a row of the net.  From z_dims through the row maps above, never from weight values; all ones with BGM_MH_ALL_KSTEPS.
+static void causal_l1_masks(const bgm_handle *h, int KT1, int KSL1, unsigned &mf, unsigned &mh, unsigned &mb) {
+  const L1RowMaps rm(h);
+  const int ks1 = 4 * (KT1 - 1) + KSL1;
+  mf = mh = mb = 0u;
+  for (int rho = 0; rho < 16 * KT1; ++rho) {
+    const int s = 4 * (rho >> 4) + (rho & 3);      // K row 16 t + 4 g + r belongs to K-step 4 t + r
+    if (s >= ks1) continue;
+    if (rm.f(rho) >= 0) mf |= 1u << s;
+    if (rm.f(rho) >= 0 && l1_feature(rho) != h->q) mb |= 1u << s;
+    if (rm.h(rho) >= 0) mh |= 1u << s;
+  }
+  if (h->mh_all_ksteps) mf = mh = mb = (1u << ks1) - 1u;
+}
+
 // Lay out and fill the forward (LDS) blob from three HostNets (g, f, h).  Also used with
 // "iota" nets to derive the canonical-parameter -> blob-position tables of the fit path.
 int causal_pack_forward(bgm_handle *h, const HostNet &G, const HostNet &F, const HostNet &H,
@@ -194,19 +233,11 @@ int causal_pack_forward(bgm_handle *h, const HostNet &G, const HostNet &F, const
   }
   blob.assign(m.total, 0.0f);
   auto ident = [](int rho) { return rho; };
-  pack_layer(blob, m.w1g, G.W(0), q, 64, KT1, 4, [&](int rho) { int f = l1_feature(rho); return f < q ? f : -1; });
-  pack_layer(blob, m.w1f, F.W(0), z0 + z1 + 1, 64, KT1, 4, [&](int rho) {
-    int f = l1_feature(rho);
-    if (f < z0 + z1) return f;
-    if (f == q) return z0 + z1;  // treatment column
-    return -1;
-  });
-  pack_layer(blob, m.w1h, H.W(0), z0 + z2, 64, KT1, 4, [&](int rho) {
-    int f = l1_feature(rho);
-    if (f < z0) return f;
-    if (f >= z0 + z1 && f < z0 + z1 + z2) return z0 + (f - z0 - z1);
-    return -1;
-  });
+  const L1RowMaps rm(h);
+  pack_layer(blob, m.w1g, G.W(0), q, 64, KT1, 4, [&](int rho) { return rm.g(rho); });
+  pack_layer(blob, m.w1f, F.W(0), z0 + z1 + 1, 64, KT1, 4, [&](int rho) { return rm.f(rho); });
+  pack_layer(blob, m.w1h, H.W(0), z0 + z2, 64, KT1, 4, [&](int rho) { return rm.h(rho); });
+  causal_l1_masks(h, KT1, KSL1, m.l1f, m.l1h, m.l1b);
   pack_bias(blob, m.b1g, G.b(0), 64, 4); pack_bias(blob, m.b1f, F.b(0), 64, 4); pack_bias(blob, m.b1h, H.b(0), 64, 4);
   for (int l = 0; l < m.n_gh; ++l) {
     pack_layer(blob, m.wg + l * 4096, G.W(1 + l), 64, 64, 4, 4, ident);
@@ -758,7 +789,11 @@ extern "C" int bgm_causal_mh_info(bgm_handle *h, int64_t n, bgm_mh_info *info) {
   info->waves_per_block = MH_WAVES;
   info->grid_blocks = mh_grid(h, n);
   // issued MFMAs per 16 rows, times R row groups (g's output layer: 16 NTL in the direct form, 16 x 4 in the Gram form)
-  const int per16 = 3 * ks1 * 4 + n_gh * 64 + (gram_wanted(h, NTL) ? 16 * 4 : 16 * NTL) + 2 * (32 + 8 + 4);
+  unsigned mf, mhh, mb;
+  causal_l1_masks(h, KT1, KSL1, mf, mhh, mb);
+  if (!causal_l1_masked(KT1, h->prior_seg != nullptr)) mf = mhh = (1u << ks1) - 1u;   // (the MH kernels that keep the unmasked first layers)
+  // (first layers: g every K-step, f and h the K-steps of their masks)
+  const int per16 = 4 * (ks1 + __builtin_popcount(mf) + __builtin_popcount(mhh)) + n_gh * 64 + (gram_wanted(h, NTL) ? 16 * 4 : 16 * NTL) + 2 * (32 + 8 + 4);
   info->mfma_per_transition_per_wave = per16 * MH_R;
   info->lds_bytes = !h->blob_valid ? 0 : (gram_wanted(h, NTL) && h->gram_valid) ? h->gmeta.total * 4 : h->meta.total * 4;
   double macs = 0.0;

@@ -27,7 +27,15 @@ struct CausalMeta {
   int wh2, bh2, wh3, bh3, wh4, bh4;
   int wxf;              // f L1 x-row, accumulator layout [64]
   int total;            // blob floats
+  // First-layer K-steps to issue, bit s = K-step s (extended input features 4 s .. 4 s + 3): the steps in which the net takes at least
+  // one feature.  From z_dims alone (causal_pack_forward), never from weight values; every other step multiplies packed zeros.
+  // l1f: f (z0, z1, x); l1h: h (z0, z2); l1b: f without the treatment column (causal_effects' dose-free `base`).  g runs every step.
+  unsigned l1f, l1h, l1b;
 };
+// The MH kernel instantiations that keep the unmasked first layers: with the conditional prior and a two-tile first layer (PriorRow's
+// registers on top of KT1 = 2) the masked forms made the Gram instances spill 72 bytes per lane where they had 12 (0 -> 12 in the
+// event form's transition kernel).  Compile-time; bgm_causal_mh_info counts every K-step for them.
+__host__ __device__ constexpr bool causal_l1_masked(int KT1, int PRIOR) { return !(PRIOR != 0 && KT1 > 1); }
 
 struct CausalMhKArgs {
   const float *blob;    // packed weights (global)
@@ -240,7 +248,7 @@ __device__ __forceinline__ void fh_tail(const float *lds, int w2, int b2, int w3
 #else
 #define PMARK(i)
 #endif
-template <int KT1, int KSL1, int NTL, int R, bool GRAM = false>
+template <int KT1, int KSL1, int NTL, int R, bool GRAM = false, bool L1MASK = true>
 __device__ __forceinline__ void causal_logp(const float *lds, const CausalMeta &m, int lane_off, int g,
                                             int j, const f32x4 (&zin)[R][KT1],
                                             const f32x4 (&vreg)[R][GRAM ? 5 : NTL], const float (&xr)[R],
@@ -297,7 +305,8 @@ __device__ __forceinline__ void causal_logp(const float *lds, const CausalMeta &
   float mu_y[R], sr_y[R], mu_x[R], sr_x[R];
   if constexpr (R == 1) {   // the two small nets in lock step (see dense_pair)
     f32x4 f1[1][4], h1[1][4];
-    dense_pair<KT1, KSL1, 4>(lds + m.w1f, lds + m.b1f, lds + m.w1h, lds + m.b1h, lane_off, g, zin, zin, f1, h1);
+    if constexpr (L1MASK) dense_pair_masked<KT1, KSL1, 4>(lds + m.w1f, lds + m.b1f, lds + m.w1h, lds + m.b1h, lane_off, g, zin, zin, f1, h1, m.l1f, m.l1h);
+    else dense_pair<KT1, KSL1, 4>(lds + m.w1f, lds + m.b1f, lds + m.w1h, lds + m.b1h, lane_off, g, zin, zin, f1, h1);
     lrelu_s_inplace<4, 1>(f1); lrelu_s_inplace<4, 1>(h1);
     f32x4 f2[1][2], h2[1][2];
     dense_pair<4, 4, 2>(lds + m.wf2, lds + m.bf2, lds + m.wh2, lds + m.bh2, lane_off, g, f1, h1, f2, h2);
@@ -312,13 +321,13 @@ __device__ __forceinline__ void causal_logp(const float *lds, const CausalMeta &
   } else {
     {
       f32x4 a1[R][4];
-      dense<KT1, KSL1, 4, R>(lds + m.w1f, lds + m.b1f, lane_off, g, zin, a1);
+      dense_masked<KT1, KSL1, 4, R>(lds + m.w1f, lds + m.b1f, lane_off, g, zin, a1, m.l1f);
       lrelu_s_inplace<4, R>(a1);
       fh_tail<R>(lds, m.wf2, m.bf2, m.wf3, m.bf3, m.wf4, m.bf4, lane_off, g, a1, mu_y, sr_y);
     }
     {
       f32x4 a1[R][4];
-      dense<KT1, KSL1, 4, R>(lds + m.w1h, lds + m.b1h, lane_off, g, zin, a1);
+      dense_masked<KT1, KSL1, 4, R>(lds + m.w1h, lds + m.b1h, lane_off, g, zin, a1, m.l1h);
       lrelu_s_inplace<4, R>(a1);
       fh_tail<R>(lds, m.wh2, m.bh2, m.wh3, m.bh3, m.wh4, m.bh4, lane_off, g, a1, mu_x, sr_x);
     }
@@ -562,7 +571,7 @@ __device__ __forceinline__ float pick_by_group(int g, float v0, float v1, float 
   return g == 0 ? v0 : (g == 1 ? v1 : (g == 2 ? v2 : v3));
 }
 
-template <int KT1, int KSL1, int R, int EFFECT, bool GROUPING = true, bool CACHE = false, bool EVAL_ONLY = false>
+template <int KT1, int KSL1, int R, int EFFECT, bool GROUPING = true, bool CACHE = false, bool EVAL_ONLY = false, bool L1MASK = true>
 __device__ __forceinline__ void causal_effects(const float *lds, const CausalMeta &m, int lane_off, int g, int j,
                                                int lane, const f32x4 (&zs)[R][KT1], const unsigned (&rowid)[R],
                                                const bool (&valid)[R], long long row0, long long n, unsigned it,
@@ -579,7 +588,8 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
 #pragma unroll
       for (int r = 0; r < 4; ++r) z0in[rr][t][r] = (16 * t + 4 * r + g == m.q) ? 0.0f : zs[rr][t][r];
   f32x4 base[R][4];
-  dense<KT1, KSL1, 4, R>(lds + m.w1f, lds + m.b1f, lane_off, g, z0in, base);
+  if constexpr (L1MASK) dense_masked<KT1, KSL1, 4, R>(lds + m.w1f, lds + m.b1f, lane_off, g, z0in, base, m.l1b);   // x is zeroed: the treatment column's K-step too
+  else dense<KT1, KSL1, 4, R>(lds + m.w1f, lds + m.b1f, lane_off, g, z0in, base);
   f32x4 wx[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) wx[t] = *reinterpret_cast<const f32x4 *>(lds + m.wxf + 16 * t + 4 * g);
@@ -803,6 +813,7 @@ __device__ __forceinline__ void causal_event_append(const CausalMhKArgs &a, int 
 template <int KT1, int KSL1, int NTL, int R, int WAVES, int EFFECT, int PRIOR = 0, bool GRAM = false, bool ROWADAPT = false>
 __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) {
   static_assert(PRIOR == 0 || R == 1, "conditional prior: one row tile per wave");
+  constexpr bool L1M = causal_l1_masked(KT1, PRIOR);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const CausalMeta &m = a.m;
   lds_fill(lds, a.blob, m.total);
@@ -861,9 +872,9 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
         }
 #ifdef BGM_PROF
       { unsigned long long tsec0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast0 = 0;
-        causal_logp<KT1, KSL1, NTL, R, GRAM>(lds, m, lane_off, g, j, zs, vreg, xr, yr, lp, tsec0, tlast0); }
+        causal_logp<KT1, KSL1, NTL, R, GRAM, L1M>(lds, m, lane_off, g, j, zs, vreg, xr, yr, lp, tsec0, tlast0); }
 #else
-      causal_logp<KT1, KSL1, NTL, R, GRAM>(lds, m, lane_off, g, j, zs, vreg, xr, yr, lp);
+      causal_logp<KT1, KSL1, NTL, R, GRAM, L1M>(lds, m, lane_off, g, j, zs, vreg, xr, yr, lp);
 #endif
       if constexpr (PRIOR) lp[0] += pr.correction(zs[0], m.q, g);
     } else {
@@ -930,9 +941,9 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
       float lpp[R];
       PMARK(0);
 #ifdef BGM_PROF
-      causal_logp<KT1, KSL1, NTL, R, GRAM>(lds, m, lane_off, g, j, zp, vreg, xr, yr, lpp, tsec, tlast);
+      causal_logp<KT1, KSL1, NTL, R, GRAM, L1M>(lds, m, lane_off, g, j, zp, vreg, xr, yr, lpp, tsec, tlast);
 #else
-      causal_logp<KT1, KSL1, NTL, R, GRAM>(lds, m, lane_off, g, j, zp, vreg, xr, yr, lpp);
+      causal_logp<KT1, KSL1, NTL, R, GRAM, L1M>(lds, m, lane_off, g, j, zp, vreg, xr, yr, lpp);
 #endif
       if constexpr (PRIOR) lpp[0] += pr.correction(zp[0], m.q, g);
       PMARK(5);
@@ -993,21 +1004,21 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
           float2 *cache = reinterpret_cast<float2 *>(a.eff_cache) + slot * (long long)((a.n_doses + 3) >> 2) * 64;
           float *adrf_slot = a.adrf_partial + slot * (long long)a.n_doses * a.n_keep;
           const bool skip = a.eff_skip && eff_cached && accmask == 0ull;                // wave-uniform: nobody moved
-          // (the evaluation is switched off through its trip count: its first layer -- 12 MFMAs -- still runs)
-          causal_effects<KT1, KSL1, R, EFFECT, true, true>(lds, m, lane_off, g, j, lane, zs, rowid, valid, row0, n, (unsigned)it, d, a.n_keep,
+          // (the evaluation is switched off through its trip count: its first layer -- 4 MFMAs per K-step of m.l1b -- still runs)
+          causal_effects<KT1, KSL1, R, EFFECT, true, true, false, L1M>(lds, m, lane_off, g, j, lane, zs, rowid, valid, row0, n, (unsigned)it, d, a.n_keep,
                                                             a.sample_y, skip ? 0 : a.n_doses, a.x_values, adrf_slot, a.ite, a.k0, a.k1, cache);
           if (skip) causal_effects_cached(g, j, lane, rowid[0], valid[0], (unsigned)it, d, a.sample_y, a.n_doses, adrf_slot, a.k0, a.k1, cache);
           eff_cached = true;
           n_eff_skipped += skip ? 1u : 0u;
         } else if constexpr (EFFECT == 2 && R == 1) {
           const bool skip = a.eff_skip && eff_cached && accmask == 0ull;                // wave-uniform: nobody moved
-          causal_effects<KT1, KSL1, R, EFFECT, true, true>(lds, m, lane_off, g, j, lane, zs, rowid, valid, row0, n, (unsigned)it, d, a.n_keep,
+          causal_effects<KT1, KSL1, R, EFFECT, true, true, false, L1M>(lds, m, lane_off, g, j, lane, zs, rowid, valid, row0, n, (unsigned)it, d, a.n_keep,
                                                             a.sample_y, skip ? 0 : 2, a.x_values, a.adrf_partial, a.ite, a.k0, a.k1, nullptr, ite_c);
           if (skip) causal_ite_cached(g, j, rowid[0], row0 + j, n, (unsigned)it, d, a.n_keep, a.sample_y, a.ite, a.k0, a.k1, ite_c);
           eff_cached = true;
           n_eff_skipped += skip ? 1u : 0u;
         } else if constexpr (EFFECT != 0) {
-          causal_effects<KT1, KSL1, R, EFFECT>(lds, m, lane_off, g, j, lane, zs, rowid, valid, row0, n, (unsigned)it, d,
+          causal_effects<KT1, KSL1, R, EFFECT, true, false, false, L1M>(lds, m, lane_off, g, j, lane, zs, rowid, valid, row0, n, (unsigned)it, d,
                                                 a.n_keep, a.sample_y, a.n_doses, a.x_values,
                                                 a.adrf_partial + slot * (long long)((EFFECT == 2) ? 2 : a.n_doses) * a.n_keep,
                                                 a.ite, a.k0, a.k1);
