@@ -85,6 +85,26 @@ def block_rows(n_keep, q, budget_bytes=None):
     return max(16, rows // 16 * 16)
 
 
+def check_fused(fused_effects, hmc, draw_budget_bytes):
+    """fused_effects of predict: it belongs to sampler='hmc' and keeps no draws, so it has no draw budget; ValueError otherwise."""
+    if not fused_effects:
+        return
+    if not hmc:
+        raise ValueError("fused_effects=True belongs to sampler='hmc': the MH sampler always computes its effects inside the kernel")
+    if draw_budget_bytes is not None:
+        raise ValueError("fused_effects=True and draw_budget_bytes exclude each other: the fused route stores no draws and samples "
+                         "a rank's rows in one piece")
+
+
+def predict_blocks(blocks, n_keep, q, draw_budget_bytes=None, fused_effects=False):
+    """The row blocks [(start, stop)] of predict(sampler='hmc') cut to block_rows(n_keep, q, draw_budget_bytes) rows each; with
+    fused_effects no draws are stored and the blocks stay whole."""
+    if fused_effects:
+        return list(blocks)
+    rows = block_rows(n_keep, q, draw_budget_bytes)
+    return [(s0, min(s0 + rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, rows)]
+
+
 def check_mass(mass, hmc=True, adapt=True, burn_in=None):
     """mass of predict / hmc_sampler -> None ('identity' or None) or 'diag'; ValueError for anything else, for 'diag' without the HMC
     sampler, without step adaptation, or with a burn-in too short for one window."""

@@ -61,6 +61,7 @@ int hmc_prepare(bgm_handle *h, const float *v, int64_t n, hipStream_t stream, Hm
   m.wf2 = take(2 * 64 * 17); m.bf2 = take(32); m.wf3 = take(32 * 17); m.bf3 = take(16); m.wf4 = take(16 * 17); m.bf4 = take(16);
   m.wh2 = take(2 * 64 * 17); m.bh2 = take(32); m.wh3 = take(32 * 17); m.bh3 = take(16); m.wh4 = take(16 * 17); m.bh4 = take(16);
   m.total = off;
+  if (m.total != bgm_causal_hmc_blob_floats(KT1, m.n_gh)) { bgm_set_error("bgm_causal_hmc: blob layout and bgm_causal_hmc_blob_floats disagree"); return BGM_E_STATE; }
   if ((size_t)m.total * 4 > 160 * 1024) { bgm_set_error("bgm_causal_hmc: the weights do not fit the 160 KiB LDS (" + std::to_string(m.total * 4) + " B)"); return BGM_E_UNSUPPORTED; }
   std::vector<float> hb((size_t)m.total, 0.0f);
   auto copy = [&](int s_off, int d_off, int count) { std::copy(gb.begin() + s_off, gb.begin() + s_off + count, hb.begin() + d_off); };
@@ -117,33 +118,47 @@ extern "C" int bgm_causal_logpost_grad(bgm_handle *h, const float *x, const floa
   });
 }
 
-extern "C" int bgm_causal_hmc_run(bgm_handle *h, const float *x, const float *y, const float *v, int64_t n, int64_t row_base, float *state,
-                                  float *logp, float *grad, float *step, const float *up, const float *dn, int32_t n_table, float s_min,
-                                  float s_max, int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog,
-                                  uint64_t seed, uint32_t *acc_count, float *draws, int32_t n_keep, void *stream_) {
-  if (int rc = bgm_causal_hmc_check(h, "bgm_causal_hmc_run")) return rc;
-  if (n <= 0 || n_iters <= 0) return BGM_OK;
-  if (!x || !y || !v || !state || !logp || !grad || !step) { bgm_set_error("bgm_causal_hmc_run: NULL data pointer"); return BGM_E_INVALID; }
-  if (n_leapfrog < 1) { bgm_set_error("bgm_causal_hmc_run: n_leapfrog must be >= 1"); return BGM_E_INVALID; }
-  if (it_begin < 0 || burn_in < 0) { bgm_set_error("bgm_causal_hmc_run: it_begin / burn_in must be >= 0"); return BGM_E_INVALID; }
-  if (row_base < 0 || row_base + n > 0xFFFFFFFFll) { bgm_set_error("bgm_causal_hmc_run: row index exceeds the 32-bit RNG counter"); return BGM_E_INVALID; }
+int bgm_causal_hmc_args(bgm_handle *h, const char *who_, const float *x, const float *y, const float *v, int64_t n, int64_t row_base,
+                        float *state, float *logp, float *grad, float *step, const float *up, const float *dn, int32_t n_table, float s_min,
+                        float s_max, int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed,
+                        uint32_t *acc_count, float *draws, int32_t n_keep, hipStream_t stream, CausalHmcKArgs &ka, HmcState *&st, int &grid) {
+  const std::string who(who_);
+  if (!x || !y || !v || !state || !logp || !grad || !step) { bgm_set_error(who + ": NULL data pointer"); return BGM_E_INVALID; }
+  if (n_leapfrog < 1) { bgm_set_error(who + ": n_leapfrog must be >= 1"); return BGM_E_INVALID; }
+  if (it_begin < 0 || burn_in < 0) { bgm_set_error(who + ": it_begin / burn_in must be >= 0"); return BGM_E_INVALID; }
+  if (row_base < 0 || row_base + n > 0xFFFFFFFFll) { bgm_set_error(who + ": row index exceeds the 32-bit RNG counter"); return BGM_E_INVALID; }
   if (up || dn) {
-    if (!up || !dn || n_table < 0) { bgm_set_error("bgm_causal_hmc_run: up_dev / dn_dev must both hold n_table >= 0 factors"); return BGM_E_INVALID; }
-    if (!(s_min > 0.0f) || !(s_max >= s_min) || !(s_max < INFINITY)) { bgm_set_error("bgm_causal_hmc_run: the clamp needs 0 < s_min <= s_max < inf"); return BGM_E_INVALID; }
+    if (!up || !dn || n_table < 0) { bgm_set_error(who + ": up_dev / dn_dev must both hold n_table >= 0 factors"); return BGM_E_INVALID; }
+    if (!(s_min > 0.0f) || !(s_max >= s_min) || !(s_max < INFINITY)) { bgm_set_error(who + ": the clamp needs 0 < s_min <= s_max < inf"); return BGM_E_INVALID; }
   }
-  if (draws && (long long)it_begin + n_iters - burn_in > n_keep) { bgm_set_error("bgm_causal_hmc_run: iterations beyond burn_in + n_keep"); return BGM_E_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
+  if (draws && (long long)it_begin + n_iters - burn_in > n_keep) { bgm_set_error(who + ": iterations beyond burn_in + n_keep"); return BGM_E_INVALID; }
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  HmcState *st = nullptr;
+  st = nullptr;
   if (int rc = hmc_prepare(h, v, n, stream, st)) return rc;
-  CausalHmcKArgs ka{};
+  ka = CausalHmcKArgs{};
   ka.blob = st->blob_dev; ka.x = x; ka.y = y; ka.uc = h->uc_dev; ka.n = n; ka.row_base = row_base;
   ka.state = state; ka.logp = logp; ka.grad = grad; ka.step = step;
   ka.up = up; ka.dn = dn; ka.n_table = up ? n_table : 0; ka.s_min = s_min; ka.s_max = s_max;
   ka.init = init ? 1 : 0; ka.it_begin = it_begin; ka.n_iters = n_iters; ka.burn_in = burn_in; ka.n_leapfrog = n_leapfrog;
   ka.k0 = (unsigned)(seed & 0xFFFFFFFFull); ka.k1 = (unsigned)(seed >> 32);
   ka.acc_count = acc_count; ka.draws = draws; ka.m = st->m;
-  const int grid = bgm_causal_grid(h, n, 1);
+  grid = bgm_causal_grid(h, n, 1);
+  return BGM_OK;
+}
+
+extern "C" int bgm_causal_hmc_run(bgm_handle *h, const float *x, const float *y, const float *v, int64_t n, int64_t row_base, float *state,
+                                  float *logp, float *grad, float *step, const float *up, const float *dn, int32_t n_table, float s_min,
+                                  float s_max, int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog,
+                                  uint64_t seed, uint32_t *acc_count, float *draws, int32_t n_keep, void *stream_) {
+  if (int rc = bgm_causal_hmc_check(h, "bgm_causal_hmc_run")) return rc;
+  if (n <= 0 || n_iters <= 0) return BGM_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  CausalHmcKArgs ka{};
+  HmcState *st = nullptr;
+  int grid = 0;
+  if (int rc = bgm_causal_hmc_args(h, "bgm_causal_hmc_run", x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init,
+                                   it_begin, n_iters, burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid))
+    return rc;
   if (st->mass.scale) return bgm_causal_hmc_mass_launch(h, ka, st->mass, grid, st->m.total * 4, stream);      // bgm_causal_hmc_set_mass
   return bgm_causal_dispatch(h, "HMC kernel", [&](auto s) {
     using S = decltype(s);

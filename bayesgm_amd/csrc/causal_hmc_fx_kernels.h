@@ -1,0 +1,200 @@
+// causal_hmc_fx_kernels.h -- the HMC transitions of causal_hmc_kernels.h / causal_hmc_mass_kernels.h with the effect pass inside
+// the sampler (gfx950): no retained draws are needed to estimate the dose-response curve or the treatment effects.
+//
+// replaces: infer_from_latent_posterior (causalbgm/base.py:671-763) behind an HMC chain; the reference has no HMC sampler for
+//   CausalBGM and computes its effects from stored MH draws.
+//
+// causal_hmc_fx_kernel / causal_hmc_mass_fx_kernel are causal_hmc_kernel / causal_hmc_mass_kernel (same registers, same LDS blob, same
+// RNG streams, same accept rule, step table and metric) with ONE addition: after the decision of every retained iteration the outcome
+// net is evaluated on the chain's state by causal_effects (causal_kernels.h), the routine bgm_causal_effects runs over stored draws.
+// z is already in its register layout (feature 16 t + 4 r + g, x at feature q), the grid and the tile walk are those of
+// causal_effects_kernel (slot = blockIdx.x * WAVES + wave, stride gridDim.x * WAVES), and the noise counters are (row, it): element
+// (slot, d, k) of adrf_partial receives the same additions in the same order on both routes, so the fused result IS the two-pass one.
+// causal_effects reads f in the layout of the SAMPLING blob (not the dual-access one of the gradient): f's pieces of that blob --
+// w1f, b1f, wf2 .. bf4, wxf, 3008 + 1024 KT1 floats -- are copied behind the HMC blob in LDS, byte for byte from where
+// bgm_causal_effects reads them.  The call sits where mom / zc / gc are dead.
+// Kernels of their own beside the old ones, not a flag on a shared body: the kernels without effects keep their code objects
+// instruction for instruction (scripts/compare_code_objects.py).  The two new kernels share one body (MASS is a template argument).
+#pragma once
+#include "causal_hmc_mass_kernels.h"
+#include "causal_kernels.h"
+
+#define CHMC_FX_PIECES 4
+
+struct CausalHmcFxArgs {
+  const float *sblob;                 // the sampling blob (bgm_causal_sampling_blob), global
+  int src[CHMC_FX_PIECES];            // f's pieces: cnt floats from sblob + src to lds_f + dst (all multiples of 4)
+  int dst[CHMC_FX_PIECES];
+  int cnt[CHMC_FX_PIECES];
+  CausalMeta mf;                      // offsets of w1f, b1f, wf2 .. bf4, wxf relative to lds_f; q, sig2_y, l1b of the handle's meta
+  int n_keep, sample_y, n_doses;
+  const float *x_values;
+  float *adrf_partial;                // [n_slots][n_keep][n_doses], += (EFFECT 1)
+  float *ite;                         // [n][n_keep] (EFFECT 2)
+};
+
+// floats of f's part of the sampling blob
+__host__ __device__ constexpr int chmc_fx_floats(int KT1) { return 3008 + 1024 * KT1; }
+
+__device__ __forceinline__ void chmc_fx_fill(float *lds_f, const CausalHmcFxArgs &fx) {
+#pragma unroll
+  for (int p = 0; p < CHMC_FX_PIECES; ++p) {
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(fx.sblob + fx.src[p]);
+    f32x4 *dst = reinterpret_cast<f32x4 *>(lds_f + fx.dst[p]);
+    for (int i = threadIdx.x; i < fx.cnt[p] / 4; i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+}
+
+template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS>
+__device__ __forceinline__ void chmc_fx_run(float *lds, const CausalHmcKArgs &a, const CausalHmcMassArgs &ma, const CausalHmcFxArgs &fx) {
+  const CausalHmcMeta &m = a.m;
+  const CausalMeta &mf = fx.mf;
+  lds_fill(lds, a.blob, m.total);
+  const float *lds_f = lds + m.total;
+  chmc_fx_fill(lds + m.total, fx);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4, lane_off = 64 * g + j;
+  const long long n = a.n, n_tiles = (n + 15) / 16;
+  const long long slot = (long long)blockIdx.x * WAVES + wave;
+  for (long long tile = slot; tile < n_tiles; tile += (long long)gridDim.x * WAVES) {
+    BGM_NO_HOIST();
+    const long long row0 = tile * 16;
+    long long row = row0 + j;
+    const bool ok = row < n;
+    row = ok ? row : n - 1;
+    const unsigned rowid[1] = {(unsigned)(a.row_base + row)};
+    const bool valid[1] = {ok};
+    float xr, yr, c, lp;
+    f32x4 u2[4], z[1][KT1], gr[KT1];
+    chmc_load_row(a.x, a.y, a.uc, n, row, g, xr, yr, u2, c);
+    float eps = a.step[row];
+    const long long eoff = row * (long long)m.q + g;      // the lane's first element of the row's [q] in scale / ref / s1 / s2
+    if (a.init) {      // current_state ~ N(0, 1) (base.py:842), RNG tag 0: the state the MH sampler starts from
+#pragma unroll
+      for (int t = 0; t < KT1; ++t) {
+        const f32x4 e = box_muller4(philox4x32_10(rowid[0], 0u, (unsigned)(g + 4 * t), TAG_INIT, a.k0, a.k1));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int f = 16 * t + 4 * r + g;
+          z[0][t][r] = (f < m.q) ? e[r] : (f == m.q ? xr : 0.0f);
+        }
+      }
+      chmc_logp_grad<KT1>(lds, m, j, g, z[0], u2, c, xr, yr, lp, gr);
+    } else {
+      chmc_load_z<KT1>(a.state, m.q, row, g, xr, z[0]);
+      chmc_load_z<KT1>(a.grad, m.q, row, g, 0.0f, gr);
+      lp = a.logp[row];
+    }
+    for (int it = a.it_begin; it < a.it_begin + a.n_iters; ++it) {
+      BGM_NO_HOIST();
+      f32x4 mom[KT1], zc[KT1], gc[KT1], sc[KT1];
+      if constexpr (MASS) chmc_mass_load<KT1>(ma.scale, eoff, m.q, g, sc);
+      float ke0 = 0.0f;
+#pragma unroll
+      for (int t = 0; t < KT1; ++t) {
+        const f32x4 e = box_muller4(philox4x32_10(rowid[0], (unsigned)it, (unsigned)(g + 4 * t), TAG_MOM, a.k0, a.k1));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pm = (16 * t + 4 * r + g < m.q) ? e[r] : 0.0f;
+          ke0 = fmaf(pm, pm, ke0);
+          if constexpr (MASS) mom[t][r] = fmaf(0.5f * (eps * sc[t][r]), gr[t][r], pm);      // first half kick
+          else mom[t][r] = fmaf(0.5f * eps, gr[t][r], pm);
+          zc[t][r] = z[0][t][r];
+          gc[t][r] = gr[t][r];
+        }
+      }
+      ke0 = sum_over_g(ke0);
+      float lpc = lp;
+      for (int l = 0; l < a.n_leapfrog; ++l) {
+        BGM_NO_HOIST();
+        if constexpr (MASS) chmc_mass_load<KT1>(ma.scale, eoff, m.q, g, sc);
+#pragma unroll
+        for (int t = 0; t < KT1; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {      // (the momentum of x and of the padding is zero)
+            if constexpr (MASS) zc[t][r] = fmaf(eps * sc[t][r], mom[t][r], zc[t][r]);
+            else zc[t][r] = fmaf(eps, mom[t][r], zc[t][r]);
+          }
+        chmc_logp_grad<KT1>(lds, m, j, g, zc, u2, c, xr, yr, lpc, gc);
+        if constexpr (MASS) {
+          BGM_NO_HOIST();
+          chmc_mass_load<KT1>(ma.scale, eoff, m.q, g, sc);
+        }
+        const float kick = (l < a.n_leapfrog - 1) ? eps : 0.5f * eps;
+#pragma unroll
+        for (int t = 0; t < KT1; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            if constexpr (MASS) mom[t][r] = fmaf(kick * sc[t][r], gc[t][r], mom[t][r]);      // (0.5 eps) s = 0.5 (eps s): a power of two
+            else mom[t][r] = fmaf(kick, gc[t][r], mom[t][r]);
+          }
+      }
+      float ke1 = 0.0f;
+#pragma unroll
+      for (int t = 0; t < KT1; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ke1 = fmaf(mom[t][r], mom[t][r], ke1);
+      ke1 = sum_over_g(ke1);
+      float log_ratio = -((-lpc + 0.5f * ke1) - (-lp + 0.5f * ke0));
+      log_ratio = (log_ratio == log_ratio && fabsf(log_ratio) != INFINITY) ? log_ratio : -INFINITY;
+      const uint4 w4 = philox4x32_10(rowid[0], (unsigned)it >> 2, 0u, TAG_HACC, a.k0, a.k1);
+      const unsigned w_ = (it & 2) ? ((it & 1) ? w4.w : w4.z) : ((it & 1) ? w4.y : w4.x);
+      const bool acc = logf(u01_open(w_)) < log_ratio;
+#pragma unroll
+      for (int t = 0; t < KT1; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          z[0][t][r] = acc ? zc[t][r] : z[0][t][r];
+          gr[t][r] = acc ? gc[t][r] : gr[t][r];
+        }
+      lp = acc ? lpc : lp;
+      if (a.up != nullptr && it < a.n_table) eps = fminf(fmaxf(eps * (acc ? a.up : a.dn)[it], a.s_min), a.s_max);
+      if (a.acc_count) {
+        const unsigned cnt = (unsigned)__popcll(__ballot(acc && ok && g == 0));
+        if (lane == 0 && cnt) atomicAdd(a.acc_count + it, cnt);
+      }
+      if constexpr (MASS) {
+        if (ma.accumulate && ok) {
+          long long off = eoff;
+          asm volatile("" : "+v"(off));
+          const float *rf = ma.ref + off;
+          float *s1 = ma.s1 + off, *s2 = ma.s2 + off;
+#pragma unroll
+          for (int t = 0; t < KT1; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int e = 16 * t + 4 * r;
+              if (e + g < m.q) {
+                const float d = z[0][t][r] - rf[e];
+                s1[e] += d;
+                s2[e] = fmaf(d, d, s2[e]);
+              }
+            }
+        }
+      }
+      if (a.draws != nullptr && it >= a.burn_in && ok) chmc_store_z<KT1>(a.draws + (long long)(it - a.burn_in) * n * m.q, m.q, row, g, z[0]);
+      if (it >= a.burn_in)      // (wave-uniform) infer_from_latent_posterior on the state the chain holds after this decision
+        causal_effects<KT1, KSL1, 1, EFFECT>(lds_f, mf, lane_off, g, j, lane, z, rowid, valid, row0, n, (unsigned)it, (long long)(it - a.burn_in),
+                                             fx.n_keep, fx.sample_y, fx.n_doses, fx.x_values,
+                                             fx.adrf_partial + slot * (long long)fx.n_doses * fx.n_keep /* unused when EFFECT == 2 */, fx.ite,
+                                             a.k0, a.k1);
+    }
+    if (ok) {
+      chmc_store_z<KT1>(a.state, m.q, row, g, z[0]);
+      chmc_store_z<KT1>(a.grad, m.q, row, g, gr);
+      if (g == 0) { a.logp[row] = lp; a.step[row] = eps; }
+    }
+  }
+}
+
+template <int KT1, int KSL1, int WAVES, int EFFECT>
+__global__ __launch_bounds__(64 * WAVES) void causal_hmc_fx_kernel(CausalHmcKArgs a, CausalHmcFxArgs fx) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  chmc_fx_run<KT1, KSL1, WAVES, EFFECT, false>(lds, a, CausalHmcMassArgs{}, fx);
+}
+
+template <int KT1, int KSL1, int WAVES, int EFFECT>
+__global__ __launch_bounds__(64 * WAVES) void causal_hmc_mass_fx_kernel(CausalHmcKArgs a, CausalHmcMassArgs ma, CausalHmcFxArgs fx) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  chmc_fx_run<KT1, KSL1, WAVES, EFFECT, true>(lds, a, ma, fx);
+}

@@ -17,7 +17,19 @@ static inline HmcState *bgm_causal_hmc_state(bgm_handle *h) {
   return static_cast<HmcState *>(h->hmc_state);
 }
 
+// floats of the dual-access blob (causal_hmc_api.hip, hmc_prepare): known from the shape alone, before anything is packed or launched
+static inline int bgm_causal_hmc_blob_floats(int KT1, int n_gh) {
+  return 3 * (4 * 16 * KT1 * 17 + 64) + n_gh * (CHMC_W64 + 64) + CHMC_W64 + 132 + 2 * (2 * 64 * 17 + 32 + 32 * 17 + 16 + 16 * 17 + 16);
+}
+
 // BGM_E_STATE for an unconfigured handle, BGM_E_UNSUPPORTED (naming the path) where the gradient / HMC kernels do not exist
 int bgm_causal_hmc_check(bgm_handle *h, const char *who);                                                     // causal_hmc_api.hip
+// the argument checks of bgm_causal_hmc_run (`who` names the entry point), the panel's Gram pre-pass and the dual-access blob, then
+// the kernel arguments of one launch and its grid
+int bgm_causal_hmc_args(bgm_handle *h, const char *who, const float *x, const float *y, const float *v, int64_t n, int64_t row_base,
+                        float *state, float *logp, float *grad, float *step, const float *up, const float *dn, int32_t n_table, float s_min,
+                        float s_max, int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed,
+                        uint32_t *acc_count, float *draws, int32_t n_keep, hipStream_t stream, CausalHmcKArgs &ka, HmcState *&st,
+                        int &grid);                                                                           // causal_hmc_api.hip
 int bgm_causal_hmc_mass_launch(bgm_handle *h, const CausalHmcKArgs &ka, const CausalHmcMassArgs &ma, int grid, int lds,
                                hipStream_t stream);                                                           // causal_hmc_mass_api.hip

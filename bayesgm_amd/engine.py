@@ -128,13 +128,24 @@ class CausalEngine(object):
         return out, grad
 
     def hmc_run(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False, row_base=0,
-                up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0):
-        """One segment of the HMC latent sampler for all rows (bgm_causal_hmc_run); state / logp / grad / step are in / out."""
-        _lib.check(self.lib.bgm_causal_hmc_run(self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp),
-                                               _ptr(grad), _ptr(step), _ptr(up), _ptr(dn), 0 if up is None else int(up.numel()),
-                                               float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters), int(burn_in),
-                                               int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws),
-                                               int(n_keep), self._stream()), "bgm_causal_hmc_run")
+                up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0, effect=_lib.EFFECT_NONE,
+                sample_y=True, x_values=None, adrf_partial=None, ite=None):
+        """One segment of the HMC latent sampler for all rows (bgm_causal_hmc_run); state / logp / grad / step are in / out.
+        effect = EFFECT_ADRF / EFFECT_ITE: the segment runs the kernels with the effect pass inside (bgm_causal_hmc_run_effects):
+        x_values [n_doses] and adrf_partial [n_slots, n_keep, n_doses] (+=), or ite [n, n_keep], receive the effects of the
+        iterations >= burn_in of this segment."""
+        args = (self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up),
+                _ptr(dn), 0 if up is None else int(up.numel()), float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters),
+                int(burn_in), int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws), int(n_keep))
+        if effect == _lib.EFFECT_NONE:
+            _lib.check(self.lib.bgm_causal_hmc_run(*args, self._stream()), "bgm_causal_hmc_run")
+            return
+        if effect not in (_lib.EFFECT_ADRF, _lib.EFFECT_ITE) or (effect == _lib.EFFECT_ITE) != bool(self.binary):
+            raise ValueError("hmc_run: effect must be EFFECT_NONE or the effect of the treatment type (EFFECT_ITE for a binary "
+                             "treatment, EFFECT_ADRF otherwise); got %r" % (effect,))
+        _lib.check(self.lib.bgm_causal_hmc_run_effects(*args, int(bool(sample_y)), _ptr(x_values),
+                                                       0 if x_values is None else int(x_values.numel()), _ptr(adrf_partial), _ptr(ite),
+                                                       self._stream()), "bgm_causal_hmc_run_effects")
 
     def set_hmc_mass(self, scale=None, ref=None, s1=None, s2=None, accumulate=False):
         """Diagonal metric of the hmc_run calls made afterwards (bgm_causal_hmc_set_mass): scale float32 [n x q] (device), the
@@ -152,7 +163,8 @@ class CausalEngine(object):
                                                        _ptr(s2), self._stream()), "bgm_causal_hmc_mass_update")
 
     def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
-                   adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None):
+                   adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None, effect=_lib.EFFECT_NONE,
+                   x_values=None, sample_y=True):
         """HMC over the latent posterior of every row, one chain per row with a step size of its own.
 
         adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
@@ -163,8 +175,12 @@ class CausalEngine(object):
         causal_hmc.mass_windows(burn_in) (mass_windows = (start, ends) replaces them) and keeps it afterwards; the step table is
         causal_hmc.mass_schedule's.  mass_scale = tensor [n x q]: that metric, frozen, no estimation.  Windows are launch
         boundaries; cuts by chunk inside them change nothing.
+
+        effect = EFFECT_ADRF (with x_values) / EFFECT_ITE: infer_from_latent_posterior runs inside the sampler on every retained
+        state (hmc_run), no draws are needed; every launch, burn-in included, is the fused kernel, so a model it refuses (LDS) is
+        refused before any state is written.  The result is engine.effects on the draws of the same run, bit for bit.
         Returns dict(draws [n_keep, n, q] | None, state, logp, grad, acc_count [burn_in + n_keep], row_step [n]) and, with a metric,
-        mass_scale [n x q]."""
+        mass_scale [n x q]; with an effect, adrf [n_doses, n_keep] or ite [n, n_keep]."""
         HM.check_args(step_size, n_leapfrog, adapt)
         diag = HM.check_mass(mass, True, adapt if adapt_table is None else True) is not None
         if diag and mass_scale is not None:
@@ -192,6 +208,20 @@ class CausalEngine(object):
         acc = torch.zeros(total, device=dev, dtype=torch.int32)
         draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
         chunk = total if chunk is None else max(1, int(chunk))
+        xv = partial = ite = None
+        n_slots = 0
+        if effect == _lib.EFFECT_ADRF:
+            if x_values is None:
+                raise ValueError("hmc_sample: effect=EFFECT_ADRF needs x_values")
+            xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), dev)
+            ns = C.c_int32()
+            _lib.check(self.lib.bgm_causal_evaluate_slots(self.h, n, C.byref(ns)), "bgm_causal_evaluate_slots")
+            n_slots = ns.value
+            partial = torch.zeros((n_slots, n_keep, xv.numel()), device=dev, dtype=torch.float32)
+        elif effect == _lib.EFFECT_ITE:
+            ite = torch.empty((n, n_keep), device=dev, dtype=torch.float32)
+        elif effect != _lib.EFFECT_NONE:
+            raise ValueError("hmc_sample: effect must be EFFECT_NONE, EFFECT_ADRF or EFFECT_ITE; got %r" % (effect,))
         scale = moments = None
         if diag:
             scale = torch.ones((n, self.q), device=dev, dtype=torch.float32)
@@ -208,7 +238,8 @@ class CausalEngine(object):
             while it < total:
                 stop = min([it + chunk, total] + [b for b in marks if b > it])
                 self.hmc_run(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0),
-                             row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep)
+                             row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep, effect=effect,
+                             sample_y=sample_y, x_values=xv, adrf_partial=partial, ite=ite)
                 if stop in marks:      # a window's edge: the first one only sets the reference point and turns the moments on
                     k = marks.index(stop)
                     self.hmc_mass_update(0 if k == 0 else stop - marks[k - 1], state, scale, *moments)
@@ -220,6 +251,10 @@ class CausalEngine(object):
         out = dict(draws=draws, state=state, logp=logp, grad=grad, acc_count=acc, row_step=step)
         if scale is not None:
             out["mass_scale"] = scale
+        if partial is not None:
+            out["adrf"] = self.adrf_reduce(partial, n_slots, xv.numel(), n_keep, n)
+        if ite is not None:
+            out["ite"] = ite
         return out
 
     def encode(self, v):

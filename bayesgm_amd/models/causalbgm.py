@@ -524,7 +524,7 @@ class CausalBGM(object):
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
                 bs=10000, verbose=1, diagnose_rows=0, row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None,
-                draw_budget_bytes=None, mass='identity'):
+                draw_budget_bytes=None, mass='identity', fused_effects=False):
         """Causal effects with posterior intervals from latent MCMC samples (base.py:573-668).
 
         ``sampler='hmc'`` (opt-in; ``'mh'`` is the reference's sampler and the default): the latents are sampled by Hamiltonian Monte
@@ -535,7 +535,11 @@ class CausalBGM(object):
         used, ``row_adapt`` and a non-positive ``q_sd`` are refused, ``diagnose_rows`` works.  The steps are left in
         ``self.hmc_row_step_``.  ``mass='diag'`` (with ``sampler='hmc'``): every chain also estimates a scale per latent coordinate
         from its own burn-in draws (a diagonal metric, causal_hmc.py) and keeps it for the retained draws; the scales are left in
-        ``self.hmc_row_mass_`` [n, q].
+        ``self.hmc_row_mass_`` [n, q].  ``fused_effects=True`` (with ``sampler='hmc'``, opt-in): the effects are computed inside the
+        sampling kernel after every retained decision and no draws are stored, so this rank's shard is sampled in one piece
+        (``draw_budget_bytes`` has no meaning and is refused; a binary treatment keeps the cap on the ITE matrix).  Chains, steps,
+        metric and seed sequence are those of the draws route, and so is the result whenever that route runs one block (several
+        blocks reassociate the float32 sums over rows).  Generators too deep for the fused kernels' LDS raise the library's error.
 
         ``bs`` bounded the host memory of the reference; here all rows are sampled in one launch per
         segment (row-blocked only if the ITE draw matrix would exceed device memory) and the result does
@@ -557,6 +561,7 @@ class CausalBGM(object):
         if hmc_mod.check_predict_options(sampler, q_sd, row_adapt):
             hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
         mass = hmc_mod.check_mass(mass, hmc is not None, True, burn_in)
+        hmc_mod.check_fused(fused_effects, hmc is not None, draw_budget_bytes)
         if hmc is not None:
             hmc = hmc + (mass,)
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
@@ -596,9 +601,8 @@ class CausalBGM(object):
             max_rows = max(16, int((32 << 30) // (4 * max(1, n_mcmc))))
             if not adaptive:
                 blocks = [(s0, min(s0 + max_rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, max_rows)]
-        if hmc is not None:              # the retained draws of a block are kept: blocks within the draw budget
-            rows = hmc_mod.block_rows(n_mcmc, eng.q, draw_budget_bytes)
-            blocks = [(s0, min(s0 + rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, rows)]
+        if hmc is not None:              # the retained draws of a block are kept: blocks within the draw budget (none kept when fused)
+            blocks = hmc_mod.predict_blocks(blocks, n_mcmc, eng.q, draw_budget_bytes, fused_effects)
         acc_tail = 0.0
         row_scale = torch.zeros(n_test, device=dev, dtype=torch.float32) if (ra_target is not None or hmc is not None) else None
         row_mass = torch.zeros((n_test, eng.q), device=dev, dtype=torch.float32) if mass is not None else None
@@ -610,7 +614,18 @@ class CausalBGM(object):
             x = self._dev(data_x[s0:e0]).reshape(-1)
             y = self._dev(data_y[s0:e0]).reshape(-1)
             v = self._dev(data_v[s0:e0])
-            if hmc is not None:          # draws kept, effects from the draws (engine.effects), accumulated as below
+            if hmc is not None and fused_effects:      # effects inside the sampler (hmc_sample, effect=), accumulated as below
+                out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=hmc[3],
+                                     effect=_lib.EFFECT_ITE if binary else _lib.EFFECT_ADRF, x_values=x_values, sample_y=sample_y)
+                if row_mass is not None:
+                    row_mass[s0:e0] = out["mass_scale"]
+                if binary:
+                    mean, lo, hi = eng.row_mean_quantiles(out["ite"], alpha / 2, 1 - alpha / 2)
+                    res[0, s0:e0], res[1, s0:e0], res[2, s0:e0] = mean, lo, hi
+                else:
+                    sums += out["adrf"].double() * float(e0 - s0)
+                out["row_scale"] = out["row_step"]
+            elif hmc is not None:        # draws kept, effects from the draws (engine.effects), accumulated as below
                 out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2], mass=hmc[3])
                 if row_mass is not None:
                     row_mass[s0:e0] = out["mass_scale"]
@@ -684,13 +699,14 @@ class CausalBGM(object):
             row_adapt_mod.check_supported(type(self).__name__, self._p)
         return target
 
-    def _refuse_hmc(self, sampler, q_sd, row_adapt, step_size, n_leapfrog, mass='identity'):
+    def _refuse_hmc(self, sampler, q_sd, row_adapt, step_size, n_leapfrog, mass='identity', fused_effects=False):
         """predict of the subclasses without an HMC path: sampler='hmc' raises the ValueError that names what is in the way (and so
-        does a mass that belongs to it)."""
+        do a mass and a fused_effects that belong to it)."""
         if hmc_mod.check_predict_options(sampler, q_sd, row_adapt):
             hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
             raise ValueError("sampler='hmc' is not available for %s" % type(self).__name__)
         hmc_mod.check_mass(mass, False)
+        hmc_mod.check_fused(fused_effects, False, None)
 
     def _adaptive_sd_target(self, adaptive_sd, target_acceptance_rate):
         """adaptive_sd of metropolis_hastings_sampler -> None (None / bool: the fixed or the block-wide scale) or, for 'row', the

@@ -458,11 +458,12 @@ class CausalBGMBayes(CausalBGM):
         return state, acc_tail, tail
 
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
-                bs=10000, verbose=1, row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None, mass='identity'):
+                bs=10000, verbose=1, row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None, mass='identity',
+                fused_effects=False):
         """Causal effects with posterior intervals (base.py:573-668).  With Bayesian nets the rows of one block of ``bs``
         rows share their input statistics and weight perturbations, as in the reference; all blocks advance together."""
         self._row_adapt_target(row_adapt)      # (raises for anything but False: the per-chain proposal scale does not exist here)
-        self._refuse_hmc(sampler, q_sd, row_adapt, step_size, n_leapfrog, mass)      # (raises for anything but 'mh' / 'identity')
+        self._refuse_hmc(sampler, q_sd, row_adapt, step_size, n_leapfrog, mass, fused_effects)      # (raises for anything but 'mh' / 'identity')
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         binary = bool(self._p['binary_treatment'])

@@ -243,12 +243,13 @@ class IdentifiableCausalBGMBayes(CausalBGMBayes):
         return samples, np.eye(int(self.params['n_segments']), dtype=np.float32)[segs]
 
     def predict(self, data, alpha=0.01, n_mcmc=3000, x_values=None, q_sd=1.0, sample_y=True, bs=100, burn_in=5000, verbose=1,
-                row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None, mass='identity'):
+                row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None, mass='identity',
+                fused_effects=False):
         """Causal effects with posterior intervals (:348-420): ONE sampler run over all rows with a fresh random U (the panel is one
         block: one perturbation per network call for all rows), effects of every retained draw fused behind it; `bs` only chunked the
         host-side effect pass of the reference and does not change the result."""
         self._row_adapt_target(row_adapt)      # (raises for anything but False: the per-chain proposal scale does not exist here)
-        self._refuse_hmc(sampler, q_sd, row_adapt, step_size, n_leapfrog, mass)      # (raises for anything but 'mh' / 'identity')
+        self._refuse_hmc(sampler, q_sd, row_adapt, step_size, n_leapfrog, mass, fused_effects)      # (raises for anything but 'mh' / 'identity')
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         binary = bool(self._p['binary_treatment'])

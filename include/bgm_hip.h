@@ -388,6 +388,25 @@ BGM_API int bgm_causal_hmc_run(bgm_handle *h, const float *x_dev, const float *y
                                int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed, uint32_t *acc_count_dev,
                                float *draws_dev, int32_t n_keep, void *stream);
 
+/* bgm_causal_hmc_run with infer_from_latent_posterior inside the sampler: after the accept decision of every iteration
+ * it >= burn_in the outcome net is evaluated on the state the chain holds, by the routine of bgm_causal_effects with the noise
+ * counters of draw d = it - burn_in, so no draws need to be kept.  The arguments of bgm_causal_hmc_run, then those of
+ * bgm_causal_effects: binary -> ite_dev [n x n_keep]; continuous -> adrf_partial_dev [n_slots x n_keep x n_doses] (+=; n_slots =
+ * bgm_causal_evaluate_slots; reduce with bgm_adrf_reduce).  The effect follows the handle's binary_treatment.  Both outputs equal
+ * bit for bit what bgm_causal_effects computes from the draws of the same run (draws_dev may be given as well), and the chain is the
+ * chain of bgm_causal_hmc_run bit for bit; iterations before burn_in produce nothing, so a run may be cut anywhere.  n_keep > 0 is
+ * required and it_begin + n_iters <= burn_in + n_keep.  A metric set by bgm_causal_hmc_set_mass applies.  f's part of the sampling
+ * weights (3008 + 1024 KT1 floats) sits in LDS behind the HMC weights: generators too deep for both (more than 6 layers of 64 with
+ * sum(z_dims) <= 11, more than 5 above) answer BGM_E_UNSUPPORTED with the byte count before anything of the sampler is launched --
+ * sample with bgm_causal_hmc_run and draws_dev, then bgm_causal_effects.  Refuses what bgm_causal_logpost_grad refuses.
+ * replaces: nothing in causalbgm/base.py; infer_from_latent_posterior (:671-763) runs there on the stored draws of the MH sampler. */
+BGM_API int bgm_causal_hmc_run_effects(bgm_handle *h, const float *x_dev, const float *y_dev, const float *v_dev, int64_t n,
+                                       int64_t row_base, float *state_dev, float *logp_dev, float *grad_dev, float *step_dev,
+                                       const float *up_dev, const float *dn_dev, int32_t n_table, float s_min, float s_max, int32_t init,
+                                       int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed,
+                                       uint32_t *acc_count_dev, float *draws_dev, int32_t n_keep, int32_t sample_y,
+                                       const float *x_values_dev, int32_t n_doses, float *adrf_partial_dev, float *ite_dev, void *stream);
+
 /* Diagonal metric per chain for the bgm_causal_hmc_run calls made afterwards (opt-in; NULL = identity mass, today's kernels).
  * scale_dev [n x q], aligned with the rows of the call like state_dev: chain r carries s = scale_dev[r], M^-1 = diag(s^2), in the
  * scaled form -- momentum and kinetic energy as with identity mass, the step of coordinate i is step * s_i in the position step and
