@@ -8,6 +8,9 @@ rate) and frozen afterwards.  The kernels are csrc/causal_hmc_kernels.h.  Nothin
 (the step of coordinate i is eps s_i; momentum and kinetic energy are those of identity mass).  s is estimated by the chain alone
 from its own burn-in draws, in the windows of ``mass_windows``, and frozen afterwards; the step table restarts its Robbins-Monro gain
 at every change of the metric (``mass_schedule``).
+
+``predict_individual``: the option checks, the row blocks of ``interval='quantile'``, the finalisation of the per-row moments and the
+subgroup formula (``group_dose_response``) are at the end of the module.
 """
 import numpy as np
 
@@ -186,3 +189,67 @@ def mass_update(W, state, scale, ref, s1, s2):
         ok = (np.isfinite(vbar) & (vbar > 0))[:, 0]
         scale[ok] = new[ok]
     return scale, np.array(state, np.float32), np.zeros_like(scale), np.zeros_like(scale)
+
+
+# ---- predict_individual: the dose-response of every row (csrc/causal_hmc_rowfx_kernels.h) ----------------------------------------
+def check_individual(binary, x_values, interval, draw_budget_bytes):
+    """The options of predict_individual that are its own: a continuous treatment, x_values, interval 'normal' or 'quantile', and
+    a draw budget only where draws are stored; ValueError otherwise."""
+    if binary:
+        raise ValueError("predict_individual is the dose-response of every row under a continuous treatment; a binary treatment has "
+                         "its per-row effect already: predict's ITE")
+    if x_values is None:
+        raise ValueError("predict_individual needs x_values: the doses at which every row's outcome is evaluated")
+    if interval not in ("normal", "quantile"):
+        raise ValueError("interval must be 'normal' or 'quantile'; got %r" % (interval,))
+    if interval == "quantile" and draw_budget_bytes is not None and int(draw_budget_bytes) <= 0:
+        raise ValueError("draw_budget_bytes must be positive; got %r" % (draw_budget_bytes,))
+    if interval == "normal" and draw_budget_bytes is not None:
+        raise ValueError("interval='normal' and draw_budget_bytes exclude each other: the moments store no draws and this rank's rows "
+                         "are sampled in one piece")
+
+
+def individual_block_rows(n_keep, n_doses, budget_bytes=None):
+    """Rows of one block of predict_individual(interval='quantile'): the block's outcome draws [rows x n_doses x n_keep] float32
+    stay within the budget; a multiple of 16 (whole row tiles), at least 16."""
+    return block_rows(n_keep, n_doses, budget_bytes)
+
+
+def individual_blocks(blocks, n_keep, n_doses, interval, draw_budget_bytes=None):
+    """The row blocks [(start, stop)] of predict_individual: whole for interval='normal' (nothing of size n_keep is stored), cut to
+    individual_block_rows rows each for 'quantile'."""
+    if interval == "normal":
+        return list(blocks)
+    rows = individual_block_rows(n_keep, n_doses, draw_budget_bytes)
+    return [(s0, min(s0 + rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, rows)]
+
+
+def row_moments_finalize(ref, s1, s2, m):
+    """The shifted sums of m retained values (ref = the first value, s1 = sum of y - ref, s2 = sum of (y - ref)^2; NumPy arrays or
+    torch tensors of one shape) -> (mean, sd) in float64: mean = ref + s1 / m, var = (s2 - s1^2 / m) / (m - 1), clamped at 0 so that
+    a constant series gives sd 0 and no NaN.  m = 1 has no spread: sd 0."""
+    ref, s1, s2 = ((a.double() if hasattr(a, "double") else np.asarray(a, np.float64)) for a in (ref, s1, s2))
+    m = int(m)
+    mean = ref + s1 / m
+    if m < 2:
+        return mean, mean * 0.0
+    var = (s2 - s1 * s1 / m) / (m - 1)
+    var = var * (var > 0)
+    return mean, var ** 0.5
+
+
+def group_dose_response(mean, sd, groups):
+    """Subgroup curves from the rows' (mean, sd) [n, n_doses] and int labels [n] -> {label: (mean_g [n_doses], sd_g [n_doses])},
+    float64: mean_g = mean over the group's rows of mean_ik, sd_g = sqrt(sum_i sd_ik^2) / m_g.  The sd is exact, not an
+    approximation: given the fitted networks the posterior factorises over rows, and the chains and noise streams are keyed per row,
+    so the rows' values are independent and the variance of their average is the sum of their variances over m_g^2."""
+    mean, sd = np.asarray(mean, np.float64), np.asarray(sd, np.float64)
+    labels = np.asarray(groups)
+    if labels.shape != (mean.shape[0],) or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError("groups must be integer labels of shape [n] = (%d,); got %s of shape %r" % (mean.shape[0], labels.dtype, labels.shape))
+    out = {}
+    for g in np.unique(labels):
+        rows = labels == g
+        m_g = int(rows.sum())
+        out[int(g)] = (mean[rows].sum(axis=0) / m_g, np.sqrt((sd[rows] ** 2).sum(axis=0)) / m_g)
+    return out

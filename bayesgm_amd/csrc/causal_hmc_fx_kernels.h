@@ -46,8 +46,11 @@ __device__ __forceinline__ void chmc_fx_fill(float *lds_f, const CausalHmcFxArgs
   __syncthreads();
 }
 
-template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS>
-__device__ __forceinline__ void chmc_fx_run(float *lds, const CausalHmcKArgs &a, const CausalHmcMassArgs &ma, const CausalHmcFxArgs &fx) {
+// ROWS (causal_hmc_rowfx_kernels.h, EFFECT 1): the values stay with their rows, in row_mom / row_y (causal_effects, ROWS); fx.adrf_partial
+// and fx.ite are not used.
+template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false>
+__device__ __forceinline__ void chmc_fx_run(float *lds, const CausalHmcKArgs &a, const CausalHmcMassArgs &ma, const CausalHmcFxArgs &fx,
+                                            float *row_mom = nullptr, float *row_y = nullptr) {
   const CausalHmcMeta &m = a.m;
   const CausalMeta &mf = fx.mf;
   lds_fill(lds, a.blob, m.total);
@@ -174,10 +177,11 @@ __device__ __forceinline__ void chmc_fx_run(float *lds, const CausalHmcKArgs &a,
       }
       if (a.draws != nullptr && it >= a.burn_in && ok) chmc_store_z<KT1>(a.draws + (long long)(it - a.burn_in) * n * m.q, m.q, row, g, z[0]);
       if (it >= a.burn_in)      // (wave-uniform) infer_from_latent_posterior on the state the chain holds after this decision
-        causal_effects<KT1, KSL1, 1, EFFECT>(lds_f, mf, lane_off, g, j, lane, z, rowid, valid, row0, n, (unsigned)it, (long long)(it - a.burn_in),
-                                             fx.n_keep, fx.sample_y, fx.n_doses, fx.x_values,
-                                             fx.adrf_partial + slot * (long long)fx.n_doses * fx.n_keep /* unused when EFFECT == 2 */, fx.ite,
-                                             a.k0, a.k1);
+        causal_effects<KT1, KSL1, 1, EFFECT, true, false, false, true, ROWS>(
+            lds_f, mf, lane_off, g, j, lane, z, rowid, valid, row0, n, (unsigned)it, (long long)(it - a.burn_in), fx.n_keep, fx.sample_y,
+            fx.n_doses, fx.x_values,
+            ROWS ? nullptr : fx.adrf_partial + slot * (long long)fx.n_doses * fx.n_keep /* unused when EFFECT == 2 */, fx.ite, a.k0, a.k1,
+            nullptr, nullptr, row_mom, row_y);
     }
     if (ok) {
       chmc_store_z<KT1>(a.state, m.q, row, g, z[0]);

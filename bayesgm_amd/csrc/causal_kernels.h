@@ -571,14 +571,21 @@ __device__ __forceinline__ float pick_by_group(int g, float v0, float v1, float 
   return g == 0 ? v0 : (g == 1 ? v1 : (g == 2 ? v2 : v3));
 }
 
-template <int KT1, int KSL1, int R, int EFFECT, bool GROUPING = true, bool CACHE = false, bool EVAL_ONLY = false, bool L1MASK = true>
+// ROWS (EFFECT 1, one row tile per wave, grouped; causal_hmc_rowfx_kernels.h): y stays with its row instead of being summed over the
+// tile -- lane (j, g) owns (row j, its dose k of the pass) and keeps the shifted moments of y over the retained draws in
+// row_mom [3][n_doses][n] (ref = y of draw 0, s1 += y - ref, s2 += (y - ref)^2; plain loads and stores, one owner per element) and,
+// when row_y is given, the value itself in row_y[(row * n_doses + k) * n_keep + d].  adrf_slot / ite are not touched.
+template <int KT1, int KSL1, int R, int EFFECT, bool GROUPING = true, bool CACHE = false, bool EVAL_ONLY = false, bool L1MASK = true,
+          bool ROWS = false>
 __device__ __forceinline__ void causal_effects(const float *lds, const CausalMeta &m, int lane_off, int g, int j,
                                                int lane, const f32x4 (&zs)[R][KT1], const unsigned (&rowid)[R],
                                                const bool (&valid)[R], long long row0, long long n, unsigned it,
                                                long long d, int n_keep, int sample_y, int n_doses,
                                                const float *x_values, float *adrf_slot, float *ite, unsigned k0,
-                                               unsigned k1, float2 *cache = nullptr, float *ite_c = nullptr) {
+                                               unsigned k1, float2 *cache = nullptr, float *ite_c = nullptr,
+                                               float *row_mom = nullptr, float *row_y = nullptr) {
   // ite_c (EFFECT == 2, one row tile per wave, CACHE): [4] registers of the caller receiving (mean, sd) of the two arms
+  static_assert(!ROWS || (EFFECT == 1 && R == 1 && GROUPING && !CACHE && !EVAL_ONLY), "ROWS: the grouped finish of the dose-response sums");
   BGM_NO_HOIST();
   f32x4 z0in[R][KT1];
 #pragma unroll
@@ -700,6 +707,23 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
       const float noise = own ? nz[0][0] : pick_by_group(g, nz[0][0], nz[0][1], nz[0][2], nz[0][3]);
       if (own) nz[0] = f32x4{nz[0][1], nz[0][2], nz[0][3], nz[0][0]};
       float y = sample_y ? fmaf(sd_m, noise, mu_m) : mu_m;
+      if constexpr (ROWS) {
+        if (valid[0] && k < nd) {
+          const long long row = row0 + j, plane = (long long)nd * n;
+          long long off = (long long)k * n + row;
+          asm volatile("" : "+v"(off));
+          float *rf = row_mom + off;
+          if (d == 0) {
+            rf[0] = y; rf[plane] = 0.0f; rf[2 * plane] = 0.0f;
+          } else {
+            const float dv = y - rf[0];
+            rf[plane] += dv;
+            rf[2 * plane] = fmaf(dv, dv, rf[2 * plane]);
+          }
+          if (row_y) row_y[(row * nd + k) * (long long)n_keep + d] = y;
+        }
+        continue;
+      }
       y = (valid[0] && k < nd) ? y : 0.0f;
       const float tot = sum_over_j_to_lane15(y);
       if (j == 15 && k < nd) unsafeAtomicAdd(adrf_slot + (long long)d * nd + k, tot);

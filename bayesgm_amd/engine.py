@@ -147,6 +147,20 @@ class CausalEngine(object):
                                                        0 if x_values is None else int(x_values.numel()), _ptr(adrf_partial), _ptr(ite),
                                                        self._stream()), "bgm_causal_hmc_run_effects")
 
+    def hmc_run_rows_effects(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
+                             row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
+                             sample_y=True, x_values=None, row_moments=None, row_draws=None):
+        """hmc_run with the dose-response of every row kept (bgm_causal_hmc_run_row_effects; a continuous treatment): x_values
+        [n_doses]; row_moments [3, n_doses, n] float32 (ref = y at retained draw 0, s1 = sum of y - ref, s2 = sum of (y - ref)^2,
+        in / out across segments) and, optionally, row_draws [n, n_doses, n_keep] receive y_i(x_k) of the iterations >= burn_in of
+        this segment."""
+        _lib.check(self.lib.bgm_causal_hmc_run_row_effects(
+            self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up), _ptr(dn),
+            0 if up is None else int(up.numel()), float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters), int(burn_in),
+            int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws), int(n_keep), int(bool(sample_y)), _ptr(x_values),
+            0 if x_values is None else int(x_values.numel()), _ptr(row_moments), _ptr(row_draws), self._stream()),
+            "bgm_causal_hmc_run_row_effects")
+
     def set_hmc_mass(self, scale=None, ref=None, s1=None, s2=None, accumulate=False):
         """Diagonal metric of the hmc_run calls made afterwards (bgm_causal_hmc_set_mass): scale float32 [n x q] (device), the
         per-coordinate factors of every chain's step, aligned with the rows of the call.  accumulate: those calls also add
@@ -164,7 +178,7 @@ class CausalEngine(object):
 
     def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
                    adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None, effect=_lib.EFFECT_NONE,
-                   x_values=None, sample_y=True):
+                   x_values=None, sample_y=True, row_effects=False, row_draws=False):
         """HMC over the latent posterior of every row, one chain per row with a step size of its own.
 
         adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
@@ -179,6 +193,12 @@ class CausalEngine(object):
         effect = EFFECT_ADRF (with x_values) / EFFECT_ITE: infer_from_latent_posterior runs inside the sampler on every retained
         state (hmc_run), no draws are needed; every launch, burn-in included, is the fused kernel, so a model it refuses (LDS) is
         refused before any state is written.  The result is engine.effects on the draws of the same run, bit for bit.
+
+        row_effects = True (a continuous treatment, with x_values, instead of an effect): the dose-response of every row,
+        y_i(x_k) of every retained state, is summarised inside the sampler (hmc_run_rows_effects) into row_mean / row_sd
+        [n, n_doses] (float64, causal_hmc.row_moments_finalize) without stored draws; row_draws = True also returns them,
+        row_draws [n, n_doses, n_keep].  The chain is that of the run without effects, and a row's result depends on (seed,
+        row_base + row, the row's data) alone.
         Returns dict(draws [n_keep, n, q] | None, state, logp, grad, acc_count [burn_in + n_keep], row_step [n]) and, with a metric,
         mass_scale [n x q]; with an effect, adrf [n_doses, n_keep] or ite [n, n_keep]."""
         HM.check_args(step_size, n_leapfrog, adapt)
@@ -222,6 +242,20 @@ class CausalEngine(object):
             ite = torch.empty((n, n_keep), device=dev, dtype=torch.float32)
         elif effect != _lib.EFFECT_NONE:
             raise ValueError("hmc_sample: effect must be EFFECT_NONE, EFFECT_ADRF or EFFECT_ITE; got %r" % (effect,))
+        row_mom = row_y = None
+        if row_effects:
+            if effect != _lib.EFFECT_NONE:
+                raise ValueError("hmc_sample: row_effects and effect exclude each other (the panel's ADRF is the mean of the rows' curves)")
+            if self.binary:
+                raise ValueError("hmc_sample: row_effects is the dose-response of a continuous treatment; a binary treatment has its "
+                                 "per-row effect already (effect=EFFECT_ITE)")
+            if x_values is None:
+                raise ValueError("hmc_sample: row_effects needs x_values")
+            xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), dev)
+            row_mom = torch.zeros((3, xv.numel(), n), device=dev, dtype=torch.float32)      # ref, s1, s2
+            row_y = torch.empty((n, xv.numel(), n_keep), device=dev, dtype=torch.float32) if row_draws else None
+        elif row_draws:
+            raise ValueError("hmc_sample: row_draws belongs to row_effects=True")
         scale = moments = None
         if diag:
             scale = torch.ones((n, self.q), device=dev, dtype=torch.float32)
@@ -237,9 +271,14 @@ class CausalEngine(object):
             it = 0
             while it < total:
                 stop = min([it + chunk, total] + [b for b in marks if b > it])
-                self.hmc_run(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0),
-                             row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep, effect=effect,
-                             sample_y=sample_y, x_values=xv, adrf_partial=partial, ite=ite)
+                if row_mom is not None:
+                    self.hmc_run_rows_effects(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0),
+                                              row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep,
+                                              sample_y=sample_y, x_values=xv, row_moments=row_mom, row_draws=row_y)
+                else:
+                    self.hmc_run(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0),
+                                 row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep, effect=effect,
+                                 sample_y=sample_y, x_values=xv, adrf_partial=partial, ite=ite)
                 if stop in marks:      # a window's edge: the first one only sets the reference point and turns the moments on
                     k = marks.index(stop)
                     self.hmc_mass_update(0 if k == 0 else stop - marks[k - 1], state, scale, *moments)
@@ -255,6 +294,11 @@ class CausalEngine(object):
             out["adrf"] = self.adrf_reduce(partial, n_slots, xv.numel(), n_keep, n)
         if ite is not None:
             out["ite"] = ite
+        if row_mom is not None:
+            mean, sd = HM.row_moments_finalize(row_mom[0], row_mom[1], row_mom[2], n_keep)
+            out["row_mean"], out["row_sd"] = mean.t().contiguous(), sd.t().contiguous()
+            if row_y is not None:
+                out["row_draws"] = row_y
         return out
 
     def encode(self, v):

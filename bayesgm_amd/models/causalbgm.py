@@ -10,6 +10,7 @@ reference's default) the constructor returns the Bayesian-network subclass of ca
 """
 import datetime
 import os
+from statistics import NormalDist
 
 import numpy as np
 import torch
@@ -61,6 +62,8 @@ class CausalBGM(object):
     mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last sampler call that asked for them
     hmc_row_step_ = None             # per-row HMC step sizes (NumPy, global row order) of the last predict(sampler='hmc') / hmc_sampler call
     hmc_row_mass_ = None             # per-row, per-coordinate HMC metric scales [n, q] (NumPy, global row order) of the last mass='diag' call; None otherwise
+    individual_sd_ = None            # per-row, per-dose posterior sd [n, n_doses] (NumPy float64) of the last predict_individual call
+    group_dose_response_ = None      # {label: (mean [n_doses], sd [n_doses])} of the last predict_individual(groups=...) call; None otherwise
     mh_row_scale_ = None             # per-row proposal scales (NumPy, global row order) of the last predict / sampler call; None when it ran without row adaptation
 
     def __new__(cls, params, *args, **kwargs):
@@ -669,6 +672,83 @@ class CausalBGM(object):
         causal_effects = (sums / float(n_test)).float().contiguous()
         adrf, lo, hi = eng.row_mean_quantiles(causal_effects, alpha / 2, 1 - alpha / 2)
         return adrf.cpu().numpy(), torch.stack([lo, hi], dim=1).cpu().numpy()
+
+    def predict_individual(self, data, x_values, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None, n_leapfrog=None,
+                           mass='identity', interval='normal', draw_budget_bytes=None, groups=None, verbose=1):
+        """The dose-response curve of every row under a continuous treatment, with its posterior uncertainty: ``(mean [n, n_doses],
+        interval [n, n_doses, 2])`` of y_i(x_k), the outcome of row i at dose ``x_values[k]``.  The reference has no counterpart
+        (its continuous-treatment ``predict`` averages over the panel); a binary treatment has ``predict``'s ITE.
+
+        The latents are always sampled by the HMC sampler of ``predict(sampler='hmc')`` (``step_size``, ``n_leapfrog``, ``mass`` and
+        the seed sequence as there; the steps and the metric are left in ``self.hmc_row_step_`` / ``self.hmc_row_mass_``), and the
+        outcome net runs inside the sampling kernel after every retained decision.  Per row and dose the kernel keeps the moments
+        of the ``n_mcmc`` values; their standard deviations are left in ``self.individual_sd_`` [n, n_doses].
+
+        ``interval='normal'`` (default): ``mean -/+ z(1 - alpha/2) * sd``.  This is a NORMAL APPROXIMATION of the posterior of
+        y_i(x_k), not a quantile of its draws.  Nothing of size ``n_mcmc`` is stored and this rank's shard is sampled in one piece.
+        ``interval='quantile'``: the exact ``alpha/2`` and ``1 - alpha/2`` quantiles of the stored draws; rows are sampled in blocks
+        whose ``rows x n_doses x n_mcmc x 4`` bytes fit ``draw_budget_bytes`` (default 2 GiB).  ``mean`` and the sd still come from
+        the moments, and a chain and its outcome noise depend on the row alone, so the blocks do not change a row's result.
+
+        ``groups`` (int labels [n], optional): ``self.group_dose_response_ = {label: (mean_g, sd_g)}``, the curve of every subgroup
+        (causal_hmc.group_dose_response).  Under torch.distributed the rows are sharded by rank and the results gathered."""
+        self.hmc_row_step_ = None
+        self.hmc_row_mass_ = None
+        self.individual_sd_ = None
+        self.group_dose_response_ = None
+        hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
+        mass = hmc_mod.check_mass(mass, True, True, burn_in)
+        hmc_mod.check_individual(bool(self._p['binary_treatment']), x_values, interval, draw_budget_bytes)
+        assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
+        parallel.check_n_mcmc(n_mcmc)
+        x_values = np.array([x_values], dtype=float) if np.isscalar(x_values) else np.array(x_values, dtype=float)
+        data_x, data_y, data_v = data
+        n_test, n_doses = len(data_x), len(x_values)
+        if groups is not None:
+            hmc_mod.group_dose_response(np.zeros((n_test, 0)), np.zeros((n_test, 0)), groups)      # (the labels' checks, before a device is touched)
+        seed = self._next_seed()
+        if verbose:
+            print('MCMC Latent Variable Sampling ...')
+        eng = self.engine
+        dev = eng.device
+        total_it = burn_in + n_mcmc
+        lo_r, hi_r = parallel.shard_range(n_test)
+        blocks = hmc_mod.individual_blocks([(lo_r, hi_r)] if hi_r > lo_r else [], n_mcmc, n_doses, interval, draw_budget_bytes)
+        quantile = interval == 'quantile'
+        res = torch.zeros((4 if quantile else 2, n_test, n_doses), device=dev, dtype=torch.float64)      # mean, sd(, lower, upper): this rank's rows filled
+        row_step = torch.zeros(n_test, device=dev, dtype=torch.float32)
+        row_mass = torch.zeros((n_test, eng.q), device=dev, dtype=torch.float32) if mass is not None else None
+        acc_tail = 0.0
+        for (s0, e0) in blocks:
+            x = self._dev(data_x[s0:e0]).reshape(-1)
+            y = self._dev(data_y[s0:e0]).reshape(-1)
+            v = self._dev(data_v[s0:e0])
+            out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=mass, row_effects=True,
+                                 row_draws=quantile, x_values=x_values, sample_y=sample_y)
+            res[0, s0:e0], res[1, s0:e0] = out["row_mean"], out["row_sd"]
+            if quantile:
+                _, lo, hi = eng.row_mean_quantiles(out["row_draws"].reshape((e0 - s0) * n_doses, n_mcmc), alpha / 2, 1 - alpha / 2)
+                res[2, s0:e0], res[3, s0:e0] = lo.reshape(e0 - s0, n_doses).double(), hi.reshape(e0 - s0, n_doses).double()
+                del out["row_draws"]
+            row_step[s0:e0] = out["row_step"]
+            if row_mass is not None:
+                row_mass[s0:e0] = out["mass_scale"]
+            acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
+        self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
+        self.hmc_row_step_ = parallel.all_reduce_sum_(row_step).cpu().numpy()      # disjoint row sets: the sum is the gather
+        if row_mass is not None:
+            self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
+        res = parallel.all_reduce_sum_(res).cpu().numpy()
+        mean, sd = res[0], res[1]
+        self.individual_sd_ = sd
+        if quantile:
+            bounds = np.stack([res[2], res[3]], axis=-1)
+        else:
+            z = NormalDist().inv_cdf(1.0 - alpha / 2)
+            bounds = np.stack([mean - z * sd, mean + z * sd], axis=-1)
+        if groups is not None:
+            self.group_dose_response_ = hmc_mod.group_dose_response(mean, sd, groups)
+        return mean, bounds
 
     @staticmethod
     def _diagnose_windows(n_test, k):

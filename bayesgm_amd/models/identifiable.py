@@ -268,6 +268,12 @@ class IdentifiableCausalBGM(CausalBGM):
             self.engine.set_prior(None, None)
         return samples, np.eye(int(self.params['n_segments']), dtype=np.float32)[segs]
 
+    def predict_individual(self, data, x_values=None, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None, n_leapfrog=None,
+                           mass='identity', interval='normal', draw_budget_bytes=None, groups=None, verbose=1):
+        """CausalBGM.predict_individual always uses the HMC sampler, which this class does not have: the refusal of
+        ``predict(sampler='hmc')``, word for word."""
+        self._refuse_hmc('hmc', 1.0, False, step_size, n_leapfrog, mass)
+
     def predict(self, data, alpha=0.01, n_mcmc=3000, x_values=None, q_sd=1.0, sample_y=True, bs=100, burn_in=5000, verbose=1,
                 row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None, mass='identity',
                 fused_effects=False):

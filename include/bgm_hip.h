@@ -407,6 +407,32 @@ BGM_API int bgm_causal_hmc_run_effects(bgm_handle *h, const float *x_dev, const 
                                        uint32_t *acc_count_dev, float *draws_dev, int32_t n_keep, int32_t sample_y,
                                        const float *x_values_dev, int32_t n_doses, float *adrf_partial_dev, float *ite_dev, void *stream);
 
+/* bgm_causal_hmc_run with the dose-response of every ROW kept inside the sampler (a continuous treatment): after the accept
+ * decision of every iteration it >= burn_in the outcome net is evaluated on the state the chain holds, exactly as
+ * bgm_causal_hmc_run_effects evaluates it (same routine, same noise counters: dose k of draw d = it - burn_in takes word k & 3 of
+ * Philox(row_base + row, it, k >> 2)), and y_i(x_k) stays with its row instead of being summed over the panel.  The arguments of
+ * bgm_causal_hmc_run_effects with row_moments_dev / row_draws_dev in place of adrf_partial_dev / ite_dev:
+ *   row_moments_dev [3 x n_doses x n] float32 (required), shifted sums over the retained draws of every (dose, row):
+ *     plane 0 = ref, the value at retained draw 0 (written by the iteration it == burn_in, which also zeroes the other two);
+ *     plane 1 = s1 = sum of (y - ref); plane 2 = s2 = sum of (y - ref)^2.  After m draws: mean = ref + s1 / m,
+ *     var = (s2 - s1^2 / m) / (m - 1) (finalise in float64).  In / out across the calls of one run;
+ *   row_draws_dev [n x n_doses x n_keep] float32 or NULL: row_draws_dev[(row * n_doses + k) * n_keep + d] = y, the layout
+ *     bgm_row_mean_quantiles reads ([n * n_doses] rows of n_keep).
+ * Every (row, dose) has one owner lane: plain loads and stores, no atomics, so a run cut at any iteration is bit-identical to one
+ * call, and a row's result depends on (seed, row_base + row, the row's data) only -- not on n, the grid or the rank count.  The
+ * chain is the chain of bgm_causal_hmc_run bit for bit; a metric set by bgm_causal_hmc_set_mass applies.  Row r of a one-row panel
+ * (row_base = r) gives in bgm_causal_hmc_run_effects' ADRF the same numbers as row_draws_dev[r] here.  n_keep > 0 is required and
+ * it_begin + n_iters <= burn_in + n_keep.  A binary-treatment handle answers BGM_E_INVALID: its per-row effect is BGM_EFFECT_ITE of
+ * bgm_causal_hmc_run_effects.  The LDS budget and every other refusal are those of bgm_causal_hmc_run_effects.
+ * replaces: nothing in causalbgm/base.py; infer_from_latent_posterior (:671-763) averages y_i(x_k) over the rows of the panel. */
+BGM_API int bgm_causal_hmc_run_row_effects(bgm_handle *h, const float *x_dev, const float *y_dev, const float *v_dev, int64_t n,
+                                           int64_t row_base, float *state_dev, float *logp_dev, float *grad_dev, float *step_dev,
+                                           const float *up_dev, const float *dn_dev, int32_t n_table, float s_min, float s_max,
+                                           int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog,
+                                           uint64_t seed, uint32_t *acc_count_dev, float *draws_dev, int32_t n_keep, int32_t sample_y,
+                                           const float *x_values_dev, int32_t n_doses, float *row_moments_dev, float *row_draws_dev,
+                                           void *stream);
+
 /* Diagonal metric per chain for the bgm_causal_hmc_run calls made afterwards (opt-in; NULL = identity mass, today's kernels).
  * scale_dev [n x q], aligned with the rows of the call like state_dev: chain r carries s = scale_dev[r], M^-1 = diag(s^2), in the
  * scaled form -- momentum and kinetic energy as with identity mass, the step of coordinate i is step * s_i in the position step and
