@@ -85,9 +85,9 @@ class BnnEngine(object):
     def set_precision(self, mode):
         """Arithmetic of logpost / mh_run / effects launched afterwards: "fp32" (default) | "f16x3" (bgm_bnn_set_precision); needs an open
         session and is kept across begin()."""
-        self._precision = mode
         if self.open:
             _lib.check(self.lib.bgm_bnn_set_precision(self.h, {"fp32": 0, "bf16x3": 1, "f16x3": 2}[mode]), "bgm_bnn_set_precision")
+        self._precision = mode          # (after the check: a refused mode is not remembered)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
