@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("BGM_HIP_LIB", os.path.join(_HERE, "libbgm_hip.so"))  
 BGM_MAX_LAYERS = 8
 NET_G, NET_F, NET_H, NET_E = 0, 1, 2, 3
 EFFECT_NONE, EFFECT_ADRF, EFFECT_ITE = 0, 1, 2
+EFFECT_GROUP_ITE = 4      # the ITE summed by row label inside the HMC sampler (bgm_causal_hmc_run_group_effects only)
+MAX_GROUP_LABELS = 64
 
 
 class CausalConfig(C.Structure):
@@ -209,6 +211,11 @@ SYMBOLS = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
                                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
                                                  C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bgm_causal_hmc_run_group_effects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
+                                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
+                                                   C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bgm_ite_group_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "bgm_causal_hmc_set_mass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "bgm_causal_hmc_mass_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),

@@ -11,6 +11,9 @@ at every change of the metric (``mass_schedule``).
 
 ``predict_individual``: the option checks, the row blocks of ``interval='quantile'``, the finalisation of the per-row moments and the
 subgroup formula (``group_dose_response``) are at the end of the module.
+
+``predict_average``: the option checks, the internal row labels and the combiner of the per-draw label sums into ATE / ATT / ATC
+(``combine_average_effects``) follow them.
 """
 import numpy as np
 
@@ -253,3 +256,80 @@ def group_dose_response(mean, sd, groups):
         m_g = int(rows.sum())
         out[int(g)] = (mean[rows].sum(axis=0) / m_g, np.sqrt((sd[rows] ** 2).sum(axis=0)) / m_g)
     return out
+
+
+# ---- predict_average: ATE / ATT / ATC and subgroup effects of a binary treatment (csrc/causal_hmc_gfx_kernels.h) ------------------
+ESTIMANDS = ("ate", "att", "atc")
+MAX_GROUPS = 32                   # 2 * MAX_GROUPS internal labels (group, arm): the 64 labels of bgm_causal_hmc_run_group_effects
+
+
+def check_average(binary, estimand, groups, n):
+    """The options of predict_average that are its own: a binary treatment, an estimand of ESTIMANDS, groups None or integer labels
+    [n] with at most MAX_GROUPS distinct values; ValueError naming the option otherwise.
+    -> (group_labels [n_groups] sorted distinct labels, or None without groups; group_index [n] int64 in [0, n_groups))."""
+    if not binary:
+        raise ValueError("predict_average is the average effect of a binary treatment (ATE / ATT / ATC); a continuous treatment has "
+                         "its dose-response: predict's ADRF")
+    if estimand not in ESTIMANDS:
+        raise ValueError("estimand must be 'ate', 'att' or 'atc'; got %r" % (estimand,))
+    if groups is None:
+        return None, np.zeros(int(n), np.int64)
+    labels = np.asarray(groups)
+    if labels.shape != (int(n),) or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError("groups must be integer labels of shape [n] = (%d,); got %s of shape %r" % (int(n), labels.dtype, labels.shape))
+    distinct, index = np.unique(labels, return_inverse=True)
+    if len(distinct) > MAX_GROUPS:
+        raise ValueError("groups: at most %d distinct labels; got %d" % (MAX_GROUPS, len(distinct)))
+    return distinct, index.reshape(-1).astype(np.int64)
+
+
+def average_labels(group_index, x):
+    """The row label of the kernels: 2 * group + arm, arm = 1 for a treated row (x_i = 1) -> int32 [n]"""
+    arm = (np.asarray(x, np.float64).reshape(-1) > 0.5).astype(np.int64)
+    return (2 * np.asarray(group_index, np.int64) + arm).astype(np.int32)
+
+
+def average_counts(labels, n_groups):
+    """Rows per (group, arm) -> float64 [n_groups, 2]"""
+    return np.bincount(np.asarray(labels, np.int64), minlength=2 * int(n_groups)).astype(np.float64).reshape(int(n_groups), 2)
+
+
+def combine_average_effects(sums, counts):
+    """Per-draw label sums S[g, arm, d] of the individual treatment effect (arm 1 = the treated rows) and row counts n[g, arm] ->
+    dict(ate, att, atc), each float64 [n_groups, n_draws]:
+        ATE_g,d = (S_g0 + S_g1) / (n_g0 + n_g1),   ATT_g,d = S_g1 / n_g1,   ATC_g,d = S_g0 / n_g0.
+    An estimand whose denominator is zero is nan for that group.  Sums and counts are additive over row shards: add the shards'
+    arrays (an all-reduce) before calling."""
+    S, cnt = np.asarray(sums, np.float64), np.asarray(counts, np.float64)
+    if S.ndim != 3 or S.shape[1] != 2 or cnt.shape != S.shape[:2]:
+        raise ValueError("combine_average_effects: sums [n_groups, 2, n_draws] and counts [n_groups, 2]; got %r and %r" % (S.shape, cnt.shape))
+
+    def ratio(num, den):
+        out = np.full(num.shape, np.nan)
+        ok = den > 0
+        out[ok] = num[ok] / den[ok][:, None]
+        return out
+    return dict(ate=ratio(S[:, 0] + S[:, 1], cnt[:, 0] + cnt[:, 1]), att=ratio(S[:, 1], cnt[:, 1]), atc=ratio(S[:, 0], cnt[:, 0]))
+
+
+def average_summary(series, alpha):
+    """Per-draw averages [n_groups, n_draws] -> (effect [n_groups], interval [n_groups, 2]): the mean over the draws and the
+    alpha / 2 and 1 - alpha / 2 quantiles with linear interpolation between order statistics (NumPy's default, the rule of
+    bgm_row_mean_quantiles that predict applies to the ADRF), in float64; nan rows stay nan."""
+    series = np.asarray(series, np.float64)
+    effect = np.full(series.shape[0], np.nan)
+    bounds = np.full((series.shape[0], 2), np.nan)
+    ok = ~np.isnan(series).any(axis=1)
+    if ok.any():
+        effect[ok] = series[ok].mean(axis=1)
+        bounds[ok] = np.quantile(series[ok], [alpha / 2, 1 - alpha / 2], axis=1).T
+    return effect, bounds
+
+
+def check_average_estimand(estimand, effect, group_labels):
+    """The estimand asked for must exist in every group; ValueError naming estimand and the groups without its rows otherwise."""
+    bad = np.flatnonzero(np.isnan(np.asarray(effect, np.float64)))
+    if len(bad):
+        which = "the panel" if group_labels is None else "groups %r" % ([int(group_labels[i]) for i in bad],)
+        raise ValueError("estimand=%r is undefined for %s: no %s rows to average over" %
+                         (estimand, which, {"ate": "", "att": "treated", "atc": "control"}[estimand]))

@@ -48,6 +48,10 @@ __device__ __forceinline__ void chmc_fx_fill(float *lds_f, const CausalHmcFxArgs
 
 // ROWS (causal_hmc_rowfx_kernels.h, EFFECT 1): the values stay with their rows, in row_mom / row_y (causal_effects, ROWS); fx.adrf_partial
 // and fx.ite are not used.
+// EFFECT 4 (causal_hmc_gfx_kernels.h): the ITE summed by row label.  fx.n_doses = n_labels, fx.adrf_partial = group_partial
+// [n_slots][n_keep][n_labels], and fx.ite, which no ITE is stored through, carries the labels [n] int: as a kernel argument of its
+// own the pointer left the KT1 = 1 kernel with a metric a 20-byte private segment.  A row's label is read at the effect call, where
+// mom / zc / gc are dead, not held across the leapfrog loop.
 template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false>
 __device__ __forceinline__ void chmc_fx_run(float *lds, const CausalHmcKArgs &a, const CausalHmcMassArgs &ma, const CausalHmcFxArgs &fx,
                                             float *row_mom = nullptr, float *row_y = nullptr) {
@@ -176,12 +180,15 @@ __device__ __forceinline__ void chmc_fx_run(float *lds, const CausalHmcKArgs &a,
         }
       }
       if (a.draws != nullptr && it >= a.burn_in && ok) chmc_store_z<KT1>(a.draws + (long long)(it - a.burn_in) * n * m.q, m.q, row, g, z[0]);
-      if (it >= a.burn_in)      // (wave-uniform) infer_from_latent_posterior on the state the chain holds after this decision
+      if (it >= a.burn_in) {    // (wave-uniform) infer_from_latent_posterior on the state the chain holds after this decision
+        int label = 0;
+        if constexpr (EFFECT == 4) label = reinterpret_cast<const int *>(fx.ite)[row];
         causal_effects<KT1, KSL1, 1, EFFECT, true, false, false, true, ROWS>(
             lds_f, mf, lane_off, g, j, lane, z, rowid, valid, row0, n, (unsigned)it, (long long)(it - a.burn_in), fx.n_keep, fx.sample_y,
             fx.n_doses, fx.x_values,
             ROWS ? nullptr : fx.adrf_partial + slot * (long long)fx.n_doses * fx.n_keep /* unused when EFFECT == 2 */, fx.ite, a.k0, a.k1,
-            nullptr, nullptr, row_mom, row_y);
+            nullptr, nullptr, row_mom, row_y, label);
+      }
     }
     if (ok) {
       chmc_store_z<KT1>(a.state, m.q, row, g, z[0]);

@@ -575,6 +575,10 @@ __device__ __forceinline__ float pick_by_group(int g, float v0, float v1, float 
 // tile -- lane (j, g) owns (row j, its dose k of the pass) and keeps the shifted moments of y over the retained draws in
 // row_mom [3][n_doses][n] (ref = y of draw 0, s1 += y - ref, s2 += (y - ref)^2; plain loads and stores, one owner per element) and,
 // when row_y is given, the value itself in row_y[(row * n_doses + k) * n_keep + d].  adrf_slot / ite are not touched.
+// EFFECT 4 (R == 1; causal_hmc_gfx_kernels.h): the ITE of EFFECT 2, line for line up to yk[0] - yk[1], summed by row label instead of
+// stored.  `label` is the row's label (the same in the four lanes of a row), n_doses carries n_labels, adrf_slot is the wave's slot
+// [n_keep][n_labels]: adrf_slot[d * n_labels + c] += sum over the tile's valid rows with label c, the labels present in the tile taken
+// in the order of their lowest row, each by ONE DPP row reduction and ONE addition from lane 15.  ite is not touched.
 template <int KT1, int KSL1, int R, int EFFECT, bool GROUPING = true, bool CACHE = false, bool EVAL_ONLY = false, bool L1MASK = true,
           bool ROWS = false>
 __device__ __forceinline__ void causal_effects(const float *lds, const CausalMeta &m, int lane_off, int g, int j,
@@ -583,9 +587,11 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
                                                long long d, int n_keep, int sample_y, int n_doses,
                                                const float *x_values, float *adrf_slot, float *ite, unsigned k0,
                                                unsigned k1, float2 *cache = nullptr, float *ite_c = nullptr,
-                                               float *row_mom = nullptr, float *row_y = nullptr) {
+                                               float *row_mom = nullptr, float *row_y = nullptr, int label = 0) {
   // ite_c (EFFECT == 2, one row tile per wave, CACHE): [4] registers of the caller receiving (mean, sd) of the two arms
   static_assert(!ROWS || (EFFECT == 1 && R == 1 && GROUPING && !CACHE && !EVAL_ONLY), "ROWS: the grouped finish of the dose-response sums");
+  static_assert(EFFECT != 4 || (R == 1 && !CACHE && !EVAL_ONLY && !ROWS), "EFFECT 4: the label sums of one row tile per wave");
+  constexpr bool ARMS = (EFFECT == 2 || EFFECT == 4);   // the two arms x = 1, x = 0 of a binary treatment
   BGM_NO_HOIST();
   f32x4 z0in[R][KT1];
 #pragma unroll
@@ -600,8 +606,8 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
   f32x4 wx[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) wx[t] = *reinterpret_cast<const f32x4 *>(lds + m.wxf + 16 * t + 4 * g);
-  const int nd = (EFFECT == 2) ? (CACHE && n_doses == 0 ? 0 : 2) : n_doses;     // (CACHE: n_doses = 0 switches the evaluation off)
-  constexpr int DB = (EFFECT == 2) ? 2 : 4;  // doses evaluated per pass (independent MFMA chains)
+  const int nd = ARMS ? (CACHE && n_doses == 0 ? 0 : 2) : n_doses;     // (CACHE: n_doses = 0 switches the evaluation off)
+  constexpr int DB = ARMS ? 2 : 4;  // doses evaluated per pass (independent MFMA chains)
   constexpr bool GROUPED = (EFFECT == 1 && R == 1 && GROUPING);   // lane group g finishes dose e = g of a pass (see above)
   const int n_calls = (nd + 3) >> 2, n_own = GROUPED ? (n_calls & ~3) : 0;   // Philox calls [0, n_own) in groups of four
   f32x4 nz[R];
@@ -619,7 +625,7 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
 #pragma unroll
     for (int e = 0; e < DB; ++e) {
       const int k = own ? 4 * (c4 + e) + p4 : 4 * kb + e;
-      xk[e] = (EFFECT == 2) ? (e == 0 ? 1.0f : 0.0f) : x_values[k < nd ? k : nd - 1];
+      xk[e] = ARMS ? (e == 0 ? 1.0f : 0.0f) : x_values[k < nd ? k : nd - 1];
     }
     float mu[DB * R], sr[DB * R];
 #ifndef BGM_NO_JIT_EFFECTS
@@ -749,6 +755,16 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
         tot = sum_over_j_to_lane15(tot);  // values are valid in lane group 0 -> lane 15
         const int k = 4 * kb + e;
         if (lane == 15 && k < nd) unsafeAtomicAdd(adrf_slot + (long long)d * nd + k, tot);
+      }
+    } else if constexpr (EFFECT == 4) {
+      const float v = valid[0] ? yk[0][0] - yk[1][0] : 0.0f;     // (a padding lane carries the clamped row's label and adds nothing)
+      unsigned rest = (unsigned)__ballot(valid[0] && g == 0);    // the tile's rows (lanes 0 .. 15) whose label has not been summed yet
+      while (rest) {
+        const int c = __builtin_amdgcn_readlane(label, __builtin_ctz(rest));     // the label of the lowest remaining row
+        const bool mine = label == c;
+        const float tot = sum_over_j_to_lane15(mine ? v : 0.0f);
+        if (lane == 15 && (unsigned)c < (unsigned)n_doses) unsafeAtomicAdd(adrf_slot + (long long)d * n_doses + c, tot);
+        rest &= ~(unsigned)__ballot(mine);
       }
     } else {
 #pragma unroll

@@ -129,16 +129,21 @@ class CausalEngine(object):
 
     def hmc_run(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False, row_base=0,
                 up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0, effect=_lib.EFFECT_NONE,
-                sample_y=True, x_values=None, adrf_partial=None, ite=None):
+                sample_y=True, x_values=None, adrf_partial=None, ite=None, labels=None, n_labels=0, group_partial=None):
         """One segment of the HMC latent sampler for all rows (bgm_causal_hmc_run); state / logp / grad / step are in / out.
         effect = EFFECT_ADRF / EFFECT_ITE: the segment runs the kernels with the effect pass inside (bgm_causal_hmc_run_effects):
         x_values [n_doses] and adrf_partial [n_slots, n_keep, n_doses] (+=), or ite [n, n_keep], receive the effects of the
-        iterations >= burn_in of this segment."""
+        iterations >= burn_in of this segment.  effect = EFFECT_GROUP_ITE: hmc_run_group_effects with labels / n_labels /
+        group_partial."""
         args = (self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up),
                 _ptr(dn), 0 if up is None else int(up.numel()), float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters),
                 int(burn_in), int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws), int(n_keep))
         if effect == _lib.EFFECT_NONE:
             _lib.check(self.lib.bgm_causal_hmc_run(*args, self._stream()), "bgm_causal_hmc_run")
+            return
+        if effect == _lib.EFFECT_GROUP_ITE:
+            _lib.check(self.lib.bgm_causal_hmc_run_group_effects(*args, int(bool(sample_y)), _ptr(labels), int(n_labels), _ptr(group_partial),
+                                                                 self._stream()), "bgm_causal_hmc_run_group_effects")
             return
         if effect not in (_lib.EFFECT_ADRF, _lib.EFFECT_ITE) or (effect == _lib.EFFECT_ITE) != bool(self.binary):
             raise ValueError("hmc_run: effect must be EFFECT_NONE or the effect of the treatment type (EFFECT_ITE for a binary "
@@ -161,6 +166,40 @@ class CausalEngine(object):
             0 if x_values is None else int(x_values.numel()), _ptr(row_moments), _ptr(row_draws), self._stream()),
             "bgm_causal_hmc_run_row_effects")
 
+    def hmc_run_group_effects(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, labels=None, n_labels=0,
+                              group_partial=None, **kw):
+        """hmc_run with the individual treatment effect of a binary treatment summed by row label inside the sampler
+        (bgm_causal_hmc_run_group_effects): labels [n] int32 on the device, every label in [0, n_labels) -- the caller's duty, the
+        kernel does not report a label outside --, group_partial [n_slots, n_keep, n_labels] float32 (+=, n_slots =
+        bgm_causal_evaluate_slots) receives the sums of the iterations >= burn_in of this segment.  The other arguments are
+        hmc_run's."""
+        self.hmc_run(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, effect=_lib.EFFECT_GROUP_ITE,
+                     labels=labels, n_labels=n_labels, group_partial=group_partial, **kw)
+
+    def _group_labels(self, labels, n_labels, n, who):
+        """labels [n] (NumPy or tensor, integer) with every label in [0, n_labels), checked on the host -> int32 tensor on the device"""
+        n_labels = int(n_labels) if n_labels is not None else 0
+        if not 1 <= n_labels <= _lib.MAX_GROUP_LABELS:
+            raise ValueError("%s: n_labels must be in [1, %d]; got %r" % (who, _lib.MAX_GROUP_LABELS, n_labels))
+        host = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        if labels is None or host.shape != (n,) or not np.issubdtype(host.dtype, np.integer):
+            raise ValueError("%s: labels must be integers of shape [n] = (%d,); got %s of shape %r" % (who, n, host.dtype, host.shape))
+        if n and (int(host.min()) < 0 or int(host.max()) >= n_labels):
+            raise ValueError("%s: labels must lie in [0, n_labels) = [0, %d); got %d .. %d" % (who, n_labels, int(host.min()), int(host.max())))
+        return torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(self.device), n_labels
+
+    def ite_group_sums(self, ite, labels, n_labels):
+        """ite [n, n_keep] float32 on the device, labels [n] in [0, n_labels) -> float64 [n_labels, n_keep]: the sums of ite over the
+        rows of every label (bgm_ite_group_sums; rows in ascending order, one owner per element, bit-identical from call to call)."""
+        ite = _f32(ite, self.device)
+        n, n_keep = ite.shape
+        lab, n_labels = self._group_labels(labels, n_labels, n, "ite_group_sums")
+        out = torch.zeros((n_labels, n_keep), device=self.device, dtype=torch.float64)
+        if n and n_keep:
+            _lib.check(self.lib.bgm_ite_group_sums(self.h, _ptr(ite), _ptr(lab), n, n_keep, n_labels, _ptr(out), self._stream()),
+                       "bgm_ite_group_sums")
+        return out
+
     def set_hmc_mass(self, scale=None, ref=None, s1=None, s2=None, accumulate=False):
         """Diagonal metric of the hmc_run calls made afterwards (bgm_causal_hmc_set_mass): scale float32 [n x q] (device), the
         per-coordinate factors of every chain's step, aligned with the rows of the call.  accumulate: those calls also add
@@ -178,7 +217,7 @@ class CausalEngine(object):
 
     def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
                    adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None, effect=_lib.EFFECT_NONE,
-                   x_values=None, sample_y=True, row_effects=False, row_draws=False):
+                   x_values=None, sample_y=True, row_effects=False, row_draws=False, labels=None, n_labels=None):
         """HMC over the latent posterior of every row, one chain per row with a step size of its own.
 
         adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
@@ -194,13 +233,19 @@ class CausalEngine(object):
         state (hmc_run), no draws are needed; every launch, burn-in included, is the fused kernel, so a model it refuses (LDS) is
         refused before any state is written.  The result is engine.effects on the draws of the same run, bit for bit.
 
+        effect = EFFECT_GROUP_ITE (a binary treatment, with labels [n] in [0, n_labels), n_labels <= 64): the ITE of every retained
+        state is summed by row label inside the sampler (hmc_run_group_effects) and no ITE matrix is stored: group_sums
+        [n_labels, n_keep] float32, the sum over each label's rows per draw (group_partial [n_slots, n_keep, n_labels], the wave
+        slots' sums it is reduced from, is returned too).  A row's value is that of EFFECT_ITE bit for bit; the sums depend on the
+        grid through the slots, not on chunk.
+
         row_effects = True (a continuous treatment, with x_values, instead of an effect): the dose-response of every row,
         y_i(x_k) of every retained state, is summarised inside the sampler (hmc_run_rows_effects) into row_mean / row_sd
         [n, n_doses] (float64, causal_hmc.row_moments_finalize) without stored draws; row_draws = True also returns them,
         row_draws [n, n_doses, n_keep].  The chain is that of the run without effects, and a row's result depends on (seed,
         row_base + row, the row's data) alone.
         Returns dict(draws [n_keep, n, q] | None, state, logp, grad, acc_count [burn_in + n_keep], row_step [n]) and, with a metric,
-        mass_scale [n x q]; with an effect, adrf [n_doses, n_keep] or ite [n, n_keep]."""
+        mass_scale [n x q]; with an effect, adrf [n_doses, n_keep], ite [n, n_keep] or group_sums [n_labels, n_keep]."""
         HM.check_args(step_size, n_leapfrog, adapt)
         diag = HM.check_mass(mass, True, adapt if adapt_table is None else True) is not None
         if diag and mass_scale is not None:
@@ -228,8 +273,8 @@ class CausalEngine(object):
         acc = torch.zeros(total, device=dev, dtype=torch.int32)
         draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
         chunk = total if chunk is None else max(1, int(chunk))
-        xv = partial = ite = None
-        n_slots = 0
+        xv = partial = ite = lab = gpartial = None
+        n_slots = n_lab = 0
         if effect == _lib.EFFECT_ADRF:
             if x_values is None:
                 raise ValueError("hmc_sample: effect=EFFECT_ADRF needs x_values")
@@ -240,8 +285,23 @@ class CausalEngine(object):
             partial = torch.zeros((n_slots, n_keep, xv.numel()), device=dev, dtype=torch.float32)
         elif effect == _lib.EFFECT_ITE:
             ite = torch.empty((n, n_keep), device=dev, dtype=torch.float32)
+        elif effect == _lib.EFFECT_GROUP_ITE:
+            if not self.binary:
+                raise ValueError("hmc_sample: effect=EFFECT_GROUP_ITE sums the treatment effect of a binary treatment; a continuous "
+                                 "treatment has its dose-response (effect=EFFECT_ADRF)")
+            lab, n_lab = self._group_labels(labels, n_labels, n, "hmc_sample")
+            ns = C.c_int32()
+            _lib.check(self.lib.bgm_causal_evaluate_slots(self.h, n, C.byref(ns)), "bgm_causal_evaluate_slots")
+            n_slots = ns.value
+            try:
+                gpartial = torch.zeros((n_slots, n_keep, n_lab), device=dev, dtype=torch.float32)
+            except torch.cuda.OutOfMemoryError:
+                raise RuntimeError("hmc_sample: cannot allocate group_partial [n_slots x n_keep x n_labels] = [%d x %d x %d] float32 (%d "
+                                   "bytes)" % (n_slots, n_keep, n_lab, 4 * n_slots * n_keep * n_lab))
         elif effect != _lib.EFFECT_NONE:
-            raise ValueError("hmc_sample: effect must be EFFECT_NONE, EFFECT_ADRF or EFFECT_ITE; got %r" % (effect,))
+            raise ValueError("hmc_sample: effect must be EFFECT_NONE, EFFECT_ADRF, EFFECT_ITE or EFFECT_GROUP_ITE; got %r" % (effect,))
+        if labels is not None and effect != _lib.EFFECT_GROUP_ITE:
+            raise ValueError("hmc_sample: labels belong to effect=EFFECT_GROUP_ITE")
         row_mom = row_y = None
         if row_effects:
             if effect != _lib.EFFECT_NONE:
@@ -278,7 +338,8 @@ class CausalEngine(object):
                 else:
                     self.hmc_run(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0),
                                  row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep, effect=effect,
-                                 sample_y=sample_y, x_values=xv, adrf_partial=partial, ite=ite)
+                                 sample_y=sample_y, x_values=xv, adrf_partial=partial, ite=ite, labels=lab, n_labels=n_lab,
+                                 group_partial=gpartial)
                 if stop in marks:      # a window's edge: the first one only sets the reference point and turns the moments on
                     k = marks.index(stop)
                     self.hmc_mass_update(0 if k == 0 else stop - marks[k - 1], state, scale, *moments)
@@ -294,6 +355,9 @@ class CausalEngine(object):
             out["adrf"] = self.adrf_reduce(partial, n_slots, xv.numel(), n_keep, n)
         if ite is not None:
             out["ite"] = ite
+        if gpartial is not None:
+            out["group_partial"] = gpartial
+            out["group_sums"] = self.adrf_reduce(gpartial, n_slots, n_lab, n_keep, 1.0)
         if row_mom is not None:
             mean, sd = HM.row_moments_finalize(row_mom[0], row_mom[1], row_mom[2], n_keep)
             out["row_mean"], out["row_sd"] = mean.t().contiguous(), sd.t().contiguous()

@@ -750,6 +750,97 @@ class CausalBGM(object):
             self.group_dose_response_ = hmc_mod.group_dose_response(mean, sd, groups)
         return mean, bounds
 
+    average_effects_ = None          # predict_average: dict(ate, att, atc, *_interval, *_draws, counts, groups)
+
+    def predict_average(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, groups=None, estimand='ate', sampler='hmc',
+                        q_sd=1.0, step_size=None, n_leapfrog=None, mass='identity', verbose=1):
+        """Average effects of a binary treatment with posterior intervals: ``(effect, interval)`` of ``estimand`` = ``'ate'`` (all
+        rows), ``'att'`` (the treated rows, x_i = 1) or ``'atc'`` (the control rows), the average of the individual treatment
+        effect over those rows.  The reference has no counterpart (its tutorial takes ``mean(ITE)`` of ``predict``: a point estimate);
+        a continuous treatment has ``predict``'s ADRF.
+
+        For every retained draw the ITE is averaged over the rows FIRST; the effect is the mean of the ``n_mcmc`` per-draw averages
+        and the interval their ``alpha / 2`` and ``1 - alpha / 2`` quantiles (linear interpolation, as ``predict``'s ADRF).  Without
+        ``groups`` the result is ``(float, [2])``; with ``groups`` (int labels [n], at most 32 distinct) it is ``([n_groups],
+        [n_groups, 2])`` in the order of the sorted distinct labels: the subgroup effects (CATE).  All three estimands, their
+        per-draw series [n_groups, n_mcmc], the row counts [n_groups, 2] (control, treated) and the group labels are left in
+        ``self.average_effects_``; an estimand without rows in a group is nan there and raises when it is the one asked for.
+
+        ``sampler='hmc'`` (default): the HMC sampler of ``predict(sampler='hmc', fused_effects=True)`` -- ``step_size``,
+        ``n_leapfrog``, ``mass`` and the seed sequence as there, ``self.hmc_row_step_`` / ``self.hmc_row_mass_`` set as there -- with
+        the ITE summed by (group, arm) inside the sampling kernel: neither draws nor an ITE matrix are stored and this rank's shard
+        is sampled in one piece.  ``sampler='mh'``: the MH sampler call of ``predict`` with a fixed ``q_sd`` and its cap on the ITE
+        matrix; the matrix of every block is reduced by label on the device.  Under torch.distributed the rows are sharded by rank
+        and the per-draw sums (float64) and counts are all-reduced."""
+        self.average_effects_ = None
+        self.hmc_row_step_ = None
+        self.hmc_row_mass_ = None
+        hmc = None
+        if hmc_mod.check_predict_options(sampler, q_sd, False):
+            hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
+        elif q_sd is None or not float(q_sd) > 0:
+            raise ValueError("predict_average needs a fixed q_sd > 0 with sampler='mh': the block-wide adaptive scale depends on "
+                             "predict's bs blocks; got %r" % (q_sd,))
+        mass = hmc_mod.check_mass(mass, hmc is not None, True, burn_in)
+        data_x, data_y, data_v = data
+        n_test = len(data_x)
+        group_labels, group_index = hmc_mod.check_average(bool(self._p['binary_treatment']), estimand, groups, n_test)
+        assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
+        parallel.check_n_mcmc(n_mcmc)
+        n_groups = 1 if group_labels is None else len(group_labels)
+        n_labels = 2 * n_groups
+        labels = hmc_mod.average_labels(group_index, data_x)
+        seed = self._next_seed()
+        if verbose:
+            print('MCMC Latent Variable Sampling ...')
+        eng = self.engine
+        dev = eng.device
+        total_it = burn_in + n_mcmc
+        lo_r, hi_r = parallel.shard_range(n_test)
+        blocks = [(lo_r, hi_r)] if hi_r > lo_r else []
+        if hmc is None:                  # the [rows x n_mcmc] ITE matrix of one launch stays below ~32 GiB, as in predict
+            max_rows = max(16, int((32 << 30) // (4 * max(1, n_mcmc))))
+            blocks = [(s0, min(s0 + max_rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, max_rows)]
+        sums = torch.zeros((n_labels, n_mcmc), device=dev, dtype=torch.float64)
+        counts = torch.from_numpy(hmc_mod.average_counts(labels[lo_r:hi_r], n_groups)).to(dev)
+        row_step = torch.zeros(n_test, device=dev, dtype=torch.float32) if hmc is not None else None
+        row_mass = torch.zeros((n_test, eng.q), device=dev, dtype=torch.float32) if mass is not None else None
+        acc_tail = 0.0
+        for (s0, e0) in blocks:
+            x = self._dev(data_x[s0:e0]).reshape(-1)
+            y = self._dev(data_y[s0:e0]).reshape(-1)
+            v = self._dev(data_v[s0:e0])
+            if hmc is not None:
+                out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=mass,
+                                     effect=_lib.EFFECT_GROUP_ITE, labels=labels[s0:e0], n_labels=n_labels, sample_y=sample_y)
+                sums += out["group_sums"].double()
+                row_step[s0:e0] = out["row_step"]
+                if row_mass is not None:
+                    row_mass[s0:e0] = out["mass_scale"]
+            else:
+                out = eng.mh_sample(x, y, v, burn_in, n_mcmc, q_sd, seed, effect=_lib.EFFECT_ITE, sample_y=sample_y, row_base=s0,
+                                    adaptive=False, row_adapt=None)
+                sums += eng.ite_group_sums(out["ite"], labels[s0:e0], n_labels)
+                del out["ite"]
+            acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
+        self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
+        if row_step is not None:
+            self.hmc_row_step_ = parallel.all_reduce_sum_(row_step).cpu().numpy()      # disjoint row sets: the sum is the gather
+            if row_mass is not None:
+                self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
+        sums = parallel.all_reduce_sum_(sums).cpu().numpy().reshape(n_groups, 2, n_mcmc)
+        counts = parallel.all_reduce_sum_(counts).cpu().numpy()
+        series = hmc_mod.combine_average_effects(sums, counts)
+        res = dict(counts=counts.astype(np.int64), groups=None if group_labels is None else np.array(group_labels))
+        for name in hmc_mod.ESTIMANDS:
+            res[name], res[name + "_interval"] = hmc_mod.average_summary(series[name], alpha)
+            res[name + "_draws"] = series[name]
+        self.average_effects_ = res
+        hmc_mod.check_average_estimand(estimand, res[estimand], group_labels)
+        if group_labels is None:
+            return float(res[estimand][0]), res[estimand + "_interval"][0]
+        return res[estimand], res[estimand + "_interval"]
+
     @staticmethod
     def _diagnose_windows(n_test, k):
         """Up to 8 evenly spaced contiguous row windows [start, stop) over the panel holding k rows in all (all rows when

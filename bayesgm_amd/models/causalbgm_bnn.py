@@ -463,6 +463,12 @@ class CausalBGMBayes(CausalBGM):
         ``predict(sampler='hmc')``, word for word."""
         self._refuse_hmc('hmc', 1.0, False, step_size, n_leapfrog, mass)
 
+    def predict_average(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, groups=None, estimand='ate', sampler='hmc',
+                        q_sd=1.0, step_size=None, n_leapfrog=None, mass='identity', verbose=1):
+        """CausalBGM.predict_average exists for the deterministic CausalBGM only: this class refuses it, whatever the sampler."""
+        raise ValueError("predict_average is not available for %s: its label sums are built on the sampling calls of CausalBGM.predict; "
+                         "average the ITE of this class's predict instead" % type(self).__name__)
+
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
                 bs=10000, verbose=1, row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None, mass='identity',
                 fused_effects=False):

@@ -433,6 +433,43 @@ BGM_API int bgm_causal_hmc_run_row_effects(bgm_handle *h, const float *x_dev, co
                                            const float *x_values_dev, int32_t n_doses, float *row_moments_dev, float *row_draws_dev,
                                            void *stream);
 
+/* bgm_causal_hmc_run with the individual treatment effect of a binary treatment summed by ROW LABEL inside the sampler: after the
+ * accept decision of every iteration it >= burn_in the outcome net is evaluated at x = 1 and x = 0 on the state the chain holds,
+ * exactly as bgm_causal_hmc_run_effects (BGM_EFFECT_ITE) evaluates it -- a row's y(1) - y(0) of draw d = it - burn_in is bit for bit
+ * the value that call writes to ite_dev[row * n_keep + d] -- and added to the sum of the row's label instead of being stored: ATE,
+ * ATT, ATC and subgroup effects per retained draw without an [n x n_keep] matrix.  The arguments of bgm_causal_hmc_run_effects with
+ * labels_dev, n_labels and group_partial_dev in place of x_values_dev, n_doses, adrf_partial_dev and ite_dev:
+ *   labels_dev [n] int32, the label c of every row, 0 <= c < n_labels;
+ *   group_partial_dev [n_slots x n_keep x n_labels] float32 (+=; n_slots = bgm_causal_evaluate_slots): element (s, d, c) = the sum
+ *     over the rows with label c that wave slot s walks; reduce with bgm_adrf_reduce (n_doses = n_labels, n_total = 1 for the sums).
+ * Order of the additions: fixed.  Per 16-row tile the labels present are taken in the order of their lowest row, the values of a
+ * label's rows are reduced by one tree over the tile and added to the slot by one lane; no two lanes add onto one address.  The
+ * partials therefore depend on the grid (which tiles share a slot) but not on how the run is cut: iterations before burn_in produce
+ * nothing, a run may be cut anywhere and is bit-identical to one call, group_partial_dev included.  The chain is the chain of
+ * bgm_causal_hmc_run bit for bit (draws_dev may be given as well); a metric set by bgm_causal_hmc_set_mass applies.  n_keep > 0 is
+ * required and it_begin + n_iters <= burn_in + n_keep.
+ * Limits: 1 <= n_labels <= 64 (BGM_E_INVALID outside, with the value).  A label outside [0, n_labels) is the caller's error: check
+ * the labels on the host before the launch (the kernel adds such a row nowhere, it does not report it).  A caller that cannot
+ * allocate group_partial_dev should name its n_slots * n_keep * n_labels * 4 bytes.  A continuous-treatment handle answers
+ * BGM_E_INVALID: its effect is BGM_EFFECT_ADRF of bgm_causal_hmc_run_effects.  The LDS budget and every other refusal are those of
+ * bgm_causal_hmc_run_effects.
+ * replaces: nothing in causalbgm/base.py; infer_from_latent_posterior (:671-763) returns the ITE of every row and draw, and the
+ * average effects are left to the caller as the mean of its posterior means. */
+BGM_API int bgm_causal_hmc_run_group_effects(bgm_handle *h, const float *x_dev, const float *y_dev, const float *v_dev, int64_t n,
+                                             int64_t row_base, float *state_dev, float *logp_dev, float *grad_dev, float *step_dev,
+                                             const float *up_dev, const float *dn_dev, int32_t n_table, float s_min, float s_max,
+                                             int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog,
+                                             uint64_t seed, uint32_t *acc_count_dev, float *draws_dev, int32_t n_keep, int32_t sample_y,
+                                             const int32_t *labels_dev, int32_t n_labels, float *group_partial_dev, void *stream);
+
+/* The same label sums from a stored ITE matrix (bgm_causal_mh_run / bgm_causal_hmc_run_effects with BGM_EFFECT_ITE, bgm_causal_effects):
+ * out_dev[c * n_keep + d] = sum over the rows with labels_dev[row] = c of ite_dev[row * n_keep + d], float64.  Every output element
+ * has one owner thread that walks the rows in ascending order: no atomics, the result does not depend on the grid and repeated
+ * calls are bit-identical.  1 <= n_labels <= 64 (BGM_E_INVALID outside); a label outside [0, n_labels) is counted nowhere.
+ * replaces: nothing in causalbgm/base.py (np.mean over the rows of the ITE's posterior mean, in the reference's tutorial). */
+BGM_API int bgm_ite_group_sums(bgm_handle *h, const float *ite_dev, const int32_t *labels_dev, int64_t n, int32_t n_keep,
+                               int32_t n_labels, double *out_dev, void *stream);
+
 /* Diagonal metric per chain for the bgm_causal_hmc_run calls made afterwards (opt-in; NULL = identity mass, today's kernels).
  * scale_dev [n x q], aligned with the rows of the call like state_dev: chain r carries s = scale_dev[r], M^-1 = diag(s^2), in the
  * scaled form -- momentum and kinetic energy as with identity mass, the step of coordinate i is step * s_i in the position step and
