@@ -1,6 +1,7 @@
 // causal_hmc_api.hip -- C-ABI entry points of the CausalBGM log posterior with its gradient and of the HMC latent sampler with a step
 // size per chain (bgm_causal_logpost_grad, bgm_causal_hmc_run; include/bgm_hip.h), and the host-side packing of their weights: the
-// Gram copy of the sampling blob (causal_api.hip) re-laid in the dual-access layout of bgm_kernels.h.  Kernels: causal_hmc_kernels.h.
+// Gram copy of the sampling blob (causal_api.hip) re-laid in the dual-access layout of bgm_kernels.h.  Kernels: causal_hmc_kernels.h;
+// the transition behind causal_hmc_kernel is chmc_run (causal_hmc_fx_kernels.h), shared with the metric and the effect kernels.
 // Of the shape table (causal_launch.h) only KT1 matters to these kernels: the Gram form takes g's output layer, and with it NTL, out
 // of them, and the dual-access first layers always run all 4 KT1 K-steps, so KSL1 has no meaning either.  They are instantiated per
 // KT1 and dispatched through bgm_causal_dispatch on the handle's shape like every other family.
@@ -135,6 +136,8 @@ int bgm_causal_hmc_args(bgm_handle *h, const char *who_, const float *x, const f
   BGM_HIP_CHECK(hipSetDevice(h->device));
   st = nullptr;
   if (int rc = hmc_prepare(h, v, n, stream, st)) return rc;
+  const CausalHmcMassArgs &ma = st->mass;      // bgm_causal_hmc_set_mass
+  if (ma.scale && ma.accumulate && (!ma.ref || !ma.s1 || !ma.s2)) { bgm_set_error("HMC metric: launched without its buffers"); return BGM_E_STATE; }
   ka = CausalHmcKArgs{};
   ka.blob = st->blob_dev; ka.x = x; ka.y = y; ka.uc = h->uc_dev; ka.n = n; ka.row_base = row_base;
   ka.state = state; ka.logp = logp; ka.grad = grad; ka.step = step;

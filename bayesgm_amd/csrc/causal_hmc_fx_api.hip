@@ -1,6 +1,6 @@
 // causal_hmc_fx_api.hip -- bgm_causal_hmc_run_effects (include/bgm_hip.h): the CausalBGM HMC latent sampler with the effect pass
-// fused into the retained iterations (causal_hmc_fx_kernels.h), in a translation unit of its own.  The paths without effects
-// (causal_hmc_api.hip, causal_hmc_mass_api.hip) are untouched: bgm_causal_hmc_run never comes here.
+// fused into the retained iterations (the EFFECT 1 / 2 instantiations of chmc_run, causal_hmc_fx_kernels.h), in a translation unit
+// of its own, compiled beside the others: bgm_causal_hmc_run (causal_hmc_api.hip, causal_hmc_mass_api.hip) never comes here.
 // replaces: nothing in causalbgm/base.py; infer_from_latent_posterior (:671-763) runs there on stored MH draws.
 #include <string>
 
@@ -12,15 +12,13 @@ namespace {
 const char *WHO = "bgm_causal_hmc_run_effects";
 
 template <int EFFECT>
-int launch_fx(bgm_handle *h, const CausalHmcKArgs &ka, const CausalHmcMassArgs &ma, const CausalHmcFxArgs &fx, int grid, int lds, hipStream_t stream) {
-  if (ma.scale)
-    return bgm_causal_dispatch(h, "HMC kernel with a diagonal metric and fused effects", [&](auto s) {
-      using S = decltype(s);
-      return bgm_launch(causal_hmc_mass_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka, ma, fx);
-    });
-  return bgm_causal_dispatch(h, "HMC kernel with fused effects", [&](auto s) {
+int launch_fx(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, const CausalHmcFxArgs &fx, int grid, int lds, hipStream_t stream) {
+  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with fused effects", [&](auto s, auto metric) {
     using S = decltype(s);
-    return bgm_launch(causal_hmc_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka, fx);
+    if constexpr (decltype(metric)::value)
+      return bgm_launch(causal_hmc_mass_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka, st->mass, fx);
+    else
+      return bgm_launch(causal_hmc_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka, fx);
   });
 }
 
@@ -47,8 +45,7 @@ extern "C" int bgm_causal_hmc_run_effects(bgm_handle *h, const float *x, const f
   if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin,
                                          n_iters, burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid, fx, lds))
     return rc;
-  const CausalHmcMassArgs &ma = st->mass;      // bgm_causal_hmc_set_mass
   fx.sample_y = sample_y; fx.n_doses = binary ? 2 : n_doses;
   fx.x_values = x_values; fx.adrf_partial = adrf_partial; fx.ite = ite;
-  return binary ? launch_fx<2>(h, ka, ma, fx, grid, (int)lds, stream) : launch_fx<1>(h, ka, ma, fx, grid, (int)lds, stream);
+  return binary ? launch_fx<2>(h, ka, st, fx, grid, (int)lds, stream) : launch_fx<1>(h, ka, st, fx, grid, (int)lds, stream);
 }

@@ -49,8 +49,6 @@ static inline int bgm_causal_hmc_fx_prepare(bgm_handle *h, const char *who_, con
   if (int rc = bgm_causal_hmc_args(h, who_, x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters,
                                    burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid))
     return rc;
-  const CausalHmcMassArgs &ma = st->mass;      // bgm_causal_hmc_set_mass
-  if (ma.scale && ma.accumulate && (!ma.ref || !ma.s1 || !ma.s2)) { bgm_set_error("HMC metric: launched without its buffers"); return BGM_E_STATE; }
   bgm_causal_hmc_fx_layout(h, fx);
   if (fx.mf.total != chmc_fx_floats(h->KT1) || (size_t)(st->m.total + fx.mf.total) * 4 != lds) { bgm_set_error(who + ": LDS layout disagrees with its byte count"); return BGM_E_STATE; }
   fx.sblob = h->sblob_dev;

@@ -1,21 +1,29 @@
-// causal_hmc_fx_kernels.h -- the HMC transitions of causal_hmc_kernels.h / causal_hmc_mass_kernels.h with the effect pass inside
-// the sampler (gfx950): no retained draws are needed to estimate the dose-response curve or the treatment effects.
+// causal_hmc_fx_kernels.h -- the HMC transition of the CausalBGM latent sampler (gfx950), chmc_run: ONE body behind all eight
+// kernels -- identity mass or the diagonal metric of causal_hmc_mass_kernels.h (MASS), without an effect pass (EFFECT 0:
+// causal_hmc_kernel, causal_hmc_mass_kernel) or with it inside the sampler (causal_hmc_fx_kernel, causal_hmc_mass_fx_kernel; the
+// per-row and label-sum kernels of causal_hmc_rowfx_kernels.h / causal_hmc_gfx_kernels.h), where no retained draws are needed to
+// estimate the dose-response curve or the treatment effects.  The kernels are thin wrappers; which of them a translation unit
+// instantiates is decided by its dispatch lambdas.
 //
-// replaces: infer_from_latent_posterior (causalbgm/base.py:671-763) behind an HMC chain; the reference has no HMC sampler for
-//   CausalBGM and computes its effects from stored MH draws.
+// replaces: nothing in causalbgm/base.py for the transition (the reference samples CausalBGM's latents by random-walk MH only; the
+//   transition is that of bgm/base.py:709-830, tfp HamiltonianMonteCarlo); infer_from_latent_posterior (causalbgm/base.py:671-763)
+//   for the effect pass, which the reference computes from stored MH draws.
 //
-// causal_hmc_fx_kernel / causal_hmc_mass_fx_kernel are causal_hmc_kernel / causal_hmc_mass_kernel (same registers, same LDS blob, same
-// RNG streams, same accept rule, step table and metric) with ONE addition: after the decision of every retained iteration the outcome
-// net is evaluated on the chain's state by causal_effects (causal_kernels.h), the routine bgm_causal_effects runs over stored draws.
+// One chain per row, persistent over a segment of iterations.  state, logp, grad and step travel between launches, so a run cut at
+// any iteration is the same run.  After the decision of iteration it < n_table the chain's step is multiplied by up[it] (it moved)
+// or dn[it] (it did not) and clamped: ONE fp32 multiply (row_adapt.py).
+// EFFECT != 0: after the decision of every retained iteration the outcome net is evaluated on the chain's state by causal_effects
+// (causal_kernels.h), the routine bgm_causal_effects runs over stored draws; registers, LDS blob, RNG streams, accept rule, step
+// table and metric are those of EFFECT 0.
 // z is already in its register layout (feature 16 t + 4 r + g, x at feature q), the grid and the tile walk are those of
 // causal_effects_kernel (slot = blockIdx.x * WAVES + wave, stride gridDim.x * WAVES), and the noise counters are (row, it): element
 // (slot, d, k) of adrf_partial receives the same additions in the same order on both routes, so the fused result IS the two-pass one.
 // causal_effects reads f in the layout of the SAMPLING blob (not the dual-access one of the gradient): f's pieces of that blob --
 // w1f, b1f, wf2 .. bf4, wxf, 3008 + 1024 KT1 floats -- are copied behind the HMC blob in LDS, byte for byte from where
 // bgm_causal_effects reads them.  The call sits where mom / zc / gc are dead.
-// Kernels of their own beside the old ones, not a flag on a shared body: the kernels without effects keep their code objects
-// instruction for instruction (scripts/compare_code_objects.py).  The two new kernels share one body (MASS is a template argument).
 #pragma once
+#include <type_traits>
+
 #include "causal_hmc_mass_kernels.h"
 #include "causal_kernels.h"
 
@@ -52,14 +60,22 @@ __device__ __forceinline__ void chmc_fx_fill(float *lds_f, const CausalHmcFxArgs
 // [n_slots][n_keep][n_labels], and fx.ite, which no ITE is stored through, carries the labels [n] int: as a kernel argument of its
 // own the pointer left the KT1 = 1 kernel with a metric a 20-byte private segment.  A row's label is read at the effect call, where
 // mom / zc / gc are dead, not held across the leapfrog loop.
+// EFFECT 0: no copy of f's pieces, no causal_effects call, fx unused.
+// How the body receives the kernel's argument structs decides the code hipcc makes of it: by const
+// reference for the kernels with an effect pass (by value every one of them changes), by value for the two kernels without -- with
+// references those load every kernel argument in the prologue and hold it in SGPRs (causal_hmc_kernel<1, 8>: 198 -> 199 VGPRs,
+// + 167 instructions).
+template <class T, int EFFECT>
+using chmc_arg = std::conditional_t<EFFECT == 0, T, const T &>;
+
 template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false>
-__device__ __forceinline__ void chmc_fx_run(float *lds, const CausalHmcKArgs &a, const CausalHmcMassArgs &ma, const CausalHmcFxArgs &fx,
-                                            float *row_mom = nullptr, float *row_y = nullptr) {
+__device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EFFECT> a, chmc_arg<CausalHmcMassArgs, EFFECT> ma,
+                                         chmc_arg<CausalHmcFxArgs, EFFECT> fx, float *row_mom = nullptr, float *row_y = nullptr) {
   const CausalHmcMeta &m = a.m;
   const CausalMeta &mf = fx.mf;
   lds_fill(lds, a.blob, m.total);
   const float *lds_f = lds + m.total;
-  chmc_fx_fill(lds + m.total, fx);
+  if constexpr (EFFECT != 0) chmc_fx_fill(lds + m.total, fx);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4, lane_off = 64 * g + j;
   const long long n = a.n, n_tiles = (n + 15) / 16;
   const long long slot = (long long)blockIdx.x * WAVES + wave;
@@ -180,7 +196,7 @@ __device__ __forceinline__ void chmc_fx_run(float *lds, const CausalHmcKArgs &a,
         }
       }
       if (a.draws != nullptr && it >= a.burn_in && ok) chmc_store_z<KT1>(a.draws + (long long)(it - a.burn_in) * n * m.q, m.q, row, g, z[0]);
-      if (it >= a.burn_in) {    // (wave-uniform) infer_from_latent_posterior on the state the chain holds after this decision
+      if constexpr (EFFECT != 0) if (it >= a.burn_in) {    // (wave-uniform) infer_from_latent_posterior on the state the chain holds after this decision
         int label = 0;
         if constexpr (EFFECT == 4) label = reinterpret_cast<const int *>(fx.ite)[row];
         causal_effects<KT1, KSL1, 1, EFFECT, true, false, false, true, ROWS>(
@@ -198,14 +214,26 @@ __device__ __forceinline__ void chmc_fx_run(float *lds, const CausalHmcKArgs &a,
   }
 }
 
+template <int KT1, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void causal_hmc_kernel(CausalHmcKArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  chmc_run<KT1, 1, WAVES, 0, false>(lds, a, CausalHmcMassArgs{}, CausalHmcFxArgs{});
+}
+
+template <int KT1, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void causal_hmc_mass_kernel(CausalHmcKArgs a, CausalHmcMassArgs ma) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  chmc_run<KT1, 1, WAVES, 0, true>(lds, a, ma, CausalHmcFxArgs{});
+}
+
 template <int KT1, int KSL1, int WAVES, int EFFECT>
 __global__ __launch_bounds__(64 * WAVES) void causal_hmc_fx_kernel(CausalHmcKArgs a, CausalHmcFxArgs fx) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  chmc_fx_run<KT1, KSL1, WAVES, EFFECT, false>(lds, a, CausalHmcMassArgs{}, fx);
+  chmc_run<KT1, KSL1, WAVES, EFFECT, false>(lds, a, CausalHmcMassArgs{}, fx);
 }
 
 template <int KT1, int KSL1, int WAVES, int EFFECT>
 __global__ __launch_bounds__(64 * WAVES) void causal_hmc_mass_fx_kernel(CausalHmcKArgs a, CausalHmcMassArgs ma, CausalHmcFxArgs fx) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  chmc_fx_run<KT1, KSL1, WAVES, EFFECT, true>(lds, a, ma, fx);
+  chmc_run<KT1, KSL1, WAVES, EFFECT, true>(lds, a, ma, fx);
 }

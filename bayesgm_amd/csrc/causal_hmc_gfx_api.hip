@@ -1,7 +1,7 @@
 // causal_hmc_gfx_api.hip -- bgm_causal_hmc_run_group_effects and bgm_ite_group_sums (include/bgm_hip.h): the CausalBGM HMC latent
 // sampler with the individual treatment effect summed by row label inside the retained iterations, and the same sums from a stored
-// ITE matrix (causal_hmc_gfx_kernels.h), in a translation unit of its own.  The fused-ADRF / ITE path (causal_hmc_fx_api.hip), the
-// per-row path (causal_hmc_rowfx_api.hip) and the paths without effects are untouched.
+// ITE matrix (causal_hmc_gfx_kernels.h: the EFFECT 4 instantiations of chmc_run), in a translation unit of its own, compiled beside
+// those of the other HMC entry points.
 // replaces: nothing in causalbgm/base.py; infer_from_latent_posterior (:671-763) returns the ITE of every row and draw.
 #include <string>
 
@@ -42,18 +42,15 @@ extern "C" int bgm_causal_hmc_run_group_effects(bgm_handle *h, const float *x, c
   if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin,
                                          n_iters, burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid, fx, lds))
     return rc;
-  const CausalHmcMassArgs &ma = st->mass;      // bgm_causal_hmc_set_mass
   fx.sample_y = sample_y; fx.n_doses = n_labels;      // (the slot's stride: [n_keep][n_labels])
   fx.adrf_partial = group_partial;
-  fx.ite = reinterpret_cast<float *>(const_cast<int32_t *>(labels));      // (read only, as int: chmc_fx_run, EFFECT 4)
-  if (ma.scale)
-    return bgm_causal_dispatch(h, "HMC kernel with a diagonal metric and label sums of the treatment effect", [&](auto s) {
-      using S = decltype(s);
-      return bgm_launch(causal_hmc_mass_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, ma, fx);
-    });
-  return bgm_causal_dispatch(h, "HMC kernel with label sums of the treatment effect", [&](auto s) {
+  fx.ite = reinterpret_cast<float *>(const_cast<int32_t *>(labels));      // (read only, as int: chmc_run, EFFECT 4)
+  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with label sums of the treatment effect", [&](auto s, auto metric) {
     using S = decltype(s);
-    return bgm_launch(causal_hmc_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, fx);
+    if constexpr (decltype(metric)::value)
+      return bgm_launch(causal_hmc_mass_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, st->mass, fx);
+    else
+      return bgm_launch(causal_hmc_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, fx);
   });
 }
 

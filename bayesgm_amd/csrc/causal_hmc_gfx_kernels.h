@@ -5,8 +5,8 @@
 // replaces: nothing in causalbgm/base.py; infer_from_latent_posterior (:671-763) returns the ITE of every row and draw, and the
 //   reference's tutorial averages its posterior mean over the rows on the host (a point estimate without an interval).
 //
-// causal_hmc_gfx_kernel / causal_hmc_mass_gfx_kernel are causal_hmc_fx_kernel / causal_hmc_mass_fx_kernel with EFFECT == 2 -- one
-// body, chmc_fx_run: same registers, same LDS blob with f's pieces of the sampling blob behind it, same RNG streams, accept rule,
+// causal_hmc_gfx_kernel / causal_hmc_mass_gfx_kernel are causal_hmc_fx_kernel / causal_hmc_mass_fx_kernel with EFFECT == 4 -- one
+// body, chmc_run: same registers, same LDS blob with f's pieces of the sampling blob behind it, same RNG streams, accept rule,
 // step table, metric and launch cuts -- and ONE difference, at the end of causal_effects (causal_kernels.h, EFFECT 4): where the
 // ITE kernels store y(1) - y(0) of (row, draw d) into ite[row * n_keep + d], these kernels add it into
 //   group_partial [n_slots][n_keep][n_labels] float32 (+=): element (slot, d, c) = sum of the values of the rows with label c over
@@ -26,13 +26,13 @@
 template <int KT1, int KSL1, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void causal_hmc_gfx_kernel(CausalHmcKArgs a, CausalHmcFxArgs fx) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  chmc_fx_run<KT1, KSL1, WAVES, 4, false>(lds, a, CausalHmcMassArgs{}, fx);
+  chmc_run<KT1, KSL1, WAVES, 4, false>(lds, a, CausalHmcMassArgs{}, fx);
 }
 
 template <int KT1, int KSL1, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void causal_hmc_mass_gfx_kernel(CausalHmcKArgs a, CausalHmcMassArgs ma, CausalHmcFxArgs fx) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  chmc_fx_run<KT1, KSL1, WAVES, 4, true>(lds, a, ma, fx);
+  chmc_run<KT1, KSL1, WAVES, 4, true>(lds, a, ma, fx);
 }
 
 // ---------------------------------------------------------------------------

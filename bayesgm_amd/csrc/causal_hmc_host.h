@@ -1,8 +1,8 @@
 // causal_hmc_host.h -- host state of the CausalBGM HMC latent sampler, shared by causal_hmc_api.hip (identity mass) and
 // causal_hmc_mass_api.hip (the diagonal metric per chain).  Host only.
 #pragma once
-#include "bgm_host.h"
-#include "causal_hmc_mass_kernels.h"
+#include "causal_launch.h"
+#include "causal_hmc_fx_kernels.h"
 
 // bgm_handle::hmc_state
 struct HmcState {
@@ -24,8 +24,8 @@ static inline int bgm_causal_hmc_blob_floats(int KT1, int n_gh) {
 
 // BGM_E_STATE for an unconfigured handle, BGM_E_UNSUPPORTED (naming the path) where the gradient / HMC kernels do not exist
 int bgm_causal_hmc_check(bgm_handle *h, const char *who);                                                     // causal_hmc_api.hip
-// the argument checks of bgm_causal_hmc_run (`who` names the entry point), the panel's Gram pre-pass and the dual-access blob, then
-// the kernel arguments of one launch and its grid
+// the argument checks of bgm_causal_hmc_run (`who` names the entry point), the panel's Gram pre-pass and the dual-access blob, the
+// metric's buffers (st->mass, once for every entry point), then the kernel arguments of one launch and its grid
 int bgm_causal_hmc_args(bgm_handle *h, const char *who, const float *x, const float *y, const float *v, int64_t n, int64_t row_base,
                         float *state, float *logp, float *grad, float *step, const float *up, const float *dn, int32_t n_table, float s_min,
                         float s_max, int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed,
@@ -33,3 +33,11 @@ int bgm_causal_hmc_args(bgm_handle *h, const char *who, const float *x, const fl
                         int &grid);                                                                           // causal_hmc_api.hip
 int bgm_causal_hmc_mass_launch(bgm_handle *h, const CausalHmcKArgs &ka, const CausalHmcMassArgs &ma, int grid, int lds,
                                hipStream_t stream);                                                           // causal_hmc_mass_api.hip
+
+// bgm_causal_dispatch for a kernel that has a twin with the metric: f(S{}, std::true_type) while a metric is set
+// (bgm_causal_hmc_set_mass; it launches the twin with st->mass), f(S{}, std::false_type) otherwise.  `what` names the kernel.
+template <class F>
+static int bgm_causal_hmc_dispatch(const bgm_handle *h, const HmcState *st, const std::string &what, F &&f) {
+  if (st->mass.scale) return bgm_causal_dispatch(h, (what + ", with a diagonal metric").c_str(), [&](auto s) { return f(s, std::true_type{}); });
+  return bgm_causal_dispatch(h, what.c_str(), [&](auto s) { return f(s, std::false_type{}); });
+}

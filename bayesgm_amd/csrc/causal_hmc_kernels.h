@@ -17,6 +17,8 @@
 // the sampling blob, so a0 / G / 2 u / c are those of the MH kernel; its derivative is 1 +- BGM_LRS.
 // Only the SIGN of every pre-activation is kept for the backward pass (one bit per unit).  The number of hidden layers of g is a
 // run-time value: the layer loops are unrolled to CHMC_MAX_GH with wave-uniform guards, so every mask has a register of its own.
+// Here: the log posterior with its gradient, the chains' loads and stores and the kernel arguments.  The transition itself, and
+// causal_hmc_kernel with it, is chmc_run in causal_hmc_fx_kernels.h.
 #pragma once
 #include "bgm_kernels.h"
 
@@ -299,107 +301,6 @@ __global__ __launch_bounds__(64 * WAVES) void causal_hmc_logpost_kernel(const fl
     if (ok) {
       if (g == 0) out_logp[row] = lp;
       chmc_store_z<KT1>(out_grad, m.q, row, g, gr);
-    }
-  }
-}
-
-// Hamiltonian Monte Carlo, identity mass, n_leapfrog steps, one chain per row, persistent over a segment of iterations.  state, logp,
-// grad and step travel between launches, so a run cut at any iteration is the same run.  After the decision of iteration it < n_table
-// the chain's step is multiplied by up[it] (it moved) or dn[it] (it did not) and clamped: ONE fp32 multiply (row_adapt.py).
-template <int KT1, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void causal_hmc_kernel(CausalHmcKArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const CausalHmcMeta &m = a.m;
-  lds_fill(lds, a.blob, m.total);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
-  const long long n = a.n, n_tiles = (n + 15) / 16;
-  for (long long tile = (long long)blockIdx.x * WAVES + wave; tile < n_tiles; tile += (long long)gridDim.x * WAVES) {
-    BGM_NO_HOIST();
-    long long row = tile * 16 + j;
-    const bool ok = row < n;
-    row = ok ? row : n - 1;
-    const unsigned rowid = (unsigned)(a.row_base + row);
-    float xr, yr, c, lp;
-    f32x4 u2[4], z[KT1], gr[KT1];
-    chmc_load_row(a.x, a.y, a.uc, n, row, g, xr, yr, u2, c);
-    float eps = a.step[row];
-    if (a.init) {      // current_state ~ N(0, 1) (base.py:842), RNG tag 0: the state the MH sampler starts from
-#pragma unroll
-      for (int t = 0; t < KT1; ++t) {
-        const f32x4 e = box_muller4(philox4x32_10(rowid, 0u, (unsigned)(g + 4 * t), TAG_INIT, a.k0, a.k1));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int f = 16 * t + 4 * r + g;
-          z[t][r] = (f < m.q) ? e[r] : (f == m.q ? xr : 0.0f);
-        }
-      }
-      chmc_logp_grad<KT1>(lds, m, j, g, z, u2, c, xr, yr, lp, gr);
-    } else {
-      chmc_load_z<KT1>(a.state, m.q, row, g, xr, z);
-      chmc_load_z<KT1>(a.grad, m.q, row, g, 0.0f, gr);
-      lp = a.logp[row];
-    }
-    for (int it = a.it_begin; it < a.it_begin + a.n_iters; ++it) {
-      BGM_NO_HOIST();
-      f32x4 mom[KT1], zc[KT1], gc[KT1];
-      float ke0 = 0.0f;
-#pragma unroll
-      for (int t = 0; t < KT1; ++t) {
-        const f32x4 e = box_muller4(philox4x32_10(rowid, (unsigned)it, (unsigned)(g + 4 * t), TAG_MOM, a.k0, a.k1));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pm = (16 * t + 4 * r + g < m.q) ? e[r] : 0.0f;
-          ke0 = fmaf(pm, pm, ke0);
-          mom[t][r] = fmaf(0.5f * eps, gr[t][r], pm);      // first half kick
-          zc[t][r] = z[t][r];
-          gc[t][r] = gr[t][r];
-        }
-      }
-      ke0 = sum_over_g(ke0);
-      float lpc = lp;
-      for (int l = 0; l < a.n_leapfrog; ++l) {
-        BGM_NO_HOIST();
-#pragma unroll
-        for (int t = 0; t < KT1; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) zc[t][r] = fmaf(eps, mom[t][r], zc[t][r]);      // (the momentum of x and of the padding is zero)
-        chmc_logp_grad<KT1>(lds, m, j, g, zc, u2, c, xr, yr, lpc, gc);
-        const float kick = (l < a.n_leapfrog - 1) ? eps : 0.5f * eps;
-#pragma unroll
-        for (int t = 0; t < KT1; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mom[t][r] = fmaf(kick, gc[t][r], mom[t][r]);
-      }
-      float ke1 = 0.0f;
-#pragma unroll
-      for (int t = 0; t < KT1; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ke1 = fmaf(mom[t][r], mom[t][r], ke1);
-      ke1 = sum_over_g(ke1);
-      float log_ratio = -((-lpc + 0.5f * ke1) - (-lp + 0.5f * ke0));
-      log_ratio = (log_ratio == log_ratio && fabsf(log_ratio) != INFINITY) ? log_ratio : -INFINITY;
-      const uint4 w4 = philox4x32_10(rowid, (unsigned)it >> 2, 0u, TAG_HACC, a.k0, a.k1);
-      const unsigned w_ = (it & 2) ? ((it & 1) ? w4.w : w4.z) : ((it & 1) ? w4.y : w4.x);
-      const bool acc = logf(u01_open(w_)) < log_ratio;
-#pragma unroll
-      for (int t = 0; t < KT1; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          z[t][r] = acc ? zc[t][r] : z[t][r];
-          gr[t][r] = acc ? gc[t][r] : gr[t][r];
-        }
-      lp = acc ? lpc : lp;
-      if (a.up != nullptr && it < a.n_table) eps = fminf(fmaxf(eps * (acc ? a.up : a.dn)[it], a.s_min), a.s_max);
-      if (a.acc_count) {
-        const unsigned cnt = (unsigned)__popcll(__ballot(acc && ok && g == 0));
-        if (lane == 0 && cnt) atomicAdd(a.acc_count + it, cnt);
-      }
-      if (a.draws != nullptr && it >= a.burn_in && ok) chmc_store_z<KT1>(a.draws + (long long)(it - a.burn_in) * n * m.q, m.q, row, g, z);
-    }
-    if (ok) {
-      chmc_store_z<KT1>(a.state, m.q, row, g, z);
-      chmc_store_z<KT1>(a.grad, m.q, row, g, gr);
-      if (g == 0) { a.logp[row] = lp; a.step[row] = eps; }
     }
   }
 }

@@ -1,7 +1,7 @@
 // causal_hmc_mass_api.hip -- the CausalBGM HMC latent sampler with a diagonal metric per chain (bgm_causal_hmc_set_mass,
-// bgm_causal_hmc_mass_update; include/bgm_hip.h): the MASS instantiations of the HMC transition (causal_hmc_kernels.h, chmc_run)
-// and the kernel that turns a window's moments into the next scales, kept in their own translation unit.  The identity-mass path
-// (causal_hmc_api.hip) is untouched: bgm_causal_hmc_run comes here only while a metric is set.
+// bgm_causal_hmc_mass_update; include/bgm_hip.h): the MASS instantiations of the HMC transition without an effect pass
+// (causal_hmc_fx_kernels.h, chmc_run) and the kernel that turns a window's moments into the next scales, in a translation unit of
+// their own, compiled beside the others: bgm_causal_hmc_run (causal_hmc_api.hip) comes here only while a metric is set.
 // replaces: nothing in causalbgm/base.py; the windowed estimate is the diagonal adaptation of Stan's warm-up, per chain (opt-in).
 #include <string>
 
@@ -72,7 +72,6 @@ extern "C" int bgm_causal_hmc_mass_update(bgm_handle *h, int64_t n, int32_t n_dr
 }
 
 int bgm_causal_hmc_mass_launch(bgm_handle *h, const CausalHmcKArgs &ka, const CausalHmcMassArgs &ma, int grid, int lds, hipStream_t stream) {
-  if (!ma.scale || (ma.accumulate && (!ma.ref || !ma.s1 || !ma.s2))) { bgm_set_error("HMC metric: launched without its buffers"); return BGM_E_STATE; }
   return bgm_causal_dispatch(h, "HMC kernel with a diagonal metric", [&](auto s) {
     using S = decltype(s);
     return bgm_launch(causal_hmc_mass_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, ma);

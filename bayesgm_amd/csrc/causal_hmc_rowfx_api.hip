@@ -1,6 +1,6 @@
 // causal_hmc_rowfx_api.hip -- bgm_causal_hmc_run_row_effects (include/bgm_hip.h): the CausalBGM HMC latent sampler with the
-// dose-response of every row kept inside the retained iterations (causal_hmc_rowfx_kernels.h), in a translation unit of its own.
-// The fused-ADRF / ITE path (causal_hmc_fx_api.hip) and the paths without effects are untouched.
+// dose-response of every row kept inside the retained iterations (causal_hmc_rowfx_kernels.h: the ROWS instantiations of chmc_run),
+// in a translation unit of its own, compiled beside those of the other HMC entry points.
 // replaces: nothing in causalbgm/base.py; infer_from_latent_posterior (:671-763) averages y_i(x_k) over the rows of the panel.
 #include <string>
 
@@ -35,16 +35,13 @@ extern "C" int bgm_causal_hmc_run_row_effects(bgm_handle *h, const float *x, con
   if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin,
                                          n_iters, burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid, fx, lds))
     return rc;
-  const CausalHmcMassArgs &ma = st->mass;      // bgm_causal_hmc_set_mass
   fx.sample_y = sample_y; fx.n_doses = n_doses; fx.x_values = x_values;
   const CausalHmcRowFxArgs rf{row_moments, row_draws};
-  if (ma.scale)
-    return bgm_causal_dispatch(h, "HMC kernel with a diagonal metric and per-row effects", [&](auto s) {
-      using S = decltype(s);
-      return bgm_launch(causal_hmc_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, ma, fx, rf);
-    });
-  return bgm_causal_dispatch(h, "HMC kernel with per-row effects", [&](auto s) {
+  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with per-row effects", [&](auto s, auto metric) {
     using S = decltype(s);
-    return bgm_launch(causal_hmc_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, fx, rf);
+    if constexpr (decltype(metric)::value)
+      return bgm_launch(causal_hmc_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, st->mass, fx, rf);
+    else
+      return bgm_launch(causal_hmc_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, fx, rf);
   });
 }

@@ -5,7 +5,7 @@
 //   (its .mean()), for a continuous treatment the reference has no per-row quantity at all.
 //
 // causal_hmc_rowfx_kernel / causal_hmc_mass_rowfx_kernel are causal_hmc_fx_kernel / causal_hmc_mass_fx_kernel with EFFECT == 1 --
-// one body, chmc_fx_run: same registers, same LDS blob with f's pieces of the sampling blob behind it, same RNG streams, accept rule,
+// one body, chmc_run: same registers, same LDS blob with f's pieces of the sampling blob behind it, same RNG streams, accept rule,
 // step table, metric and launch cuts -- and ONE difference, inside causal_effects (causal_kernels.h, ROWS): at the end of a pass
 // lane (j, g) holds y of (row j of the tile, dose k of lane group g).  Where the fused-ADRF kernels reduce it over j and add the
 // sum into the wave slot's partial with an atomic, these kernels leave it with the row:
@@ -29,12 +29,12 @@ struct CausalHmcRowFxArgs {
 template <int KT1, int KSL1, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void causal_hmc_rowfx_kernel(CausalHmcKArgs a, CausalHmcFxArgs fx, CausalHmcRowFxArgs rf) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  chmc_fx_run<KT1, KSL1, WAVES, 1, false, true>(lds, a, CausalHmcMassArgs{}, fx, rf.moments, rf.draws);
+  chmc_run<KT1, KSL1, WAVES, 1, false, true>(lds, a, CausalHmcMassArgs{}, fx, rf.moments, rf.draws);
 }
 
 template <int KT1, int KSL1, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void causal_hmc_mass_rowfx_kernel(CausalHmcKArgs a, CausalHmcMassArgs ma, CausalHmcFxArgs fx,
                                                                            CausalHmcRowFxArgs rf) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  chmc_fx_run<KT1, KSL1, WAVES, 1, true, true>(lds, a, ma, fx, rf.moments, rf.draws);
+  chmc_run<KT1, KSL1, WAVES, 1, true, true>(lds, a, ma, fx, rf.moments, rf.draws);
 }
