@@ -14,6 +14,9 @@ subgroup formula (``group_dose_response``) are at the end of the module.
 
 ``predict_average``: the option checks, the internal row labels and the combiner of the per-draw label sums into ATE / ATT / ATC
 (``combine_average_effects``) follow them.
+
+``predict_new`` / ``partial=True``: rows whose outcome, or outcome and treatment, are not observed carry NaN there; the checks of the
+pattern (``check_partial_rows``) and of predict_new's own options (``check_new``) close the module.
 """
 import numpy as np
 
@@ -333,3 +336,48 @@ def check_average_estimand(estimand, effect, group_labels):
         which = "the panel" if group_labels is None else "groups %r" % ([int(group_labels[i]) for i in bad],)
         raise ValueError("estimand=%r is undefined for %s: no %s rows to average over" %
                          (estimand, which, {"ate": "", "att": "treated", "atc": "control"}[estimand]))
+
+
+# ---- predict_new / partial=True: rows whose outcome, or outcome and treatment, are not observed (csrc/causal_hmc_obs_kernels.h) -----
+def check_partial_rows(x, y):
+    """The observation pattern of partial=True is carried by NaN in x / y (NumPy arrays or torch tensors [n]).  A row may lack its
+    outcome, or its outcome and its treatment; a row with y observed and x not has no defined target, because the outcome net f
+    needs the treatment: ValueError naming the first such row."""
+    bad = (x != x) & (y == y)
+    if bool(bad.any()):
+        row = int(bad.nonzero()[0].reshape(-1)[0])
+        raise ValueError("partial=True: row %d has its outcome y observed and its treatment x not (NaN); the outcome term f(z, x) "
+                         "needs the treatment -- drop y (NaN) or give x" % row)
+
+
+def check_new(binary, data_v, data_x, x_values, interval, draw_budget_bytes):
+    """The options of predict_new that are its own, before a device is touched -> (v [n, p], x [n], y [n]) float32, x NaN where
+    the treatment is not known (data_x None: everywhere) and y NaN everywhere.  ValueError for NaN in data_v (missing covariates
+    are not modelled), for a continuous treatment without x_values, for a binary data_x with values other than 0, 1 or NaN, for a
+    data_x whose length is not data_v's, for an interval that is neither 'normal' nor 'quantile', and for a draw budget that is
+    not positive or, with a continuous treatment and interval='normal', has nothing to bound."""
+    v = np.asarray(data_v, np.float32)
+    if v.ndim != 2:
+        raise ValueError("predict_new: data_v must be [n, p]; got shape %r" % (v.shape,))
+    if np.isnan(v).any():
+        raise ValueError("predict_new: data_v holds NaN in row %d; missing covariates are not modelled (only the treatment and the "
+                         "outcome may be unobserved)" % int(np.flatnonzero(np.isnan(v).any(axis=1))[0]))
+    n = v.shape[0]
+    if interval not in ("normal", "quantile"):
+        raise ValueError("interval must be 'normal' or 'quantile'; got %r" % (interval,))
+    if draw_budget_bytes is not None and int(draw_budget_bytes) <= 0:
+        raise ValueError("draw_budget_bytes must be positive; got %r" % (draw_budget_bytes,))
+    if not binary:
+        if x_values is None:
+            raise ValueError("predict_new needs x_values for a continuous treatment: the doses at which every row's outcome is evaluated")
+        check_individual(False, x_values, interval, draw_budget_bytes)
+    if data_x is None:
+        x = np.full(n, np.nan, np.float32)
+    else:
+        x = np.asarray(data_x, np.float32).reshape(-1)
+        if x.shape[0] != n:
+            raise ValueError("predict_new: data_x has %d rows, data_v %d" % (x.shape[0], n))
+        if binary and not np.all(np.isnan(x) | (x == 0.0) | (x == 1.0)):
+            raise ValueError("predict_new: a binary treatment takes data_x in {0, 1} or NaN (not known); got %r in row %d" %
+                             (float(x[~(np.isnan(x) | (x == 0.0) | (x == 1.0))][0]), int(np.flatnonzero(~(np.isnan(x) | (x == 0.0) | (x == 1.0)))[0])))
+    return v, x, np.full(n, np.nan, np.float32)

@@ -131,6 +131,8 @@ struct bgm_handle {
   // HMC latent sampler (causal_hmc_api.hip): the dual-access copy of the Gram blob; rebuilt whenever the Gram copy is
   void *hmc_state = nullptr;
   bool hmc_valid = false;
+  // bgm_causal_hmc_set_partial (causal_hmc_obs_api.hip): the gradient / HMC entry points read NaN in x / y as "not observed"
+  bool hmc_partial = false;
   // encoder blob
   float *eblob_dev = nullptr;
   size_t eblob_cap = 0;

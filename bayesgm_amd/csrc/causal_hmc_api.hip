@@ -10,6 +10,7 @@
 
 #include "causal_launch.h"
 #include "causal_hmc_host.h"
+#include "causal_hmc_obs_host.h"
 #include "bnf_det_host.h"
 #include "gx_host.h"
 
@@ -112,6 +113,7 @@ extern "C" int bgm_causal_logpost_grad(bgm_handle *h, const float *x, const floa
   HmcState *st = nullptr;
   if (int rc = hmc_prepare(h, v, n, stream, st)) return rc;
   const int grid = bgm_causal_grid(h, n, 1);
+  if (h->hmc_partial) return bgm_causal_hmc_obs_logpost(h, st, x, y, z, n, out_logp, out_grad, grid, stream);      // bgm_causal_hmc_set_partial
   return bgm_causal_dispatch(h, "log-posterior gradient kernel", [&](auto s) {
     using S = decltype(s);
     return bgm_launch(causal_hmc_logpost_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, st->m.total * 4, stream, st->blob_dev, st->m, x, y,
@@ -162,6 +164,7 @@ extern "C" int bgm_causal_hmc_run(bgm_handle *h, const float *x, const float *y,
   if (int rc = bgm_causal_hmc_args(h, "bgm_causal_hmc_run", x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init,
                                    it_begin, n_iters, burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid))
     return rc;
+  if (h->hmc_partial) return bgm_causal_hmc_obs_launch(h, ka, st, grid, st->m.total * 4, stream);      // bgm_causal_hmc_set_partial
   if (st->mass.scale) return bgm_causal_hmc_mass_launch(h, ka, st->mass, grid, st->m.total * 4, stream);      // bgm_causal_hmc_set_mass
   return bgm_causal_dispatch(h, "HMC kernel", [&](auto s) {
     using S = decltype(s);

@@ -6,6 +6,7 @@
 
 #include "causal_launch.h"
 #include "causal_hmc_fx_host.h"
+#include "causal_hmc_obs_host.h"
 
 namespace {
 
@@ -34,6 +35,11 @@ extern "C" int bgm_causal_hmc_run_effects(bgm_handle *h, const float *x, const f
   if (n <= 0 || n_iters <= 0) return BGM_OK;
   const std::string who(WHO);
   const bool binary = h->cfg.binary_treatment != 0;
+  if (h->hmc_partial && !binary) {
+    bgm_set_error(who + ": the panel's dose-response has no kernel for partially observed rows (bgm_causal_hmc_set_partial); the "
+                        "per-row dose-response has: bgm_causal_hmc_run_row_effects");
+    return BGM_E_UNSUPPORTED;
+  }
   if (binary && !ite) { bgm_set_error(who + ": ite_dev required for binary treatment"); return BGM_E_INVALID; }
   if (!binary && (!x_values || n_doses <= 0 || !adrf_partial)) { bgm_set_error(who + ": x_values / adrf_partial required"); return BGM_E_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
@@ -47,5 +53,6 @@ extern "C" int bgm_causal_hmc_run_effects(bgm_handle *h, const float *x, const f
     return rc;
   fx.sample_y = sample_y; fx.n_doses = binary ? 2 : n_doses;
   fx.x_values = x_values; fx.adrf_partial = adrf_partial; fx.ite = ite;
+  if (h->hmc_partial) return bgm_causal_hmc_obs_ite_launch(h, ka, st, fx, grid, (int)lds, stream);      // (binary: checked above)
   return binary ? launch_fx<2>(h, ka, st, fx, grid, (int)lds, stream) : launch_fx<1>(h, ka, st, fx, grid, (int)lds, stream);
 }

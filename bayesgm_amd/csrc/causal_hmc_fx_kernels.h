@@ -68,7 +68,9 @@ __device__ __forceinline__ void chmc_fx_fill(float *lds_f, const CausalHmcFxArgs
 template <class T, int EFFECT>
 using chmc_arg = std::conditional_t<EFFECT == 0, T, const T &>;
 
-template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false>
+// OBS (causal_hmc_obs_kernels.h): rows whose outcome, or outcome and treatment, are not observed (NaN in y / x): chmc_logp_grad
+// leaves their f / h terms out; nothing else of the transition or of the effect pass, which never reads a row's own x or y, differs.
+template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false, bool OBS = false>
 __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EFFECT> a, chmc_arg<CausalHmcMassArgs, EFFECT> ma,
                                          chmc_arg<CausalHmcFxArgs, EFFECT> fx, float *row_mom = nullptr, float *row_y = nullptr) {
   const CausalHmcMeta &m = a.m;
@@ -90,6 +92,8 @@ __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EF
     float xr, yr, c, lp;
     f32x4 u2[4], z[1][KT1], gr[KT1];
     chmc_load_row(a.x, a.y, a.uc, n, row, g, xr, yr, u2, c);
+    bool has_x = true, has_y = true;
+    if constexpr (OBS) chmc_observed(xr, yr, has_x, has_y);
     float eps = a.step[row];
     const long long eoff = row * (long long)m.q + g;      // the lane's first element of the row's [q] in scale / ref / s1 / s2
     if (a.init) {      // current_state ~ N(0, 1) (base.py:842), RNG tag 0: the state the MH sampler starts from
@@ -102,7 +106,7 @@ __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EF
           z[0][t][r] = (f < m.q) ? e[r] : (f == m.q ? xr : 0.0f);
         }
       }
-      chmc_logp_grad<KT1>(lds, m, j, g, z[0], u2, c, xr, yr, lp, gr);
+      chmc_logp_grad<KT1, OBS>(lds, m, j, g, z[0], u2, c, xr, yr, lp, gr, has_x, has_y);
     } else {
       chmc_load_z<KT1>(a.state, m.q, row, g, xr, z[0]);
       chmc_load_z<KT1>(a.grad, m.q, row, g, 0.0f, gr);
@@ -138,7 +142,7 @@ __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EF
             if constexpr (MASS) zc[t][r] = fmaf(eps * sc[t][r], mom[t][r], zc[t][r]);
             else zc[t][r] = fmaf(eps, mom[t][r], zc[t][r]);
           }
-        chmc_logp_grad<KT1>(lds, m, j, g, zc, u2, c, xr, yr, lpc, gc);
+        chmc_logp_grad<KT1, OBS>(lds, m, j, g, zc, u2, c, xr, yr, lpc, gc, has_x, has_y);
         if constexpr (MASS) {
           BGM_NO_HOIST();
           chmc_mass_load<KT1>(ma.scale, eoff, m.q, g, sc);

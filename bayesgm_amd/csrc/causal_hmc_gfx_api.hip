@@ -23,6 +23,11 @@ extern "C" int bgm_causal_hmc_run_group_effects(bgm_handle *h, const float *x, c
   if (int rc = bgm_causal_hmc_check(h, WHO)) return rc;
   if (n <= 0 || n_iters <= 0) return BGM_OK;
   const std::string who(WHO);
+  if (h->hmc_partial) {
+    bgm_set_error(who + ": the label sums have no kernel for partially observed rows (bgm_causal_hmc_set_partial); the treatment "
+                        "effect of every row has: bgm_causal_hmc_run_effects (BGM_EFFECT_ITE)");
+    return BGM_E_UNSUPPORTED;
+  }
   if (h->cfg.binary_treatment == 0) {
     bgm_set_error(who + ": the label sums are those of the individual treatment effect of a binary treatment; a continuous treatment "
                         "has its dose-response: bgm_causal_hmc_run_effects (BGM_EFFECT_ADRF)");

@@ -94,8 +94,12 @@ __device__ __forceinline__ float chmc_gauss(float rsq, float s_raw, float dim, f
 
 // the tail of f / h behind the activated first hidden layer a1: 64 -> 32 -> 8 -> (mu, s), the likelihood of the scalar target and the
 // gradient back to a1's PRE-activation side (d1 = dlogp/d a1).  which: 0 = f (Gaussian, target y), 1 = h (Gaussian or Bernoulli logit, target x)
+// OBS: a row whose target is not observed (has = false; the target may be NaN) has no likelihood term: nll and what enters the
+// backward chain are SELECTED to zero -- a product would keep the NaN -- so the chain carries exact zeros and d1 is zero for that row.
+template <bool OBS = false>
 __device__ __forceinline__ float chmc_tail(const float *lds, int w2, int b2, int w3, int b3, int w4, int b4, int j, int g,
-                                           const f32x4 (&a1)[4], float target, bool bernoulli, float fixed, f32x4 (&d1)[4]) {
+                                           const f32x4 (&a1)[4], float target, bool bernoulli, float fixed, f32x4 (&d1)[4],
+                                           bool has = true) {
   f32x4 a2[2], a3[1], a4[1];
   bias17<2>(lds + b2, g, a2);
   fwd17<4, 2>(lds + w2, j, g, a1, a2);
@@ -120,9 +124,12 @@ __device__ __forceinline__ float chmc_tail(const float *lds, int w2, int b2, int
     dmu = r * inv;
     dsr = -dn;
   }
-  // dlogp/d(mu, s) enters through lane group 0's copy of the replicated columns only
+  if constexpr (OBS) nll = has ? nll : 0.0f;
+  // dlogp/d(mu, s) enters through lane group 0's copy of the replicated columns only -- and, OBS, only where the row has its target:
+  // the mask rides on this select, so the arithmetic that forms dmu and dsr is the one of the kernels without OBS
+  const bool enters = OBS ? (g == 0 && has) : (g == 0);
   f32x4 d4[1], d3[1], d2[2];
-  d4[0] = f32x4{g == 0 ? dmu : 0.0f, g == 0 ? dsr : 0.0f, 0.0f, 0.0f};
+  d4[0] = f32x4{enters ? dmu : 0.0f, enters ? dsr : 0.0f, 0.0f, 0.0f};
   chmc_zero<1>(d3);
   bwd17<1, 1>(lds + w4, j, g, d4, d3);
   chmc_dact<1>(d3, s3m);
@@ -138,9 +145,16 @@ __device__ __forceinline__ float chmc_tail(const float *lds, int w2, int b2, int
 //   zin : feature 16 t + 4 r + g (z, then x at feature q, then 0)
 //   u2  : the row's 2 u in accumulator layout (feature 16 t + 4 g + r);  c: the row's |m0 - v|^2
 // logp is replicated over the lane groups; grad has the layout of zin and is zero at every feature >= q.
-template <int KT1>
+// OBS (partially observed rows, chmc_observed): the target is p(z | v) or p(z | x, v) -- a row without its outcome (has_y = false)
+// has no f term, a row without its treatment (has_x = false; xr is 0 then) no h term; g's term and the prior are those of every row.
+// The masked passes add exact zeros to nll and grad, so a row's value does not depend on the patterns of the other rows of its tile.
+// No tile skips a net's passes, even where none of its rows has the target: a wave-uniform branch around them was tried in two
+// forms and is left out -- it changed hipcc's fused multiply-add choices in the likelihood head, so an
+// observed panel was no longer bit-identical to the kernels without OBS, and one form put a kernel into scratch.
+template <int KT1, bool OBS = false>
 __device__ __forceinline__ void chmc_logp_grad(const float *lds, const CausalHmcMeta &m, int j, int g, const f32x4 (&zin)[KT1],
-                                               const f32x4 (&u2)[4], float c, float xr, float yr, float &logp, f32x4 (&grad)[KT1]) {
+                                               const f32x4 (&u2)[4], float c, float xr, float yr, float &logp, f32x4 (&grad)[KT1],
+                                               bool has_x = true, bool has_y = true) {
   chmc_zero<KT1>(grad);
   float nll;
   // ---- g: Gram form of the covariates' Gaussian term
@@ -216,7 +230,7 @@ __device__ __forceinline__ void chmc_logp_grad(const float *lds, const CausalHmc
     bias17<4>(lds + m.b1f, g, a1);
     fwd17<KT1, 4>(lds + m.w1f, j, g, zin, a1);
     const unsigned s1 = chmc_act<4>(a1);
-    nll += chmc_tail(lds, m.wf2, m.bf2, m.wf3, m.bf3, m.wf4, m.bf4, j, g, a1, yr, false, m.sig2_y, d1);
+    nll += chmc_tail<OBS>(lds, m.wf2, m.bf2, m.wf3, m.bf3, m.wf4, m.bf4, j, g, a1, yr, false, m.sig2_y, d1, has_y);
     chmc_dact<4>(d1, s1);
     bwd17<KT1, 4>(lds + m.w1f, j, g, d1, grad);
   }
@@ -227,7 +241,7 @@ __device__ __forceinline__ void chmc_logp_grad(const float *lds, const CausalHmc
     bias17<4>(lds + m.b1h, g, a1);
     fwd17<KT1, 4>(lds + m.w1h, j, g, zin, a1);
     const unsigned s1 = chmc_act<4>(a1);
-    nll += chmc_tail(lds, m.wh2, m.bh2, m.wh3, m.bh3, m.wh4, m.bh4, j, g, a1, xr, m.binary != 0, m.sig2_x, d1);
+    nll += chmc_tail<OBS>(lds, m.wh2, m.bh2, m.wh3, m.bh3, m.wh4, m.bh4, j, g, a1, xr, m.binary != 0, m.sig2_x, d1, has_x);
     chmc_dact<4>(d1, s1);
     bwd17<KT1, 4>(lds + m.w1h, j, g, d1, grad);
   }
@@ -255,6 +269,13 @@ __device__ __forceinline__ void chmc_load_row(const float *x, const float *y, co
   for (int t = 0; t < 4; ++t) u2[t] = ur[4 * t + g];
   c = uc[64 * n + row];
 }
+// OBS: the observation pattern of a row is carried by its data -- x or y is NaN where it is not observed.  Returns the pattern
+// and replaces a missing x by 0, the value its input slot (feature q of z) then holds.
+__device__ __forceinline__ void chmc_observed(float &xr, float yr, bool &has_x, bool &has_y) {
+  has_x = (xr == xr);
+  has_y = (yr == yr);
+  xr = has_x ? xr : 0.0f;
+}
 template <int KT1>
 __device__ __forceinline__ void chmc_load_z(const float *z, int q, long long row, int g, float xr, f32x4 (&zin)[KT1]) {
   const float *zr = z + row * (long long)q;
@@ -279,12 +300,10 @@ __device__ __forceinline__ void chmc_store_z(float *z, int q, long long row, int
     }
 }
 
-// get_log_posterior and its gradient for n rows (one evaluation)
-template <int KT1, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void causal_hmc_logpost_kernel(const float *blob, CausalHmcMeta m, const float *x, const float *y,
-                                                                        const float *uc, const float *z, long long n, float *out_logp,
-                                                                        float *out_grad) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+// get_log_posterior and its gradient for n rows (one evaluation); OBS: causal_hmc_obs_logpost_kernel (causal_hmc_obs_kernels.h)
+template <int KT1, int WAVES, bool OBS = false>
+__device__ __forceinline__ void chmc_logpost_run(float *lds, const float *blob, CausalHmcMeta m, const float *x, const float *y,
+                                                 const float *uc, const float *z, long long n, float *out_logp, float *out_grad) {
   lds_fill(lds, blob, m.total);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
   const long long n_tiles = (n + 15) / 16;
@@ -296,11 +315,21 @@ __global__ __launch_bounds__(64 * WAVES) void causal_hmc_logpost_kernel(const fl
     float xr, yr, c, lp;
     f32x4 u2[4], zin[KT1], gr[KT1];
     chmc_load_row(x, y, uc, n, row, g, xr, yr, u2, c);
+    bool has_x = true, has_y = true;
+    if constexpr (OBS) chmc_observed(xr, yr, has_x, has_y);
     chmc_load_z<KT1>(z, m.q, row, g, xr, zin);
-    chmc_logp_grad<KT1>(lds, m, j, g, zin, u2, c, xr, yr, lp, gr);
+    chmc_logp_grad<KT1, OBS>(lds, m, j, g, zin, u2, c, xr, yr, lp, gr, has_x, has_y);
     if (ok) {
       if (g == 0) out_logp[row] = lp;
       chmc_store_z<KT1>(out_grad, m.q, row, g, gr);
     }
   }
+}
+
+template <int KT1, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void causal_hmc_logpost_kernel(const float *blob, CausalHmcMeta m, const float *x, const float *y,
+                                                                        const float *uc, const float *z, long long n, float *out_logp,
+                                                                        float *out_grad) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  chmc_logpost_run<KT1, WAVES>(lds, blob, m, x, y, uc, z, n, out_logp, out_grad);
 }

@@ -1,0 +1,59 @@
+// causal_hmc_obs_api.hip -- bgm_causal_hmc_set_partial (include/bgm_hip.h) and the launches of the CausalBGM gradient / HMC kernels for
+// partially observed rows (causal_hmc_obs_kernels.h: the OBS instantiations of chmc_logpost_run and chmc_run), in a translation
+// unit of their own, compiled beside those of the other HMC entry points: bgm_causal_logpost_grad, bgm_causal_hmc_run,
+// bgm_causal_hmc_run_effects and bgm_causal_hmc_run_row_effects come here only while the option is on.
+// replaces: nothing in causalbgm/base.py; the reference's predict needs the outcome of every row.
+#include <string>
+
+#include "causal_launch.h"
+#include "causal_hmc_obs_host.h"
+#include "causal_hmc_obs_kernels.h"
+
+extern "C" int bgm_causal_hmc_set_partial(bgm_handle *h, int32_t on) {
+  if (!h) { bgm_set_error("bgm_causal_hmc_set_partial: NULL handle"); return BGM_E_INVALID; }
+  if (!on) { h->hmc_partial = false; return BGM_OK; }
+  if (int rc = bgm_causal_hmc_check(h, "bgm_causal_hmc_set_partial")) return rc;
+  h->hmc_partial = true;
+  return BGM_OK;
+}
+
+int bgm_causal_hmc_obs_logpost(bgm_handle *h, const HmcState *st, const float *x, const float *y, const float *z, int64_t n, float *out_logp,
+                               float *out_grad, int grid, hipStream_t stream) {
+  return bgm_causal_dispatch(h, "log-posterior gradient kernel for partially observed rows", [&](auto s) {
+    using S = decltype(s);
+    return bgm_launch(causal_hmc_obs_logpost_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, st->m.total * 4, stream, st->blob_dev, st->m, x, y,
+                      h->uc_dev, z, (long long)n, out_logp, out_grad);
+  });
+}
+
+int bgm_causal_hmc_obs_launch(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, int grid, int lds, hipStream_t stream) {
+  return bgm_causal_hmc_dispatch(h, st, "HMC kernel for partially observed rows", [&](auto s, auto metric) {
+    using S = decltype(s);
+    if constexpr (decltype(metric)::value)
+      return bgm_launch(causal_hmc_obs_mass_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, st->mass);
+    else
+      return bgm_launch(causal_hmc_obs_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka);
+  });
+}
+
+int bgm_causal_hmc_obs_ite_launch(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, const CausalHmcFxArgs &fx, int grid, int lds,
+                                  hipStream_t stream) {
+  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with fused effects for partially observed rows", [&](auto s, auto metric) {
+    using S = decltype(s);
+    if constexpr (decltype(metric)::value)
+      return bgm_launch(causal_hmc_obs_mass_ite_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, st->mass, fx);
+    else
+      return bgm_launch(causal_hmc_obs_ite_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, fx);
+  });
+}
+
+int bgm_causal_hmc_obs_rowfx_launch(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, const CausalHmcFxArgs &fx,
+                                    const CausalHmcRowFxArgs &rf, int grid, int lds, hipStream_t stream) {
+  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with per-row effects for partially observed rows", [&](auto s, auto metric) {
+    using S = decltype(s);
+    if constexpr (decltype(metric)::value)
+      return bgm_launch(causal_hmc_obs_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, st->mass, fx, rf);
+    else
+      return bgm_launch(causal_hmc_obs_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, fx, rf);
+  });
+}

@@ -7,6 +7,7 @@
 #include "causal_launch.h"
 #include "causal_hmc_fx_host.h"
 #include "causal_hmc_rowfx_kernels.h"
+#include "causal_hmc_obs_host.h"
 
 namespace {
 const char *WHO = "bgm_causal_hmc_run_row_effects";
@@ -37,6 +38,7 @@ extern "C" int bgm_causal_hmc_run_row_effects(bgm_handle *h, const float *x, con
     return rc;
   fx.sample_y = sample_y; fx.n_doses = n_doses; fx.x_values = x_values;
   const CausalHmcRowFxArgs rf{row_moments, row_draws};
+  if (h->hmc_partial) return bgm_causal_hmc_obs_rowfx_launch(h, ka, st, fx, rf, grid, (int)lds, stream);      // bgm_causal_hmc_set_partial
   return bgm_causal_hmc_dispatch(h, st, "HMC kernel with per-row effects", [&](auto s, auto metric) {
     using S = decltype(s);
     if constexpr (decltype(metric)::value)

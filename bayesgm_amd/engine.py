@@ -4,6 +4,7 @@ PyTorch supplies device memory and the HIP stream only; all arithmetic of the
 hot path runs in libbgm_hip.so.  There is no CPU fallback: constructing an
 engine without a gfx950 GPU or without the built library raises.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -116,25 +117,48 @@ class CausalEngine(object):
                                                self._stream()), "bgm_causal_logpost")
         return out
 
-    def logpost_grad(self, x, y, v, z):
+    @contextlib.contextmanager
+    def _partial_rows(self, partial, x, y):
+        """partial=True of the gradient / HMC calls: NaN in x / y means "not observed" for the calls made inside (the handle flag
+        bgm_causal_hmc_set_partial, cleared on the way out).  A row with y observed and x not is refused first (causal_hmc.py)."""
+        if not partial:
+            yield
+            return
+        HM.check_partial_rows(x, y)
+        _lib.check(self.lib.bgm_causal_hmc_set_partial(self.h, 1), "bgm_causal_hmc_set_partial")
+        try:
+            yield
+        finally:
+            _lib.check(self.lib.bgm_causal_hmc_set_partial(self.h, 0), "bgm_causal_hmc_set_partial")
+
+    def logpost_grad(self, x, y, v, z, partial=False):
         """get_log_posterior and its gradient with respect to z -> (logp [n], grad [n, q]) on the device (bgm_causal_logpost_grad:
-        g's Gaussian term in the Gram form on every shape; fp32 LDS-resident shapes with the standard-normal prior)."""
+        g's Gaussian term in the Gram form on every shape; fp32 LDS-resident shapes with the standard-normal prior).
+        partial=True: NaN in y, or in x and y, marks what a row does not observe; its target is p(z | x, v) or p(z | v)."""
         x, y, v, z = (_f32(t, self.device) for t in (x, y, v, z))
         n = v.shape[0]
         out = torch.empty(n, device=self.device, dtype=torch.float32)
         grad = torch.empty((n, self.q), device=self.device, dtype=torch.float32)
-        _lib.check(self.lib.bgm_causal_logpost_grad(self.h, _ptr(x), _ptr(y), _ptr(v), _ptr(z), n, _ptr(out), _ptr(grad),
-                                                    self._stream()), "bgm_causal_logpost_grad")
+        with self._partial_rows(partial, x, y):
+            _lib.check(self.lib.bgm_causal_logpost_grad(self.h, _ptr(x), _ptr(y), _ptr(v), _ptr(z), n, _ptr(out), _ptr(grad),
+                                                        self._stream()), "bgm_causal_logpost_grad")
         return out, grad
 
     def hmc_run(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False, row_base=0,
                 up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0, effect=_lib.EFFECT_NONE,
-                sample_y=True, x_values=None, adrf_partial=None, ite=None, labels=None, n_labels=0, group_partial=None):
+                sample_y=True, x_values=None, adrf_partial=None, ite=None, labels=None, n_labels=0, group_partial=None, partial=False):
         """One segment of the HMC latent sampler for all rows (bgm_causal_hmc_run); state / logp / grad / step are in / out.
         effect = EFFECT_ADRF / EFFECT_ITE: the segment runs the kernels with the effect pass inside (bgm_causal_hmc_run_effects):
         x_values [n_doses] and adrf_partial [n_slots, n_keep, n_doses] (+=), or ite [n, n_keep], receive the effects of the
         iterations >= burn_in of this segment.  effect = EFFECT_GROUP_ITE: hmc_run_group_effects with labels / n_labels /
-        group_partial."""
+        group_partial.  partial=True: NaN in y, or in x and y, marks what a row does not observe (logpost_grad); EFFECT_ADRF and
+        EFFECT_GROUP_ITE have no kernels for it and raise the library's error."""
+        with self._partial_rows(partial, x, y):
+            self._hmc_run(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min, s_max,
+                          acc_count, draws, n_keep, effect, sample_y, x_values, adrf_partial, ite, labels, n_labels, group_partial)
+
+    def _hmc_run(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min, s_max,
+                 acc_count, draws, n_keep, effect, sample_y, x_values, adrf_partial, ite, labels, n_labels, group_partial):
         args = (self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up),
                 _ptr(dn), 0 if up is None else int(up.numel()), float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters),
                 int(burn_in), int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws), int(n_keep))
@@ -154,17 +178,18 @@ class CausalEngine(object):
 
     def hmc_run_rows_effects(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
                              row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
-                             sample_y=True, x_values=None, row_moments=None, row_draws=None):
+                             sample_y=True, x_values=None, row_moments=None, row_draws=None, partial=False):
         """hmc_run with the dose-response of every row kept (bgm_causal_hmc_run_row_effects; a continuous treatment): x_values
         [n_doses]; row_moments [3, n_doses, n] float32 (ref = y at retained draw 0, s1 = sum of y - ref, s2 = sum of (y - ref)^2,
         in / out across segments) and, optionally, row_draws [n, n_doses, n_keep] receive y_i(x_k) of the iterations >= burn_in of
-        this segment."""
-        _lib.check(self.lib.bgm_causal_hmc_run_row_effects(
-            self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up), _ptr(dn),
-            0 if up is None else int(up.numel()), float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters), int(burn_in),
-            int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws), int(n_keep), int(bool(sample_y)), _ptr(x_values),
-            0 if x_values is None else int(x_values.numel()), _ptr(row_moments), _ptr(row_draws), self._stream()),
-            "bgm_causal_hmc_run_row_effects")
+        this segment.  partial=True: as in hmc_run."""
+        with self._partial_rows(partial, x, y):
+            _lib.check(self.lib.bgm_causal_hmc_run_row_effects(
+                self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up), _ptr(dn),
+                0 if up is None else int(up.numel()), float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters), int(burn_in),
+                int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws), int(n_keep), int(bool(sample_y)), _ptr(x_values),
+                0 if x_values is None else int(x_values.numel()), _ptr(row_moments), _ptr(row_draws), self._stream()),
+                "bgm_causal_hmc_run_row_effects")
 
     def hmc_run_group_effects(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, labels=None, n_labels=0,
                               group_partial=None, **kw):
@@ -217,7 +242,7 @@ class CausalEngine(object):
 
     def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
                    adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None, effect=_lib.EFFECT_NONE,
-                   x_values=None, sample_y=True, row_effects=False, row_draws=False, labels=None, n_labels=None):
+                   x_values=None, sample_y=True, row_effects=False, row_draws=False, labels=None, n_labels=None, partial=False):
         """HMC over the latent posterior of every row, one chain per row with a step size of its own.
 
         adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
@@ -244,6 +269,10 @@ class CausalEngine(object):
         [n, n_doses] (float64, causal_hmc.row_moments_finalize) without stored draws; row_draws = True also returns them,
         row_draws [n, n_doses, n_keep].  The chain is that of the run without effects, and a row's result depends on (seed,
         row_base + row, the row's data) alone.
+
+        partial = True: NaN in y, or in x and y, marks what a row does not observe (new units): its chain samples p(z | x, v) or
+        p(z | v) (logpost_grad).  A row with y observed and x not is refused.  Works without an effect, with EFFECT_ITE and with
+        row_effects; a fully observed panel gives the run of partial = False bit for bit.
         Returns dict(draws [n_keep, n, q] | None, state, logp, grad, acc_count [burn_in + n_keep], row_step [n]) and, with a metric,
         mass_scale [n x q]; with an effect, adrf [n_doses, n_keep], ite [n, n_keep] or group_sums [n_labels, n_keep]."""
         HM.check_args(step_size, n_leapfrog, adapt)
@@ -273,7 +302,7 @@ class CausalEngine(object):
         acc = torch.zeros(total, device=dev, dtype=torch.int32)
         draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
         chunk = total if chunk is None else max(1, int(chunk))
-        xv = partial = ite = lab = gpartial = None
+        xv = adrf_part = ite = lab = gpartial = None
         n_slots = n_lab = 0
         if effect == _lib.EFFECT_ADRF:
             if x_values is None:
@@ -282,7 +311,7 @@ class CausalEngine(object):
             ns = C.c_int32()
             _lib.check(self.lib.bgm_causal_evaluate_slots(self.h, n, C.byref(ns)), "bgm_causal_evaluate_slots")
             n_slots = ns.value
-            partial = torch.zeros((n_slots, n_keep, xv.numel()), device=dev, dtype=torch.float32)
+            adrf_part = torch.zeros((n_slots, n_keep, xv.numel()), device=dev, dtype=torch.float32)
         elif effect == _lib.EFFECT_ITE:
             ite = torch.empty((n, n_keep), device=dev, dtype=torch.float32)
         elif effect == _lib.EFFECT_GROUP_ITE:
@@ -326,6 +355,9 @@ class CausalEngine(object):
                 raise ValueError("hmc_sample: mass_scale must be [n x q] = %r; got %r" % ((n, self.q), tuple(scale.shape)))
         marks = [start] + ends if diag else []
         try:
+            if partial:      # the pattern is checked once; the launches below find the handle's flag set
+                HM.check_partial_rows(x, y)
+                _lib.check(self.lib.bgm_causal_hmc_set_partial(self.h, 1), "bgm_causal_hmc_set_partial")
             if scale is not None:
                 self.set_hmc_mass(scale)
             it = 0
@@ -338,7 +370,7 @@ class CausalEngine(object):
                 else:
                     self.hmc_run(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0),
                                  row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep, effect=effect,
-                                 sample_y=sample_y, x_values=xv, adrf_partial=partial, ite=ite, labels=lab, n_labels=n_lab,
+                                 sample_y=sample_y, x_values=xv, adrf_partial=adrf_part, ite=ite, labels=lab, n_labels=n_lab,
                                  group_partial=gpartial)
                 if stop in marks:      # a window's edge: the first one only sets the reference point and turns the moments on
                     k = marks.index(stop)
@@ -348,11 +380,13 @@ class CausalEngine(object):
         finally:
             if scale is not None:
                 self.set_hmc_mass(None)
+            if partial:
+                _lib.check(self.lib.bgm_causal_hmc_set_partial(self.h, 0), "bgm_causal_hmc_set_partial")
         out = dict(draws=draws, state=state, logp=logp, grad=grad, acc_count=acc, row_step=step)
         if scale is not None:
             out["mass_scale"] = scale
-        if partial is not None:
-            out["adrf"] = self.adrf_reduce(partial, n_slots, xv.numel(), n_keep, n)
+        if adrf_part is not None:
+            out["adrf"] = self.adrf_reduce(adrf_part, n_slots, xv.numel(), n_keep, n)
         if ite is not None:
             out["ite"] = ite
         if gpartial is not None:

@@ -706,6 +706,19 @@ class CausalBGM(object):
         n_test, n_doses = len(data_x), len(x_values)
         if groups is not None:
             hmc_mod.group_dose_response(np.zeros((n_test, 0)), np.zeros((n_test, 0)), groups)      # (the labels' checks, before a device is touched)
+        mean, bounds = self._individual_rows(data_x, data_y, data_v, x_values, alpha, n_mcmc, burn_in, sample_y, hmc, mass, interval,
+                                             draw_budget_bytes, verbose)
+        if groups is not None:
+            self.group_dose_response_ = hmc_mod.group_dose_response(mean, self.individual_sd_, groups)
+        return mean, bounds
+
+    def _individual_rows(self, data_x, data_y, data_v, x_values, alpha, n_mcmc, burn_in, sample_y, hmc, mass, interval, draw_budget_bytes,
+                         verbose, partial=False):
+        """The row blocks of predict_individual (and of predict_new for a continuous treatment, partial=True: NaN in data_x / data_y
+        marks what a row does not observe): this rank's shard in the blocks of causal_hmc.individual_blocks, every block sampled with
+        the per-row effects inside the kernel, the results gathered over the ranks -> (mean, bounds); sets hmc_row_step_,
+        hmc_row_mass_ and individual_sd_."""
+        n_test, n_doses = len(data_x), len(x_values)
         seed = self._next_seed()
         if verbose:
             print('MCMC Latent Variable Sampling ...')
@@ -724,7 +737,7 @@ class CausalBGM(object):
             y = self._dev(data_y[s0:e0]).reshape(-1)
             v = self._dev(data_v[s0:e0])
             out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=mass, row_effects=True,
-                                 row_draws=quantile, x_values=x_values, sample_y=sample_y)
+                                 row_draws=quantile, x_values=x_values, sample_y=sample_y, partial=partial)
             res[0, s0:e0], res[1, s0:e0] = out["row_mean"], out["row_sd"]
             if quantile:
                 _, lo, hi = eng.row_mean_quantiles(out["row_draws"].reshape((e0 - s0) * n_doses, n_mcmc), alpha / 2, 1 - alpha / 2)
@@ -746,9 +759,76 @@ class CausalBGM(object):
         else:
             z = NormalDist().inv_cdf(1.0 - alpha / 2)
             bounds = np.stack([mean - z * sd, mean + z * sd], axis=-1)
-        if groups is not None:
-            self.group_dose_response_ = hmc_mod.group_dose_response(mean, sd, groups)
         return mean, bounds
+
+    def predict_new(self, data_v, data_x=None, x_values=None, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None,
+                    n_leapfrog=None, mass='identity', interval='normal', draw_budget_bytes=None, verbose=1):
+        """Effects for NEW units, whose outcome is not observed: the covariates ``data_v`` [n, p], perhaps the treatment ``data_x``
+        [n] (None: not known for any row; NaN entries: not known for those rows), never the outcome.  The reference has no
+        counterpart (its ``predict`` takes the triplet (x, y, v) of every row).
+
+        The latent posterior of such a row is p(z | x, v), or p(z | v) without the treatment: the log posterior of ``predict``
+        with the outcome term, and the treatment term where x is not known, left out.  It is sampled by the HMC sampler of
+        ``predict(sampler='hmc')`` (``step_size``, ``n_leapfrog``, ``mass`` and the seed sequence as there; the steps and the metric
+        are left in ``self.hmc_row_step_`` / ``self.hmc_row_mass_``) and the outcome net runs inside the sampling kernel.
+
+        Continuous treatment (``x_values`` required): what ``predict_individual`` returns, ``(mean [n, n_doses], interval
+        [n, n_doses, 2])`` of y_i(x_k), the sd in ``self.individual_sd_``; ``interval`` and ``draw_budget_bytes`` as there.
+        Binary treatment: what ``predict`` returns, ``(ite [n], interval [n, 2])``, from the fused ITE kernel; ``interval=
+        'quantile'`` gives ``predict``'s quantiles of the ITE draws, ``'normal'`` (default) ``mean -/+ z(1 - alpha/2) * sd`` of
+        them (sd in ``self.individual_sd_`` [n]); the [rows x n_mcmc] ITE matrix of a block fits ``draw_budget_bytes`` (default
+        2 GiB).  A row's result depends on (seed, its global row, its data) only; under torch.distributed the rows are sharded by
+        rank and the results gathered."""
+        self.hmc_row_step_ = None
+        self.hmc_row_mass_ = None
+        self.individual_sd_ = None
+        binary = bool(self._p['binary_treatment'])
+        hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
+        mass = hmc_mod.check_mass(mass, True, True, burn_in)
+        data_v, data_x, data_y = hmc_mod.check_new(binary, data_v, data_x, x_values, interval, draw_budget_bytes)
+        assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
+        parallel.check_n_mcmc(n_mcmc)
+        if not binary:
+            x_values = np.array([x_values], dtype=float) if np.isscalar(x_values) else np.array(x_values, dtype=float)
+            return self._individual_rows(data_x, data_y, data_v, x_values, alpha, n_mcmc, burn_in, sample_y, hmc, mass, interval,
+                                         draw_budget_bytes, verbose, partial=True)
+        n_test = len(data_x)
+        seed = self._next_seed()
+        if verbose:
+            print('MCMC Latent Variable Sampling ...')
+        eng = self.engine
+        dev = eng.device
+        total_it = burn_in + n_mcmc
+        lo_r, hi_r = parallel.shard_range(n_test)
+        rows = hmc_mod.block_rows(n_mcmc, 1, draw_budget_bytes)      # the ITE matrix [rows x n_mcmc] of one block
+        blocks = [(s0, min(s0 + rows, hi_r)) for s0 in range(lo_r, hi_r, rows)]
+        res = torch.zeros((4, n_test), device=dev, dtype=torch.float64)      # mean, sd, lower, upper (this rank's rows filled)
+        row_step = torch.zeros(n_test, device=dev, dtype=torch.float32)
+        row_mass = torch.zeros((n_test, eng.q), device=dev, dtype=torch.float32) if mass is not None else None
+        acc_tail = 0.0
+        for (s0, e0) in blocks:
+            x, y, v = self._dev(data_x[s0:e0]).reshape(-1), self._dev(data_y[s0:e0]).reshape(-1), self._dev(data_v[s0:e0])
+            out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=mass,
+                                 effect=_lib.EFFECT_ITE, sample_y=sample_y, partial=True)
+            mean, lo, hi = eng.row_mean_quantiles(out["ite"], alpha / 2, 1 - alpha / 2)
+            res[0, s0:e0], res[2, s0:e0], res[3, s0:e0] = mean.double(), lo.double(), hi.double()
+            res[1, s0:e0] = out["ite"].double().std(dim=1) if n_mcmc > 1 else 0.0
+            del out["ite"]
+            row_step[s0:e0] = out["row_step"]
+            if row_mass is not None:
+                row_mass[s0:e0] = out["mass_scale"]
+            acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
+        self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
+        self.hmc_row_step_ = parallel.all_reduce_sum_(row_step).cpu().numpy()      # disjoint row sets: the sum is the gather
+        if row_mass is not None:
+            self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
+        res = parallel.all_reduce_sum_(res).cpu().numpy()
+        mean, sd = res[0], res[1]
+        self.individual_sd_ = sd
+        if interval == 'quantile':
+            return mean, np.stack([res[2], res[3]], axis=1)
+        z = NormalDist().inv_cdf(1.0 - alpha / 2)
+        return mean, np.stack([mean - z * sd, mean + z * sd], axis=1)
 
     average_effects_ = None          # predict_average: dict(ate, att, atc, *_interval, *_draws, counts, groups)
 
@@ -946,20 +1026,24 @@ class CausalBGM(object):
         return out["draws"].cpu().numpy()
 
     def hmc_sampler(self, data, n_keep=3000, burn_in=5000, step_size=hmc_mod.DEFAULT_STEP_SIZE, n_leapfrog=hmc_mod.DEFAULT_N_LEAPFROG,
-                    target_acceptance_rate=hmc_mod.DEFAULT_TARGET, adapt=True, diagnostics=False, mass='identity'):
+                    target_acceptance_rate=hmc_mod.DEFAULT_TARGET, adapt=True, diagnostics=False, mass='identity', partial=False):
         """Posterior samples of Z, shape (n_keep, n, q), by Hamiltonian Monte Carlo on get_log_posterior: ``n_leapfrog`` steps per
         transition, identity mass, one chain per row.  ``adapt=True``: every chain adapts a step size of its own during burn-in
         towards ``target_acceptance_rate``, starting from ``step_size`` (causal_hmc.py); the retained chain is plain HMC.  The steps
         are left in ``self.hmc_row_step_``.  ``mass='diag'`` (needs ``adapt=True``): every chain also estimates a scale per latent
         coordinate from its own burn-in draws, in windows, and keeps it afterwards (a diagonal metric, causal_hmc.py); the scales
-        are left in ``self.hmc_row_mass_`` [n, q].  diagnostics=True: as in metropolis_hastings_sampler."""
+        are left in ``self.hmc_row_mass_`` [n, q].  diagnostics=True: as in metropolis_hastings_sampler.  ``partial=True``: NaN in
+        ``data_y``, or in ``data_x`` and ``data_y``, marks what a row does not observe; its chain samples p(z | x, v) or p(z | v)
+        (``predict_new``).  A row with its outcome observed and its treatment not is refused."""
         step_size, n_leapfrog, target = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, target_acceptance_rate, adapt)
         mass = hmc_mod.check_mass(mass, True, adapt, burn_in)
         self.hmc_row_step_ = None
         self.hmc_row_mass_ = None
         data_x, data_y, data_v = data
+        if partial:
+            hmc_mod.check_partial_rows(np.asarray(data_x, np.float32).reshape(-1), np.asarray(data_y, np.float32).reshape(-1))
         out = self.engine.hmc_sample(self._dev(data_x).reshape(-1), self._dev(data_y).reshape(-1), self._dev(data_v), burn_in, n_keep,
-                                     step_size, n_leapfrog, self._next_seed(), want_draws=True, adapt=target, mass=mass)
+                                     step_size, n_leapfrog, self._next_seed(), want_draws=True, adapt=target, mass=mass, partial=bool(partial))
         self.hmc_row_step_ = out["row_step"].cpu().numpy()
         if mass is not None:
             self.hmc_row_mass_ = out["mass_scale"].cpu().numpy()

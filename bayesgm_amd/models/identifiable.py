@@ -274,6 +274,12 @@ class IdentifiableCausalBGM(CausalBGM):
         ``predict(sampler='hmc')``, word for word."""
         self._refuse_hmc('hmc', 1.0, False, step_size, n_leapfrog, mass)
 
+    def predict_new(self, data_v, data_x=None, x_values=None, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None,
+                    n_leapfrog=None, mass='identity', interval='normal', draw_budget_bytes=None, verbose=1):
+        """CausalBGM.predict_new samples the latents of new units with the HMC sampler, which this class does not have."""
+        raise ValueError("predict_new is not available for %s: the latents of units without an outcome are sampled by the HMC sampler "
+                         "of the deterministic CausalBGM, which this class does not have" % type(self).__name__)
+
     def predict_average(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, groups=None, estimand='ate', sampler='hmc',
                         q_sd=1.0, step_size=None, n_leapfrog=None, mass='identity', verbose=1):
         """CausalBGM.predict_average exists for the deterministic CausalBGM only: this class refuses it, whatever the sampler."""

@@ -488,6 +488,20 @@ BGM_API int bgm_causal_hmc_set_mass(bgm_handle *h, const float *scale_dev, const
 BGM_API int bgm_causal_hmc_mass_update(bgm_handle *h, int64_t n, int32_t n_draws, const float *state_dev, float *scale_dev,
                                        float *ref_dev, float *s1_dev, float *s2_dev, void *stream);
 
+/* Partially observed rows for the gradient / HMC calls made afterwards (opt-in; on = 0, the default: today's kernels, where NaN in
+ * the data is not looked at).  on != 0: x_dev[row] / y_dev[row] = NaN means "not observed", and the target of that row is the same
+ * log posterior with the terms of the unobserved variables left out: p(z | x, v) for a row without its outcome, p(z | v) for a row
+ * without outcome and treatment -- the effects of NEW units, whose outcome is not known yet.  g's term and the prior are those of
+ * every row; a row's logp, gradient and chain do not depend on the other rows of its tile.  A row with y observed and x not has no
+ * defined target (f needs the treatment): the caller's duty, the kernels do not report it.  On a fully observed panel every output
+ * is bit-identical to the run with on = 0.  Read by bgm_causal_logpost_grad, bgm_causal_hmc_run (with or without a metric),
+ * bgm_causal_hmc_run_effects for a binary treatment (BGM_EFFECT_ITE) and bgm_causal_hmc_run_row_effects; signatures, buffers, RNG
+ * streams and launch cuts are unchanged.  While on, bgm_causal_hmc_run_group_effects and the continuous-treatment
+ * bgm_causal_hmc_run_effects (the panel's ADRF) answer BGM_E_UNSUPPORTED naming this option.  Refuses what bgm_causal_logpost_grad
+ * refuses.
+ * replaces: nothing in causalbgm/base.py; the reference's predict (:573-668) takes the training triplet (x, y, v) of every row. */
+BGM_API int bgm_causal_hmc_set_partial(bgm_handle *h, int32_t on);
+
 /* ------------------------------------------------------------------------------------------
  * CausalBGM.fit step functions (iterative theta / Z updates).
  * replaces: update_g_net :156-180, update_h_net :183-214, update_f_net :217-243,
