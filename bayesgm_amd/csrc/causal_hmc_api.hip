@@ -121,33 +121,34 @@ extern "C" int bgm_causal_logpost_grad(bgm_handle *h, const float *x, const floa
   });
 }
 
-int bgm_causal_hmc_args(bgm_handle *h, const char *who_, const float *x, const float *y, const float *v, int64_t n, int64_t row_base,
-                        float *state, float *logp, float *grad, float *step, const float *up, const float *dn, int32_t n_table, float s_min,
-                        float s_max, int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed,
-                        uint32_t *acc_count, float *draws, int32_t n_keep, hipStream_t stream, CausalHmcKArgs &ka, HmcState *&st, int &grid) {
+int bgm_causal_hmc_args(bgm_handle *h, const char *who_, const CausalHmcCall &c, CausalHmcLaunch &l) {
   const std::string who(who_);
-  if (!x || !y || !v || !state || !logp || !grad || !step) { bgm_set_error(who + ": NULL data pointer"); return BGM_E_INVALID; }
-  if (n_leapfrog < 1) { bgm_set_error(who + ": n_leapfrog must be >= 1"); return BGM_E_INVALID; }
-  if (it_begin < 0 || burn_in < 0) { bgm_set_error(who + ": it_begin / burn_in must be >= 0"); return BGM_E_INVALID; }
-  if (row_base < 0 || row_base + n > 0xFFFFFFFFll) { bgm_set_error(who + ": row index exceeds the 32-bit RNG counter"); return BGM_E_INVALID; }
-  if (up || dn) {
-    if (!up || !dn || n_table < 0) { bgm_set_error(who + ": up_dev / dn_dev must both hold n_table >= 0 factors"); return BGM_E_INVALID; }
-    if (!(s_min > 0.0f) || !(s_max >= s_min) || !(s_max < INFINITY)) { bgm_set_error(who + ": the clamp needs 0 < s_min <= s_max < inf"); return BGM_E_INVALID; }
+  if (!c.x || !c.y || !c.v || !c.state || !c.logp || !c.grad || !c.step) { bgm_set_error(who + ": NULL data pointer"); return BGM_E_INVALID; }
+  if (c.n_leapfrog < 1) { bgm_set_error(who + ": n_leapfrog must be >= 1"); return BGM_E_INVALID; }
+  if (c.it_begin < 0 || c.burn_in < 0) { bgm_set_error(who + ": it_begin / burn_in must be >= 0"); return BGM_E_INVALID; }
+  if (c.row_base < 0 || c.row_base + c.n > 0xFFFFFFFFll) { bgm_set_error(who + ": row index exceeds the 32-bit RNG counter"); return BGM_E_INVALID; }
+  if (c.up || c.dn) {
+    if (!c.up || !c.dn || c.n_table < 0) { bgm_set_error(who + ": up_dev / dn_dev must both hold n_table >= 0 factors"); return BGM_E_INVALID; }
+    if (!(c.s_min > 0.0f) || !(c.s_max >= c.s_min) || !(c.s_max < INFINITY)) { bgm_set_error(who + ": the clamp needs 0 < s_min <= s_max < inf"); return BGM_E_INVALID; }
   }
-  if (draws && (long long)it_begin + n_iters - burn_in > n_keep) { bgm_set_error(who + ": iterations beyond burn_in + n_keep"); return BGM_E_INVALID; }
+  if (c.draws && (long long)c.it_begin + c.n_iters - c.burn_in > c.n_keep) { bgm_set_error(who + ": iterations beyond burn_in + n_keep"); return BGM_E_INVALID; }
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  st = nullptr;
-  if (int rc = hmc_prepare(h, v, n, stream, st)) return rc;
+  HmcState *st = nullptr;
+  if (int rc = hmc_prepare(h, c.v, c.n, c.stream, st)) return rc;
   const CausalHmcMassArgs &ma = st->mass;      // bgm_causal_hmc_set_mass
   if (ma.scale && ma.accumulate && (!ma.ref || !ma.s1 || !ma.s2)) { bgm_set_error("HMC metric: launched without its buffers"); return BGM_E_STATE; }
+  CausalHmcKArgs &ka = l.ka;
   ka = CausalHmcKArgs{};
-  ka.blob = st->blob_dev; ka.x = x; ka.y = y; ka.uc = h->uc_dev; ka.n = n; ka.row_base = row_base;
-  ka.state = state; ka.logp = logp; ka.grad = grad; ka.step = step;
-  ka.up = up; ka.dn = dn; ka.n_table = up ? n_table : 0; ka.s_min = s_min; ka.s_max = s_max;
-  ka.init = init ? 1 : 0; ka.it_begin = it_begin; ka.n_iters = n_iters; ka.burn_in = burn_in; ka.n_leapfrog = n_leapfrog;
-  ka.k0 = (unsigned)(seed & 0xFFFFFFFFull); ka.k1 = (unsigned)(seed >> 32);
-  ka.acc_count = acc_count; ka.draws = draws; ka.m = st->m;
-  grid = bgm_causal_grid(h, n, 1);
+  ka.blob = st->blob_dev; ka.x = c.x; ka.y = c.y; ka.uc = h->uc_dev; ka.n = c.n; ka.row_base = c.row_base;
+  ka.state = c.state; ka.logp = c.logp; ka.grad = c.grad; ka.step = c.step;
+  ka.up = c.up; ka.dn = c.dn; ka.n_table = c.up ? c.n_table : 0; ka.s_min = c.s_min; ka.s_max = c.s_max;
+  ka.init = c.init ? 1 : 0; ka.it_begin = c.it_begin; ka.n_iters = c.n_iters; ka.burn_in = c.burn_in; ka.n_leapfrog = c.n_leapfrog;
+  ka.k0 = (unsigned)(c.seed & 0xFFFFFFFFull); ka.k1 = (unsigned)(c.seed >> 32);
+  ka.acc_count = c.acc_count; ka.draws = c.draws; ka.m = st->m;
+  l.st = st;
+  l.grid = bgm_causal_grid(h, c.n, 1);
+  l.lds = st->m.total * 4;
+  l.stream = c.stream;
   return BGM_OK;
 }
 
@@ -157,17 +158,14 @@ extern "C" int bgm_causal_hmc_run(bgm_handle *h, const float *x, const float *y,
                                   uint64_t seed, uint32_t *acc_count, float *draws, int32_t n_keep, void *stream_) {
   if (int rc = bgm_causal_hmc_check(h, "bgm_causal_hmc_run")) return rc;
   if (n <= 0 || n_iters <= 0) return BGM_OK;
-  hipStream_t stream = (hipStream_t)stream_;
-  CausalHmcKArgs ka{};
-  HmcState *st = nullptr;
-  int grid = 0;
-  if (int rc = bgm_causal_hmc_args(h, "bgm_causal_hmc_run", x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init,
-                                   it_begin, n_iters, burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid))
-    return rc;
-  if (h->hmc_partial) return bgm_causal_hmc_obs_launch(h, ka, st, grid, st->m.total * 4, stream);      // bgm_causal_hmc_set_partial
-  if (st->mass.scale) return bgm_causal_hmc_mass_launch(h, ka, st->mass, grid, st->m.total * 4, stream);      // bgm_causal_hmc_set_mass
+  const CausalHmcCall call{x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in,
+                           n_leapfrog, seed, acc_count, draws, n_keep, (hipStream_t)stream_};
+  CausalHmcLaunch l{};
+  if (int rc = bgm_causal_hmc_args(h, "bgm_causal_hmc_run", call, l)) return rc;
+  if (h->hmc_partial) return bgm_causal_hmc_obs_launch(h, l);      // bgm_causal_hmc_set_partial
+  if (l.st->mass.scale) return bgm_causal_hmc_mass_launch(h, l);      // bgm_causal_hmc_set_mass
   return bgm_causal_dispatch(h, "HMC kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_launch(causal_hmc_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, st->m.total * 4, stream, ka);
+    return bgm_launch(causal_hmc_kernel<S::KT1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka);
   });
 }

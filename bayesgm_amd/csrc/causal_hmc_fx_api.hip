@@ -13,13 +13,13 @@ namespace {
 const char *WHO = "bgm_causal_hmc_run_effects";
 
 template <int EFFECT>
-int launch_fx(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, const CausalHmcFxArgs &fx, int grid, int lds, hipStream_t stream) {
-  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with fused effects", [&](auto s, auto metric) {
+int launch_fx(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx) {
+  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with fused effects", [&](auto s, auto metric) {
     using S = decltype(s);
     if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_mass_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka, st->mass, fx);
+      return bgm_launch(causal_hmc_mass_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx);
     else
-      return bgm_launch(causal_hmc_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, grid, MH_WAVES, lds, stream, ka, fx);
+      return bgm_launch(causal_hmc_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx);
   });
 }
 
@@ -42,17 +42,13 @@ extern "C" int bgm_causal_hmc_run_effects(bgm_handle *h, const float *x, const f
   }
   if (binary && !ite) { bgm_set_error(who + ": ite_dev required for binary treatment"); return BGM_E_INVALID; }
   if (!binary && (!x_values || n_doses <= 0 || !adrf_partial)) { bgm_set_error(who + ": x_values / adrf_partial required"); return BGM_E_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
-  CausalHmcKArgs ka{};
+  const CausalHmcCall call{x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in,
+                           n_leapfrog, seed, acc_count, draws, n_keep, (hipStream_t)stream_};
+  CausalHmcLaunch l{};
   CausalHmcFxArgs fx{};
-  HmcState *st = nullptr;
-  int grid = 0;
-  size_t lds = 0;
-  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin,
-                                         n_iters, burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid, fx, lds))
-    return rc;
+  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, call, l, fx)) return rc;
   fx.sample_y = sample_y; fx.n_doses = binary ? 2 : n_doses;
   fx.x_values = x_values; fx.adrf_partial = adrf_partial; fx.ite = ite;
-  if (h->hmc_partial) return bgm_causal_hmc_obs_ite_launch(h, ka, st, fx, grid, (int)lds, stream);      // (binary: checked above)
-  return binary ? launch_fx<2>(h, ka, st, fx, grid, (int)lds, stream) : launch_fx<1>(h, ka, st, fx, grid, (int)lds, stream);
+  if (h->hmc_partial) return bgm_causal_hmc_obs_ite_launch(h, l, fx);      // (binary: checked above)
+  return binary ? launch_fx<2>(h, l, fx) : launch_fx<1>(h, l, fx);
 }

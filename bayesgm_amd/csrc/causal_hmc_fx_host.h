@@ -29,29 +29,23 @@ static inline void bgm_causal_hmc_fx_layout(const bgm_handle *h, CausalHmcFxArgs
 // After bgm_causal_hmc_check and the entry point's own argument checks: n_keep / it_begin / burn_in, the sampling blob, the LDS
 // budget refusal (naming the bytes, before the panel's pre-pass or any kernel of the sampler is launched), bgm_causal_hmc_args,
 // then fx.sblob / src / dst / cnt / mf / n_keep and the LDS bytes of the launch.  The caller fills in the rest of fx.
-static inline int bgm_causal_hmc_fx_prepare(bgm_handle *h, const char *who_, const float *x, const float *y, const float *v, int64_t n,
-                                            int64_t row_base, float *state, float *logp, float *grad, float *step, const float *up,
-                                            const float *dn, int32_t n_table, float s_min, float s_max, int32_t init, int32_t it_begin,
-                                            int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed, uint32_t *acc_count,
-                                            float *draws, int32_t n_keep, hipStream_t stream, CausalHmcKArgs &ka, HmcState *&st, int &grid,
-                                            CausalHmcFxArgs &fx, size_t &lds) {
+static inline int bgm_causal_hmc_fx_prepare(bgm_handle *h, const char *who_, const CausalHmcCall &c, CausalHmcLaunch &l, CausalHmcFxArgs &fx) {
   const std::string who(who_);
-  if (n_keep <= 0 || (long long)it_begin + n_iters - burn_in > n_keep) { bgm_set_error(who + ": iterations beyond burn_in + n_keep"); return BGM_E_INVALID; }
+  if (c.n_keep <= 0 || (long long)c.it_begin + c.n_iters - c.burn_in > c.n_keep) { bgm_set_error(who + ": iterations beyond burn_in + n_keep"); return BGM_E_INVALID; }
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  if (int rc = bgm_causal_sampling_blob(h, stream)) return rc;
+  if (int rc = bgm_causal_sampling_blob(h, c.stream)) return rc;
   // the LDS budget is known from the shape: refuse before the panel's pre-pass or any kernel of the sampler is launched
-  lds = ((size_t)bgm_causal_hmc_blob_floats(h->KT1, h->meta.n_gh) + chmc_fx_floats(h->KT1)) * 4;
+  const size_t lds = ((size_t)bgm_causal_hmc_blob_floats(h->KT1, h->meta.n_gh) + chmc_fx_floats(h->KT1)) * 4;
   if (lds > 160 * 1024) {
     bgm_set_error(who + ": the HMC weights with f's part of the sampling blob do not fit the 160 KiB LDS (" + std::to_string(lds) +
                   " B); use the draws route: bgm_causal_hmc_run with draws_dev, then bgm_causal_effects");
     return BGM_E_UNSUPPORTED;
   }
-  if (int rc = bgm_causal_hmc_args(h, who_, x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters,
-                                   burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid))
-    return rc;
+  if (int rc = bgm_causal_hmc_args(h, who_, c, l)) return rc;
   bgm_causal_hmc_fx_layout(h, fx);
-  if (fx.mf.total != chmc_fx_floats(h->KT1) || (size_t)(st->m.total + fx.mf.total) * 4 != lds) { bgm_set_error(who + ": LDS layout disagrees with its byte count"); return BGM_E_STATE; }
+  if (fx.mf.total != chmc_fx_floats(h->KT1) || (size_t)(l.st->m.total + fx.mf.total) * 4 != lds) { bgm_set_error(who + ": LDS layout disagrees with its byte count"); return BGM_E_STATE; }
+  l.lds = (int)lds;
   fx.sblob = h->sblob_dev;
-  fx.n_keep = n_keep;
+  fx.n_keep = c.n_keep;
   return BGM_OK;
 }

@@ -38,24 +38,20 @@ extern "C" int bgm_causal_hmc_run_group_effects(bgm_handle *h, const float *x, c
     return BGM_E_INVALID;
   }
   if (!labels || !group_partial) { bgm_set_error(who + ": labels / group_partial required"); return BGM_E_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
-  CausalHmcKArgs ka{};
+  const CausalHmcCall call{x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in,
+                           n_leapfrog, seed, acc_count, draws, n_keep, (hipStream_t)stream_};
+  CausalHmcLaunch l{};
   CausalHmcFxArgs fx{};
-  HmcState *st = nullptr;
-  int grid = 0;
-  size_t lds = 0;
-  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin,
-                                         n_iters, burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid, fx, lds))
-    return rc;
+  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, call, l, fx)) return rc;
   fx.sample_y = sample_y; fx.n_doses = n_labels;      // (the slot's stride: [n_keep][n_labels])
   fx.adrf_partial = group_partial;
   fx.ite = reinterpret_cast<float *>(const_cast<int32_t *>(labels));      // (read only, as int: chmc_run, EFFECT 4)
-  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with label sums of the treatment effect", [&](auto s, auto metric) {
+  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with label sums of the treatment effect", [&](auto s, auto metric) {
     using S = decltype(s);
     if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_mass_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, st->mass, fx);
+      return bgm_launch(causal_hmc_mass_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx);
     else
-      return bgm_launch(causal_hmc_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, fx);
+      return bgm_launch(causal_hmc_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx);
   });
 }
 

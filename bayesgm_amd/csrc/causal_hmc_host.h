@@ -24,15 +24,37 @@ static inline int bgm_causal_hmc_blob_floats(int KT1, int n_gh) {
 
 // BGM_E_STATE for an unconfigured handle, BGM_E_UNSUPPORTED (naming the path) where the gradient / HMC kernels do not exist
 int bgm_causal_hmc_check(bgm_handle *h, const char *who);                                                     // causal_hmc_api.hip
+// The arguments every HMC segment takes (bgm_causal_hmc_run and the three entry points with an effect pass; include/bgm_hip.h says
+// what each means), in the order of the C ABI.  An entry point fills one from its parameters and passes it on by reference.
+struct CausalHmcCall {
+  const float *x, *y, *v;
+  int64_t n, row_base;
+  float *state, *logp, *grad, *step;
+  const float *up, *dn;
+  int32_t n_table;
+  float s_min, s_max;
+  int32_t init, it_begin, n_iters, burn_in, n_leapfrog;
+  uint64_t seed;
+  uint32_t *acc_count;
+  float *draws;
+  int32_t n_keep;
+  hipStream_t stream;
+};
+
+// What preparation makes of a call: the kernel arguments of one launch, the handle's HMC state (blob, meta, metric), the grid and
+// the dynamic LDS bytes (the HMC blob; with f's part of the sampling blob behind it after bgm_causal_hmc_fx_prepare)
+struct CausalHmcLaunch {
+  CausalHmcKArgs ka;
+  HmcState *st;
+  int grid;
+  int lds;
+  hipStream_t stream;
+};
+
 // the argument checks of bgm_causal_hmc_run (`who` names the entry point), the panel's Gram pre-pass and the dual-access blob, the
-// metric's buffers (st->mass, once for every entry point), then the kernel arguments of one launch and its grid
-int bgm_causal_hmc_args(bgm_handle *h, const char *who, const float *x, const float *y, const float *v, int64_t n, int64_t row_base,
-                        float *state, float *logp, float *grad, float *step, const float *up, const float *dn, int32_t n_table, float s_min,
-                        float s_max, int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog, uint64_t seed,
-                        uint32_t *acc_count, float *draws, int32_t n_keep, hipStream_t stream, CausalHmcKArgs &ka, HmcState *&st,
-                        int &grid);                                                                           // causal_hmc_api.hip
-int bgm_causal_hmc_mass_launch(bgm_handle *h, const CausalHmcKArgs &ka, const CausalHmcMassArgs &ma, int grid, int lds,
-                               hipStream_t stream);                                                           // causal_hmc_mass_api.hip
+// metric's buffers (st->mass, once for every entry point), then the launch record
+int bgm_causal_hmc_args(bgm_handle *h, const char *who, const CausalHmcCall &call, CausalHmcLaunch &launch);      // causal_hmc_api.hip
+int bgm_causal_hmc_mass_launch(bgm_handle *h, const CausalHmcLaunch &launch);                                     // causal_hmc_mass_api.hip
 
 // bgm_causal_dispatch for a kernel that has a twin with the metric: f(S{}, std::true_type) while a metric is set
 // (bgm_causal_hmc_set_mass; it launches the twin with st->mass), f(S{}, std::false_type) otherwise.  `what` names the kernel.

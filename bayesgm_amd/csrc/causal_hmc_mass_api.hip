@@ -71,9 +71,9 @@ extern "C" int bgm_causal_hmc_mass_update(bgm_handle *h, int64_t n, int32_t n_dr
   return BGM_OK;
 }
 
-int bgm_causal_hmc_mass_launch(bgm_handle *h, const CausalHmcKArgs &ka, const CausalHmcMassArgs &ma, int grid, int lds, hipStream_t stream) {
+int bgm_causal_hmc_mass_launch(bgm_handle *h, const CausalHmcLaunch &l) {
   return bgm_causal_dispatch(h, "HMC kernel with a diagonal metric", [&](auto s) {
     using S = decltype(s);
-    return bgm_launch(causal_hmc_mass_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, ma);
+    return bgm_launch(causal_hmc_mass_kernel<S::KT1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass);
   });
 }

@@ -26,34 +26,32 @@ int bgm_causal_hmc_obs_logpost(bgm_handle *h, const HmcState *st, const float *x
   });
 }
 
-int bgm_causal_hmc_obs_launch(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, int grid, int lds, hipStream_t stream) {
-  return bgm_causal_hmc_dispatch(h, st, "HMC kernel for partially observed rows", [&](auto s, auto metric) {
+int bgm_causal_hmc_obs_launch(bgm_handle *h, const CausalHmcLaunch &l) {
+  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel for partially observed rows", [&](auto s, auto metric) {
     using S = decltype(s);
     if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_obs_mass_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, st->mass);
+      return bgm_launch(causal_hmc_obs_mass_kernel<S::KT1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass);
     else
-      return bgm_launch(causal_hmc_obs_kernel<S::KT1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka);
+      return bgm_launch(causal_hmc_obs_kernel<S::KT1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka);
   });
 }
 
-int bgm_causal_hmc_obs_ite_launch(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, const CausalHmcFxArgs &fx, int grid, int lds,
-                                  hipStream_t stream) {
-  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with fused effects for partially observed rows", [&](auto s, auto metric) {
+int bgm_causal_hmc_obs_ite_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx) {
+  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with fused effects for partially observed rows", [&](auto s, auto metric) {
     using S = decltype(s);
     if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_obs_mass_ite_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, st->mass, fx);
+      return bgm_launch(causal_hmc_obs_mass_ite_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx);
     else
-      return bgm_launch(causal_hmc_obs_ite_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, fx);
+      return bgm_launch(causal_hmc_obs_ite_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx);
   });
 }
 
-int bgm_causal_hmc_obs_rowfx_launch(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, const CausalHmcFxArgs &fx,
-                                    const CausalHmcRowFxArgs &rf, int grid, int lds, hipStream_t stream) {
-  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with per-row effects for partially observed rows", [&](auto s, auto metric) {
+int bgm_causal_hmc_obs_rowfx_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx, const CausalHmcRowFxArgs &rf) {
+  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with per-row effects for partially observed rows", [&](auto s, auto metric) {
     using S = decltype(s);
     if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_obs_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, st->mass, fx, rf);
+      return bgm_launch(causal_hmc_obs_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx, rf);
     else
-      return bgm_launch(causal_hmc_obs_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, lds, stream, ka, fx, rf);
+      return bgm_launch(causal_hmc_obs_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx, rf);
   });
 }

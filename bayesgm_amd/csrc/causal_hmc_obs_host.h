@@ -7,9 +7,7 @@
 
 int bgm_causal_hmc_obs_logpost(bgm_handle *h, const HmcState *st, const float *x, const float *y, const float *z, int64_t n, float *out_logp,
                                float *out_grad, int grid, hipStream_t stream);                                 // bgm_causal_logpost_grad
-int bgm_causal_hmc_obs_launch(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, int grid, int lds,
-                              hipStream_t stream);                                                            // bgm_causal_hmc_run
-int bgm_causal_hmc_obs_ite_launch(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, const CausalHmcFxArgs &fx, int grid, int lds,
-                                  hipStream_t stream);                                                        // bgm_causal_hmc_run_effects, binary
-int bgm_causal_hmc_obs_rowfx_launch(bgm_handle *h, const CausalHmcKArgs &ka, const HmcState *st, const CausalHmcFxArgs &fx,
-                                    const CausalHmcRowFxArgs &rf, int grid, int lds, hipStream_t stream);      // bgm_causal_hmc_run_row_effects
+int bgm_causal_hmc_obs_launch(bgm_handle *h, const CausalHmcLaunch &l);                                       // bgm_causal_hmc_run
+int bgm_causal_hmc_obs_ite_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx);        // bgm_causal_hmc_run_effects, binary
+int bgm_causal_hmc_obs_rowfx_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx,
+                                    const CausalHmcRowFxArgs &rf);                                            // bgm_causal_hmc_run_row_effects

@@ -27,23 +27,19 @@ extern "C" int bgm_causal_hmc_run_row_effects(bgm_handle *h, const float *x, con
     return BGM_E_INVALID;
   }
   if (!x_values || n_doses <= 0 || !row_moments) { bgm_set_error(who + ": x_values / row_moments required"); return BGM_E_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
-  CausalHmcKArgs ka{};
+  const CausalHmcCall call{x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in,
+                           n_leapfrog, seed, acc_count, draws, n_keep, (hipStream_t)stream_};
+  CausalHmcLaunch l{};
   CausalHmcFxArgs fx{};
-  HmcState *st = nullptr;
-  int grid = 0;
-  size_t lds = 0;
-  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin,
-                                         n_iters, burn_in, n_leapfrog, seed, acc_count, draws, n_keep, stream, ka, st, grid, fx, lds))
-    return rc;
+  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, call, l, fx)) return rc;
   fx.sample_y = sample_y; fx.n_doses = n_doses; fx.x_values = x_values;
   const CausalHmcRowFxArgs rf{row_moments, row_draws};
-  if (h->hmc_partial) return bgm_causal_hmc_obs_rowfx_launch(h, ka, st, fx, rf, grid, (int)lds, stream);      // bgm_causal_hmc_set_partial
-  return bgm_causal_hmc_dispatch(h, st, "HMC kernel with per-row effects", [&](auto s, auto metric) {
+  if (h->hmc_partial) return bgm_causal_hmc_obs_rowfx_launch(h, l, fx, rf);      // bgm_causal_hmc_set_partial
+  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with per-row effects", [&](auto s, auto metric) {
     using S = decltype(s);
     if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, st->mass, fx, rf);
+      return bgm_launch(causal_hmc_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx, rf);
     else
-      return bgm_launch(causal_hmc_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, grid, MH_WAVES, (int)lds, stream, ka, fx, rf);
+      return bgm_launch(causal_hmc_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx, rf);
   });
 }

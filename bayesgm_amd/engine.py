@@ -154,27 +154,28 @@ class CausalEngine(object):
         group_partial.  partial=True: NaN in y, or in x and y, marks what a row does not observe (logpost_grad); EFFECT_ADRF and
         EFFECT_GROUP_ITE have no kernels for it and raise the library's error."""
         with self._partial_rows(partial, x, y):
-            self._hmc_run(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min, s_max,
-                          acc_count, draws, n_keep, effect, sample_y, x_values, adrf_partial, ite, labels, n_labels, group_partial)
+            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
+                                  s_max, acc_count, draws, n_keep)
+            if effect == _lib.EFFECT_NONE:
+                _lib.check(self.lib.bgm_causal_hmc_run(*args, self._stream()), "bgm_causal_hmc_run")
+            elif effect == _lib.EFFECT_GROUP_ITE:
+                _lib.check(self.lib.bgm_causal_hmc_run_group_effects(*args, int(bool(sample_y)), _ptr(labels), int(n_labels), _ptr(group_partial),
+                                                                     self._stream()), "bgm_causal_hmc_run_group_effects")
+            elif effect == (_lib.EFFECT_ITE if self.binary else _lib.EFFECT_ADRF):
+                _lib.check(self.lib.bgm_causal_hmc_run_effects(*args, int(bool(sample_y)), _ptr(x_values),
+                                                               0 if x_values is None else int(x_values.numel()), _ptr(adrf_partial), _ptr(ite),
+                                                               self._stream()), "bgm_causal_hmc_run_effects")
+            else:
+                raise ValueError("hmc_run: effect must be EFFECT_NONE or the effect of the treatment type (EFFECT_ITE for a binary "
+                                 "treatment, EFFECT_ADRF otherwise); got %r" % (effect,))
 
-    def _hmc_run(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min, s_max,
-                 acc_count, draws, n_keep, effect, sample_y, x_values, adrf_partial, ite, labels, n_labels, group_partial):
-        args = (self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up),
+    def _hmc_args(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min, s_max,
+                  acc_count, draws, n_keep):
+        """The handle and the 24 arguments that each of the four entry points of an HMC segment takes first (include/bgm_hip.h),
+        marshalled for ctypes; the entry point's own arguments and the stream follow them."""
+        return (self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up),
                 _ptr(dn), 0 if up is None else int(up.numel()), float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters),
                 int(burn_in), int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws), int(n_keep))
-        if effect == _lib.EFFECT_NONE:
-            _lib.check(self.lib.bgm_causal_hmc_run(*args, self._stream()), "bgm_causal_hmc_run")
-            return
-        if effect == _lib.EFFECT_GROUP_ITE:
-            _lib.check(self.lib.bgm_causal_hmc_run_group_effects(*args, int(bool(sample_y)), _ptr(labels), int(n_labels), _ptr(group_partial),
-                                                                 self._stream()), "bgm_causal_hmc_run_group_effects")
-            return
-        if effect not in (_lib.EFFECT_ADRF, _lib.EFFECT_ITE) or (effect == _lib.EFFECT_ITE) != bool(self.binary):
-            raise ValueError("hmc_run: effect must be EFFECT_NONE or the effect of the treatment type (EFFECT_ITE for a binary "
-                             "treatment, EFFECT_ADRF otherwise); got %r" % (effect,))
-        _lib.check(self.lib.bgm_causal_hmc_run_effects(*args, int(bool(sample_y)), _ptr(x_values),
-                                                       0 if x_values is None else int(x_values.numel()), _ptr(adrf_partial), _ptr(ite),
-                                                       self._stream()), "bgm_causal_hmc_run_effects")
 
     def hmc_run_rows_effects(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
                              row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
@@ -184,12 +185,11 @@ class CausalEngine(object):
         in / out across segments) and, optionally, row_draws [n, n_doses, n_keep] receive y_i(x_k) of the iterations >= burn_in of
         this segment.  partial=True: as in hmc_run."""
         with self._partial_rows(partial, x, y):
-            _lib.check(self.lib.bgm_causal_hmc_run_row_effects(
-                self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up), _ptr(dn),
-                0 if up is None else int(up.numel()), float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters), int(burn_in),
-                int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws), int(n_keep), int(bool(sample_y)), _ptr(x_values),
-                0 if x_values is None else int(x_values.numel()), _ptr(row_moments), _ptr(row_draws), self._stream()),
-                "bgm_causal_hmc_run_row_effects")
+            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
+                                  s_max, acc_count, draws, n_keep)
+            _lib.check(self.lib.bgm_causal_hmc_run_row_effects(*args, int(bool(sample_y)), _ptr(x_values),
+                                                               0 if x_values is None else int(x_values.numel()), _ptr(row_moments),
+                                                               _ptr(row_draws), self._stream()), "bgm_causal_hmc_run_row_effects")
 
     def hmc_run_group_effects(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, labels=None, n_labels=0,
                               group_partial=None, **kw):
@@ -302,49 +302,7 @@ class CausalEngine(object):
         acc = torch.zeros(total, device=dev, dtype=torch.int32)
         draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
         chunk = total if chunk is None else max(1, int(chunk))
-        xv = adrf_part = ite = lab = gpartial = None
-        n_slots = n_lab = 0
-        if effect == _lib.EFFECT_ADRF:
-            if x_values is None:
-                raise ValueError("hmc_sample: effect=EFFECT_ADRF needs x_values")
-            xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), dev)
-            ns = C.c_int32()
-            _lib.check(self.lib.bgm_causal_evaluate_slots(self.h, n, C.byref(ns)), "bgm_causal_evaluate_slots")
-            n_slots = ns.value
-            adrf_part = torch.zeros((n_slots, n_keep, xv.numel()), device=dev, dtype=torch.float32)
-        elif effect == _lib.EFFECT_ITE:
-            ite = torch.empty((n, n_keep), device=dev, dtype=torch.float32)
-        elif effect == _lib.EFFECT_GROUP_ITE:
-            if not self.binary:
-                raise ValueError("hmc_sample: effect=EFFECT_GROUP_ITE sums the treatment effect of a binary treatment; a continuous "
-                                 "treatment has its dose-response (effect=EFFECT_ADRF)")
-            lab, n_lab = self._group_labels(labels, n_labels, n, "hmc_sample")
-            ns = C.c_int32()
-            _lib.check(self.lib.bgm_causal_evaluate_slots(self.h, n, C.byref(ns)), "bgm_causal_evaluate_slots")
-            n_slots = ns.value
-            try:
-                gpartial = torch.zeros((n_slots, n_keep, n_lab), device=dev, dtype=torch.float32)
-            except torch.cuda.OutOfMemoryError:
-                raise RuntimeError("hmc_sample: cannot allocate group_partial [n_slots x n_keep x n_labels] = [%d x %d x %d] float32 (%d "
-                                   "bytes)" % (n_slots, n_keep, n_lab, 4 * n_slots * n_keep * n_lab))
-        elif effect != _lib.EFFECT_NONE:
-            raise ValueError("hmc_sample: effect must be EFFECT_NONE, EFFECT_ADRF, EFFECT_ITE or EFFECT_GROUP_ITE; got %r" % (effect,))
-        if labels is not None and effect != _lib.EFFECT_GROUP_ITE:
-            raise ValueError("hmc_sample: labels belong to effect=EFFECT_GROUP_ITE")
-        row_mom = row_y = None
-        if row_effects:
-            if effect != _lib.EFFECT_NONE:
-                raise ValueError("hmc_sample: row_effects and effect exclude each other (the panel's ADRF is the mean of the rows' curves)")
-            if self.binary:
-                raise ValueError("hmc_sample: row_effects is the dose-response of a continuous treatment; a binary treatment has its "
-                                 "per-row effect already (effect=EFFECT_ITE)")
-            if x_values is None:
-                raise ValueError("hmc_sample: row_effects needs x_values")
-            xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), dev)
-            row_mom = torch.zeros((3, xv.numel(), n), device=dev, dtype=torch.float32)      # ref, s1, s2
-            row_y = torch.empty((n, xv.numel(), n_keep), device=dev, dtype=torch.float32) if row_draws else None
-        elif row_draws:
-            raise ValueError("hmc_sample: row_draws belongs to row_effects=True")
+        launch, route_kw, collect = self._hmc_route(n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws)
         scale = moments = None
         if diag:
             scale = torch.ones((n, self.q), device=dev, dtype=torch.float32)
@@ -354,50 +312,99 @@ class CausalEngine(object):
             if tuple(scale.shape) != (n, self.q):
                 raise ValueError("hmc_sample: mass_scale must be [n x q] = %r; got %r" % ((n, self.q), tuple(scale.shape)))
         marks = [start] + ends if diag else []
-        try:
-            if partial:      # the pattern is checked once; the launches below find the handle's flag set
-                HM.check_partial_rows(x, y)
-                _lib.check(self.lib.bgm_causal_hmc_set_partial(self.h, 1), "bgm_causal_hmc_set_partial")
-            if scale is not None:
-                self.set_hmc_mass(scale)
-            it = 0
-            while it < total:
-                stop = min([it + chunk, total] + [b for b in marks if b > it])
-                if row_mom is not None:
-                    self.hmc_run_rows_effects(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0),
-                                              row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep,
-                                              sample_y=sample_y, x_values=xv, row_moments=row_mom, row_draws=row_y)
-                else:
-                    self.hmc_run(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0),
-                                 row_base=row_base, up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep, effect=effect,
-                                 sample_y=sample_y, x_values=xv, adrf_partial=adrf_part, ite=ite, labels=lab, n_labels=n_lab,
-                                 group_partial=gpartial)
-                if stop in marks:      # a window's edge: the first one only sets the reference point and turns the moments on
-                    k = marks.index(stop)
-                    self.hmc_mass_update(0 if k == 0 else stop - marks[k - 1], state, scale, *moments)
-                    self.set_hmc_mass(scale, *moments, accumulate=(k < len(marks) - 1))
-                it = stop
-        finally:
-            if scale is not None:
-                self.set_hmc_mass(None)
-            if partial:
-                _lib.check(self.lib.bgm_causal_hmc_set_partial(self.h, 0), "bgm_causal_hmc_set_partial")
+        with self._partial_rows(partial, x, y):      # the pattern is checked and the handle's flag set once, not per segment
+            try:
+                if scale is not None:
+                    self.set_hmc_mass(scale)
+                it = 0
+                while it < total:
+                    stop = min([it + chunk, total] + [b for b in marks if b > it])
+                    launch(x, y, v, state, logp, grad, step, it, stop - it, burn_in, n_leapfrog, seed, init=(it == 0), row_base=row_base,
+                           up=up, dn=dn, acc_count=acc, draws=draws, n_keep=n_keep, sample_y=sample_y, **route_kw)
+                    if stop in marks:      # a window's edge: the first one only sets the reference point and turns the moments on
+                        k = marks.index(stop)
+                        self.hmc_mass_update(0 if k == 0 else stop - marks[k - 1], state, scale, *moments)
+                        self.set_hmc_mass(scale, *moments, accumulate=(k < len(marks) - 1))
+                    it = stop
+            finally:
+                if scale is not None:
+                    self.set_hmc_mass(None)
         out = dict(draws=draws, state=state, logp=logp, grad=grad, acc_count=acc, row_step=step)
         if scale is not None:
             out["mass_scale"] = scale
-        if adrf_part is not None:
-            out["adrf"] = self.adrf_reduce(adrf_part, n_slots, xv.numel(), n_keep, n)
-        if ite is not None:
-            out["ite"] = ite
-        if gpartial is not None:
-            out["group_partial"] = gpartial
-            out["group_sums"] = self.adrf_reduce(gpartial, n_slots, n_lab, n_keep, 1.0)
-        if row_mom is not None:
-            mean, sd = HM.row_moments_finalize(row_mom[0], row_mom[1], row_mom[2], n_keep)
+        collect(out)
+        return out
+
+    # The result routes of hmc_sample, one per kind of result.  Each checks what is its own, allocates its buffers and returns
+    # (launch, kw, collect): the engine method that runs a segment, the keyword arguments it takes besides the common ones, and
+    # the function that adds the route's keys to the returned dict.
+    def _hmc_route(self, n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws):
+        kinds = {_lib.EFFECT_NONE: self._route_none, _lib.EFFECT_ADRF: self._route_adrf, _lib.EFFECT_ITE: self._route_ite,
+                 _lib.EFFECT_GROUP_ITE: self._route_group_ite}
+        if effect not in kinds:
+            raise ValueError("hmc_sample: effect must be EFFECT_NONE, EFFECT_ADRF, EFFECT_ITE or EFFECT_GROUP_ITE; got %r" % (effect,))
+        route = kinds[effect](n, n_keep, x_values, labels, n_labels)
+        if labels is not None and effect != _lib.EFFECT_GROUP_ITE:
+            raise ValueError("hmc_sample: labels belong to effect=EFFECT_GROUP_ITE")
+        if row_effects:
+            if effect != _lib.EFFECT_NONE:
+                raise ValueError("hmc_sample: row_effects and effect exclude each other (the panel's ADRF is the mean of the rows' curves)")
+            return self._route_rows(n, n_keep, x_values, row_draws)
+        if row_draws:
+            raise ValueError("hmc_sample: row_draws belongs to row_effects=True")
+        return route
+
+    def _evaluate_slots(self, n):
+        ns = C.c_int32()
+        _lib.check(self.lib.bgm_causal_evaluate_slots(self.h, n, C.byref(ns)), "bgm_causal_evaluate_slots")
+        return ns.value
+
+    def _route_none(self, n, n_keep, x_values, labels, n_labels):
+        return self.hmc_run, {}, lambda out: None
+
+    def _route_adrf(self, n, n_keep, x_values, labels, n_labels):
+        if x_values is None:
+            raise ValueError("hmc_sample: effect=EFFECT_ADRF needs x_values")
+        xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), self.device)
+        n_slots = self._evaluate_slots(n)
+        part = torch.zeros((n_slots, n_keep, xv.numel()), device=self.device, dtype=torch.float32)
+        return (self.hmc_run, dict(effect=_lib.EFFECT_ADRF, x_values=xv, adrf_partial=part),
+                lambda out: out.update(adrf=self.adrf_reduce(part, n_slots, xv.numel(), n_keep, n)))
+
+    def _route_ite(self, n, n_keep, x_values, labels, n_labels):
+        ite = torch.empty((n, n_keep), device=self.device, dtype=torch.float32)
+        return self.hmc_run, dict(effect=_lib.EFFECT_ITE, ite=ite), lambda out: out.update(ite=ite)
+
+    def _route_group_ite(self, n, n_keep, x_values, labels, n_labels):
+        if not self.binary:
+            raise ValueError("hmc_sample: effect=EFFECT_GROUP_ITE sums the treatment effect of a binary treatment; a continuous "
+                             "treatment has its dose-response (effect=EFFECT_ADRF)")
+        lab, n_lab = self._group_labels(labels, n_labels, n, "hmc_sample")
+        n_slots = self._evaluate_slots(n)
+        try:
+            part = torch.zeros((n_slots, n_keep, n_lab), device=self.device, dtype=torch.float32)
+        except torch.cuda.OutOfMemoryError:
+            raise RuntimeError("hmc_sample: cannot allocate group_partial [n_slots x n_keep x n_labels] = [%d x %d x %d] float32 (%d "
+                               "bytes)" % (n_slots, n_keep, n_lab, 4 * n_slots * n_keep * n_lab))
+        return (self.hmc_run, dict(effect=_lib.EFFECT_GROUP_ITE, labels=lab, n_labels=n_lab, group_partial=part),
+                lambda out: out.update(group_partial=part, group_sums=self.adrf_reduce(part, n_slots, n_lab, n_keep, 1.0)))
+
+    def _route_rows(self, n, n_keep, x_values, row_draws):
+        if self.binary:
+            raise ValueError("hmc_sample: row_effects is the dose-response of a continuous treatment; a binary treatment has its "
+                             "per-row effect already (effect=EFFECT_ITE)")
+        if x_values is None:
+            raise ValueError("hmc_sample: row_effects needs x_values")
+        xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), self.device)
+        mom = torch.zeros((3, xv.numel(), n), device=self.device, dtype=torch.float32)      # ref, s1, s2
+        row_y = torch.empty((n, xv.numel(), n_keep), device=self.device, dtype=torch.float32) if row_draws else None
+
+        def collect(out):
+            mean, sd = HM.row_moments_finalize(mom[0], mom[1], mom[2], n_keep)
             out["row_mean"], out["row_sd"] = mean.t().contiguous(), sd.t().contiguous()
             if row_y is not None:
                 out["row_draws"] = row_y
-        return out
+        return self.hmc_run_rows_effects, dict(x_values=xv, row_moments=mom, row_draws=row_y), collect
 
     def encode(self, v):
         v = _f32(v, self.device)
@@ -471,12 +478,11 @@ class CausalEngine(object):
                                                     None, _ptr(ite), self._stream()), "bgm_causal_evaluate")
             return sums, ite
         xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), self.device)
-        ns = C.c_int32()
-        _lib.check(self.lib.bgm_causal_evaluate_slots(self.h, n, C.byref(ns)), "bgm_causal_evaluate_slots")
-        partial = torch.zeros((ns.value, xv.numel()), device=self.device, dtype=torch.float32)
+        n_slots = self._evaluate_slots(n)
+        partial = torch.zeros((n_slots, xv.numel()), device=self.device, dtype=torch.float32)
         _lib.check(self.lib.bgm_causal_evaluate(self.h, _ptr(x), _ptr(y), _ptr(v), _ptr(z), n, _ptr(xv), xv.numel(),
                                                 _ptr(sums), _ptr(partial), None, self._stream()), "bgm_causal_evaluate")
-        dose_sums = self.adrf_reduce(partial, ns.value, xv.numel(), 1, 1.0).reshape(-1)
+        dose_sums = self.adrf_reduce(partial, n_slots, xv.numel(), 1, 1.0).reshape(-1)
         return sums, dose_sums
 
     def effects(self, x, draws, burn_in, seed, x_values=None, sample_y=True, row_base=0):
@@ -492,13 +498,12 @@ class CausalEngine(object):
                                                    int(bool(sample_y)), None, 0, None, _ptr(ite), self._stream()), "bgm_causal_effects")
             return ite.t().contiguous()
         xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), self.device)
-        ns = C.c_int32()
-        _lib.check(self.lib.bgm_causal_evaluate_slots(self.h, n, C.byref(ns)), "bgm_causal_evaluate_slots")
-        partial = torch.zeros((ns.value, n_keep, xv.numel()), device=self.device, dtype=torch.float32)
+        n_slots = self._evaluate_slots(n)
+        partial = torch.zeros((n_slots, n_keep, xv.numel()), device=self.device, dtype=torch.float32)
         _lib.check(self.lib.bgm_causal_effects(self.h, _ptr(x), _ptr(draws), n, int(row_base), n_keep, int(burn_in), seed,
                                                int(bool(sample_y)), _ptr(xv), xv.numel(), _ptr(partial), None, self._stream()),
                    "bgm_causal_effects")
-        return self.adrf_reduce(partial, ns.value, xv.numel(), n_keep, n)
+        return self.adrf_reduce(partial, n_slots, xv.numel(), n_keep, n)
 
     # -- fit step functions ------------------------------------------------------
     def fit_begin(self, n_rows, max_batch):

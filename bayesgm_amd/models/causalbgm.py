@@ -525,6 +525,69 @@ class CausalBGM(object):
         return self._evaluate_dev(x, y, v, z, n_total, lo_r, nb_intervals)
 
     # ------------------------------------------------------------------ predict
+    def _sampling_options(self, reset, use_hmc, sampler_opts, own_checks, alpha, n_mcmc, x_values):
+        """What predict, predict_individual, predict_new and predict_average do before they look at their data, in this order: the
+        attributes named in ``reset`` are cleared; ``use_hmc()`` (None: always) says whether the HMC sampler runs, and its options
+        ``sampler_opts = (step_size, n_leapfrog, mass, burn_in)`` are resolved and checked; ``own_checks(hmc in use)`` runs the
+        method's own checks; then alpha, n_mcmc and the normalisation of ``x_values`` (None stays None).  Touches no device.
+        -> (hmc, x_values, what own_checks returned), hmc = (step size, leapfrog steps, target acceptance rate, mass) or None."""
+        for name in reset:
+            setattr(self, name, None)
+        step_size, n_leapfrog, mass, burn_in = sampler_opts
+        hmc = None
+        if use_hmc is None or use_hmc():
+            hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
+        mass = hmc_mod.check_mass(mass, hmc is not None, True, burn_in)
+        own = own_checks(hmc is not None)
+        if hmc is not None:
+            hmc = hmc + (mass,)
+        assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
+        parallel.check_n_mcmc(n_mcmc)
+        if x_values is not None:
+            x_values = np.array([x_values], dtype=float) if np.isscalar(x_values) else np.array(x_values, dtype=float)
+        return hmc, x_values, own
+
+    def _begin_sampling(self, verbose):
+        """The seed of a sampler call, drawn after every refusal that needs no device"""
+        seed = self._next_seed()
+        if verbose:
+            print('MCMC Latent Variable Sampling ...')
+        return seed
+
+    def _sample_blocks(self, data, blocks, run, consume, verbose, sample=None, keep_mh_scale=False, **route_kw):
+        """The loop over row blocks behind predict, predict_individual, predict_new and predict_average.  ``run = (burn_in, n_mcmc,
+        seed, hmc)``, hmc as _sampling_options returns it.  Every block [s0, e0) of ``data = (x, y, v)`` goes to the device and is
+        sampled by engine.hmc_sample with the route's keyword arguments ``route_kw`` -- by ``sample(x, y, v, s0)``, the caller's MH
+        call, where hmc is None --; ``consume(s0, e0, x, out)`` takes what the block returned, and the block's steps, metric and
+        acceptance tail are recorded.  Afterwards the acceptance rate is reported and the steps and the metric are gathered over
+        the ranks into hmc_row_step_ / hmc_row_mass_ (the MH sampler's per-row scales into mh_row_scale_, with keep_mh_scale)."""
+        burn_in, n_mcmc, seed, hmc = run
+        data_x, data_y, data_v = data
+        eng, n_test, total_it = self.engine, len(data_x), burn_in + n_mcmc
+        scale_key, scale_attr = ("row_step", "hmc_row_step_") if hmc is not None else ("row_scale", "mh_row_scale_" if keep_mh_scale else None)
+        row_scale = torch.zeros(n_test, device=eng.device, dtype=torch.float32) if scale_attr else None
+        row_mass = torch.zeros((n_test, eng.q), device=eng.device, dtype=torch.float32) if hmc is not None and hmc[3] is not None else None
+        acc_tail = 0.0
+        for (s0, e0) in blocks:
+            x = self._dev(data_x[s0:e0]).reshape(-1)
+            y = self._dev(data_y[s0:e0]).reshape(-1)
+            v = self._dev(data_v[s0:e0])
+            if hmc is not None:
+                out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=hmc[3], **route_kw)
+            else:
+                out = sample(x, y, v, s0)
+            consume(s0, e0, x, out)
+            if row_scale is not None:
+                row_scale[s0:e0] = out[scale_key]
+            if row_mass is not None:
+                row_mass[s0:e0] = out["mass_scale"]
+            acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
+        self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
+        if row_scale is not None:
+            setattr(self, scale_attr, parallel.all_reduce_sum_(row_scale).cpu().numpy())      # disjoint row sets: the sum is the gather
+        if row_mass is not None:
+            self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
+
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
                 bs=10000, verbose=1, diagnose_rows=0, row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None,
                 draw_budget_bytes=None, mass='identity', fused_effects=False):
@@ -557,23 +620,13 @@ class CausalBGM(object):
         chain depends on its own row only, so a rank's shard is sampled in one piece, the result does not depend on ``bs`` or the
         rank count, and ``diagnose_rows`` works.  The scales are left in ``self.mh_row_scale_``."""
         ra_target = self._row_adapt_target(row_adapt)
-        self.mh_row_scale_ = None
-        self.hmc_row_step_ = None
-        self.hmc_row_mass_ = None
-        hmc = None                       # (step size, leapfrog steps, target acceptance rate, mass) of sampler='hmc'
-        if hmc_mod.check_predict_options(sampler, q_sd, row_adapt):
-            hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
-        mass = hmc_mod.check_mass(mass, hmc is not None, True, burn_in)
-        hmc_mod.check_fused(fused_effects, hmc is not None, draw_budget_bytes)
-        if hmc is not None:
-            hmc = hmc + (mass,)
-        assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
-        parallel.check_n_mcmc(n_mcmc)
+        hmc, x_values, _ = self._sampling_options(
+            ("mh_row_scale_", "hmc_row_step_", "hmc_row_mass_"), lambda: hmc_mod.check_predict_options(sampler, q_sd, row_adapt),
+            (step_size, n_leapfrog, mass, burn_in), lambda use_hmc: hmc_mod.check_fused(fused_effects, use_hmc, draw_budget_bytes),
+            alpha, n_mcmc, x_values)
         binary = bool(self._p['binary_treatment'])
         if not binary and x_values is None:
             raise ValueError("For continuous treatment, 'x_values' must not be None. Provide a list or a single treatment value.")
-        if x_values is not None:
-            x_values = np.array([x_values], dtype=float) if np.isscalar(x_values) else np.array(x_values, dtype=float)
         data_x, data_y, data_v = data
         n_test = len(data_x)
         bs = max(1, int(bs))
@@ -584,12 +637,9 @@ class CausalBGM(object):
         if diagnose_rows > 0 and adaptive:
             raise ValueError("predict(diagnose_rows=...) needs a fixed q_sd: with the adaptive scale (q_sd None or <= 0) every block's "
                              "scale schedule depends on the whole block's acceptance and cannot be reproduced from a window of rows")
-        seed = self._next_seed()
-        if verbose:
-            print('MCMC Latent Variable Sampling ...')
+        seed = self._begin_sampling(verbose)
         eng = self.engine
         dev = eng.device
-        total_it = burn_in + n_mcmc
         world, rank = parallel.world_size(), parallel.rank()
         # Row blocks.  A fixed proposal scale makes every chain independent of its block (the Philox stream is keyed by the
         # global row), so each rank samples its contiguous shard in one piece.  With the adaptive scale (q_sd <= 0) the
@@ -606,62 +656,32 @@ class CausalBGM(object):
                 blocks = [(s0, min(s0 + max_rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, max_rows)]
         if hmc is not None:              # the retained draws of a block are kept: blocks within the draw budget (none kept when fused)
             blocks = hmc_mod.predict_blocks(blocks, n_mcmc, eng.q, draw_budget_bytes, fused_effects)
-        acc_tail = 0.0
-        row_scale = torch.zeros(n_test, device=dev, dtype=torch.float32) if (ra_target is not None or hmc is not None) else None
-        row_mass = torch.zeros((n_test, eng.q), device=dev, dtype=torch.float32) if mass is not None else None
         if binary:
             res = torch.zeros((3, n_test), device=dev, dtype=torch.float32)     # mean, lower, upper (this rank's rows filled)
         else:
             sums = torch.zeros((len(x_values), n_mcmc), device=dev, dtype=torch.float64)   # adrf_draw_sums (base.py:660)
-        for (s0, e0) in blocks:
-            x = self._dev(data_x[s0:e0]).reshape(-1)
-            y = self._dev(data_y[s0:e0]).reshape(-1)
-            v = self._dev(data_v[s0:e0])
-            if hmc is not None and fused_effects:      # effects inside the sampler (hmc_sample, effect=), accumulated as below
-                out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=hmc[3],
-                                     effect=_lib.EFFECT_ITE if binary else _lib.EFFECT_ADRF, x_values=x_values, sample_y=sample_y)
-                if row_mass is not None:
-                    row_mass[s0:e0] = out["mass_scale"]
+        # The effect of a block comes out of the sampler (the MH sampler, and HMC with fused_effects) or, on HMC's draws route, out
+        # of engine.effects on the block's draws; either way it is accumulated below.
+        effect_kw = dict(effect=_lib.EFFECT_ITE if binary else _lib.EFFECT_ADRF, x_values=x_values, sample_y=sample_y)
+        from_draws = hmc is not None and not fused_effects
+
+        def sample_mh(x, y, v, s0):
+            return eng.mh_sample(x, y, v, burn_in, n_mcmc, q_sd, seed, row_base=s0, adaptive=adaptive, row_adapt=ra_target, **effect_kw)
+
+        def consume(s0, e0, x, out):
+            if from_draws:
+                draws = out.pop("draws")
                 if binary:
-                    mean, lo, hi = eng.row_mean_quantiles(out["ite"], alpha / 2, 1 - alpha / 2)
-                    res[0, s0:e0], res[1, s0:e0], res[2, s0:e0] = mean, lo, hi
+                    out["ite"] = eng.effects(x, draws, burn_in, seed, sample_y=sample_y, row_base=s0).t().contiguous()      # [rows, n_mcmc]
                 else:
-                    sums += out["adrf"].double() * float(e0 - s0)
-                out["row_scale"] = out["row_step"]
-            elif hmc is not None:        # draws kept, effects from the draws (engine.effects), accumulated as below
-                out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2], mass=hmc[3])
-                if row_mass is not None:
-                    row_mass[s0:e0] = out["mass_scale"]
-                if binary:
-                    ite = eng.effects(x, out["draws"], burn_in, seed, sample_y=sample_y, row_base=s0)          # [n_mcmc, rows]
-                    mean, lo, hi = eng.row_mean_quantiles(ite.t().contiguous(), alpha / 2, 1 - alpha / 2)
-                    res[0, s0:e0], res[1, s0:e0], res[2, s0:e0] = mean, lo, hi
-                else:
-                    adrf = eng.effects(x, out["draws"], burn_in, seed, x_values=x_values, sample_y=sample_y, row_base=s0)
-                    sums += adrf.double() * float(e0 - s0)
-                out["row_scale"] = out["row_step"]
-                del out["draws"]
-            elif binary:
-                out = eng.mh_sample(x, y, v, burn_in, n_mcmc, q_sd, seed, effect=_lib.EFFECT_ITE, sample_y=sample_y,
-                                    row_base=s0, adaptive=adaptive, row_adapt=ra_target)
+                    out["adrf"] = eng.effects(x, draws, burn_in, seed, x_values=x_values, sample_y=sample_y, row_base=s0)
+            if binary:
                 mean, lo, hi = eng.row_mean_quantiles(out["ite"], alpha / 2, 1 - alpha / 2)
                 res[0, s0:e0], res[1, s0:e0], res[2, s0:e0] = mean, lo, hi
             else:
-                out = eng.mh_sample(x, y, v, burn_in, n_mcmc, q_sd, seed, effect=_lib.EFFECT_ADRF, x_values=x_values,
-                                    sample_y=sample_y, row_base=s0, adaptive=adaptive, row_adapt=ra_target)
-                sums += out["adrf"].double() * float(e0 - s0)
-            if row_scale is not None:
-                row_scale[s0:e0] = out["row_scale"]
-            acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
-        self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
-        if row_scale is not None:
-            gathered = parallel.all_reduce_sum_(row_scale).cpu().numpy()      # disjoint row sets: the sum is the gather
-            if hmc is not None:
-                self.hmc_row_step_ = gathered
-                if row_mass is not None:
-                    self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
-            else:
-                self.mh_row_scale_ = gathered
+                sums.add_(out["adrf"].double() * float(e0 - s0))
+        self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, sample=sample_mh, keep_mh_scale=ra_target is not None,
+                            **(dict(want_draws=True) if from_draws else effect_kw))
         if diagnose_rows > 0:
             self._diagnose_rows(data, diagnose_rows, burn_in, n_mcmc, q_sd, seed, row_adapt=ra_target, hmc=hmc)
         if binary:
@@ -692,65 +712,39 @@ class CausalBGM(object):
 
         ``groups`` (int labels [n], optional): ``self.group_dose_response_ = {label: (mean_g, sd_g)}``, the curve of every subgroup
         (causal_hmc.group_dose_response).  Under torch.distributed the rows are sharded by rank and the results gathered."""
-        self.hmc_row_step_ = None
-        self.hmc_row_mass_ = None
-        self.individual_sd_ = None
-        self.group_dose_response_ = None
-        hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
-        mass = hmc_mod.check_mass(mass, True, True, burn_in)
-        hmc_mod.check_individual(bool(self._p['binary_treatment']), x_values, interval, draw_budget_bytes)
-        assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
-        parallel.check_n_mcmc(n_mcmc)
-        x_values = np.array([x_values], dtype=float) if np.isscalar(x_values) else np.array(x_values, dtype=float)
-        data_x, data_y, data_v = data
-        n_test, n_doses = len(data_x), len(x_values)
+        hmc, x_values, _ = self._sampling_options(
+            ("hmc_row_step_", "hmc_row_mass_", "individual_sd_", "group_dose_response_"), None, (step_size, n_leapfrog, mass, burn_in),
+            lambda _: hmc_mod.check_individual(bool(self._p['binary_treatment']), x_values, interval, draw_budget_bytes), alpha, n_mcmc,
+            x_values)
+        n_test = len(data[0])
         if groups is not None:
             hmc_mod.group_dose_response(np.zeros((n_test, 0)), np.zeros((n_test, 0)), groups)      # (the labels' checks, before a device is touched)
-        mean, bounds = self._individual_rows(data_x, data_y, data_v, x_values, alpha, n_mcmc, burn_in, sample_y, hmc, mass, interval,
-                                             draw_budget_bytes, verbose)
+        mean, bounds = self._individual_rows(data, x_values, alpha, (burn_in, n_mcmc, hmc), sample_y, interval, draw_budget_bytes, verbose)
         if groups is not None:
             self.group_dose_response_ = hmc_mod.group_dose_response(mean, self.individual_sd_, groups)
         return mean, bounds
 
-    def _individual_rows(self, data_x, data_y, data_v, x_values, alpha, n_mcmc, burn_in, sample_y, hmc, mass, interval, draw_budget_bytes,
-                         verbose, partial=False):
-        """The row blocks of predict_individual (and of predict_new for a continuous treatment, partial=True: NaN in data_x / data_y
+    def _individual_rows(self, data, x_values, alpha, run, sample_y, interval, draw_budget_bytes, verbose, partial=False):
+        """The row blocks of predict_individual (and of predict_new for a continuous treatment, partial=True: NaN in data's x / y
         marks what a row does not observe): this rank's shard in the blocks of causal_hmc.individual_blocks, every block sampled with
-        the per-row effects inside the kernel, the results gathered over the ranks -> (mean, bounds); sets hmc_row_step_,
-        hmc_row_mass_ and individual_sd_."""
-        n_test, n_doses = len(data_x), len(x_values)
-        seed = self._next_seed()
-        if verbose:
-            print('MCMC Latent Variable Sampling ...')
+        the per-row effects inside the kernel, the results gathered over the ranks -> (mean, bounds); run = (burn_in, n_mcmc, hmc);
+        sets hmc_row_step_, hmc_row_mass_ and individual_sd_."""
+        burn_in, n_mcmc, hmc = run
+        n_test, n_doses = len(data[0]), len(x_values)
+        seed = self._begin_sampling(verbose)
         eng = self.engine
-        dev = eng.device
-        total_it = burn_in + n_mcmc
         lo_r, hi_r = parallel.shard_range(n_test)
         blocks = hmc_mod.individual_blocks([(lo_r, hi_r)] if hi_r > lo_r else [], n_mcmc, n_doses, interval, draw_budget_bytes)
         quantile = interval == 'quantile'
-        res = torch.zeros((4 if quantile else 2, n_test, n_doses), device=dev, dtype=torch.float64)      # mean, sd(, lower, upper): this rank's rows filled
-        row_step = torch.zeros(n_test, device=dev, dtype=torch.float32)
-        row_mass = torch.zeros((n_test, eng.q), device=dev, dtype=torch.float32) if mass is not None else None
-        acc_tail = 0.0
-        for (s0, e0) in blocks:
-            x = self._dev(data_x[s0:e0]).reshape(-1)
-            y = self._dev(data_y[s0:e0]).reshape(-1)
-            v = self._dev(data_v[s0:e0])
-            out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=mass, row_effects=True,
-                                 row_draws=quantile, x_values=x_values, sample_y=sample_y, partial=partial)
+        res = torch.zeros((4 if quantile else 2, n_test, n_doses), device=eng.device, dtype=torch.float64)      # mean, sd(, lower, upper): this rank's rows filled
+
+        def consume(s0, e0, x, out):
             res[0, s0:e0], res[1, s0:e0] = out["row_mean"], out["row_sd"]
             if quantile:
-                _, lo, hi = eng.row_mean_quantiles(out["row_draws"].reshape((e0 - s0) * n_doses, n_mcmc), alpha / 2, 1 - alpha / 2)
+                _, lo, hi = eng.row_mean_quantiles(out.pop("row_draws").reshape((e0 - s0) * n_doses, n_mcmc), alpha / 2, 1 - alpha / 2)
                 res[2, s0:e0], res[3, s0:e0] = lo.reshape(e0 - s0, n_doses).double(), hi.reshape(e0 - s0, n_doses).double()
-                del out["row_draws"]
-            row_step[s0:e0] = out["row_step"]
-            if row_mass is not None:
-                row_mass[s0:e0] = out["mass_scale"]
-            acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
-        self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
-        self.hmc_row_step_ = parallel.all_reduce_sum_(row_step).cpu().numpy()      # disjoint row sets: the sum is the gather
-        if row_mass is not None:
-            self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
+        self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, row_effects=True, row_draws=quantile,
+                            x_values=x_values, sample_y=sample_y, partial=partial)
         res = parallel.all_reduce_sum_(res).cpu().numpy()
         mean, sd = res[0], res[1]
         self.individual_sd_ = sd
@@ -779,49 +773,30 @@ class CausalBGM(object):
         them (sd in ``self.individual_sd_`` [n]); the [rows x n_mcmc] ITE matrix of a block fits ``draw_budget_bytes`` (default
         2 GiB).  A row's result depends on (seed, its global row, its data) only; under torch.distributed the rows are sharded by
         rank and the results gathered."""
-        self.hmc_row_step_ = None
-        self.hmc_row_mass_ = None
-        self.individual_sd_ = None
         binary = bool(self._p['binary_treatment'])
-        hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
-        mass = hmc_mod.check_mass(mass, True, True, burn_in)
-        data_v, data_x, data_y = hmc_mod.check_new(binary, data_v, data_x, x_values, interval, draw_budget_bytes)
-        assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
-        parallel.check_n_mcmc(n_mcmc)
+        hmc, x_values, (data_v, data_x, data_y) = self._sampling_options(
+            ("hmc_row_step_", "hmc_row_mass_", "individual_sd_"), None, (step_size, n_leapfrog, mass, burn_in),
+            lambda _: hmc_mod.check_new(binary, data_v, data_x, x_values, interval, draw_budget_bytes), alpha, n_mcmc,
+            None if binary else x_values)
+        data = (data_x, data_y, data_v)
         if not binary:
-            x_values = np.array([x_values], dtype=float) if np.isscalar(x_values) else np.array(x_values, dtype=float)
-            return self._individual_rows(data_x, data_y, data_v, x_values, alpha, n_mcmc, burn_in, sample_y, hmc, mass, interval,
-                                         draw_budget_bytes, verbose, partial=True)
+            return self._individual_rows(data, x_values, alpha, (burn_in, n_mcmc, hmc), sample_y, interval, draw_budget_bytes, verbose,
+                                         partial=True)
         n_test = len(data_x)
-        seed = self._next_seed()
-        if verbose:
-            print('MCMC Latent Variable Sampling ...')
+        seed = self._begin_sampling(verbose)
         eng = self.engine
-        dev = eng.device
-        total_it = burn_in + n_mcmc
         lo_r, hi_r = parallel.shard_range(n_test)
         rows = hmc_mod.block_rows(n_mcmc, 1, draw_budget_bytes)      # the ITE matrix [rows x n_mcmc] of one block
         blocks = [(s0, min(s0 + rows, hi_r)) for s0 in range(lo_r, hi_r, rows)]
-        res = torch.zeros((4, n_test), device=dev, dtype=torch.float64)      # mean, sd, lower, upper (this rank's rows filled)
-        row_step = torch.zeros(n_test, device=dev, dtype=torch.float32)
-        row_mass = torch.zeros((n_test, eng.q), device=dev, dtype=torch.float32) if mass is not None else None
-        acc_tail = 0.0
-        for (s0, e0) in blocks:
-            x, y, v = self._dev(data_x[s0:e0]).reshape(-1), self._dev(data_y[s0:e0]).reshape(-1), self._dev(data_v[s0:e0])
-            out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=mass,
-                                 effect=_lib.EFFECT_ITE, sample_y=sample_y, partial=True)
-            mean, lo, hi = eng.row_mean_quantiles(out["ite"], alpha / 2, 1 - alpha / 2)
+        res = torch.zeros((4, n_test), device=eng.device, dtype=torch.float64)      # mean, sd, lower, upper (this rank's rows filled)
+
+        def consume(s0, e0, x, out):
+            ite = out.pop("ite")
+            mean, lo, hi = eng.row_mean_quantiles(ite, alpha / 2, 1 - alpha / 2)
             res[0, s0:e0], res[2, s0:e0], res[3, s0:e0] = mean.double(), lo.double(), hi.double()
-            res[1, s0:e0] = out["ite"].double().std(dim=1) if n_mcmc > 1 else 0.0
-            del out["ite"]
-            row_step[s0:e0] = out["row_step"]
-            if row_mass is not None:
-                row_mass[s0:e0] = out["mass_scale"]
-            acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
-        self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
-        self.hmc_row_step_ = parallel.all_reduce_sum_(row_step).cpu().numpy()      # disjoint row sets: the sum is the gather
-        if row_mass is not None:
-            self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
+            res[1, s0:e0] = ite.double().std(dim=1) if n_mcmc > 1 else 0.0
+        self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, effect=_lib.EFFECT_ITE, sample_y=sample_y,
+                            partial=True)
         res = parallel.all_reduce_sum_(res).cpu().numpy()
         mean, sd = res[0], res[1]
         self.individual_sd_ = sd
@@ -852,30 +827,24 @@ class CausalBGM(object):
         is sampled in one piece.  ``sampler='mh'``: the MH sampler call of ``predict`` with a fixed ``q_sd`` and its cap on the ITE
         matrix; the matrix of every block is reduced by label on the device.  Under torch.distributed the rows are sharded by rank
         and the per-draw sums (float64) and counts are all-reduced."""
-        self.average_effects_ = None
-        self.hmc_row_step_ = None
-        self.hmc_row_mass_ = None
-        hmc = None
-        if hmc_mod.check_predict_options(sampler, q_sd, False):
-            hmc = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, hmc_mod.DEFAULT_TARGET)
-        elif q_sd is None or not float(q_sd) > 0:
-            raise ValueError("predict_average needs a fixed q_sd > 0 with sampler='mh': the block-wide adaptive scale depends on "
-                             "predict's bs blocks; got %r" % (q_sd,))
-        mass = hmc_mod.check_mass(mass, hmc is not None, True, burn_in)
+        def use_hmc():
+            if hmc_mod.check_predict_options(sampler, q_sd, False):
+                return True
+            if q_sd is None or not float(q_sd) > 0:
+                raise ValueError("predict_average needs a fixed q_sd > 0 with sampler='mh': the block-wide adaptive scale depends on "
+                                 "predict's bs blocks; got %r" % (q_sd,))
+            return False
+        hmc, _, (group_labels, group_index) = self._sampling_options(
+            ("average_effects_", "hmc_row_step_", "hmc_row_mass_"), use_hmc, (step_size, n_leapfrog, mass, burn_in),
+            lambda _: hmc_mod.check_average(bool(self._p['binary_treatment']), estimand, groups, len(data[0])), alpha, n_mcmc, None)
         data_x, data_y, data_v = data
         n_test = len(data_x)
-        group_labels, group_index = hmc_mod.check_average(bool(self._p['binary_treatment']), estimand, groups, n_test)
-        assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
-        parallel.check_n_mcmc(n_mcmc)
         n_groups = 1 if group_labels is None else len(group_labels)
         n_labels = 2 * n_groups
         labels = hmc_mod.average_labels(group_index, data_x)
-        seed = self._next_seed()
-        if verbose:
-            print('MCMC Latent Variable Sampling ...')
+        seed = self._begin_sampling(verbose)
         eng = self.engine
         dev = eng.device
-        total_it = burn_in + n_mcmc
         lo_r, hi_r = parallel.shard_range(n_test)
         blocks = [(lo_r, hi_r)] if hi_r > lo_r else []
         if hmc is None:                  # the [rows x n_mcmc] ITE matrix of one launch stays below ~32 GiB, as in predict
@@ -883,31 +852,16 @@ class CausalBGM(object):
             blocks = [(s0, min(s0 + max_rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, max_rows)]
         sums = torch.zeros((n_labels, n_mcmc), device=dev, dtype=torch.float64)
         counts = torch.from_numpy(hmc_mod.average_counts(labels[lo_r:hi_r], n_groups)).to(dev)
-        row_step = torch.zeros(n_test, device=dev, dtype=torch.float32) if hmc is not None else None
-        row_mass = torch.zeros((n_test, eng.q), device=dev, dtype=torch.float32) if mass is not None else None
-        acc_tail = 0.0
-        for (s0, e0) in blocks:
-            x = self._dev(data_x[s0:e0]).reshape(-1)
-            y = self._dev(data_y[s0:e0]).reshape(-1)
-            v = self._dev(data_v[s0:e0])
-            if hmc is not None:
-                out = eng.hmc_sample(x, y, v, burn_in, n_mcmc, hmc[0], hmc[1], seed, row_base=s0, adapt=hmc[2], mass=mass,
-                                     effect=_lib.EFFECT_GROUP_ITE, labels=labels[s0:e0], n_labels=n_labels, sample_y=sample_y)
-                sums += out["group_sums"].double()
-                row_step[s0:e0] = out["row_step"]
-                if row_mass is not None:
-                    row_mass[s0:e0] = out["mass_scale"]
-            else:
-                out = eng.mh_sample(x, y, v, burn_in, n_mcmc, q_sd, seed, effect=_lib.EFFECT_ITE, sample_y=sample_y, row_base=s0,
-                                    adaptive=False, row_adapt=None)
-                sums += eng.ite_group_sums(out["ite"], labels[s0:e0], n_labels)
-                del out["ite"]
-            acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
-        self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
-        if row_step is not None:
-            self.hmc_row_step_ = parallel.all_reduce_sum_(row_step).cpu().numpy()      # disjoint row sets: the sum is the gather
-            if row_mass is not None:
-                self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
+
+        def sample_mh(x, y, v, s0):
+            return eng.mh_sample(x, y, v, burn_in, n_mcmc, q_sd, seed, effect=_lib.EFFECT_ITE, sample_y=sample_y, row_base=s0, adaptive=False,
+                                 row_adapt=None)
+
+        def consume(s0, e0, x, out):
+            sums.add_(out["group_sums"].double() if hmc is not None else eng.ite_group_sums(out.pop("ite"), labels[s0:e0], n_labels))
+        # (HMC samples this rank's shard in one block, so its labels are that block's)
+        self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, sample=sample_mh, effect=_lib.EFFECT_GROUP_ITE,
+                            labels=labels[lo_r:hi_r], n_labels=n_labels, sample_y=sample_y)
         sums = parallel.all_reduce_sum_(sums).cpu().numpy().reshape(n_groups, 2, n_mcmc)
         counts = parallel.all_reduce_sum_(counts).cpu().numpy()
         series = hmc_mod.combine_average_effects(sums, counts)

@@ -42,15 +42,20 @@ for f_, src_ in py.items():
 
 
 def wrappers_of(sym):
-    """(file, class, function) triples whose own body mentions the symbol, plus the methods of the same class that call those"""
+    """(file, class, function) triples whose own body mentions the symbol, plus the methods of the same class that call those; a
+    private method (one underscore) passes the search on to its own callers, also where they take it as a bound method"""
     direct = [(f_, c, name) for f_, c, name, seg in FUNCS if re.search(r"\b%s\b" % sym, seg)]
     out = list(direct)
-    for f_, c, name in direct:
+    todo = list(direct)
+    while todo:
+        f_, c, name = todo.pop(0)
         if c is None or name in GENERIC:
             continue
         for f2, c2, n2, seg in FUNCS:
-            if f2 == f_ and c2 == c and n2 != name and re.search(r"self\.%s\(" % re.escape(name), seg) and (f2, c2, n2) not in out:
+            if f2 == f_ and c2 == c and n2 != name and re.search(r"self\.%s[(,]" % re.escape(name), seg) and (f2, c2, n2) not in out:
                 out.append((f2, c2, n2))
+                if n2.startswith("_") and not n2.startswith("__"):
+                    todo.append((f2, c2, n2))
     return out
 
 
