@@ -13,6 +13,13 @@
 #include "bgm_launch.h"
 #include "gx_bgm_host.h"
 
+// the kernel with a number of steps per chain when something of it is asked for, else the plain per-chain step, which takes ka's base
+template <int KTQ, int NTX, int NH, int W, int PREC = 0, bool X4 = false>
+static int bgm_hmc_rows_launch(bool want_traj, int grid, int lds, hipStream_t stream, const BgmTrajHmcKArgs &ka) {
+  return want_traj ? bgm_launch(bgm_hmc_rows_traj_kernel<KTQ, NTX, NH, W, PREC, X4>, grid, W, lds, stream, ka)
+                   : bgm_launch(bgm_hmc_rows_kernel<KTQ, NTX, NH, W, PREC, X4>, grid, W, lds, stream, ka);
+}
+
 // the two entries' common body; traj = nullptr: bgm_bgm_hmc_run_rows
 struct BgmTrajOpts { float max_trajectory; int jitter; int *n_steps; };
 
@@ -52,34 +59,22 @@ static int bgm_hmc_rows_run(const char *fn_, bgm_handle *h, const bgm_hmc_args *
   // the kernels with a number of steps per chain run only when something of it is asked for
   const bool want_traj = traj && (traj->max_trajectory > 0.0f || traj->jitter != 0 || traj->n_steps != nullptr);
   if (want_traj) { ka.max_traj = traj->max_trajectory; ka.jitter = traj->jitter; ka.n_steps = traj->n_steps; }
-  const BgmRowHmcKArgs &kr = ka;      // (the argument block of the kernels without: the base, by value)
   const long long tiles = (a->n + 15) / 16;
   if (s->precision != 0) {      // split precision (bgm_kernels.h, PREC 2), as bgm_bgm_hmc_run
     ka.blob = s->sx3_bias_dev; ka.m = s->sx3_meta; ka.hx3 = s->sx3_dev;
-    constexpr int W = BGM_SX3_WAVES_DEFAULT;
-    const bool x4 = (s->sx3_meta.p & 3) == 0;
-    if (!want_traj)
-      return bgm_bgm_dispatch(BgmSx3Variants{}, s->KTQ, s->NTX, s->NH, "BGM HMC with per-chain steps (split precision)", [&](auto v) {
-        using V = decltype(v);
-        return bgm_launch(x4 ? bgm_hmc_rows_kernel<V::KTQ, 0, V::NH, W, 2, true> : bgm_hmc_rows_kernel<V::KTQ, 0, V::NH, W, 2, false>,
-                          bgm_tile_grid(h, tiles, W), W, s->lds_bytes_sx3, stream, kr);
-      });
-    return bgm_bgm_dispatch(BgmSx3Variants{}, s->KTQ, s->NTX, s->NH, "BGM HMC with per-chain steps and trajectories (split precision)", [&](auto v) {
+    const char *what = want_traj ? "BGM HMC with per-chain steps and trajectories (split precision)" : "BGM HMC with per-chain steps (split precision)";
+    return bgm_bgm_dispatch(BgmSx3Variants{}, s->KTQ, s->NTX, s->NH, what, [&](auto v) {
       using V = decltype(v);
-      return bgm_launch(x4 ? bgm_hmc_rows_traj_kernel<V::KTQ, 0, V::NH, W, 2, true> : bgm_hmc_rows_traj_kernel<V::KTQ, 0, V::NH, W, 2, false>,
-                        bgm_tile_grid(h, tiles, W), W, s->lds_bytes_sx3, stream, ka);
+      constexpr int W = BGM_SX3_WAVES_DEFAULT;
+      const int grid = bgm_tile_grid(h, tiles, W);
+      return (s->sx3_meta.p & 3) == 0 ? bgm_hmc_rows_launch<V::KTQ, 0, V::NH, W, 2, true>(want_traj, grid, s->lds_bytes_sx3, stream, ka)
+                                      : bgm_hmc_rows_launch<V::KTQ, 0, V::NH, W, 2, false>(want_traj, grid, s->lds_bytes_sx3, stream, ka);
     });
   }
-  if (!want_traj)
-    return bgm_bgm_dispatch(s, "BGM HMC with per-chain steps", [&](auto v) {
-      using V = decltype(v);
-      constexpr int W = V::NTX == 0 ? BGM_WAVES_WIDE_HMC : BGM_WAVES;
-      return bgm_launch(bgm_hmc_rows_kernel<V::KTQ, V::NTX, V::NH, W>, bgm_tile_grid(h, tiles, W), W, s->lds_bytes, stream, kr);
-    });
-  return bgm_bgm_dispatch(s, "BGM HMC with per-chain steps and trajectories", [&](auto v) {
+  return bgm_bgm_dispatch(s, want_traj ? "BGM HMC with per-chain steps and trajectories" : "BGM HMC with per-chain steps", [&](auto v) {
     using V = decltype(v);
     constexpr int W = V::NTX == 0 ? BGM_WAVES_WIDE_HMC : BGM_WAVES;
-    return bgm_launch(bgm_hmc_rows_traj_kernel<V::KTQ, V::NTX, V::NH, W>, bgm_tile_grid(h, tiles, W), W, s->lds_bytes, stream, ka);
+    return bgm_hmc_rows_launch<V::KTQ, V::NTX, V::NH, W>(want_traj, bgm_tile_grid(h, tiles, W), s->lds_bytes, stream, ka);
   });
 }
 

@@ -2,174 +2,47 @@
 //
 // replaces: the one scalar step of tfp.mcmc.SimpleStepSizeAdaptation in tfp_mcmc_sampler (bgm/base.py:798-821), opt-in; the transition
 //   is bgm_hmc_kernel's (bgm_kernels.h) and the rule is causal_hmc_kernel's (causal_hmc_kernels.h): the Robbins-Monro table of
-//   row_adapt.py, ONE fp32 multiply and a clamp after the accept decision.
+//   row_adapt.py, ONE fp32 multiply and a clamp after the accept decision.  One body, bgm_hmc_run<..., STEP>, serves both kernels.
 //
-// A sibling of bgm_hmc_kernel rather than a flag on it: the scalar-step instantiations keep their names and their code.  Momentum,
-// accept uniform, initial state, leapfrog order, the non-finite-ratio rule, the tile deal of the streamed variant and the statistics
-// are those of bgm_hmc_kernel line for line; with every step equal and no table the two kernels give the same bits.  What differs:
-// eps is read from step[row] when a wave takes up a row tile (so a second pass reloads it), lives in a VGPR, is updated after the
-// decision of iteration it < n_table and written back with the state.  state, logp, grad and step travel between launches, so a
-// run cut at any iteration is the same run.
+// STEP 1 (bgm_hmc_rows_kernel) adds to the scalar-step transition: eps is read from row_step[row] when a wave takes up a row tile,
+// lives in a VGPR, is updated after the decision of iteration it < n_table and written back with the state.  state, logp, grad and
+// step travel between launches, so a run cut at any iteration is the same run.
+// STEP 2 (bgm_hmc_rows_traj_kernel; opt-in, bgm_bgm_hmc_run_rows_traj) adds a number of leapfrog steps per chain.  From the launch's
+// n_leapfrog = L and the chain's current eps, in fp32 and without a quotient: cap = #{l in 0 .. L-1 : l == 0 or float(l) * eps <
+// max_traj} (max_traj = 0: cap = L), and with jitter L_i = 1 + min(cap - 1, int(u * float(cap))), u = word it & 3 of Philox(row,
+// it >> 2, 1, TAG_HACC) (the accept uniform is call 0), else L_i = cap.  The loop still runs to L for the whole wave -- 16 chains share
+// an MFMA tile and the streamed variants need every wave of the workgroup to make the same number of bgm_logp_grad calls -- but a chain
+// past its L_i drifts by 0 and kicks by 0: it re-evaluates the point of step L_i - 1 and reproduces that step's gradient and log
+// posterior, so what reaches the accept decision is the L_i-step proposal.  L_i depends on (eps, row, it, seed) only, never on z or the
+// momentum; n_steps[row] collects the sum of L_i.
 #pragma once
 #include "bgm_kernels.h"
 
-struct BgmRowHmcKArgs : BgmHmcKArgs {      // (BgmHmcKArgs::step is not read)
+struct BgmRowHmcKArgs : BgmHmcKArgs {      // STEP 1 (BgmHmcKArgs::step is not read)
   float *row_step;           // [n] step size of every chain, in / out
   const float *up, *dn;      // [n_table] factor after the decision of iteration it < n_table (moved / did not), or NULL: fixed steps
   int n_table;
   float s_min, s_max;
 };
-
-template <int KTQ, int NTX, int NH, int WAVES, int PREC = 0, bool X4 = false>
-__global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_kernel(BgmRowHmcKArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const BgmMeta &m = a.m;
-  lds_fill(lds, a.blob, m.lds_resident);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
-  using HS = typename bgm_stream_of<PREC, WAVES, X4>::type;
-  HS hs;
-  if constexpr (PREC >= 1) hs.begin(a.hx3, m, lds);
-  else if constexpr (NTX == 0) hs.begin(a.blob, m, lds);
-  const long long n = a.n, n_tiles = (n + 15) / 16, passes = bgm_block_passes(n_tiles, WAVES);
-  for (long long ps = 0; ps < passes; ++ps) {
-    // (the tile deal of bgm_hmc_kernel: wave-major in the streamed variant, whose tile-less waves only keep the head stream moving)
-    long long tile = NTX == 0 ? (ps * WAVES + wave) * gridDim.x + blockIdx.x : (ps * gridDim.x + blockIdx.x) * WAVES + wave;
-    const bool tile_ok = tile < n_tiles;
-    if (NTX > 0 && !tile_ok) break;
-    if constexpr (NTX == 0) {
-      if (!tile_ok) {
-        const int evals = (a.init ? 1 : 0) + a.n_iters * a.n_leapfrog;
-        const int n_steps = PREC == 0 ? m.ntx : (m.ntx + BGM_X3_STEP - 1) / BGM_X3_STEP + (PREC == 2 ? 2 * ((NH + BGM_X3_STEP - 1) / BGM_X3_STEP) : 0);      // (steps of the stream per evaluation)
-        for (int e = 0; e < evals; ++e)
-          for (int tx = 0; tx < n_steps; ++tx) { hs.fetch(tx + 1 < n_steps ? tx + 1 : 0); hs.commit(); }
-        continue;
-      }
-    }
-    tile = tile_ok ? tile : n_tiles - 1;
-    long long row = tile * 16 + j;
-    const bool ok = tile_ok && row < n;
-    row = row < n ? row : n - 1;
-    const unsigned rowid = (unsigned)(a.row_base + row);
-    BgmX<NTX> xr;
-    f32x4 z[KTQ], gr[KTQ];
-    bgm_load_x<NTX>(a.x, n, m.p, row, g, xr);
-    if constexpr (PREC >= 1) hs.x_valid = false;       // (a new row: nothing of it has been requested ahead)
-    float eps = a.row_step[row];      // (every pass: the rows are new)
-    float lp;
-    if (a.init) {   // initial_state ~ N(0,1)  (bgm/base.py:778), RNG tag 0
-#pragma unroll
-      for (int t = 0; t < KTQ; ++t) {
-        const f32x4 e = box_muller4(philox4x32_10(rowid, 0u, (unsigned)(g + 4 * t), TAG_INIT, a.k0, a.k1));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) z[t][r] = (16 * t + 4 * r + g < m.q) ? e[r] : 0.0f;
-      }
-      bgm_logp_grad<KTQ, NTX, NH, true, PREC, HS>(lds, m, j, g, z, xr, hs, lp, gr);
-    } else {
-      bgm_load_z<KTQ>(a.state, m.q, row, g, z);
-      bgm_load_z<KTQ>(a.grad, m.q, row, g, gr);
-      lp = a.logp[row];
-    }
-    for (int it = a.it_begin; it < a.it_begin + a.n_iters; ++it) {
-      BGM_NO_HOIST();
-      f32x4 mom[KTQ], zc[KTQ], gc[KTQ];
-      float ke0 = 0.0f;
-#pragma unroll
-      for (int t = 0; t < KTQ; ++t) {
-        const f32x4 e = box_muller4(philox4x32_10(rowid, (unsigned)it, (unsigned)(g + 4 * t), TAG_MOM, a.k0, a.k1));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pm = (16 * t + 4 * r + g < m.q) ? e[r] : 0.0f;
-          ke0 = fmaf(pm, pm, ke0);
-          mom[t][r] = fmaf(0.5f * eps, gr[t][r], pm);   // first half kick
-          zc[t][r] = z[t][r];
-        }
-      }
-      ke0 = sum_over_g(ke0);
-      float lpc = lp;
-      for (int l = 0; l < a.n_leapfrog; ++l) {
-        BGM_NO_HOIST();
-#pragma unroll
-        for (int t = 0; t < KTQ; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) zc[t][r] = fmaf(eps, mom[t][r], zc[t][r]);
-        bgm_logp_grad<KTQ, NTX, NH, true, PREC, HS>(lds, m, j, g, zc, xr, hs, lpc, gc, PREC == 0 || l == a.n_leapfrog - 1);
-        const float kick = (l < a.n_leapfrog - 1) ? eps : 0.5f * eps;
-#pragma unroll
-        for (int t = 0; t < KTQ; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mom[t][r] = fmaf(kick, gc[t][r], mom[t][r]);
-      }
-      float ke1 = 0.0f;
-#pragma unroll
-      for (int t = 0; t < KTQ; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ke1 = fmaf(mom[t][r], mom[t][r], ke1);
-      ke1 = sum_over_g(ke1);
-      float log_ratio = -((-lpc + 0.5f * ke1) - (-lp + 0.5f * ke0));
-      log_ratio = (log_ratio == log_ratio && fabsf(log_ratio) != INFINITY) ? log_ratio : -INFINITY;
-      const uint4 w4 = philox4x32_10(rowid, (unsigned)it >> 2, 0u, TAG_HACC, a.k0, a.k1);
-      const unsigned w_ = (it & 2) ? ((it & 1) ? w4.w : w4.z) : ((it & 1) ? w4.y : w4.x);
-      const float u = u01_open(w_);
-      const bool acc = logf(u) < log_ratio;
-#pragma unroll
-      for (int t = 0; t < KTQ; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          z[t][r] = acc ? zc[t][r] : z[t][r];
-          gr[t][r] = acc ? gc[t][r] : gr[t][r];
-        }
-      lp = acc ? lpc : lp;
-      if (a.up != nullptr && it < a.n_table) eps = fminf(fmaxf(eps * (acc ? a.up : a.dn)[it], a.s_min), a.s_max);
-      // per-iteration statistics of the acceptance report
-      {
-        float pa = (ok && g == 0) ? expf(fminf(log_ratio, 0.0f)) : 0.0f;
-        for (int off = 8; off > 0; off >>= 1) pa += __shfl_xor(pa, off);
-        const unsigned cnt = (unsigned)__popcll(__ballot(acc && ok && g == 0));
-        if (lane == 0) {
-          if (a.acc_prob_sum) atomicAdd(a.acc_prob_sum + it, (double)pa);
-          if (a.acc_count) atomicAdd(a.acc_count + it, cnt);
-        }
-      }
-      if (a.draws != nullptr && it >= a.burn_in && ok)
-        bgm_store_z<KTQ>(a.draws + (long long)(it - a.burn_in) * n * m.q, m.q, row, g, z);
-    }
-    if (ok) {
-      bgm_store_z<KTQ>(a.state, m.q, row, g, z);
-      bgm_store_z<KTQ>(a.grad, m.q, row, g, gr);
-      if (g == 0) { a.logp[row] = lp; a.row_step[row] = eps; }
-    }
-  }
-}
-
-// ---- a number of leapfrog steps per chain (opt-in, bgm_bgm_hmc_run_rows_traj).  From the launch's n_leapfrog = L and the chain's
-// current eps, in fp32 and without a quotient: cap = #{l in 0 .. L-1 : l == 0 or float(l) * eps < max_traj} (max_traj = 0: cap = L), and
-// with jitter L_i = 1 + min(cap - 1, int(u * float(cap))), u = word it & 3 of Philox(row, it >> 2, 1, TAG_HACC) (the accept uniform is
-// call 0), else L_i = cap.  The loop still runs to L for the whole wave -- 16 chains share an MFMA tile and the streamed variants need
-// every wave of the workgroup to make the same number of bgm_logp_grad calls -- but a chain past its L_i drifts by 0 and kicks by 0: it
-// re-evaluates the point of step L_i - 1 and reproduces that step's gradient and log posterior, so what reaches the accept decision is
-// the L_i-step proposal.  L_i depends on (eps, row, it, seed) only, never on z or the momentum.
-// A sibling of bgm_hmc_rows_kernel, as that one is of bgm_hmc_kernel, and for its reason: through a shared body the instantiations
-// above came out of the compiler with other instructions, and the plain per-chain step is to pay nothing.  Everything but the lines
-// on li, n_taken, drift and kick is bgm_hmc_rows_kernel line for line; with max_traj = 0 and no jitter the two give the same bits.
-struct BgmTrajHmcKArgs : BgmRowHmcKArgs {
+struct BgmTrajHmcKArgs : BgmRowHmcKArgs {  // STEP 2
   float max_traj;            // cap on eps x L_i (> 0), or 0: none
   int jitter;                // 0 / 1: L_i uniform on 1 .. cap, drawn per chain and iteration
   int *n_steps;              // [n] += the leapfrog steps the chain took over this launch's iterations, or NULL
 };
 
-template <int KTQ, int NTX, int NH, int WAVES, int PREC = 0, bool X4 = false>
-__global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_traj_kernel(BgmTrajHmcKArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+// The transition of the two kernels below, once: bgm_hmc_kernel's (bgm_kernels.h) line for line, and under if constexpr what a rule adds.
+// STEP 1 (BgmRowHmcKArgs): the step per chain.  STEP 2 (BgmTrajHmcKArgs): STEP 1 and the number of leapfrog steps per chain -- the
+// lines on li, n_taken, drift, kick and want_lp, and n_steps written back.  With every step equal and no table STEP 1 gives
+// bgm_hmc_kernel's bits; with max_traj = 0 and no jitter STEP 2 gives STEP 1's.
+template <int KTQ, int NTX, int NH, int WAVES, int PREC, bool X4, int STEP, class Args, class HS>
+__device__ __forceinline__ void bgm_hmc_run(Args a, float *lds, HS &hs) {
   const BgmMeta &m = a.m;
-  lds_fill(lds, a.blob, m.lds_resident);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
-  using HS = typename bgm_stream_of<PREC, WAVES, X4>::type;
-  HS hs;
-  if constexpr (PREC >= 1) hs.begin(a.hx3, m, lds);
-  else if constexpr (NTX == 0) hs.begin(a.blob, m, lds);
   const long long n = a.n, n_tiles = (n + 15) / 16, passes = bgm_block_passes(n_tiles, WAVES);
   for (long long ps = 0; ps < passes; ++ps) {
-    // (the tile deal of bgm_hmc_kernel: wave-major in the streamed variant, whose tile-less waves only keep the head stream moving)
+    // Wide variant: tiles are dealt wave-major (wave w of every block before wave w + 1 of any), so the tiles of a partly filled last
+    // round spread over ALL blocks as whole waves; a wave without a tile only keeps the block's head stream moving (no matrix work).
+    // The round then costs what its ceil(active waves / 4) waves per SIMD cost instead of a full round on some CUs.
     long long tile = NTX == 0 ? (ps * WAVES + wave) * gridDim.x + blockIdx.x : (ps * gridDim.x + blockIdx.x) * WAVES + wave;
     const bool tile_ok = tile < n_tiles;
     if (NTX > 0 && !tile_ok) break;
@@ -193,7 +66,7 @@ __global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_traj_kernel(BgmTrajHm
     if constexpr (PREC >= 1) hs.x_valid = false;       // (a new row: nothing of it has been requested ahead)
     float eps = a.row_step[row];      // (every pass: the rows are new)
     float lp;
-    int n_taken = 0;      // (leapfrog steps of this chain over the launch)
+    int n_taken = 0;      // (STEP 2: leapfrog steps of this chain over the launch)
     if (a.init) {   // initial_state ~ N(0,1)  (bgm/base.py:778), RNG tag 0
 #pragma unroll
       for (int t = 0; t < KTQ; ++t) {
@@ -224,28 +97,34 @@ __global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_traj_kernel(BgmTrajHm
       }
       ke0 = sum_over_g(ke0);
       float lpc = lp;
-      int li = a.n_leapfrog;      // (this chain's steps of this transition, from eps as it stands)
-      if (a.max_traj > 0.0f) {
-        li = 1;
-        for (int l = 1; l < a.n_leapfrog; ++l) li += ((float)l * eps < a.max_traj) ? 1 : 0;
+      int li = a.n_leapfrog;      // (STEP 2: this chain's steps of this transition, from eps as it stands)
+      if constexpr (STEP >= 2) {
+        if (a.max_traj > 0.0f) {
+          li = 1;
+          for (int l = 1; l < a.n_leapfrog; ++l) li += ((float)l * eps < a.max_traj) ? 1 : 0;
+        }
+        if (a.jitter) {
+          const uint4 j4 = philox4x32_10(rowid, (unsigned)it >> 2, 1u, TAG_HACC, a.k0, a.k1);
+          const unsigned jw = (it & 2) ? ((it & 1) ? j4.w : j4.z) : ((it & 1) ? j4.y : j4.x);
+          const int k = (int)(u01_open(jw) * (float)li);
+          li = 1 + (k < li - 1 ? k : li - 1);
+        }
+        n_taken += li;
       }
-      if (a.jitter) {
-        const uint4 j4 = philox4x32_10(rowid, (unsigned)it >> 2, 1u, TAG_HACC, a.k0, a.k1);
-        const unsigned jw = (it & 2) ? ((it & 1) ? j4.w : j4.z) : ((it & 1) ? j4.y : j4.x);
-        const int k = (int)(u01_open(jw) * (float)li);
-        li = 1 + (k < li - 1 ? k : li - 1);
-      }
-      n_taken += li;
       for (int l = 0; l < a.n_leapfrog; ++l) {
         BGM_NO_HOIST();
-        const float drift = l < li ? eps : 0.0f;      // (past L_i: the same point again)
+        float drift = eps;
+        if constexpr (STEP >= 2) drift = l < li ? eps : 0.0f;      // (past L_i: the same point again)
 #pragma unroll
         for (int t = 0; t < KTQ; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) zc[t][r] = fmaf(drift, mom[t][r], zc[t][r]);
-        // (the value of the log posterior from this chain's last step on; its half kick there, none after)
-        bgm_logp_grad<KTQ, NTX, NH, true, PREC, HS>(lds, m, j, g, zc, xr, hs, lpc, gc, PREC == 0 || l >= li - 1);
-        const float kick = (l < li - 1) ? eps : (l == li - 1) ? 0.5f * eps : 0.0f;
+        // (STEP 2: the value of the log posterior from this chain's last step on; its half kick there, none after)
+        bool want_lp = PREC == 0 || l == a.n_leapfrog - 1;
+        if constexpr (STEP >= 2) want_lp = PREC == 0 || l >= li - 1;
+        bgm_logp_grad<KTQ, NTX, NH, true, PREC, HS>(lds, m, j, g, zc, xr, hs, lpc, gc, want_lp);
+        float kick = (l < a.n_leapfrog - 1) ? eps : 0.5f * eps;
+        if constexpr (STEP >= 2) kick = (l < li - 1) ? eps : (l == li - 1) ? 0.5f * eps : 0.0f;
 #pragma unroll
         for (int t = 0; t < KTQ; ++t)
 #pragma unroll
@@ -272,7 +151,7 @@ __global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_traj_kernel(BgmTrajHm
         }
       lp = acc ? lpc : lp;
       if (a.up != nullptr && it < a.n_table) eps = fminf(fmaxf(eps * (acc ? a.up : a.dn)[it], a.s_min), a.s_max);
-      // per-iteration statistics of the acceptance report
+      // per-iteration statistics for SimpleStepSizeAdaptation and the acceptance report
       {
         float pa = (ok && g == 0) ? expf(fminf(log_ratio, 0.0f)) : 0.0f;
         for (int off = 8; off > 0; off >>= 1) pa += __shfl_xor(pa, off);
@@ -289,7 +168,25 @@ __global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_traj_kernel(BgmTrajHm
       bgm_store_z<KTQ>(a.state, m.q, row, g, z);
       bgm_store_z<KTQ>(a.grad, m.q, row, g, gr);
       if (g == 0) { a.logp[row] = lp; a.row_step[row] = eps; }
-      if (g == 0 && a.n_steps != nullptr) a.n_steps[row] += n_taken;
+      if constexpr (STEP >= 2)
+        if (g == 0 && a.n_steps != nullptr) a.n_steps[row] += n_taken;
     }
   }
 }
+
+// The text of the two kernels.  The LDS fill and the head stream's begin stay in the kernel itself: they read blockDim.x, and hipcc
+// folds that read to the workgroup size only where it meets it in a kernel before the first common-subexpression pass -- inside
+// bgm_hmc_run the streamed fp32 kernels kept a select on the workgroup id in the stream's fetch loops.
+#define BGM_HMC_KERNEL(STEP)                                                   \
+  extern __shared__ __attribute__((aligned(16))) float lds[];                  \
+  lds_fill(lds, a.blob, a.m.lds_resident);                                     \
+  typename bgm_stream_of<PREC, WAVES, X4>::type hs;                            \
+  if constexpr (PREC >= 1) hs.begin(a.hx3, a.m, lds);                          \
+  else if constexpr (NTX == 0) hs.begin(a.blob, a.m, lds);                     \
+  bgm_hmc_run<KTQ, NTX, NH, WAVES, PREC, X4, STEP>(a, lds, hs);
+
+template <int KTQ, int NTX, int NH, int WAVES, int PREC = 0, bool X4 = false>
+__global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_kernel(BgmRowHmcKArgs a) { BGM_HMC_KERNEL(1) }
+
+template <int KTQ, int NTX, int NH, int WAVES, int PREC = 0, bool X4 = false>
+__global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_traj_kernel(BgmTrajHmcKArgs a) { BGM_HMC_KERNEL(2) }

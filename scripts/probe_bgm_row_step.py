@@ -21,11 +21,11 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
-def _engine(p, prec, q=10):
+def _engine(p, prec, q=10, nh=5):
     from bayesgm_amd.engine import BgmEngine
     from oracle import bgm as OB
-    m = OB.init_model(11, q, p)
-    eng = BgmEngine(p, q)
+    m = OB.init_model(11, q, p, g_units=(64,) * nh)
+    eng = BgmEngine(p, q, g_units=[64] * nh)
     eng.set_weights(m["g"])
     eng.set_precision(prec)
     return eng
