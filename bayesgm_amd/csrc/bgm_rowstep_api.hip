@@ -5,11 +5,9 @@
 // or the step count is asked for, so the plain per-chain step runs the kernels it ran before.  The default path
 // (bgm_api.hip, bgm_bgm_hmc_run + bgm_bgm_hmc_adapt) is untouched.
 // replaces: the shared step of tfp.mcmc.SimpleStepSizeAdaptation in tfp_mcmc_sampler (bgm/base.py:798-821), opt-in.
-#include <cmath>
 #include <string>
 
-#include "bgm_host.h"
-#include "bgm_rowstep_kernels.h"
+#include "bgm_rowstep_host.h"
 #include "bgm_launch.h"
 #include "gx_bgm_host.h"
 
@@ -21,25 +19,12 @@ static int bgm_hmc_rows_launch(bool want_traj, int grid, int lds, hipStream_t st
 }
 
 // the two entries' common body; traj = nullptr: bgm_bgm_hmc_run_rows
-struct BgmTrajOpts { float max_trajectory; int jitter; int *n_steps; };
-
 static int bgm_hmc_rows_run(const char *fn_, bgm_handle *h, const bgm_hmc_args *a, const float *up_dev, const float *dn_dev, int32_t n_table,
                             float s_min, float s_max, const BgmTrajOpts *traj, void *stream_) {
   const std::string fn = std::string(fn_) + ": ";
-  if (!h || !h->bgm_state || !bst(h)->configured) { bgm_set_error(fn + "not configured"); return BGM_E_STATE; }
-  if (!a) { bgm_set_error(fn + "NULL args"); return BGM_E_INVALID; }
-  if ((up_dev == nullptr) != (dn_dev == nullptr)) { bgm_set_error(fn + "up_dev and dn_dev must both be given or both be NULL"); return BGM_E_INVALID; }
-  if (n_table < 0) { bgm_set_error(fn + "n_table must be >= 0"); return BGM_E_INVALID; }
-  if (!(s_min > 0.0f) || !(s_max >= s_min) || !std::isfinite(s_max)) { bgm_set_error(fn + "the clamp needs 0 < s_min <= s_max < inf"); return BGM_E_INVALID; }
-  if (traj) {
-    if (!(traj->max_trajectory >= 0.0f) || !std::isfinite(traj->max_trajectory)) { bgm_set_error(fn + "max_trajectory must be 0 (no cap) or a finite number > 0"); return BGM_E_INVALID; }
-    if (traj->jitter != 0 && traj->jitter != 1) { bgm_set_error(fn + "jitter must be 0 or 1"); return BGM_E_INVALID; }
-  }
-  if (a->n <= 0 || a->n_iters <= 0) return BGM_OK;
-  const char *null_arg = !a->x_dev ? "x_dev" : !a->state_dev ? "state_dev" : !a->logp_dev ? "logp_dev" : !a->grad_dev ? "grad_dev" : !a->step_dev ? "step_dev" : nullptr;
-  if (null_arg) { bgm_set_error(fn + "NULL pointer " + null_arg); return BGM_E_INVALID; }
-  if (a->n_leapfrog < 1) { bgm_set_error(fn + "n_leapfrog (num_leapfrog_steps) must be >= 1"); return BGM_E_INVALID; }
-  if (a->row_base < 0 || a->row_base + a->n > 0xFFFFFFFFll) { bgm_set_error(fn + "row_base + n: row index exceeds the 32-bit RNG counter"); return BGM_E_INVALID; }
+  bool go;
+  int rc = bgm_hmc_rows_check(fn, h, a, up_dev, dn_dev, n_table, s_min, s_max, traj, &go);
+  if (rc || !go) return rc;
   BgmState *s = bst(h);
   if (gxb_wanted(s)) {
     bgm_set_error(fn + "the per-chain step exists for trunks [64] x 3 / [64] x 5 with z_dim <= 16; this shape runs on the "
@@ -48,17 +33,12 @@ static int bgm_hmc_rows_run(const char *fn_, bgm_handle *h, const bgm_hmc_args *
   }
   hipStream_t stream = (hipStream_t)stream_;
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  int rc = bgm_bgm_build_blob(h, stream);
+  rc = bgm_bgm_build_blob(h, stream);
   if (rc) return rc;
-  BgmTrajHmcKArgs ka{};
-  bgm_hmc_fill(ka, a);
-  ka.step = nullptr;
-  ka.row_step = const_cast<float *>(a->step_dev);      // (in / out here: [n] steps)
-  ka.up = up_dev; ka.dn = dn_dev; ka.n_table = up_dev ? n_table : 0; ka.s_min = s_min; ka.s_max = s_max;
-  ka.blob = s->blob_dev; ka.m = s->meta;
   // the kernels with a number of steps per chain run only when something of it is asked for
   const bool want_traj = traj && (traj->max_trajectory > 0.0f || traj->jitter != 0 || traj->n_steps != nullptr);
-  if (want_traj) { ka.max_traj = traj->max_trajectory; ka.jitter = traj->jitter; ka.n_steps = traj->n_steps; }
+  BgmTrajHmcKArgs ka{};
+  bgm_hmc_rows_fill(ka, s, a, up_dev, dn_dev, n_table, s_min, s_max, traj, want_traj);
   const long long tiles = (a->n + 15) / 16;
   if (s->precision != 0) {      // split precision (bgm_kernels.h, PREC 2), as bgm_bgm_hmc_run
     ka.blob = s->sx3_bias_dev; ka.m = s->sx3_meta; ka.hx3 = s->sx3_dev;

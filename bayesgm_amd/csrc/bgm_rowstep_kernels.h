@@ -2,7 +2,7 @@
 //
 // replaces: the one scalar step of tfp.mcmc.SimpleStepSizeAdaptation in tfp_mcmc_sampler (bgm/base.py:798-821), opt-in; the transition
 //   is bgm_hmc_kernel's (bgm_kernels.h) and the rule is causal_hmc_kernel's (causal_hmc_kernels.h): the Robbins-Monro table of
-//   row_adapt.py, ONE fp32 multiply and a clamp after the accept decision.  One body, bgm_hmc_run<..., STEP>, serves both kernels.
+//   row_adapt.py, ONE fp32 multiply and a clamp after the accept decision.  One body, bgm_hmc_run<..., STEP>, serves the three kernels.
 //
 // STEP 1 (bgm_hmc_rows_kernel) adds to the scalar-step transition: eps is read from row_step[row] when a wave takes up a row tile,
 // lives in a VGPR, is updated after the decision of iteration it < n_table and written back with the state.  state, logp, grad and
@@ -15,6 +15,9 @@
 // past its L_i drifts by 0 and kicks by 0: it re-evaluates the point of step L_i - 1 and reproduces that step's gradient and log
 // posterior, so what reaches the accept decision is the L_i-step proposal.  L_i depends on (eps, row, it, seed) only, never on z or the
 // momentum; n_steps[row] collects the sum of L_i.
+// STEP 3 (bgm_hmc_rows_impute_kernel; opt-in, bgm_bgm_hmc_run_rows_impute, fp32) adds to STEP 2 a decode pass after the decision of every
+// retained iteration: the predictive value of every missing cell of the state the chain is left in, summed into shifted moments per
+// (row, cell) -- bgm_impute_decode below.  The chain itself is STEP 2's (STEP 1's with the trajectory options off), bit for bit.
 #pragma once
 #include "bgm_kernels.h"
 
@@ -29,11 +32,111 @@ struct BgmTrajHmcKArgs : BgmRowHmcKArgs {  // STEP 2
   int jitter;                // 0 / 1: L_i uniform on 1 .. cap, drawn per chain and iteration
   int *n_steps;              // [n] += the leapfrog steps the chain took over this launch's iterations, or NULL
 };
+struct BgmImputeHmcKArgs : BgmTrajHmcKArgs {  // STEP 3
+  float *moments;            // [3][n][p]: ref (the predictive value at retained draw 0), sum (x - ref), sum (x - ref)^2; missing cells only
+  float *cells;              // [(row * k_slots + slot) * n_keep + d] as bgm_predict_kernel's, or NULL
+  const int *slot;           // [n x p] (read only with cells)
+  int k_slots, n_keep;
+  int add_noise;             // 0: the head's mean instead of a draw
+};
 
-// The transition of the two kernels below, once: bgm_hmc_kernel's (bgm_kernels.h) line for line, and under if constexpr what a rule adds.
+// STEP 3: the predictive value of every MISSING cell of the state a retained transition ends on, summarised where it is made.  The
+// trunk, the head tile and the noise are bgm_predict_kernel's (bgm_kernels.h) -- copied, not shared: that kernel's lambda also serves
+// full / var_full and its code object must stay what it is -- with Philox counter (row, it, 4 tx + g, TAG_XNOISE), it = burn_in + d, so a
+// value is bit for bit what bgm_bgm_predict_draws makes of the stored draw d.  Lane (j, g), register r owns cell c = 16 tx + 4 g + r of
+// row j and no other lane touches it: plain loads and stores.  Shifted sums as in causal_hmc_rowfx_kernels.h: plane 0 holds the value at
+// it == burn_in, planes 1 / 2 the sums of (x - ref) and (x - ref)^2 over the retained iterations, so launches cut anywhere add up to the
+// same bits.  Streamed variant: one walk of the head stream exactly as a gradient evaluation makes it, by EVERY wave of the workgroup.
+template <int KTQ, int NTX, int NH, class HS>
+__device__ __forceinline__ void bgm_impute_decode(const BgmImputeHmcKArgs &a, const float *lds, HS &hs, int j, int g, const f32x4 (&z)[KTQ],
+                                                  const BgmX<NTX> &xs, long long row, unsigned rowid, bool ok, int it) {
+  const BgmMeta &m = a.m;
+  f32x4 h[4], h2[4];
+  bias17<4>(lds + m.b1, g, h);
+  fwd17<KTQ, 4>(lds + m.w1, j, g, z, h);
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h[t][r] = lrelu(h[t][r]);
+  for (int l = 1; l < NH; ++l) {
+    BGM_NO_HOIST();
+    bias17<4>(lds + m.bh + (l - 1) * 64, g, h2);
+    fwd17<4, 4>(lds + m.wh + (l - 1) * (4 * 64 * 17), j, g, h, h2);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) h[t][r] = lrelu(h2[t][r]);
+  }
+  const long long plane = a.n * (long long)m.p;
+  auto head = [&](int tx, const float *wl, f32x4 xv) {
+    // (g and the data values do not change over the iterations: without this empty asm statement the column tests, the missing-cell
+    // tests, the cell addresses and the first Philox round of every tile are formed once at kernel entry and stay live -- DESIGN 4aa)
+    asm volatile("" : "+v"(g), "+v"(xv));
+    const long long cell0 = row * (long long)m.p + 16 * tx + 4 * g;
+    // the tile's loads first, all of them and ahead of the head product, then the arithmetic, then the stores: a cell at a time every
+    // wave waits out three dependent round trips to memory per cell (measured: the decode then costs 2.5 gradient evaluations at p = 500)
+    float *mo = a.moments + cell0;
+    const bool first = it == a.burn_in;
+    bool mine[4];
+    float ref[4], s1[4], s2[4];
+    int sl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      mine[r] = ok && 16 * tx + 4 * g + r < m.p && xv[r] != xv[r];      // (NaN = missing; an observed cell and a column beyond p are never touched)
+      ref[r] = s1[r] = s2[r] = 0.0f;
+      sl[r] = -1;
+      if (mine[r] && !first) { ref[r] = mo[r]; s1[r] = mo[plane + r]; s2[r] = mo[2 * plane + r]; }
+      if (mine[r] && a.cells != nullptr) sl[r] = a.slot[cell0 + r];
+    }
+    f32x4 ms[2];
+    ms[0] = *reinterpret_cast<const f32x4 *>(lds + m.bhd + 16 * tx + 4 * g);
+    ms[1] = *reinterpret_cast<const f32x4 *>(lds + m.bhd + 16 * (m.ntx + tx) + 4 * g);
+    heads_fwd17(wl, j, g, h, ms);
+    const f32x4 e = box_muller4(philox4x32_10(rowid, (unsigned)it, (unsigned)(4 * tx + g), TAG_XNOISE, a.k0, a.k1));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float v = softplus_f(ms[1][r]) + BGM_EPS;
+      const float xp = a.add_noise ? fmaf(__builtin_sqrtf(v), e[r], ms[0][r]) : ms[0][r];
+      if (mine[r]) {
+        if (first) {
+          mo[r] = xp; mo[plane + r] = 0.0f; mo[2 * plane + r] = 0.0f;
+        } else {
+          const float d = xp - ref[r];
+          mo[plane + r] = s1[r] + d;
+          mo[2 * plane + r] = fmaf(d, d, s2[r]);
+        }
+        if (sl[r] >= 0) a.cells[(row * (long long)a.k_slots + sl[r]) * a.n_keep + (it - a.burn_in)] = xp;
+      }
+    }
+  };
+  if constexpr (NTX > 0) {
+#pragma unroll
+    for (int tx = 0; tx < NTX; ++tx) {
+      BGM_NO_HOIST();
+      head(tx, lds + m.whd + tx * BGM_PAIR, xs.r[tx]);
+    }
+  } else {
+#pragma unroll 1
+    for (int tx = 0; tx < m.ntx; ++tx) {      // (tile 0 is current on entry and again on exit, as around bgm_logp_grad)
+      BGM_NO_HOIST();
+      hs.fetch(tx + 1 < m.ntx ? tx + 1 : 0);
+      f32x4 xv;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int c = 16 * tx + 4 * g + r;
+        xv[r] = (c < m.p) ? xs.row[c] : 0.0f;
+      }
+      head(tx, hs.tile(), xv);
+      hs.commit();
+    }
+  }
+}
+
+// The transition of the three kernels below, once: bgm_hmc_kernel's (bgm_kernels.h) line for line, and under if constexpr what a rule adds.
 // STEP 1 (BgmRowHmcKArgs): the step per chain.  STEP 2 (BgmTrajHmcKArgs): STEP 1 and the number of leapfrog steps per chain -- the
 // lines on li, n_taken, drift, kick and want_lp, and n_steps written back.  With every step equal and no table STEP 1 gives
-// bgm_hmc_kernel's bits; with max_traj = 0 and no jitter STEP 2 gives STEP 1's.
+// bgm_hmc_kernel's bits; with max_traj = 0 and no jitter STEP 2 gives STEP 1's.  STEP 3 (BgmImputeHmcKArgs): STEP 2 and the decode pass of
+// bgm_impute_decode after the decision of every retained iteration; the chain is STEP 2's.
 template <int KTQ, int NTX, int NH, int WAVES, int PREC, bool X4, int STEP, class Args, class HS>
 __device__ __forceinline__ void bgm_hmc_run(Args a, float *lds, HS &hs) {
   const BgmMeta &m = a.m;
@@ -48,7 +151,11 @@ __device__ __forceinline__ void bgm_hmc_run(Args a, float *lds, HS &hs) {
     if (NTX > 0 && !tile_ok) break;
     if constexpr (NTX == 0) {
       if (!tile_ok) {
-        const int evals = (a.init ? 1 : 0) + a.n_iters * a.n_leapfrog;
+        int evals = (a.init ? 1 : 0) + a.n_iters * a.n_leapfrog;
+        if constexpr (STEP >= 3) {      // (one more walk of the stream per retained iteration of this launch: the decode pass)
+          const int first = a.it_begin > a.burn_in ? a.it_begin : a.burn_in, kept = a.it_begin + a.n_iters - first;
+          evals += kept > 0 ? kept : 0;
+        }
         const int n_steps = PREC == 0 ? m.ntx : (m.ntx + BGM_X3_STEP - 1) / BGM_X3_STEP + (PREC == 2 ? 2 * ((NH + BGM_X3_STEP - 1) / BGM_X3_STEP) : 0);      // (steps of the stream per evaluation)
         for (int e = 0; e < evals; ++e)
           for (int tx = 0; tx < n_steps; ++tx) { hs.fetch(tx + 1 < n_steps ? tx + 1 : 0); hs.commit(); }
@@ -163,6 +270,9 @@ __device__ __forceinline__ void bgm_hmc_run(Args a, float *lds, HS &hs) {
       }
       if (a.draws != nullptr && it >= a.burn_in && ok)
         bgm_store_z<KTQ>(a.draws + (long long)(it - a.burn_in) * n * m.q, m.q, row, g, z);
+      if constexpr (STEP >= 3) {      // (mom, zc and gc are dead here; it >= burn_in is the same for every wave of the launch)
+        if (it >= a.burn_in) bgm_impute_decode<KTQ, NTX, NH>(a, lds, hs, j, g, z, xr, row, rowid, ok, it);
+      }
     }
     if (ok) {
       bgm_store_z<KTQ>(a.state, m.q, row, g, z);
@@ -174,7 +284,7 @@ __device__ __forceinline__ void bgm_hmc_run(Args a, float *lds, HS &hs) {
   }
 }
 
-// The text of the two kernels.  The LDS fill and the head stream's begin stay in the kernel itself: they read blockDim.x, and hipcc
+// The text of the kernels.  The LDS fill and the head stream's begin stay in the kernel itself: they read blockDim.x, and hipcc
 // folds that read to the workgroup size only where it meets it in a kernel before the first common-subexpression pass -- inside
 // bgm_hmc_run the streamed fp32 kernels kept a select on the workgroup id in the stream's fetch loops.
 #define BGM_HMC_KERNEL(STEP)                                                   \
@@ -190,3 +300,11 @@ __global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_kernel(BgmRowHmcKArgs
 
 template <int KTQ, int NTX, int NH, int WAVES, int PREC = 0, bool X4 = false>
 __global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_traj_kernel(BgmTrajHmcKArgs a) { BGM_HMC_KERNEL(2) }
+
+// fp32 only (instantiated in bgm_impute_api.hip)
+template <int KTQ, int NTX, int NH, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_impute_kernel(BgmImputeHmcKArgs a) {
+  constexpr int PREC = 0;
+  constexpr bool X4 = false;
+  BGM_HMC_KERNEL(3)
+}

@@ -884,9 +884,15 @@ class BgmEngine(object):
 
     def hmc_run_rows(self, x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False, row_base=0, up=None,
                      dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_prob=None, acc_count=None, draws=None, max_trajectory=None, jitter=False,
-                     n_steps=None):
+                     n_steps=None, moments=None, cells=None, slot=None, k_slots=0, n_keep=None, add_noise=True):
         """hmc_run with a step size per chain (bgm_bgm_hmc_run_rows): step float32 [n], in / out; up / dn: the factor tables of
         row_adapt.row_adapt_factors on the device (None: the steps stay as given).
+
+        moments (opt-in, bgm_bgm_hmc_run_rows_impute, fp32): float32 [3, n, p], in / out.  Every iteration it >= burn_in decodes the
+        state it ends on and keeps, for the NaN cells of x only, plane 0 = the predictive value at it == burn_in, plane 1 += x - ref,
+        plane 2 += (x - ref)^2; nothing else of the planes is written.  cells float32 [n * k_slots, n_keep] with slot int32 [n, p]:
+        the values themselves as well, in predict_draws' layout.  n_keep: the retained iterations of the whole run (default: those of
+        this call).  The chain is the one the call makes without these arguments, bit for bit.
 
         max_trajectory / jitter / n_steps (opt-in, bgm_bgm_hmc_run_rows_traj): a number of leapfrog steps per chain, from the chain's
         own step -- capped so that step x steps stays below max_trajectory (row_adapt.leapfrog_cap), drawn uniformly from 1 .. cap
@@ -894,6 +900,29 @@ class BgmEngine(object):
         n_leapfrog evaluations: the option buys mixing, not time."""
         a = self._hmc_args(x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, acc_prob, acc_count,
                            draws)
+        if moments is not None or cells is not None:
+            if moments is None:
+                raise ValueError("hmc_run_rows: cells needs moments (the fused imputation, bgm_bgm_hmc_run_rows_impute)")
+            try:
+                T = 0.0 if max_trajectory is None else float(max_trajectory)
+                jit = int(jitter)
+            except (TypeError, ValueError):
+                raise ValueError("hmc_run_rows: max_trajectory must be None or a number and jitter a bool; got %r, %r" % (max_trajectory, jitter))
+            n, p = x.shape
+            if moments.dtype != torch.float32 or tuple(moments.shape) != (3, n, p) or not moments.is_contiguous():
+                raise ValueError("hmc_run_rows: moments must be a contiguous float32 tensor [3, n, p] = [3, %d, %d]; got %s %s"
+                                 % (n, p, moments.dtype, tuple(moments.shape)))
+            keep = max(0, int(it_begin) + int(n_iters) - int(burn_in)) if n_keep is None else int(n_keep)
+            if cells is not None and (cells.dtype != torch.float32 or cells.numel() != n * int(k_slots) * keep or not cells.is_contiguous()):
+                raise ValueError("hmc_run_rows: cells must be a contiguous float32 tensor of n * k_slots * n_keep = %d values; got %s %s"
+                                 % (n * int(k_slots) * keep, cells.dtype, tuple(cells.shape)))
+            if slot is not None and (slot.dtype != torch.int32 or tuple(slot.shape) != (n, p) or not slot.is_contiguous()):
+                raise ValueError("hmc_run_rows: slot must be a contiguous int32 tensor [n, p]; got %s %s" % (slot.dtype, tuple(slot.shape)))
+            _lib.check(self.lib.bgm_bgm_hmc_run_rows_impute(self.h, C.byref(a), _ptr(up), _ptr(dn), 0 if up is None else int(up.numel()),
+                                                            float(s_min), float(s_max), T, jit, _ptr(n_steps), _ptr(moments), _ptr(cells),
+                                                            _ptr(slot), int(k_slots), keep, int(bool(add_noise)), self._stream()),
+                       "bgm_bgm_hmc_run_rows_impute")
+            return
         if max_trajectory is not None or jitter is not False or n_steps is not None:
             # (the C entry checks the two values itself, as it does s_min / s_max: what is not a number at all is refused here)
             try:
@@ -913,7 +942,7 @@ class BgmEngine(object):
                                               float(target), float(rate), self._stream()), "bgm_bgm_hmc_adapt")
 
     def hmc_sample(self, x, n_mcmc, burn_in, step_size=0.01, n_leapfrog=10, seed=42, row_base=0, want_draws=True,
-                   n_chains_global=None, reduce_fn=None, row_adapt=None, max_trajectory=None, jitter=False):
+                   n_chains_global=None, reduce_fn=None, row_adapt=None, max_trajectory=None, jitter=False, impute=False, add_noise=True):
         """tfp_mcmc_sampler (bgm/base.py:709-830): HMC + SimpleStepSizeAdaptation over int(0.8*burn_in)
         steps, all rows one chain each.  `reduce_fn(tensor)` all-reduces the per-iteration acceptance
         statistic across ranks (the step size is shared by ALL chains).
@@ -922,8 +951,15 @@ class BgmEngine(object):
         multiplied after each of the burn_in decisions by the factor of row_adapt.row_adapt_factors(burn_in, row_adapt) for "moved" /
         "did not"; burn-in and retained draws run in ONE launch, reduce_fn is not called, and the result holds row_step [n] instead
         of step.  max_trajectory / jitter (with row_adapt only): the number of leapfrog steps per chain of hmc_run_rows; the result
-        then holds n_steps int32 [n] as well, the steps every chain took over the n_mcmc retained transitions."""
+        then holds n_steps int32 [n] as well, the steps every chain took over the n_mcmc retained transitions.
+
+        impute=True (with row_adapt only, fp32): the predictive moments of the NaN cells of x are summed inside the sampler (hmc_run_rows
+        with moments); the result holds moments float32 [3, n, p] (NaN where nothing was written) and no draws are allocated."""
         T, jit = RA.resolve_trajectory(row_adapt, max_trajectory, jitter, what="hmc_sample: max_trajectory / jitter")
+        if impute:
+            if row_adapt is None:
+                raise ValueError("hmc_sample: impute needs row_adapt (the fused imputation lives in the per-chain step kernel)")
+            want_draws = False
         dev = self.device
         x = _f32(x, dev)
         n = x.shape[0]
@@ -938,6 +974,23 @@ class BgmEngine(object):
         if row_adapt is not None:
             up, dn = self.row_step_table(burn_in, row_adapt)
             step = torch.full((n,), float(step_size), device=dev, dtype=torch.float32)
+            if impute:      # (one launch; the planes are the only per-cell memory)
+                moments = torch.full((3, n, self.p), float("nan"), device=dev, dtype=torch.float32)
+                n_steps = torch.zeros(n, device=dev, dtype=torch.int32) if (T > 0.0 or jit) else None
+                tr = dict(max_trajectory=T if T > 0.0 else None, jitter=bool(jit))
+                first = 0
+                if n_steps is not None and burn_in > 0:      # (n_steps counts the retained transitions alone, as below)
+                    self.hmc_run_rows(x, state, logp, grad, step, 0, burn_in, burn_in, n_leapfrog, seed, init=True, row_base=row_base,
+                                      up=up, dn=dn, acc_prob=acc_prob, acc_count=acc_count, **tr)
+                    first = burn_in
+                if total > first:
+                    self.hmc_run_rows(x, state, logp, grad, step, first, total - first, burn_in, n_leapfrog, seed, init=(first == 0),
+                                      row_base=row_base, up=up, dn=dn, acc_prob=acc_prob, acc_count=acc_count, n_steps=n_steps,
+                                      moments=moments, n_keep=max(1, n_mcmc), add_noise=add_noise, **tr)
+                out = dict(state=state, logp=logp, grad=grad, row_step=step, acc_prob=acc_prob, acc_count=acc_count, draws=None, moments=moments)
+                if n_steps is not None:
+                    out["n_steps"] = n_steps
+                return out
             if T > 0.0 or jit:      # (two launches, so that n_steps counts the retained transitions alone: a cut changes nothing else)
                 n_steps = torch.zeros(n, device=dev, dtype=torch.int32)
                 tr = dict(max_trajectory=T if T > 0.0 else None, jitter=bool(jit))

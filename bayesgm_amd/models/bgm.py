@@ -376,6 +376,68 @@ class BGM(object):
             self._store_diagnostics(out["draws"])
         return out["draws"].cpu().numpy()
 
+    def _resolve_fused_predict(self, fused_predict, target, return_samples):
+        """predict's fused_predict as a bool, or the ValueError that names what it does not go with (before any device work)."""
+        if not isinstance(fused_predict, (bool, np.bool_)):
+            raise ValueError("fused_predict must be True or False; got %r" % (fused_predict,))
+        if not fused_predict:
+            return False
+        if target is None:
+            raise ValueError("fused_predict needs row_adapt: the imputation inside the sampler lives in the kernel with a step per chain")
+        if return_samples:
+            raise ValueError("fused_predict keeps moments, not draws: it cannot be combined with return_samples=True")
+        prec = getattr(self, "params", {}).get("hmc_precision", "fp32")
+        if prec != "fp32":
+            raise ValueError("fused_predict is built for params['hmc_precision'] = 'fp32' only; got %r" % (prec,))
+        return True
+
+    def _predict_fused(self, data_np, miss, x, state, logp, grad, step, acc_count, n_steps, traj, alpha, n_mcmc, burn_in, n_leapfrog, seed,
+                       lo_r, _mark, _t):
+        """predict's retained phase with fused_predict, from the state burn-in left: one launch over the rank's rows that keeps the
+        moments of every missing cell's predictive draws (engine.hmc_run_rows with moments), then mean, sd and the normal interval."""
+        import statistics
+        eng = self.engine
+        n, p = data_np.shape
+        n_loc = x.shape[0]
+        mom = torch.full((3, n_loc, p), float("nan"), device=eng.device)
+        if n_loc > 0 and n_mcmc > 0:      # (the steps are frozen from here on: every iteration lies behind the table)
+            eng.hmc_run_rows(x, state, logp, grad, step, burn_in, n_mcmc, burn_in, n_leapfrog, seed, init=(burn_in == 0), row_base=lo_r,
+                             acc_count=acc_count, n_steps=n_steps, moments=mom, n_keep=n_mcmc, **traj)
+        _mark("sample_predict_moments")
+        acc = acc_count[burn_in:].sum().double().reshape(1)
+        parallel.all_reduce_sum_(acc)
+        self.last_acceptance_rate = float(acc.item()) / max(1, n_mcmc * n)
+        print(f"TFP MCMC Acceptance Rate: {self.last_acceptance_rate:.4f}")
+        # mean = ref + s1 / k, sd = sqrt((s2 - s1^2 / k) / (k - 1)), in float64 and in place: plane 0 becomes the imputed panel, plane 1
+        # the sd.  The planes are NaN at observed cells (the kernel never writes them), and so is the sd.
+        k = float(max(1, n_mcmc))
+        for s in range(0, n_loc, 1 << 16):
+            e = min(s + (1 << 16), n_loc)
+            ref, s1, s2 = (mom[i, s:e].double() for i in range(3))
+            sd = torch.sqrt((s2 - s1 * s1 / k).clamp_(min=0.0) / max(1.0, k - 1.0))
+            mom[0, s:e] = torch.where(torch.isnan(x[s:e]), (ref + s1 / k).float(), x[s:e])
+            mom[1, s:e] = sd.float()
+        self.hmc_row_step_ = parallel.all_gather_rows(step, n).cpu().numpy()
+        if n_steps is not None:
+            self.hmc_row_leapfrog_ = (parallel.all_gather_rows(n_steps, n).cpu().numpy() / np.float32(max(1, n_mcmc))).astype(np.float32)
+        imputed_dev, sd_dev = mom[0], mom[1]
+        if parallel.is_dist():
+            imputed_dev, sd_dev = parallel.all_gather_rows(imputed_dev, n), parallel.all_gather_rows(sd_dev, n)
+        imputed, sd = imputed_dev.cpu().numpy(), sd_dev.cpu().numpy()
+        self.impute_sd_ = sd
+        zq = np.float32(statistics.NormalDist().inv_cdf(1.0 - alpha / 2.0))
+        lo, hi = imputed - zq * sd, imputed + zq * sd
+        # ---- the reference's two layouts, as in predict
+        if bool(np.all(miss == miss[0])):
+            mi = np.where(miss[0])[0]
+            pred_interval = np.stack([lo[:, mi], hi[:, mi]], axis=-1).astype(np.float32)
+        else:
+            flat = np.stack([lo[miss], hi[miss]], axis=-1).astype(np.float32)          # row-major: row i's cells together
+            pred_interval = np.split(flat, np.cumsum(miss.sum(axis=1))[:-1]) if n else []
+        _mark("intervals")
+        self.last_predict_timing = {k_: v for k_, v in _t.items() if k_ != "_last"}
+        return imputed, pred_interval
+
     def _store_diagnostics(self, draws_dev):
         from .. import diagnostics as dg         # the sampler's `diagnostics` flag shadows the module in its body
         self.mcmc_diagnostics_ = dg.chain_diagnostics(draws_dev)
@@ -411,7 +473,8 @@ class BGM(object):
 
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.05, return_samples=False, bs=100, n_mcmc=5000, burn_in=5000, step_size=0.01,
-                num_leapfrog_steps=10, seed=42, max_draw_bytes=64 << 30, row_adapt=False, max_trajectory=None, jitter_leapfrog=False):
+                num_leapfrog_steps=10, seed=42, max_draw_bytes=64 << 30, row_adapt=False, max_trajectory=None, jitter_leapfrog=False,
+                fused_predict=False):
         """Posterior-predictive imputation of the NaN cells (bgm/base.py:527-663).
 
         HMC burn-in (with the shared step-size adaptation) runs over ALL rows at once as in the reference;
@@ -427,12 +490,23 @@ class BGM(object):
         (pi / 2 is a quarter period of a unit-variance coordinate); with ``jitter_leapfrog`` the number is drawn uniformly from
         1 .. that cap for every transition.  Without them a row with little observed ends up with step x steps near a full period
         and returns to where it started.  A transition still costs ``num_leapfrog_steps`` gradient evaluations: the options buy
-        mixing, not time.  ``self.hmc_row_leapfrog_`` [n] holds every chain's mean steps per retained transition."""
+        mixing, not time.  ``self.hmc_row_leapfrog_`` [n] holds every chain's mean steps per retained transition.
+
+        ``fused_predict`` (opt-in, with ``row_adapt`` only, fp32): the retained phase is ONE launch over the rank's rows, and every
+        retained transition decodes the state it ends on inside the sampler and adds the predictive draw of every missing cell to
+        running moments (engine.hmc_run_rows with ``moments``).  No latent draws, no cells matrix and no sort: ``max_draw_bytes`` is not
+        used and the memory is three floats per cell of the panel.  The chains, ``hmc_row_step_`` and the predictive draws are those of
+        the default route at the same seed; ``imputed`` is their mean.  The interval is NOT the default route's quantile pair: it is
+        the normal approximation  mean -/+ z_{1 - alpha/2} sd  from the draws' mean and standard deviation (n - 1 in the
+        denominator), which is off where a cell's predictive distribution is skewed or heavy-tailed.  The sd is left in
+        ``self.impute_sd_`` [n, p], NaN at observed cells.  Not with ``return_samples`` and not with ``params['hmc_precision']``
+        other than 'fp32'."""
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         target = row_adapt_mod.resolve_step_target(row_adapt)
         max_traj, jit = row_adapt_mod.resolve_trajectory(target, max_trajectory, jitter_leapfrog, what="max_trajectory / jitter_leapfrog")
+        fused = self._resolve_fused_predict(fused_predict, target, return_samples)
         traj = dict(max_trajectory=max_traj if max_traj > 0.0 else None, jitter=bool(jit)) if (max_traj > 0.0 or jit) else {}
-        self.hmc_row_step_ = self.hmc_row_leapfrog_ = None
+        self.hmc_row_step_ = self.hmc_row_leapfrog_ = self.impute_sd_ = None
         parallel.check_n_mcmc(n_mcmc)
         import time as _time
         _t = {"_last": _time.perf_counter()}
@@ -480,6 +554,9 @@ class BGM(object):
                 eng.hmc_run(x, state, logp, grad, step, n_adapt, burn_in - n_adapt, burn_in, num_leapfrog_steps, seed,
                             init=(n_adapt == 0), row_base=lo_r, acc_prob=acc_prob, acc_count=acc_count)
         _mark("burn_in")
+        if fused:
+            return self._predict_fused(data_np, miss, x, state, logp, grad, step, acc_count, n_steps if traj else None, traj, alpha, n_mcmc,
+                                       burn_in, num_leapfrog_steps, seed, lo_r, _mark, _t)
         # ---- sampling + predictive draws per row block (slot maps, moments and the imputation stay in HBM)
         miss_dev = torch.isnan(x)
         k_row_dev = miss_dev.sum(dim=1)

@@ -77,6 +77,13 @@ def _refuse_trajectory(max_trajectory, jitter_leapfrog):
                          % (max_trajectory, jitter_leapfrog))
 
 
+def _refuse_fused_predict(fused_predict):
+    """The imputation inside the sampler (BGM.predict, fused_predict) lives in the per-chain step kernel of the deterministic generator."""
+    if not (isinstance(fused_predict, (bool, np.bool_)) and not fused_predict):
+        raise ValueError("fused_predict is not available with params['use_bnn'] = True: it needs row_adapt, the HMC step per chain, which "
+                         "the Bayesian generator's kernels do not have; got fused_predict=%r" % (fused_predict,))
+
+
 class BGMBayes(BGM):
     def __init__(self, params, timestamp=None, random_seed=None, device=None):
         self.params = params
@@ -421,12 +428,14 @@ class BGMBayes(BGM):
 
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.05, return_samples=False, bs=100, n_mcmc=5000, burn_in=5000, step_size=0.01,
-                num_leapfrog_steps=10, seed=42, max_draw_bytes=16 << 30, row_adapt=False, max_trajectory=None, jitter_leapfrog=False):
+                num_leapfrog_steps=10, seed=42, max_draw_bytes=16 << 30, row_adapt=False, max_trajectory=None, jitter_leapfrog=False,
+                fused_predict=False):
         """Posterior-predictive imputation of the NaN cells (bgm/base.py:527-663).  HMC over ALL rows as in the reference
         (one generator call per gradient evaluation), then one predictive generator call per block of `bs` rows.  row_adapt,
-        max_trajectory, jitter_leapfrog: BGM's keywords, refused here for anything but their defaults."""
+        max_trajectory, jitter_leapfrog, fused_predict: BGM's keywords, refused here for anything but their defaults."""
         _refuse_row_adapt(row_adapt)
         _refuse_trajectory(max_trajectory, jitter_leapfrog)
+        _refuse_fused_predict(fused_predict)
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         self._warn_fresh_noise()

@@ -741,6 +741,25 @@ BGM_API int bgm_bgm_hmc_run_rows(bgm_handle *h, const bgm_hmc_args *args, const 
 BGM_API int bgm_bgm_hmc_run_rows_traj(bgm_handle *h, const bgm_hmc_args *args, const float *up_dev, const float *dn_dev, int32_t n_table,
                                       float s_min, float s_max, float max_trajectory, int32_t jitter, int32_t *n_steps_dev, void *stream);
 
+/* bgm_bgm_hmc_run_rows_traj with the imputation inside the sampler (opt-in, fp32): after the accept decision of every iteration
+ * it >= burn_in the kernel decodes the state the chain is left in -- the forward pass, the noise and the Philox counters of
+ * bgm_bgm_predict_draws with burn_in + d = it, so a value is what that call makes of stored draw d -- and keeps, for the MISSING cells
+ * (NaN in x_dev) only, shifted moments in moments_dev [3][n][p] float32: plane 0 = ref, the value at it == burn_in (written then,
+ * with zeros in planes 1 and 2), plane 1 += x - ref, plane 2 += (x - ref)^2.  Over k retained iterations mean = ref + s1 / k and
+ * var = (s2 - s1^2 / k) / (k - 1).  Observed cells and the planes' other entries are never written; no latent draw, no cells matrix
+ * and no sort is needed, and the planes carry a run cut into segments as state_dev does.  cells_dev (or NULL): also
+ * cells_dev[(row * k_slots + slot) * n_keep + (it - burn_in)] = x for the cells with slot_dev[row * p + c] >= 0, the layout of
+ * bgm_bgm_predict_draws.  add_noise = 0: the head's mean instead of a draw.  The chain is bgm_bgm_hmc_run_rows_traj's bit for bit
+ * (bgm_bgm_hmc_run_rows' with (max_trajectory, jitter, n_steps_dev) = (0, 0, NULL)); args->draws_dev may still be given.
+ * BGM_E_INVALID, naming the argument: everything bgm_bgm_hmc_run_rows_traj refuses, moments_dev == NULL, cells_dev without slot_dev
+ * or with k_slots < 1, n_keep < 1, add_noise other than 0 / 1, it_begin + n_iters beyond burn_in + n_keep.  BGM_E_UNSUPPORTED (the
+ * handle stays usable), naming this path: split precision (bgm_bgm_set_precision(h, 2)) and the general-width engine.
+ * replaces: predict_on_posteriors over the stored draws and the per-cell mean in BGM.predict, bgm/base.py:511-525, 527-663 (opt-in). */
+BGM_API int bgm_bgm_hmc_run_rows_impute(bgm_handle *h, const bgm_hmc_args *args, const float *up_dev, const float *dn_dev, int32_t n_table,
+                                        float s_min, float s_max, float max_trajectory, int32_t jitter, int32_t *n_steps_dev,
+                                        float *moments_dev, float *cells_dev, const int32_t *slot_dev, int32_t k_slots, int32_t n_keep,
+                                        int32_t add_noise, void *stream);
+
 /* Posterior-predictive draws x ~ N(mu(z_d), sigma^2(z_d)) for draws_dev [n_draws x n x q]:
  * full_dev [n_draws x n x p] (or NULL) and / or cells_dev [(row*k_slots + slot)*n_draws + d] for
  * the cells with slot_dev[row*p + c] >= 0 (or NULL); var_full_dev [n_draws x n x p] receives sigma^2
