@@ -109,6 +109,7 @@ SYMBOLS = {
     "bgm_set_disc_norm": (C.c_int, [C.c_void_p, C.c_int32]),
     "bgm_causal_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "bgm_bnn_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
+    "bgm_bnn_sampling_family": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "bgm_causal_set_prior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "bgm_causal_set_row_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float]),
     "bgm_destroy": (C.c_int, [C.c_void_p]),

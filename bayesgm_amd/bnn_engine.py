@@ -209,16 +209,17 @@ class BnnEngine(object):
                                                  comm.handle, self._stream()), "bgm_bnn_fit_epoch_dp")
         return n_done.value
 
+    def sampling_family(self):
+        """The kernel family behind the session's sampling calls (bgm_bnn_sampling_family): "bnf" default shapes with inference-mode
+        normalisation | "bns" batch statistics | "bnw" any width.  Needs an open session."""
+        family = C.c_int32(-1)
+        _lib.check(self.lib.bgm_bnn_sampling_family(self.h, C.byref(family)), "bgm_bnn_sampling_family")
+        return ("bnf", "bns", "bnw")[family.value]
+
     def serves_block_shares(self):
         """True when the session samples on the default-shape kernels (csrc/bnf_kernels.h), the family that can run a rank's share of one
-        block (mh_run(block_row0 > 0)) -- probed through the split-precision switch, which exists for exactly those sessions."""
-        prev = getattr(self, "_precision", "fp32")
-        if prev == "f16x3":
-            return True
-        if not self.open or self.lib.bgm_bnn_set_precision(self.h, 2) != 0:
-            return False
-        _lib.check(self.lib.bgm_bnn_set_precision(self.h, {"fp32": 0, "bf16x3": 1}[prev]), "bgm_bnn_set_precision")
-        return True
+        block (mh_run(block_row0 > 0))."""
+        return self.open and self.sampling_family() == "bnf"
 
     # -- large-batch side ------------------------------------------------------------------------------
     def logpost(self, x, y, v, z, block_rows, seed, stream_id, block0=0):

@@ -34,11 +34,19 @@ static int bgm_reserve(T *&ptr, size_t &cap, size_t count) {
   return BGM_OK;
 }
 
-// One launch of `waves` waves per workgroup with `lds` bytes of dynamic LDS (beyond the 64 KiB a kernel gets without asking): the one
-// place that raises the dynamic-LDS limit, launches and checks, for every kernel family of the library
+// Raises the dynamic-LDS limit of `kernel` to `lds` bytes (beyond the 64 KiB a kernel gets without asking).  On its own where one call
+// launches the kernel many times: once in front of the loop.
+template <class K>
+static int bgm_set_lds(K kernel, int lds) {
+  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  return BGM_OK;
+}
+
+// One launch of `waves` waves per workgroup with `lds` bytes of dynamic LDS: raises the limit, launches and checks, for every kernel
+// family of the library
 template <class... KA, class... A>
 static int bgm_launch(void (*kernel)(KA...), int grid, int waves, int lds, hipStream_t stream, A &&...args) {
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  if (int rc = bgm_set_lds(kernel, lds)) return rc;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, stream, static_cast<KA>(args)...);
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;

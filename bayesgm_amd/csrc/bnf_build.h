@@ -214,7 +214,7 @@ static inline bool bnf_upload(BnfState *n, const BnfTabs &tb) {
     if (hipMalloc(dst, bytes) != hipSuccess) return false;
     return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
   };
-  static const float pair_host[2] = {1.0f, 0.0f};
+  static const float pair[2] = {1.0f, 0.0f};
   std::vector<int> np(tb.W.size()), npe(tb.WE.size()), px(tb.W.size()), pxe(tb.WE.size());
   for (size_t i = 0; i < tb.W.size(); ++i) { np[i] = tb.W[i].pos | ((tb.W[i].rep - 1) << 28); px[i] = tb.W[i].posx; }
   for (size_t i = 0; i < tb.WE.size(); ++i) { npe[i] = tb.WE[i].pos | ((tb.WE[i].rep - 1) << 28); pxe[i] = tb.WE[i].posx; }
@@ -223,7 +223,7 @@ static inline bool bnf_upload(BnfState *n, const BnfTabs &tb) {
             up((void **)&n->w_dev, tb.W.data(), tb.W.size() * sizeof(BnfWElem)) && up((void **)&n->b_dev, tb.B.data(), tb.B.size() * sizeof(BnfBElem)) &&
             up((void **)&n->n_dev, tb.N.data(), tb.N.size() * sizeof(BnfNElem)) && up((void **)&n->we_dev, tb.WE.data(), tb.WE.size() * sizeof(BnfWElem)) &&
             up((void **)&n->be_dev, tb.BE.data(), tb.BE.size() * sizeof(BnfBElem)) && up((void **)&n->ne_dev, tb.NE.data(), tb.NE.size() * sizeof(BnfNElem)) &&
-            up((void **)&n->pair_dev, pair_host, sizeof(pair_host));
+            up((void **)&n->pair_dev, pair, sizeof(pair));
   ok = ok && hipMalloc((void **)&n->blob_dev, sizeof(float) * n->P.blob_floats) == hipSuccess &&
        hipMalloc((void **)&n->eblob_dev, sizeof(float) * n->P.e_blob_floats) == hipSuccess &&
        hipMalloc((void **)&n->sf_dev, sizeof(float) * n->P.set_floats) == hipSuccess &&

@@ -44,12 +44,6 @@ EffFn det_eff_fn(int KSF) {
   }
 }
 
-template <class K>
-int set_lds(K kernel, int bytes) {
-  BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return BGM_OK;
-}
-
 BnfNetSrc src_of(const HostNet &n, int base, int net_id) {
   BnfNetSrc s;
   s.n_layers = (int)n.dims.size() - 1; s.net_id = net_id;
@@ -136,7 +130,7 @@ int launch_effects(bgm_handle *h, BnfState *st, const float *z, long long n, lon
   const float sy = h->cfg.sigma_y;
   ea.sig2_y = sy > 0.0f ? sy * sy : -1.0f;
   EffFn fn = det_eff_fn(st->KSFc);
-  int rc = set_lds(fn, st->lds_eff);
+  int rc = bgm_set_lds(fn, st->lds_eff);
   if (rc) return rc;
   BGM_HIP_CHECK(hipMemsetAsync(st->queue_dev + 8, 0, 8 * sizeof(unsigned), stream));
   hipLaunchKernelGGL(fn, dim3(grid_for(h)), dim3(64 * DW_), st->lds_eff, stream, ea);
@@ -171,7 +165,7 @@ int bnf_det_logpost(bgm_handle *h, const float *x, const float *y, const float *
   fill_common(h, st, a, x, y, v, const_cast<float *>(z), n);
   a.mode = 0; a.out = out;
   MhFn fn = det_fn<0>(st->KSc, st->wide);
-  rc = set_lds(fn, st->lds_mh);
+  rc = bgm_set_lds(fn, st->lds_mh);
   if (rc) return rc;
   return launch_mh(h, st, fn, a, stream);
 }
@@ -187,7 +181,7 @@ int bnf_det_evaluate(bgm_handle *h, const float *x, const float *y, const float 
   fill_common(h, st, a, x, y, v, const_cast<float *>(z), n);
   a.mode = 2; a.sums = sums;
   MhFn fn = det_fn<2>(st->KSc, st->wide);
-  rc = set_lds(fn, st->lds_mh);
+  rc = bgm_set_lds(fn, st->lds_mh);
   if (rc) return rc;
   rc = launch_mh(h, st, fn, a, stream);
   if (rc) return rc;
@@ -229,7 +223,7 @@ int bnf_det_mh_run(bgm_handle *h, const bgm_mh_args *g, hipStream_t stream) {
   a.row_base = g->row_base; a.mode = 1; a.q_sd = g->q_sd; a.q_sd_blocks = nullptr;
   a.k0 = (uint32_t)g->seed; a.k1 = (uint32_t)(g->seed >> 32); a.lp_cache = g->logp_dev;
   MhFn fn = det_fn<1>(st->KSc, st->wide);
-  rc = set_lds(fn, st->lds_mh);
+  rc = bgm_set_lds(fn, st->lds_mh);
   if (rc) return rc;
   if (g->acc_count_dev) BGM_HIP_CHECK(hipMemsetAsync(g->acc_count_dev + g->it_begin, 0, sizeof(unsigned) * g->n_iters, stream));
   for (int i = 0; i < g->n_iters; ++i) {

@@ -9,6 +9,7 @@
 #define BNN_ADAM_B2 0.99f
 #define BNN_ADAM_EPS 1e-7f
 
+#include "bnn_sample_host.h"
 #include "bprior_types.h"
 struct BnnState {
   bgm_bnn_config cfg{};
@@ -28,7 +29,9 @@ struct BnnState {
   float *samp_dev = nullptr;
   size_t samp_cap = 0;
   void *bnf = nullptr;         // BnfState (bnf_api.hip): the fixed-normalisation sampling path's tables, packed blob, buffers
-  bool bnf_valid = false, bnf_unsupported = false;
+  bool bnf_valid = false;
+  BnnRoute route;              // which kernel family serves the sampling calls (bnn_sample_host.h)
+  float *pair_dev = nullptr;   // (1, 0): the two treatments of a binary model (bnn_pair)
   int precision = 0;           // arithmetic of the sampling calls: 0 fp32, 2 split precision "f16 x 3" (bgm_bnn_set_precision; bnx_kernels.h)
   void *egm = nullptr;         // BnnEgmState (bnn_egm_api.hip)
   void *chain = nullptr;       // BnnFitChain (bnn_api.hip): tables / workspace of the row-tile-chain step kernels, or NULL
@@ -49,17 +52,6 @@ int bprior_rows(bgm_handle *h, BnnState *s, long long n, int bs, int block0, uin
                 long long rib0 = 0);
 
 void bgm_bnn_egm_free(void *egm_state);
-void bnf_free(void *state);
-void bnw_free(void *state);
-int bnw_logpost(bgm_handle *h, BnnState *s, const float *x, const float *y, const float *v, const float *z, int64_t n, int32_t bs, int32_t block0,
-                uint64_t seed, uint32_t stream_id, float *out, hipStream_t stream);
-int bnw_mh_run(bgm_handle *h, BnnState *s, const bgm_bnn_mh_args *g, hipStream_t stream);
-int bnw_effects(bgm_handle *h, BnnState *s, const float *draws, int64_t n, int32_t bs, int32_t block0, int64_t row_base, int32_t n_keep, int32_t it0,
-                uint64_t seed, int32_t effect, int32_t sample_y, const float *x_values, int32_t n_doses, double *adrf_sum, float *ite,
-                hipStream_t stream);
-int bnw_evaluate(bgm_handle *h, BnnState *s, const float *x, const float *y, const float *v, float *z, int32_t encode, int64_t n, const float *x_values,
-                 int32_t n_doses, uint64_t seed, uint32_t stream_id, double *sums, double *dose_sums, float *ite, hipStream_t stream);
-
 inline void bnn_free_sampler(BnnState *s) {
   if (s->samp_dev) hipFree(s->samp_dev);
   s->samp_dev = nullptr;
@@ -70,6 +62,9 @@ inline void bnn_free_sampler(BnnState *s) {
   if (s->bnw) bnw_free(s->bnw);
   s->bnw = nullptr;
   s->bnf_valid = false;
+  s->route = BnnRoute{};
+  if (s->pair_dev) hipFree(s->pair_dev);
+  s->pair_dev = nullptr;
   if (s->bp_rows) hipFree(s->bp_rows);
   s->bp_rows = nullptr; s->bp_rows_cap = 0;
   if (s->bp_hist) hipFree(s->bp_hist);

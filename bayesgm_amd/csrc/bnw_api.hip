@@ -1,5 +1,5 @@
 // bnw_api.hip -- host side of the any-width sampling / evaluation path of CausalBGM with Bayesian networks (bnw_kernels.h).  Entered
-// from the bgm_bnn_* entry points (bnn_sample_api.hip) when no LDS-fragment family holds the session's shape.
+// from the bgm_bnn_* entry points (bnn_sample_api.hip) when no LDS-fragment family holds the session's shape (bnn_sample_host.h).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -9,7 +9,7 @@
 #include "bnw_kernels.h"
 
 struct BnwState {
-  float *dw = nullptr, *ws = nullptr, *pair = nullptr, *loct = nullptr;
+  float *dw = nullptr, *ws = nullptr, *loct = nullptr;
   BnwNets *nets = nullptr;      // [2]: the nets of the call's sets, the outcome net's own
   size_t dw_cap = 0, ws_cap = 0, loct_cap = 0;
   float *st = nullptr;          // batch statistics (params['bnn_norm'] = "batch"), doubles: [2 parities][n_blocks][256] | x [n_blocks][2] | v [2][p]
@@ -21,7 +21,6 @@ void bnw_free(void *p) {
   if (!b) return;
   if (b->dw) hipFree(b->dw);
   if (b->ws) hipFree(b->ws);
-  if (b->pair) hipFree(b->pair);
   if (b->loct) hipFree(b->loct);
   if (b->nets) hipFree(b->nets);
   if (b->st) hipFree(b->st);
@@ -47,19 +46,12 @@ void bnw_nets(const BnnState *s, const int *ids, int n_ids, BnwNets &m) {
   m.set_floats = off;
   m.theta = s->theta_dev;
   m.q = s->q; m.p = s->p; m.z0 = s->cfg.z_dims[0]; m.z1 = s->cfg.z_dims[1]; m.z2 = s->cfg.z_dims[2]; m.binary = s->cfg.binary_treatment;
-  m.sig2[0] = s->cfg.sigma_v > 0.0f ? s->cfg.sigma_v * s->cfg.sigma_v : 0.0f;
-  m.sig2[1] = s->cfg.sigma_x > 0.0f ? s->cfg.sigma_x * s->cfg.sigma_x : 0.0f;
-  m.sig2[2] = s->cfg.sigma_y > 0.0f ? s->cfg.sigma_y * s->cfg.sigma_y : 0.0f;
+  const BnnSig2 sig2 = bnn_sig2(s->cfg);
+  m.sig2[0] = sig2.v; m.sig2[1] = sig2.x; m.sig2[2] = sig2.y;
 }
-int bnw_grow(float **p, size_t *cap, size_t floats, hipStream_t stream) {
-  if (floats <= *cap) return BGM_OK;
-  BGM_HIP_CHECK(hipStreamSynchronize(stream));
-  if (*p) BGM_HIP_CHECK(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  BGM_HIP_CHECK(hipMalloc((void **)p, sizeof(float) * floats));
-  *cap = floats;
-  return BGM_OK;
-}
+const int kGhf[3] = {BNN_G, BNN_H, BNN_F}, kGhfe[4] = {BNN_G, BNN_H, BNN_F, BNN_E}, kF[1] = {BNN_F};
+int bnw_tiles(int bs) { return (bs + BNW_RT - 1) / BNW_RT; }      // row tiles of a block
+
 #define BNW_LDS_BYTES (sizeof(float) * 2 * BNW_STAGE_FLOATS)      // the double-buffered stage of bnw_gemm2
 struct BnwPlan { BnwState *b; int grid; long long ws_stride; };
 int bnw_plan(bgm_handle *h, BnnState *s, const BnwNets &m, long long n_sets_total, int n_items, BnwPlan &pl, hipStream_t stream) {
@@ -68,21 +60,15 @@ int bnw_plan(bgm_handle *h, BnnState *s, const BnwNets &m, long long n_sets_tota
   pl.b = b;
   pl.grid = std::max(1, std::min(n_items, 4 * h->n_cus));
   pl.ws_stride = (long long)((bnw_ws_floats(m) + 63) & ~(size_t)63);
-  int rc = bnw_grow(&b->ws, &b->ws_cap, (size_t)pl.ws_stride * (size_t)(4 * h->n_cus), stream);
+  int rc = bnn_reserve(b->ws, b->ws_cap, (size_t)pl.ws_stride * (size_t)(4 * h->n_cus), stream);
   if (rc) return rc;
-  rc = bnw_grow(&b->dw, &b->dw_cap, (size_t)n_sets_total * (size_t)m.set_floats + 64, stream);
+  rc = bnn_reserve(b->dw, b->dw_cap, (size_t)n_sets_total * (size_t)m.set_floats + 64, stream);
   if (rc) return rc;
-  rc = bnw_grow(&b->loct, &b->loct_cap, 2 * (size_t)m.set_floats + 128, stream);      // the call's sets and the outcome net's own sets
-  if (rc) return rc;
+  rc = bnn_reserve(b->loct, b->loct_cap, 2 * (size_t)m.set_floats + 128, stream);      // the call's sets and the outcome net's own sets
+  if (rc || (rc = bnn_pair(s))) return rc;
   if (!b->nets) {
     BGM_HIP_CHECK(hipMalloc((void **)&b->nets, 2 * sizeof(BnwNets)));
-    BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(bnw_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BNW_LDS_BYTES));
-    BGM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(bnw_effects_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BNW_LDS_BYTES));
-  }
-  if (!b->pair) {
-    BGM_HIP_CHECK(hipMalloc((void **)&b->pair, 2 * sizeof(float)));
-    static const float pair_host[2] = {1.0f, 0.0f};
-    BGM_HIP_CHECK(hipMemcpy(b->pair, pair_host, sizeof(pair_host), hipMemcpyHostToDevice));
+    if ((rc = bgm_set_lds(bnw_rows_kernel, (int)BNW_LDS_BYTES)) || (rc = bgm_set_lds(bnw_effects_kernel, (int)BNW_LDS_BYTES))) return rc;
   }
   return BGM_OK;
 }
@@ -105,14 +91,14 @@ struct BnwBatch {
   bool on = false;
   double *stats = nullptr, *xstats = nullptr, *vstats = nullptr;
   int n_blocks = 0;
-  const double *parity(int par) const { return stats + (long long)par * n_blocks * 256; }
+  const double *parity(int par) const { return on ? stats + (long long)par * n_blocks * 256 : nullptr; }
 };
 int bnw_batch(BnnState *s, BnwState *b, int n_blocks, BnwBatch &bt, hipStream_t stream) {
   bt.on = s->cfg.norm_mode != 1;
   bt.n_blocks = n_blocks;
   if (!bt.on) return BGM_OK;
   const size_t doubles = (size_t)2 * n_blocks * 256 + (size_t)2 * n_blocks + (size_t)2 * s->p + 16;
-  int rc = bnw_grow(&b->st, &b->st_cap, 2 * doubles, stream);
+  int rc = bnn_reserve(b->st, b->st_cap, 2 * doubles, stream);
   if (rc) return rc;
   bt.stats = reinterpret_cast<double *>(b->st);
   bt.xstats = bt.stats + (size_t)2 * n_blocks * 256;
@@ -120,141 +106,145 @@ int bnw_batch(BnnState *s, BnwState *b, int n_blocks, BnwBatch &bt, hipStream_t 
   BGM_HIP_CHECK(hipMemsetAsync(b->st, 0, sizeof(double) * doubles, stream));
   return BGM_OK;
 }
-// column sums of the states z (slot 1) and of their proposals of iteration `it` (slot 0) into parity `par`; with_x: the treatment column too
-void bnw_stats(const BnwBatch &bt, const float *z, long long n, long long row_base, int q, int bs, int it, int init, float q_sd, const float *q_sd_blocks,
-               uint64_t seed, int par, const float *x, bool with_x, hipStream_t stream) {
+// Statistics pass: column sums of the states sa.z (slot 1) and of their proposals of iteration sa.it (slot 0) into parity sa.par; with
+// sa.xstats, the treatment column sa.x too.  The fields a call fixes:
+BnwStatArgs bnw_stat_args(const BnwBatch &bt, const BnnRows &r, int q, uint64_t seed) {
   BnwStatArgs sa{};
-  sa.z = z; sa.n = n; sa.row_base = row_base; sa.q = q; sa.bs = bs; sa.wg_per_block = (bs + 255) / 256; sa.it = it; sa.init = init;
-  sa.q_sd = q_sd; sa.q_sd_blocks = q_sd_blocks; sa.k0 = (uint32_t)seed; sa.k1 = (uint32_t)(seed >> 32);
-  sa.stats = bt.stats; sa.n_blocks = bt.n_blocks; sa.par = par; sa.x = x; sa.xstats = with_x ? bt.xstats : nullptr;
-  hipLaunchKernelGGL(bnw_stats_kernel, dim3((unsigned)(bt.n_blocks * sa.wg_per_block)), dim3(256), 0, stream, sa);
+  sa.n = r.n; sa.row_base = r.row_base; sa.q = q; sa.bs = r.bs; sa.wg_per_block = (r.bs + 255) / 256;
+  sa.k0 = (uint32_t)seed; sa.k1 = (uint32_t)(seed >> 32); sa.stats = bt.stats; sa.n_blocks = bt.n_blocks;
+  return sa;
 }
-void bnw_noise(const BnwNets &m, float *dw, int n_blocks, int n_calls, int block0, uint64_t seed, uint32_t stream0, uint32_t stride, hipStream_t stream) {
+void bnw_stats(const BnwStatArgs &sa, hipStream_t stream) {
+  hipLaunchKernelGGL(bnw_stats_kernel, dim3((unsigned)(sa.n_blocks * sa.wg_per_block)), dim3(256), 0, stream, sa);
+}
+// one set per block and call; call c draws from stream stream0 + c
+void bnw_noise(const BnwNets &m, float *dw, const BnnRows &r, int n_calls, uint64_t seed, uint32_t stream0, hipStream_t stream) {
   BnwNoiseArgs na{};
-  na.m = m; na.dw = dw; na.n_calls = n_calls; na.block0 = block0;
-  na.k0 = (uint32_t)seed; na.k1 = (uint32_t)(seed >> 32); na.stream0 = stream0; na.stream_stride = stride;
+  na.m = m; na.dw = dw; na.n_calls = n_calls; na.block0 = r.block0;
+  na.k0 = (uint32_t)seed; na.k1 = (uint32_t)(seed >> 32); na.stream0 = stream0; na.stream_stride = 1u;
   long long mx = 0;
   for (int k = 0; k < 4; ++k) if (m.noff[k] >= 0) mx = std::max<long long>(mx, m.net[k].eoff[m.net[k].n_layers]);
   const int gx = (int)std::max<long long>(1, std::min<long long>(64, (mx / 4 + 255) / 256));
-  hipLaunchKernelGGL(bnw_noise_kernel, dim3(gx, n_blocks * n_calls), dim3(256), 0, stream, na);
+  hipLaunchKernelGGL(bnw_noise_kernel, dim3(gx, r.n_blocks * n_calls), dim3(256), 0, stream, na);
+}
+// the fields a call fixes of its bnw_rows_kernel launches (a.m is the caller's: bnw_nets, bnw_pack)
+void bnw_rows_args(BnwRowsArgs &a, const BnwPlan &pl, const BnnRows &r, int n_calls, uint64_t seed) {
+  a.mp = a.m.dev; a.dw = pl.b->dw; a.n_calls = n_calls; a.n = r.n; a.row_base = r.row_base; a.bs = r.bs; a.block0 = r.block0;
+  a.tiles_per_block = bnw_tiles(r.bs); a.n_items = r.n_blocks * a.tiles_per_block;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.ws = pl.b->ws; a.ws_stride = pl.ws_stride;
+}
+void bnw_launch_rows(const BnwPlan &pl, const BnwRowsArgs &a, hipStream_t stream) {
+  hipLaunchKernelGGL(bnw_rows_kernel, dim3(pl.grid), dim3(BNN_THREADS), BNW_LDS_BYTES, stream, a);
+}
+
+// the effects launches of one call: everything but the draw.  dw: where the outcome net's sets (one per block and dose) go
+struct BnwEffects { BnwEffArgs e; BnnRows r; uint64_t seed; int grid; };
+BnwEffects bnw_effects_begin(const BnwNets &mf, const BnwPlan &pl, float *dw, const BnnRows &r, uint64_t seed, int sample_y) {
+  BnwEffects x{BnwEffArgs{}, r, seed, pl.grid};
+  BnwEffArgs &e = x.e;
+  e.m = mf; e.mp = mf.dev; e.dw = dw; e.n = r.n; e.row_base = r.row_base; e.bs = r.bs; e.block0 = r.block0;
+  e.tiles_per_block = bnw_tiles(r.bs); e.n_items = r.n_blocks * e.tiles_per_block;
+  e.k0 = (uint32_t)seed; e.k1 = (uint32_t)(seed >> 32); e.sample_y = sample_y;
+  e.ws = pl.b->ws; e.ws_stride = pl.ws_stride;
+  return x;
+}
+// effects of ONE draw (states z; stats: their batch statistics, or NULL)
+int bnw_effects_of(BnwEffects &x, const BnnEffectSlot &sl, const float *z, const double *stats, uint32_t it_noise, hipStream_t stream) {
+  BnwEffArgs &e = x.e;
+  bnw_noise(e.m, const_cast<float *>(e.dw), x.r, sl.n_doses, x.seed, sl.stream0, stream);
+  e.stats = stats; e.z = z; e.n_doses = sl.n_doses; e.xvals = sl.xvals; e.stream0 = sl.stream0; e.it_noise = it_noise;
+  e.sum_out = sl.sum_out; e.sum_stride = sl.stride; e.ite_out = sl.ite_out; e.ite_stride = sl.stride;
+  hipLaunchKernelGGL(bnw_effects_kernel, dim3(std::max(1, std::min(e.n_items, x.grid))), dim3(BNN_THREADS), BNW_LDS_BYTES, stream, e);
+  BGM_HIP_CHECK(hipGetLastError());
+  return BGM_OK;
 }
 }  // namespace
 
-int bnw_logpost(bgm_handle *h, BnnState *s, const float *x, const float *y, const float *v, const float *z, int64_t n, int32_t bs, int32_t block0,
-                uint64_t seed, uint32_t stream_id, float *out, hipStream_t stream) {
+int bnw_logpost(bgm_handle *h, BnnState *s, const BnnLogpostCall &c, hipStream_t stream) {
   int rc = bnw_need(s, "bgm_bnn_logpost");
   if (rc) return rc;
-  const int ids[3] = {BNN_G, BNN_H, BNN_F};
   BnwRowsArgs a{};
-  bnw_nets(s, ids, 3, a.m);
-  const int n_blocks = (int)((n + bs - 1) / bs), tpb = (bs + BNW_RT - 1) / BNW_RT;
+  bnw_nets(s, kGhf, 3, a.m);
+  const BnnRows r = bnn_rows(c.n, c.block_rows, c.block0, 0);
   BnwPlan pl;
-  rc = bnw_plan(h, s, a.m, n_blocks, n_blocks * tpb, pl, stream);
+  rc = bnw_plan(h, s, a.m, r.n_blocks, r.n_blocks * bnw_tiles(r.bs), pl, stream);
   if (rc) return rc;
   if ((rc = bnw_pack(pl.b, a.m, 0, stream))) return rc;
-  a.mp = a.m.dev;
-  bnw_noise(a.m, pl.b->dw, n_blocks, 1, block0, seed, stream_id, 0u, stream);
+  bnw_noise(a.m, pl.b->dw, r, 1, c.seed, c.stream_id, stream);
   BnwBatch bt;
-  rc = bnw_batch(s, pl.b, n_blocks, bt, stream);
+  rc = bnw_batch(s, pl.b, r.n_blocks, bt, stream);
   if (rc) return rc;
   if (bt.on) {                          // the call's batch = a block of rows: its statistics (slot 1 = the states themselves)
-    bnw_stats(bt, z, n, 0, s->q, bs, 0, 0, 0.0f, nullptr, seed, 0, x, true, stream);
+    BnwStatArgs sa = bnw_stat_args(bt, r, s->q, c.seed);
+    sa.z = c.z; sa.x = c.x; sa.xstats = bt.xstats;
+    bnw_stats(sa, stream);
     a.stats = bt.parity(0); a.xstats = bt.xstats;
   }
   if (s->bp_on) {                       // conditional prior: one noisy call of the prior net for this evaluation (bprior_api.hip)
-    if ((rc = bprior_rows(h, s, n, bs, block0, seed, stream_id, 1, stream))) return rc;
+    if ((rc = bprior_rows(h, s, c.n, r.bs, c.block0, c.seed, c.stream_id, 1, stream))) return rc;
     a.prior = s->bp_rows; a.prior_stride = 0;
   }
-  a.dw = pl.b->dw; a.n_calls = 1; a.x = x; a.y = y; a.v = v; a.z = const_cast<float *>(z); a.n = n; a.row_base = 0;
-  a.bs = bs; a.block0 = block0; a.tiles_per_block = tpb; a.n_items = n_blocks * tpb; a.mode = 0;
-  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.stream0 = stream_id; a.out = out; a.ws = pl.b->ws; a.ws_stride = pl.ws_stride;
-  hipLaunchKernelGGL(bnw_rows_kernel, dim3(pl.grid), dim3(BNN_THREADS), BNW_LDS_BYTES, stream, a);
+  bnw_rows_args(a, pl, r, 1, c.seed);
+  a.x = c.x; a.y = c.y; a.v = c.v; a.z = const_cast<float *>(c.z); a.mode = 0; a.stream0 = c.stream_id; a.out = c.out;
+  bnw_launch_rows(pl, a, stream);
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;
 }
 
-namespace {
-int bnw_effects_of(const BnwNets &mf, const BnwPlan &pl, float *dw_eff, const float *z, long long n, int bs, int n_blocks, int block0, long long row_base,
-                   int n_doses, const float *xvals, uint64_t seed, uint32_t stream0, uint32_t it_noise, int sample_y, double *sum_out,
-                   long long sum_stride, float *ite_out, long long ite_stride, hipStream_t stream, const double *stats = nullptr) {
-  bnw_noise(mf, dw_eff, n_blocks, n_doses, block0, seed, stream0, 1u, stream);
-  BnwEffArgs e{};
-  e.stats = stats;
-  e.m = mf; e.mp = mf.dev; e.dw = dw_eff; e.z = z; e.n = n; e.row_base = row_base; e.bs = bs; e.block0 = block0;
-  e.tiles_per_block = (bs + BNW_RT - 1) / BNW_RT; e.n_items = n_blocks * e.tiles_per_block; e.n_doses = n_doses; e.xvals = xvals;
-  e.k0 = (uint32_t)seed; e.k1 = (uint32_t)(seed >> 32); e.stream0 = stream0; e.it_noise = it_noise; e.sample_y = sample_y;
-  e.sum_out = sum_out; e.sum_stride = sum_stride; e.ite_out = ite_out; e.ite_stride = ite_stride;
-  e.ws = pl.b->ws; e.ws_stride = pl.ws_stride;
-  hipLaunchKernelGGL(bnw_effects_kernel, dim3(std::max(1, std::min(e.n_items, pl.grid))), dim3(BNN_THREADS), BNW_LDS_BYTES, stream, e);
-  BGM_HIP_CHECK(hipGetLastError());
-  return BGM_OK;
-}
-}  // namespace
-
-int bnw_mh_run(bgm_handle *h, BnnState *s, const bgm_bnn_mh_args *g, hipStream_t stream) {
+int bnw_mh_run(bgm_handle *h, BnnState *s, const bgm_bnn_mh_args &g, hipStream_t stream) {
   int rc = bnw_need(s, "bgm_bnn_mh_run");
   if (rc) return rc;
-  const int ids[3] = {BNN_G, BNN_H, BNN_F}, idf[1] = {BNN_F};
   BnwRowsArgs a{};
-  bnw_nets(s, ids, 3, a.m);
+  bnw_nets(s, kGhf, 3, a.m);
   BnwNets mf;
-  bnw_nets(s, idf, 1, mf);
-  const long long n = g->n;
-  const int bs = g->block_rows, n_blocks = (int)((n + bs - 1) / bs), tpb = (bs + BNW_RT - 1) / BNW_RT, q = s->q;
-  const int n_doses = g->effect == 1 ? g->n_doses : (g->effect == 2 ? 2 : 0);
+  bnw_nets(s, kF, 1, mf);
+  const BnnRows r = bnn_rows(g);
+  const int n_blocks = r.n_blocks, q = s->q, n_doses = bnn_effect_doses(g.effect, g.n_doses);
   BnwPlan pl;
   // one buffer: [2 sets per block of g | h | f] then [n_doses sets per block of f]
   const size_t mh_floats = (size_t)2 * n_blocks * a.m.set_floats, eff_floats = (size_t)n_blocks * n_doses * mf.set_floats;
-  rc = bnw_plan(h, s, a.m, (long long)((mh_floats + eff_floats) / std::max<long long>(1, a.m.set_floats) + 2), n_blocks * tpb, pl, stream);
+  rc = bnw_plan(h, s, a.m, (long long)((mh_floats + eff_floats) / std::max<long long>(1, a.m.set_floats) + 2), n_blocks * bnw_tiles(r.bs), pl, stream);
   if (rc) return rc;
   if ((rc = bnw_pack(pl.b, a.m, 0, stream)) || (rc = bnw_pack(pl.b, mf, ((size_t)a.m.set_floats + 63) & ~(size_t)63, stream))) return rc;
-  a.mp = a.m.dev;
-  float *dw_eff = pl.b->dw + ((mh_floats + 63) & ~(size_t)63);
-  a.dw = pl.b->dw; a.n_calls = 2; a.x = g->x_dev; a.y = g->y_dev; a.v = g->v_dev; a.z = g->state_dev; a.n = n; a.row_base = g->row_base;
-  a.bs = bs; a.block0 = g->block0; a.tiles_per_block = tpb; a.n_items = n_blocks * tpb; a.mode = 1;
-  a.q_sd = g->q_sd; a.q_sd_blocks = g->q_sd_blocks_dev;
-  a.k0 = (uint32_t)g->seed; a.k1 = (uint32_t)(g->seed >> 32); a.acc_count = g->acc_count_dev;
-  a.ws = pl.b->ws; a.ws_stride = pl.ws_stride;
+  bnw_rows_args(a, pl, r, 2, g.seed);
+  a.x = g.x_dev; a.y = g.y_dev; a.v = g.v_dev; a.z = g.state_dev; a.mode = 1;
+  a.q_sd = g.q_sd; a.q_sd_blocks = g.q_sd_blocks_dev; a.acc_count = g.acc_count_dev;
   BnwBatch bt;
   rc = bnw_batch(s, pl.b, n_blocks, bt, stream);
   if (rc) return rc;
   a.xstats = bt.xstats;
+  BnwStatArgs sa = bnw_stat_args(bt, r, q, g.seed);
+  sa.z = g.state_dev; sa.q_sd = g.q_sd; sa.q_sd_blocks = g.q_sd_blocks_dev; sa.x = g.x_dev;
   // effects of the draw kept by iteration it_kept; batch statistics: those of the states AFTER its accept step = slot 1 of the
   // statistics pass in front of the next iteration (parity `par`)
+  BnwEffects eff = bnw_effects_begin(mf, pl, pl.b->dw + ((mh_floats + 63) & ~(size_t)63), r, g.seed, g.sample_y);
   auto effects = [&](int it_kept, int par) -> int {
-    const int d = it_kept - g->burn_in;
-    return bnw_effects_of(mf, pl, dw_eff, g->state_dev, n, bs, n_blocks, g->block0, g->row_base, n_doses,
-                          g->effect == 1 ? g->x_values_dev : pl.b->pair, g->seed, 0x40000000u + (uint32_t)d * (uint32_t)n_doses, (uint32_t)it_kept,
-                          g->sample_y, g->effect == 1 ? g->adrf_sum_dev + d : nullptr, g->n_keep, g->effect == 2 ? g->ite_dev + d : nullptr,
-                          g->n_keep, stream, bt.on ? bt.parity(par) : nullptr);
+    return bnw_effects_of(eff, bnn_effect_slot(g, s->pair_dev, it_kept - g.burn_in), g.state_dev, bt.parity(par), (uint32_t)it_kept, stream);
   };
-  auto kept = [&](int it) { return g->effect && it >= g->burn_in && it - g->burn_in < g->n_keep; };
-  for (int i = 0; i < g->n_iters; ++i) {
-    const int it = g->it_begin + i;
-    bnw_noise(a.m, pl.b->dw, n_blocks, 2, g->block0, g->seed, 2u * (uint32_t)it, 1u, stream);
-    a.it = it; a.init = (i == 0 && g->init) ? 1 : 0;
+  for (int i = 0; i < g.n_iters; ++i) {
+    const int it = g.it_begin + i;
+    bnw_noise(a.m, pl.b->dw, r, 2, g.seed, 2u * (uint32_t)it, stream);
+    a.it = it; a.init = (i == 0 && g.init) ? 1 : 0;
     if (bt.on) {
-      bnw_stats(bt, g->state_dev, n, g->row_base, q, bs, it, a.init, g->q_sd, g->q_sd_blocks_dev, g->seed, i & 1, g->x_dev, i == 0, stream);
-      if (i > 0 && kept(it - 1) && (rc = effects(it - 1, i & 1))) return rc;
+      sa.it = it; sa.init = a.init; sa.par = i & 1; sa.xstats = i == 0 ? bt.xstats : nullptr;
+      bnw_stats(sa, stream);
+      if (i > 0 && bnn_kept_effect(g, it - 1) && (rc = effects(it - 1, i & 1))) return rc;
       a.stats = bt.parity(i & 1);
     }
     if (s->bp_on) {                     // the two evaluations' own calls of the prior net (streams 2 it, 2 it + 1)
-      if ((rc = bprior_rows(h, s, n, bs, g->block0, g->seed, 2u * (uint32_t)it, 2, stream))) return rc;
-      a.prior = s->bp_rows; a.prior_stride = n * (long long)(q + 2);
+      if ((rc = bprior_rows(h, s, r.n, r.bs, g.block0, g.seed, 2u * (uint32_t)it, 2, stream))) return rc;
+      a.prior = s->bp_rows; a.prior_stride = r.n * (long long)(q + 2);
     }
-    a.acc_blocks = g->acc_blocks_dev ? g->acc_blocks_dev + (long long)i * n_blocks : nullptr;
-    hipLaunchKernelGGL(bnw_rows_kernel, dim3(pl.grid), dim3(BNN_THREADS), BNW_LDS_BYTES, stream, a);
-    const int d = it - g->burn_in;
-    if (d >= 0 && d < g->n_keep) {
-      if (g->draws_dev)
-        BGM_HIP_CHECK(hipMemcpyAsync(g->draws_dev + (long long)d * n * q, g->state_dev, sizeof(float) * n * q, hipMemcpyDeviceToDevice, stream));
-      if (!bt.on && g->effect && (rc = effects(it, 0))) return rc;
-    }
+    a.acc_blocks = g.acc_blocks_dev ? g.acc_blocks_dev + (long long)i * n_blocks : nullptr;
+    bnw_launch_rows(pl, a, stream);
+    if ((rc = bnn_keep_draw(g, bnn_kept(g, it), q, stream))) return rc;
+    if (!bt.on && bnn_kept_effect(g, it) && (rc = effects(it, 0))) return rc;
   }
-  if (bt.on && g->n_iters > 0 && kept(g->it_begin + g->n_iters - 1)) {      // statistics of the final states: one more pass (its proposals are not used)
-    const int i = g->n_iters;
-    bnw_stats(bt, g->state_dev, n, g->row_base, q, bs, g->it_begin + i, 0, g->q_sd, g->q_sd_blocks_dev, g->seed, i & 1, g->x_dev, false, stream);
-    if ((rc = effects(g->it_begin + i - 1, i & 1))) return rc;
+  if (bt.on && g.n_iters > 0 && bnn_kept_effect(g, g.it_begin + g.n_iters - 1)) {      // statistics of the final states: one more pass (its proposals are not used)
+    const int i = g.n_iters;
+    sa.it = g.it_begin + i; sa.init = 0; sa.par = i & 1; sa.xstats = nullptr;
+    bnw_stats(sa, stream);
+    if ((rc = effects(g.it_begin + i - 1, i & 1))) return rc;
   }
   BGM_HIP_CHECK(hipGetLastError());
 #ifdef BNW_PROF
@@ -272,82 +262,77 @@ int bnw_mh_run(bgm_handle *h, BnnState *s, const bgm_bnn_mh_args *g, hipStream_t
   return BGM_OK;
 }
 
-int bnw_effects(bgm_handle *h, BnnState *s, const float *draws, int64_t n, int32_t bs, int32_t block0, int64_t row_base, int32_t n_keep, int32_t it0,
-                uint64_t seed, int32_t effect, int32_t sample_y, const float *x_values, int32_t n_doses, double *adrf_sum, float *ite,
-                hipStream_t stream) {
+int bnw_effects(bgm_handle *h, BnnState *s, const BnnEffectsCall &c, hipStream_t stream) {
   int rc = bnw_need(s, "bgm_bnn_effects");
   if (rc) return rc;
-  const int idf[1] = {BNN_F};
   BnwNets mf;
-  bnw_nets(s, idf, 1, mf);
-  const int n_blocks = (int)((n + bs - 1) / bs), tpb = (bs + BNW_RT - 1) / BNW_RT, nd = effect == 1 ? n_doses : 2, q = s->q;
+  bnw_nets(s, kF, 1, mf);
+  const BnnRows r = bnn_rows(c);
+  const int nd = bnn_effect_doses(c.effect, c.n_doses), q = s->q;
   BnwPlan pl;
-  rc = bnw_plan(h, s, mf, (long long)n_blocks * nd, n_blocks * tpb, pl, stream);
+  rc = bnw_plan(h, s, mf, (long long)r.n_blocks * nd, r.n_blocks * bnw_tiles(r.bs), pl, stream);
   if (rc) return rc;
   if ((rc = bnw_pack(pl.b, mf, 0, stream))) return rc;
   BnwBatch bt;
-  rc = bnw_batch(s, pl.b, n_blocks, bt, stream);
+  rc = bnw_batch(s, pl.b, r.n_blocks, bt, stream);
   if (rc) return rc;
-  for (int d = 0; d < n_keep; ++d) {
-    const float *zd = draws + (long long)d * n * q;
-    if (bt.on) bnw_stats(bt, zd, n, row_base, q, bs, d, 0, 0.0f, nullptr, seed, d & 1, nullptr, false, stream);      // statistics of this draw (slot 1)
-    rc = bnw_effects_of(mf, pl, pl.b->dw, zd, n, bs, n_blocks, block0, row_base, nd, effect == 1 ? x_values : pl.b->pair, seed,
-                        0x40000000u + (uint32_t)d * (uint32_t)nd, (uint32_t)(it0 + d), sample_y, effect == 1 ? adrf_sum + d : nullptr, n_keep,
-                        effect == 2 ? ite + d : nullptr, n_keep, stream, bt.on ? bt.parity(d & 1) : nullptr);
-    if (rc) return rc;
+  BnwStatArgs sa = bnw_stat_args(bt, r, q, c.seed);
+  BnwEffects eff = bnw_effects_begin(mf, pl, pl.b->dw, r, c.seed, c.sample_y);
+  for (int d = 0; d < c.n_keep; ++d) {
+    const float *zd = c.draws + (long long)d * c.n * q;
+    if (bt.on) { sa.z = zd; sa.it = d; sa.par = d & 1; bnw_stats(sa, stream); }      // statistics of this draw (slot 1)
+    if ((rc = bnw_effects_of(eff, bnn_effect_slot(c, s->pair_dev, d), zd, bt.parity(d & 1), (uint32_t)(c.it0 + d), stream))) return rc;
   }
   return BGM_OK;
 }
 
-int bnw_evaluate(bgm_handle *h, BnnState *s, const float *x, const float *y, const float *v, float *z, int32_t encode, int64_t n, const float *x_values,
-                 int32_t n_doses, uint64_t seed, uint32_t stream_id, double *sums, double *dose_sums, float *ite, hipStream_t stream) {
+int bnw_evaluate(bgm_handle *h, BnnState *s, const BnnEvalCall &c, hipStream_t stream) {
   int rc = bnw_need(s, "bgm_bnn_evaluate");
   if (rc) return rc;
-  const int ids[4] = {BNN_G, BNN_H, BNN_F, BNN_E}, idf[1] = {BNN_F};
   BnwRowsArgs a{};
-  bnw_nets(s, ids, 4, a.m);
+  bnw_nets(s, kGhfe, 4, a.m);
   BnwNets mf;
-  bnw_nets(s, idf, 1, mf);
-  const int nd = dose_sums ? n_doses : (ite ? 2 : 0);
-  const int bs = (int)n, tpb = (bs + BNW_RT - 1) / BNW_RT;        // the whole panel is ONE block (base.py:534-570)
+  bnw_nets(s, kF, 1, mf);
+  const long long n = c.n;
+  const int nd = c.dose_sums ? c.n_doses : (c.ite ? 2 : 0);
+  const BnnRows r = bnn_rows(n, (int)n, 0, 0);        // the whole panel is ONE block (base.py:534-570)
   BnwPlan pl;
   const size_t all_floats = (size_t)a.m.set_floats, eff_floats = (size_t)nd * mf.set_floats;
-  rc = bnw_plan(h, s, a.m, (long long)((all_floats + eff_floats) / std::max<long long>(1, a.m.set_floats) + 2), tpb, pl, stream);
+  rc = bnw_plan(h, s, a.m, (long long)((all_floats + eff_floats) / std::max<long long>(1, a.m.set_floats) + 2), bnw_tiles(r.bs), pl, stream);
   if (rc) return rc;
   if ((rc = bnw_pack(pl.b, a.m, 0, stream)) || (rc = bnw_pack(pl.b, mf, ((size_t)a.m.set_floats + 63) & ~(size_t)63, stream))) return rc;
-  a.mp = a.m.dev;
-  float *dw_eff = pl.b->dw + ((all_floats + 63) & ~(size_t)63);
-  bnw_noise(a.m, pl.b->dw, 1, 1, 0, seed, stream_id, 0u, stream);
-  a.dw = pl.b->dw; a.n_calls = 1; a.x = x; a.y = y; a.v = v; a.z = z; a.n = n; a.row_base = 0; a.bs = bs; a.block0 = 0;
-  a.tiles_per_block = tpb; a.n_items = tpb; a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.stream0 = stream_id;
-  a.ws = pl.b->ws; a.ws_stride = pl.ws_stride;
+  bnw_noise(a.m, pl.b->dw, r, 1, c.seed, c.stream_id, stream);
+  bnw_rows_args(a, pl, r, 1, c.seed);
+  a.x = c.x; a.y = c.y; a.v = c.v; a.z = c.z; a.stream0 = c.stream_id;
   BnwBatch bt;                          // "batch": the whole panel is the batch of every call
   rc = bnw_batch(s, pl.b, 1, bt, stream);
   if (rc) return rc;
-  if (encode) {
+  if (c.encode) {
     if (bt.on) {
       hipLaunchKernelGGL(bnw_colstats_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 256), (unsigned)std::min(s->p, 1024)), dim3(256), 0, stream,
-                         v, (long long)n, s->p, bt.vstats);
+                         c.v, n, s->p, bt.vstats);
       a.vstats = bt.vstats;
     }
     a.mode = 3;
-    hipLaunchKernelGGL(bnw_rows_kernel, dim3(pl.grid), dim3(BNN_THREADS), BNW_LDS_BYTES, stream, a);
+    bnw_launch_rows(pl, a, stream);
     a.vstats = nullptr;
   }
-  if (bt.on && (sums || nd)) {          // statistics of z (slot 1) and of x
-    bnw_stats(bt, z, n, 0, s->q, bs, 0, 0, 0.0f, nullptr, seed, 0, x, x != nullptr, stream);
+  if (bt.on && (c.sums || nd)) {          // statistics of z (slot 1) and of x
+    BnwStatArgs sa = bnw_stat_args(bt, r, s->q, c.seed);
+    sa.z = c.z; sa.x = c.x; sa.xstats = c.x ? bt.xstats : nullptr;
+    bnw_stats(sa, stream);
     a.stats = bt.parity(0); a.xstats = bt.xstats;
   }
-  if (sums) {
-    BGM_HIP_CHECK(hipMemsetAsync(sums, 0, 3 * sizeof(double), stream));
-    a.mode = 2; a.sums = sums;
-    hipLaunchKernelGGL(bnw_rows_kernel, dim3(pl.grid), dim3(BNN_THREADS), BNW_LDS_BYTES, stream, a);
+  if (c.sums) {
+    BGM_HIP_CHECK(hipMemsetAsync(c.sums, 0, 3 * sizeof(double), stream));
+    a.mode = 2; a.sums = c.sums;
+    bnw_launch_rows(pl, a, stream);
   }
   if (nd) {
-    if (dose_sums) BGM_HIP_CHECK(hipMemsetAsync(dose_sums, 0, sizeof(double) * nd, stream));
-    rc = bnw_effects_of(mf, pl, dw_eff, z, n, bs, 1, 0, 0, nd, dose_sums ? x_values : pl.b->pair, seed, stream_id + 1u, 0u, 0, dose_sums, 1,
-                        dose_sums ? nullptr : ite, 1, stream, bt.on ? bt.parity(0) : nullptr);
-    if (rc) return rc;
+    if (c.dose_sums) BGM_HIP_CHECK(hipMemsetAsync(c.dose_sums, 0, sizeof(double) * nd, stream));
+    BnwEffects eff = bnw_effects_begin(mf, pl, pl.b->dw + ((all_floats + 63) & ~(size_t)63), r, c.seed, 0);
+    const BnnEffectSlot sl{nd, c.dose_sums ? c.x_values : s->pair_dev, c.stream_id + 1u, c.dose_sums, c.dose_sums ? nullptr : c.ite, 1};
+    if ((rc = bnw_effects_of(eff, sl, c.z, bt.parity(0), 0u, stream))) return rc;
   }
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;

@@ -171,6 +171,15 @@ BGM_API int bgm_bnn_set_prior(bgm_handle *h, const bgm_prior_config *cfg, const 
  * Built for the sessions the default-shape kernels serve (inference-mode input normalisation, default widths); BGM_E_UNSUPPORTED otherwise
  * and for mode 1 (there is no bf16 form of this family).  The minibatch steps and bgm_bnn_evaluate stay fp32. */
 BGM_API int bgm_bnn_set_precision(bgm_handle *h, int32_t mode);
+/* Which kernel family serves the sampling calls of the open Bayesian-network session, decided from its shapes and normalisation alone
+ * (no device work):
+ *   0  bnf  the default-shape kernels with inference-mode input normalisation (csrc/bnf_kernels.h): the family that has the split
+ *           precision of bgm_bnn_set_precision and runs a rank's share of one block (bgm_bnn_mh_args::block_row0 > 0);
+ *   1  bns  batch statistics on LDS fragments (csrc/bnn_sample_kernels.h: hidden widths <= 64, inputs <= 208);
+ *   2  bnw  any width (csrc/bnw_kernels.h).
+ * A single call may still run on the session's second family (1 or 2): bgm_bnn_evaluate always, and an effects call of more than 256
+ * doses; that does not move this answer.  BGM_E_STATE without a session (bgm_bnn_begin). */
+BGM_API int bgm_bnn_sampling_family(bgm_handle *h, int32_t *family);
 BGM_API int bgm_destroy(bgm_handle *h);
 
 /* Declare the model shape.  Synchronous.  replaces: CausalBGM.__init__ network

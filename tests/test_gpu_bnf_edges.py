@@ -194,6 +194,23 @@ def test_shapes_inside_the_table_are_served(z_dims, p):
     assert E.plan(sum(z_dims), p, z_dims[0], z_dims[1]).served
     with _case_session(_shape_case(z_dims, p), "fp32") as eng:
         assert eng.serves_block_shares()
+        assert eng.sampling_family() == "bnf"
+
+
+def _check_refusals_outside_the_family(eng, c, args, z):
+    """Split precision and a share of one block exist on the default-shape kernels only; a refusal leaves the session and the states as
+    they were."""
+    family = eng.sampling_family()
+    assert family != "bnf" and not eng.serves_block_shares()
+    with pytest.raises(RuntimeError, match="split precision exists on the default-shape"):
+        eng.set_precision("f16x3")
+    assert not eng.serves_block_shares()          # (a refused mode is not remembered)
+    assert eng.sampling_family() == family
+    state = _T(z[:10], eng.device)
+    with pytest.raises(RuntimeError, match="share of one block"):
+        eng.mh_run(args[0][:10].contiguous(), args[1][:10].contiguous(), args[2][:10].contiguous(), state, c["bs"], 0, 1, 0, 0.3, c["seed"],
+                   block_row0=5)
+    assert torch.equal(state, _T(z[:10], eng.device))
 
 
 @pytest.mark.parametrize("z_dims,p", E.UNSERVED_SHAPES)
@@ -207,21 +224,59 @@ def test_shapes_outside_the_table_fall_back(z_dims, p):
     _, m64, (z, x, y, v) = E.setup(c)
     with _case_session(c, "fp32") as eng:
         dev = eng.device
-        assert not eng.serves_block_shares()
-        with pytest.raises(RuntimeError, match="split precision exists on the default-shape"):
-            eng.set_precision("f16x3")
-        assert not eng.serves_block_shares()          # (a refused mode is not remembered)
+        assert eng.sampling_family() == "bns"
         args = (_T(x[:, 0], dev), _T(y[:, 0], dev), _T(v, dev))
+        _check_refusals_outside_the_family(eng, c, args, z)
+        assert eng.sampling_family() == "bns"
         got = eng.logpost(*args, _T(z, dev), c["bs"], E.LP_SEED, E.LP_STREAM, block0=E.LP_BLOCK0).cpu().numpy()
         ref = OB.log_posterior_blocks(m64, f64(x), f64(y), f64(v), f64(z), c["bs"], E.LP_SEED, E.LP_STREAM, block0=E.LP_BLOCK0)
         e = np.abs(got - ref).max()
         _note("C", "fp32", "%s fallback logpost" % c["name"], e, 2e-3 * np.abs(ref).max())
         assert e < 2e-3 * np.abs(ref).max(), e
-        state = _T(z[:10], dev)
-        with pytest.raises(RuntimeError, match="share of one block"):
-            eng.mh_run(args[0][:10].contiguous(), args[1][:10].contiguous(), args[2][:10].contiguous(), state, c["bs"], 0, 1, 0, 0.3, c["seed"],
-                       block_row0=5)
-        assert torch.equal(state, _T(z[:10], dev))
+
+
+def test_widths_outside_the_fragment_kernels_go_to_the_any_width_family():
+    """g_units = [128, 96]: no LDS-fragment family holds a hidden width above 64, so the session samples on the any-width kernels
+    (csrc/bnw_kernels.h) -- with the same two refusals as every session outside the default-shape family."""
+    from test_gpu_bnf import _model, _panel
+    units = dict(g_units=[128, 96])
+    c = E.case("C-bnw", (1, 1, 1, 7), 20, 40, 24)
+    m = _model(False, z_dims=c["z_dims"], p=c["p"], **units)
+    z, x, y, v = _panel(m, c["n"])
+    with _session(m, **units) as eng:
+        assert eng.sampling_family() == "bnw"
+        assert not eng.serves_block_shares()
+        args = (_T(x[:, 0], eng.device), _T(y[:, 0], eng.device), _T(v, eng.device))
+        _check_refusals_outside_the_family(eng, c, args, z)
+        assert eng.sampling_family() == "bnw"
+
+
+def test_sampling_family_needs_a_session():
+    from bayesgm_amd.bnn_engine import BnnEngine
+    eng = BnnEngine(50, (1, 1, 1, 7), False, kl_weight=1e-4, max_batch=32, norm_mode=1)
+    try:
+        with pytest.raises(RuntimeError, match="no session"):
+            eng.sampling_family()
+        assert not eng.serves_block_shares()
+    finally:
+        eng.close()
+
+
+def test_the_capability_query_leaves_the_precision_alone():
+    """serves_block_shares() asks the library for the session's family; it does not pass through the precision switch, so the
+    remembered precision and the next log posterior are the ones from before the query."""
+    c = _shape_case((1, 1, 1, 7), 50)
+    _, _, (z, x, y, v) = E.setup(c)
+    for mode in MODES:
+        with _case_session(c, mode) as eng:
+            dev = eng.device
+            args = (_T(x[:, 0], dev), _T(y[:, 0], dev), _T(v, dev), _T(z, dev))
+            run = lambda: eng.logpost(*args, c["bs"], E.LP_SEED, E.LP_STREAM, block0=E.LP_BLOCK0)
+            before, prec = run(), getattr(eng, "_precision", "fp32")
+            assert prec == mode
+            assert eng.serves_block_shares()
+            assert getattr(eng, "_precision", "fp32") == prec
+            assert torch.equal(run(), before)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -236,6 +291,7 @@ def test_dose_counts(n_doses, mode):
     xs = np.linspace(0.0, 3.0, n_doses).astype(np.float32) if n_doses > 1 else np.array([1.5], np.float32)
     with _case_session(c, mode) as eng:
         got = eng.effects(_T(z[None], eng.device), c["bs"], seed, it0=3, x_values=xs, sample_y=True, row_base=40, block0=1).cpu().numpy()
+        assert eng.sampling_family() == "bnf"          # (the one call that went elsewhere does not move the session)
     ref = OB.effects_draw(m64, f64(z), f64(xs), 0, 3, True, seed, c["bs"], block0=1, row_base=40).mean(axis=1)
     assert got.shape == (n_doses, 1)
     e = np.abs(got[:, 0] - ref).max()
