@@ -9,8 +9,8 @@ rate) and frozen afterwards.  The kernels are csrc/causal_hmc_kernels.h.  Nothin
 from its own burn-in draws, in the windows of ``mass_windows``, and frozen afterwards; the step table restarts its Robbins-Monro gain
 at every change of the metric (``mass_schedule``).
 
-``predict_individual``: the option checks, the row blocks of ``interval='quantile'``, the finalisation of the per-row moments and the
-subgroup formula (``group_dose_response``) are at the end of the module.
+``predict_individual``: the option checks, the row blocks of ``interval='quantile'`` and ``'tails'``, the size of a tail buffer
+(``tail_size``), the finalisation of the per-row moments and the subgroup formula (``group_dose_response``) are at the end of the module.
 
 ``predict_average``: the option checks, the internal row labels and the combiner of the per-draw label sums into ATE / ATT / ATC
 (``combine_average_effects``) follow them.
@@ -198,17 +198,47 @@ def mass_update(W, state, scale, ref, s1, s2):
 
 
 # ---- predict_individual: the dose-response of every row (csrc/causal_hmc_rowfx_kernels.h) ----------------------------------------
+INTERVALS = ("normal", "quantile", "tails")
+
+
+def check_interval(interval):
+    """interval of predict_individual / predict_new: one of INTERVALS; ValueError otherwise."""
+    if interval not in INTERVALS:
+        raise ValueError("interval must be 'normal' or 'quantile'; got %r (or 'tails': the bounds of 'quantile' from the two tail buffers "
+                         "of every series, kept inside the sampler)" % (interval,))
+
+
+def tail_size(alpha, m):
+    """K of interval='tails': how many of the smallest and of the largest of m retained values the two bounds read.  With q = alpha / 2
+    and 1 - alpha / 2, vi = q * (m - 1) in double, i0 = floor(vi) clamped to [0, m - 1] and i1 = min(i0 + 1, m - 1) -- the arithmetic
+    of bgm_row_mean_quantiles, restated operation for operation and never as a closed form (0.55 * 100 is 55.00000000000001 in double) -- the
+    lower bound reads the i1 + 1 smallest values and the upper one the m - i0 largest: K = min(m, max(i1_lo + 1, m - i0_hi)).
+    K = m (few draws or a wide alpha) keeps everything."""
+    m = int(m)
+    if m < 1:
+        raise ValueError("tail_size: m must be >= 1; got %r" % (m,))
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("tail_size: alpha must be in [0, 1]; got %r" % (alpha,))
+
+    def idx(q):
+        vi = q * float(m - 1)
+        i0 = min(max(int(np.floor(vi)), 0), m - 1)
+        return i0, min(i0 + 1, m - 1)
+    (_, i1_lo), (i0_hi, _) = idx(alpha / 2), idx(1 - alpha / 2)
+    return min(m, max(i1_lo + 1, m - i0_hi))
+
+
 def check_individual(binary, x_values, interval, draw_budget_bytes):
-    """The options of predict_individual that are its own: a continuous treatment, x_values, interval 'normal' or 'quantile', and
-    a draw budget only where draws are stored; ValueError otherwise."""
+    """The options of predict_individual that are its own: a continuous treatment, x_values, interval 'normal', 'quantile' or
+    'tails', and a draw budget only where something of size n_keep or K is stored; ValueError otherwise."""
     if binary:
         raise ValueError("predict_individual is the dose-response of every row under a continuous treatment; a binary treatment has "
                          "its per-row effect already: predict's ITE")
     if x_values is None:
         raise ValueError("predict_individual needs x_values: the doses at which every row's outcome is evaluated")
-    if interval not in ("normal", "quantile"):
-        raise ValueError("interval must be 'normal' or 'quantile'; got %r" % (interval,))
-    if interval == "quantile" and draw_budget_bytes is not None and int(draw_budget_bytes) <= 0:
+    check_interval(interval)
+    if interval != "normal" and draw_budget_bytes is not None and int(draw_budget_bytes) <= 0:
         raise ValueError("draw_budget_bytes must be positive; got %r" % (draw_budget_bytes,))
     if interval == "normal" and draw_budget_bytes is not None:
         raise ValueError("interval='normal' and draw_budget_bytes exclude each other: the moments store no draws and this rank's rows "
@@ -221,12 +251,21 @@ def individual_block_rows(n_keep, n_doses, budget_bytes=None):
     return block_rows(n_keep, n_doses, budget_bytes)
 
 
-def individual_blocks(blocks, n_keep, n_doses, interval, draw_budget_bytes=None):
+def tails_block_rows(k_tail, n_doses, budget_bytes=None):
+    """Rows of one block of predict_individual(interval='tails'): the block's tail buffers [2 x k_tail x n_doses x rows] float32 stay
+    within the budget, rows = budget // (8 * k_tail * n_doses); a multiple of 16 (whole row tiles), at least 16."""
+    return block_rows(2 * int(k_tail), n_doses, budget_bytes)
+
+
+def individual_blocks(blocks, n_keep, n_doses, interval, draw_budget_bytes=None, k_tail=None):
     """The row blocks [(start, stop)] of predict_individual: whole for interval='normal' (nothing of size n_keep is stored), cut to
-    individual_block_rows rows each for 'quantile'."""
+    individual_block_rows rows each for 'quantile' and to tails_block_rows(k_tail, n_doses) rows each for 'tails'."""
     if interval == "normal":
         return list(blocks)
-    rows = individual_block_rows(n_keep, n_doses, draw_budget_bytes)
+    if interval == "tails":
+        rows = tails_block_rows(k_tail, n_doses, draw_budget_bytes)
+    else:
+        rows = individual_block_rows(n_keep, n_doses, draw_budget_bytes)
     return [(s0, min(s0 + rows, e0)) for (b0, e0) in blocks for s0 in range(b0, e0, rows)]
 
 
@@ -363,8 +402,10 @@ def check_new(binary, data_v, data_x, x_values, interval, draw_budget_bytes):
         raise ValueError("predict_new: data_v holds NaN in row %d; missing covariates are not modelled (only the treatment and the "
                          "outcome may be unobserved)" % int(np.flatnonzero(np.isnan(v).any(axis=1))[0]))
     n = v.shape[0]
-    if interval not in ("normal", "quantile"):
-        raise ValueError("interval must be 'normal' or 'quantile'; got %r" % (interval,))
+    check_interval(interval)
+    if binary and interval == "tails":
+        raise ValueError("predict_new: interval='tails' belongs to the dose-response of a continuous treatment; a binary treatment goes "
+                         "the ITE route (one value per row and draw): use interval='quantile'")
     if draw_budget_bytes is not None and int(draw_budget_bytes) <= 0:
         raise ValueError("draw_budget_bytes must be positive; got %r" % (draw_budget_bytes,))
     if not binary:

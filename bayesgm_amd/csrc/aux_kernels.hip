@@ -3,10 +3,12 @@
 // replaces (src/bayesgm/models/causalbgm/base.py):
 //   self.e_net(data_v)                       :479, :538   -> causal_encode_kernel
 //   adrf_draw_sums / n_seen                  :660-663     -> adrf_reduce_kernel
-//   np.mean / np.quantile(axis)              :640-642, :664-666 -> row_mean_quantiles_kernel
+//   np.mean / np.quantile(axis)              :640-642, :664-666 -> row_mean_quantiles_kernel; row_tail_quantiles_kernel (the same
+//                                                                 two quantiles from the tails of causal_hmc_tails_kernels.h)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 
 #include "bgm_host.h"
 #include "gx_host.h"
@@ -161,6 +163,85 @@ __device__ __forceinline__ float np_lerp(float a, float b, double t) {  // numpy
   const double d = (double)b - (double)a;
   const double r = (t >= 0.5) ? (double)b - d * (1.0 - t) : (double)a + d * t;
   return (float)r;
+}
+
+// ---------------------------------------------------------------------------
+// The same two quantiles from the TAILS of every series (causal_hmc_tails_kernels.h): tails [2][K][n_series], tail 0 the K smallest of
+// the series' m values and tail 1 the K largest, each in no particular order.  One thread per series (consecutive threads read
+// consecutive floats of a slot).  The index arithmetic is that of row_mean_quantiles_kernel; the order statistic at sorted index i
+// of the m values is rank i of tail 0 (i < K) or rank i - (m - K) of tail 1 (i >= m - K).
+// ---------------------------------------------------------------------------
+struct RowQuantileIdx { int i0, i1; double t; };
+
+__host__ __device__ inline RowQuantileIdx row_quantile_idx(double q, int m) {
+  const double vi = q * (double)(m - 1);
+  int i0 = (int)floor(vi);
+  i0 = i0 < 0 ? 0 : (i0 > m - 1 ? m - 1 : i0);
+  const int i1 = i0 + 1 > m - 1 ? m - 1 : i0 + 1;
+  return RowQuantileIdx{i0, i1, vi - (double)i0};
+}
+
+// The value of rank r (0-based, ascending) among the K values buf[s * stride].  FROM_TOP walks down from the largest (cheap when r is
+// near K - 1: tail 0, whose needed ranks are its last ones), otherwise up from the smallest (tail 1): one pass over the K slots per
+// DISTINCT value passed, at most K passes; values that compare equal are counted together, so ties cost nothing and change nothing.
+template <bool FROM_TOP>
+__device__ __forceinline__ float row_tail_rank(const float *buf, long long stride, int K, int r) {
+  int remaining = FROM_TOP ? K - r : r + 1;          // the remaining-th largest / smallest
+  float bound = 0.0f, v = FROM_TOP ? -INFINITY : INFINITY;
+  bool bounded = false;
+  for (int pass = 0; pass < K; ++pass) {
+    v = FROM_TOP ? -INFINITY : INFINITY;
+    int cnt = 0;
+    for (int s = 0; s < K; ++s) {
+      const float x = buf[s * stride];
+      if (bounded && !(FROM_TOP ? x < bound : x > bound)) continue;
+      if (FROM_TOP ? x > v : x < v) { v = x; cnt = 1; }
+      else if (x == v) ++cnt;
+    }
+    if (remaining <= cnt || cnt == 0) break;
+    remaining -= cnt;
+    bound = v;
+    bounded = true;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void row_tail_quantiles_kernel(const float *tails, long long n_series, int K, int m, double q_lo,
+                                                                double q_hi, float *lo, float *hi) {
+  const RowQuantileIdx a = row_quantile_idx(q_lo, m), b = row_quantile_idx(q_hi, m);
+  const int shift = m - K;                           // sorted index of tail 1's smallest value
+  for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < n_series; s += (long long)gridDim.x * 256) {
+    const float *t0 = tails + s, *t1 = tails + (long long)K * n_series + s;
+    const float a0 = row_tail_rank<true>(t0, n_series, K, a.i0);
+    const float a1 = a.i1 == a.i0 ? a0 : row_tail_rank<true>(t0, n_series, K, a.i1);
+    const float b0 = row_tail_rank<false>(t1, n_series, K, b.i0 - shift);
+    const float b1 = b.i1 == b.i0 ? b0 : row_tail_rank<false>(t1, n_series, K, b.i1 - shift);
+    lo[s] = np_lerp(a0, a1, a.t);
+    hi[s] = np_lerp(b0, b1, b.t);
+  }
+}
+
+extern "C" int bgm_row_tail_quantiles(bgm_handle *h, const float *tails, int64_t n_series, int32_t k_tail, int32_t m, double q_lo,
+                                      double q_hi, float *lo, float *hi, void *stream_) {
+  if (!h || !tails || !lo || !hi) { bgm_set_error("bgm_row_tail_quantiles: NULL handle / tails_dev / lo_dev / hi_dev"); return BGM_E_INVALID; }
+  if (m <= 0 || !(q_lo >= 0 && q_lo <= 1) || !(q_hi >= 0 && q_hi <= 1)) {
+    bgm_set_error("bgm_row_tail_quantiles: m must be positive and q_lo, q_hi in [0, 1]"); return BGM_E_INVALID;
+  }
+  const RowQuantileIdx a = row_quantile_idx(q_lo, m), b = row_quantile_idx(q_hi, m);
+  const int need = std::min<int>(m, std::max(a.i1 + 1, m - b.i0));
+  if (k_tail < need || k_tail > m) {
+    bgm_set_error("bgm_row_tail_quantiles: k_tail must be in [" + std::to_string(need) + ", m = " + std::to_string(m) + "] for q_lo = " +
+                  std::to_string(q_lo) + ", q_hi = " + std::to_string(q_hi) + " (the " + std::to_string(a.i1 + 1) + " smallest and the " +
+                  std::to_string(m - b.i0) + " largest values are read); got " + std::to_string(k_tail));
+    return BGM_E_INVALID;
+  }
+  if (n_series <= 0) return BGM_OK;
+  BGM_HIP_CHECK(hipSetDevice(h->device));
+  const int grid = (int)std::min<int64_t>((n_series + 255) / 256, (int64_t)h->n_cus * 8);
+  hipLaunchKernelGGL(row_tail_quantiles_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream_, tails, (long long)n_series, k_tail, m, q_lo,
+                     q_hi, lo, hi);
+  BGM_HIP_CHECK(hipGetLastError());
+  return BGM_OK;
 }
 
 __global__ __launch_bounds__(256) void row_mean_quantiles_kernel(const float *in, long long n_rows, int m, int m_pow2,

@@ -70,9 +70,13 @@ using chmc_arg = std::conditional_t<EFFECT == 0, T, const T &>;
 
 // OBS (causal_hmc_obs_kernels.h): rows whose outcome, or outcome and treatment, are not observed (NaN in y / x): chmc_logp_grad
 // leaves their f / h terms out; nothing else of the transition or of the effect pass, which never reads a row's own x or y, differs.
-template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false, bool OBS = false>
+// TAILS (causal_hmc_tails_kernels.h, with ROWS): the rows' values also enter the two tail buffers of their series, row_tails
+// [2][k_tail][n_doses][n] (causal_effects, TAILS); nothing else differs.
+template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false, bool OBS = false, bool TAILS = false>
 __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EFFECT> a, chmc_arg<CausalHmcMassArgs, EFFECT> ma,
-                                         chmc_arg<CausalHmcFxArgs, EFFECT> fx, float *row_mom = nullptr, float *row_y = nullptr) {
+                                         chmc_arg<CausalHmcFxArgs, EFFECT> fx, float *row_mom = nullptr, float *row_y = nullptr,
+                                         float *row_tails = nullptr, int k_tail = 0) {
+  static_assert(!TAILS || ROWS, "TAILS: the tail buffers of the per-row dose-response");
   const CausalHmcMeta &m = a.m;
   const CausalMeta &mf = fx.mf;
   lds_fill(lds, a.blob, m.total);
@@ -203,11 +207,11 @@ __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EF
       if constexpr (EFFECT != 0) if (it >= a.burn_in) {    // (wave-uniform) infer_from_latent_posterior on the state the chain holds after this decision
         int label = 0;
         if constexpr (EFFECT == 4) label = reinterpret_cast<const int *>(fx.ite)[row];
-        causal_effects<KT1, KSL1, 1, EFFECT, true, false, false, true, ROWS>(
+        causal_effects<KT1, KSL1, 1, EFFECT, true, false, false, true, ROWS, TAILS>(
             lds_f, mf, lane_off, g, j, lane, z, rowid, valid, row0, n, (unsigned)it, (long long)(it - a.burn_in), fx.n_keep, fx.sample_y,
             fx.n_doses, fx.x_values,
             ROWS ? nullptr : fx.adrf_partial + slot * (long long)fx.n_doses * fx.n_keep /* unused when EFFECT == 2 */, fx.ite, a.k0, a.k1,
-            nullptr, nullptr, row_mom, row_y, label);
+            nullptr, nullptr, row_mom, row_y, label, row_tails, k_tail);
       }
     }
     if (ok) {

@@ -191,6 +191,44 @@ class CausalEngine(object):
                                                                0 if x_values is None else int(x_values.numel()), _ptr(row_moments),
                                                                _ptr(row_draws), self._stream()), "bgm_causal_hmc_run_row_effects")
 
+    def hmc_run_rows_tails(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
+                           row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
+                           sample_y=True, x_values=None, row_moments=None, row_draws=None, row_tails=None, partial=False):
+        """hmc_run_rows_effects with the two tails of every (row, dose) series kept beside its moments
+        (bgm_causal_hmc_run_row_tails): row_tails [2, K, n_doses, n] float32, in / out across segments, tail 0 the K smallest and
+        tail 1 the K largest of the retained y_i(x_k), each a heap in no sorted order (row_tail_quantiles reads them); 1 <= K <=
+        n_keep.  Chain, moments and row_draws are those of hmc_run_rows_effects bit for bit."""
+        if row_tails is not None and (row_tails.dim() != 4 or row_tails.shape[0] != 2 or row_tails.dtype != torch.float32
+                                      or not row_tails.is_contiguous()):
+            raise ValueError("hmc_run_rows_tails: row_tails must be a contiguous float32 tensor [2, K, n_doses, n]; got %s %r" %
+                             (row_tails.dtype, tuple(row_tails.shape)))
+        n_doses = 0 if x_values is None else int(x_values.numel())
+        if row_tails is not None and tuple(row_tails.shape[2:]) != (n_doses, v.shape[0]):
+            raise ValueError("hmc_run_rows_tails: row_tails must be [2, K, n_doses, n] = [2, K, %d, %d]; got %r" %
+                             (n_doses, v.shape[0], tuple(row_tails.shape)))
+        with self._partial_rows(partial, x, y):
+            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
+                                  s_max, acc_count, draws, n_keep)
+            _lib.check(self.lib.bgm_causal_hmc_run_row_tails(*args, int(bool(sample_y)), _ptr(x_values), n_doses, _ptr(row_moments),
+                                                             _ptr(row_draws), _ptr(row_tails),
+                                                             0 if row_tails is None else int(row_tails.shape[1]), self._stream()),
+                       "bgm_causal_hmc_run_row_tails")
+
+    def row_tail_quantiles(self, tails, m, q_lo, q_hi):
+        """tails [2, K, ...] float32 on the device (hmc_sample's out["tails"]: the K smallest and the K largest of every series' m
+        values) -> (lo, hi), each of shape tails.shape[2:]: the quantiles row_mean_quantiles gives on the m values, bit for bit
+        (bgm_row_tail_quantiles).  K below what (m, q_lo, q_hi) need (causal_hmc.tail_size) raises the library's error."""
+        if tails.dim() < 3 or tails.shape[0] != 2 or tails.dtype != torch.float32:
+            raise ValueError("row_tail_quantiles: tails must be float32 [2, K, ...]; got %s %r" % (tails.dtype, tuple(tails.shape)))
+        tails = tails.contiguous()
+        k_tail, shape = int(tails.shape[1]), tuple(tails.shape[2:])
+        n_series = int(np.prod(shape))
+        lo = torch.empty(shape, device=self.device, dtype=torch.float32)
+        hi = torch.empty_like(lo)
+        _lib.check(self.lib.bgm_row_tail_quantiles(self.h, _ptr(tails), n_series, k_tail, int(m), float(q_lo), float(q_hi), _ptr(lo), _ptr(hi),
+                                                   self._stream()), "bgm_row_tail_quantiles")
+        return lo, hi
+
     def hmc_run_group_effects(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, labels=None, n_labels=0,
                               group_partial=None, **kw):
         """hmc_run with the individual treatment effect of a binary treatment summed by row label inside the sampler
@@ -242,7 +280,8 @@ class CausalEngine(object):
 
     def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
                    adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None, effect=_lib.EFFECT_NONE,
-                   x_values=None, sample_y=True, row_effects=False, row_draws=False, labels=None, n_labels=None, partial=False):
+                   x_values=None, sample_y=True, row_effects=False, row_draws=False, labels=None, n_labels=None, partial=False,
+                   row_tails=None):
         """HMC over the latent posterior of every row, one chain per row with a step size of its own.
 
         adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
@@ -268,7 +307,10 @@ class CausalEngine(object):
         y_i(x_k) of every retained state, is summarised inside the sampler (hmc_run_rows_effects) into row_mean / row_sd
         [n, n_doses] (float64, causal_hmc.row_moments_finalize) without stored draws; row_draws = True also returns them,
         row_draws [n, n_doses, n_keep].  The chain is that of the run without effects, and a row's result depends on (seed,
-        row_base + row, the row's data) alone.
+        row_base + row, the row's data) alone.  row_tails = K (with row_effects, 1 <= K <= n_keep): the K smallest and the K
+        largest values of every (row, dose) series are kept as well (hmc_run_rows_tails) and returned as tails [2, K, n_doses, n],
+        from which row_tail_quantiles gives the exact quantile bounds (K = causal_hmc.tail_size(alpha, n_keep)); chain, moments
+        and row_draws are those of the run without it.
 
         partial = True: NaN in y, or in x and y, marks what a row does not observe (new units): its chain samples p(z | x, v) or
         p(z | v) (logpost_grad).  A row with y observed and x not is refused.  Works without an effect, with EFFECT_ITE and with
@@ -302,7 +344,7 @@ class CausalEngine(object):
         acc = torch.zeros(total, device=dev, dtype=torch.int32)
         draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
         chunk = total if chunk is None else max(1, int(chunk))
-        launch, route_kw, collect = self._hmc_route(n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws)
+        launch, route_kw, collect = self._hmc_route(n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails)
         scale = moments = None
         if diag:
             scale = torch.ones((n, self.q), device=dev, dtype=torch.float32)
@@ -338,7 +380,7 @@ class CausalEngine(object):
     # The result routes of hmc_sample, one per kind of result.  Each checks what is its own, allocates its buffers and returns
     # (launch, kw, collect): the engine method that runs a segment, the keyword arguments it takes besides the common ones, and
     # the function that adds the route's keys to the returned dict.
-    def _hmc_route(self, n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws):
+    def _hmc_route(self, n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails=None):
         kinds = {_lib.EFFECT_NONE: self._route_none, _lib.EFFECT_ADRF: self._route_adrf, _lib.EFFECT_ITE: self._route_ite,
                  _lib.EFFECT_GROUP_ITE: self._route_group_ite}
         if effect not in kinds:
@@ -349,9 +391,11 @@ class CausalEngine(object):
         if row_effects:
             if effect != _lib.EFFECT_NONE:
                 raise ValueError("hmc_sample: row_effects and effect exclude each other (the panel's ADRF is the mean of the rows' curves)")
-            return self._route_rows(n, n_keep, x_values, row_draws)
+            return self._route_rows(n, n_keep, x_values, row_draws, row_tails)
         if row_draws:
             raise ValueError("hmc_sample: row_draws belongs to row_effects=True")
+        if row_tails is not None:
+            raise ValueError("hmc_sample: row_tails belongs to row_effects=True")
         return route
 
     def _evaluate_slots(self, n):
@@ -389,7 +433,7 @@ class CausalEngine(object):
         return (self.hmc_run, dict(effect=_lib.EFFECT_GROUP_ITE, labels=lab, n_labels=n_lab, group_partial=part),
                 lambda out: out.update(group_partial=part, group_sums=self.adrf_reduce(part, n_slots, n_lab, n_keep, 1.0)))
 
-    def _route_rows(self, n, n_keep, x_values, row_draws):
+    def _route_rows(self, n, n_keep, x_values, row_draws, row_tails=None):
         if self.binary:
             raise ValueError("hmc_sample: row_effects is the dose-response of a continuous treatment; a binary treatment has its "
                              "per-row effect already (effect=EFFECT_ITE)")
@@ -398,12 +442,21 @@ class CausalEngine(object):
         xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), self.device)
         mom = torch.zeros((3, xv.numel(), n), device=self.device, dtype=torch.float32)      # ref, s1, s2
         row_y = torch.empty((n, xv.numel(), n_keep), device=self.device, dtype=torch.float32) if row_draws else None
+        tails = None
+        if row_tails is not None:
+            if isinstance(row_tails, bool) or int(row_tails) != row_tails or not 1 <= int(row_tails) <= int(n_keep):
+                raise ValueError("hmc_sample: row_tails must be an integer K with 1 <= K <= n_keep = %d; got %r" % (int(n_keep), row_tails))
+            tails = torch.empty((2, int(row_tails), xv.numel(), n), device=self.device, dtype=torch.float32)      # draw 0 initialises it
 
         def collect(out):
             mean, sd = HM.row_moments_finalize(mom[0], mom[1], mom[2], n_keep)
             out["row_mean"], out["row_sd"] = mean.t().contiguous(), sd.t().contiguous()
             if row_y is not None:
                 out["row_draws"] = row_y
+            if tails is not None:
+                out["tails"] = tails
+        if tails is not None:
+            return self.hmc_run_rows_tails, dict(x_values=xv, row_moments=mom, row_draws=row_y, row_tails=tails), collect
         return self.hmc_run_rows_effects, dict(x_values=xv, row_moments=mom, row_draws=row_y), collect
 
     def encode(self, v):

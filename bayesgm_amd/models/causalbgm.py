@@ -709,6 +709,10 @@ class CausalBGM(object):
         ``interval='quantile'``: the exact ``alpha/2`` and ``1 - alpha/2`` quantiles of the stored draws; rows are sampled in blocks
         whose ``rows x n_doses x n_mcmc x 4`` bytes fit ``draw_budget_bytes`` (default 2 GiB).  ``mean`` and the sd still come from
         the moments, and a chain and its outcome noise depend on the row alone, so the blocks do not change a row's result.
+        ``interval='tails'``: the bounds of ``'quantile'``, bit for bit, without the draws: per row and dose the sampling kernel keeps
+        the ``K`` smallest and the ``K`` largest of the ``n_mcmc`` values (``K = causal_hmc.tail_size(alpha, n_mcmc)``, about
+        ``alpha/2 * n_mcmc + 2``: 16 at the defaults), which is all the two interpolated quantiles read.  Rows are sampled in blocks
+        whose ``rows x n_doses x K x 8`` bytes fit ``draw_budget_bytes``; ``mean``, the sd and ``groups`` as with ``'normal'``.
 
         ``groups`` (int labels [n], optional): ``self.group_dose_response_ = {label: (mean_g, sd_g)}``, the curve of every subgroup
         (causal_hmc.group_dose_response).  Under torch.distributed the rows are sharded by rank and the results gathered."""
@@ -734,21 +738,25 @@ class CausalBGM(object):
         seed = self._begin_sampling(verbose)
         eng = self.engine
         lo_r, hi_r = parallel.shard_range(n_test)
-        blocks = hmc_mod.individual_blocks([(lo_r, hi_r)] if hi_r > lo_r else [], n_mcmc, n_doses, interval, draw_budget_bytes)
-        quantile = interval == 'quantile'
-        res = torch.zeros((4 if quantile else 2, n_test, n_doses), device=eng.device, dtype=torch.float64)      # mean, sd(, lower, upper): this rank's rows filled
+        quantile, tails = interval == 'quantile', interval == 'tails'
+        k_tail = hmc_mod.tail_size(alpha, n_mcmc) if tails else None
+        blocks = hmc_mod.individual_blocks([(lo_r, hi_r)] if hi_r > lo_r else [], n_mcmc, n_doses, interval, draw_budget_bytes, k_tail)
+        res = torch.zeros((4 if quantile or tails else 2, n_test, n_doses), device=eng.device, dtype=torch.float64)      # mean, sd(, lower, upper): this rank's rows filled
 
         def consume(s0, e0, x, out):
             res[0, s0:e0], res[1, s0:e0] = out["row_mean"], out["row_sd"]
             if quantile:
                 _, lo, hi = eng.row_mean_quantiles(out.pop("row_draws").reshape((e0 - s0) * n_doses, n_mcmc), alpha / 2, 1 - alpha / 2)
                 res[2, s0:e0], res[3, s0:e0] = lo.reshape(e0 - s0, n_doses).double(), hi.reshape(e0 - s0, n_doses).double()
+            if tails:      # [2, K, n_doses, rows] -> bounds [n_doses, rows]
+                lo, hi = eng.row_tail_quantiles(out.pop("tails"), n_mcmc, alpha / 2, 1 - alpha / 2)
+                res[2, s0:e0], res[3, s0:e0] = lo.t().double(), hi.t().double()
         self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, row_effects=True, row_draws=quantile,
-                            x_values=x_values, sample_y=sample_y, partial=partial)
+                            x_values=x_values, sample_y=sample_y, partial=partial, **(dict(row_tails=k_tail) if tails else {}))
         res = parallel.all_reduce_sum_(res).cpu().numpy()
         mean, sd = res[0], res[1]
         self.individual_sd_ = sd
-        if quantile:
+        if quantile or tails:
             bounds = np.stack([res[2], res[3]], axis=-1)
         else:
             z = NormalDist().inv_cdf(1.0 - alpha / 2)
@@ -767,11 +775,12 @@ class CausalBGM(object):
         are left in ``self.hmc_row_step_`` / ``self.hmc_row_mass_``) and the outcome net runs inside the sampling kernel.
 
         Continuous treatment (``x_values`` required): what ``predict_individual`` returns, ``(mean [n, n_doses], interval
-        [n, n_doses, 2])`` of y_i(x_k), the sd in ``self.individual_sd_``; ``interval`` and ``draw_budget_bytes`` as there.
+        [n, n_doses, 2])`` of y_i(x_k), the sd in ``self.individual_sd_``; ``interval`` (``'tails'`` included) and
+        ``draw_budget_bytes`` as there.
         Binary treatment: what ``predict`` returns, ``(ite [n], interval [n, 2])``, from the fused ITE kernel; ``interval=
         'quantile'`` gives ``predict``'s quantiles of the ITE draws, ``'normal'`` (default) ``mean -/+ z(1 - alpha/2) * sd`` of
         them (sd in ``self.individual_sd_`` [n]); the [rows x n_mcmc] ITE matrix of a block fits ``draw_budget_bytes`` (default
-        2 GiB).  A row's result depends on (seed, its global row, its data) only; under torch.distributed the rows are sharded by
+        2 GiB); ``'tails'`` is refused (the ITE route keeps no tails).  A row's result depends on (seed, its global row, its data) only; under torch.distributed the rows are sharded by
         rank and the results gathered."""
         binary = bool(self._p['binary_treatment'])
         hmc, x_values, (data_v, data_x, data_y) = self._sampling_options(

@@ -442,6 +442,39 @@ BGM_API int bgm_causal_hmc_run_row_effects(bgm_handle *h, const float *x_dev, co
                                            const float *x_values_dev, int32_t n_doses, float *row_moments_dev, float *row_draws_dev,
                                            void *stream);
 
+/* bgm_causal_hmc_run_row_effects with the two TAILS of every (row, dose) series kept beside its moments: exact quantile bounds per
+ * row without stored draws.  The arguments of bgm_causal_hmc_run_row_effects plus
+ *   row_tails_dev [2 x k_tail x n_doses x n] float32 (required): for series (k, row), slot s of tail t is element
+ *     ((t * k_tail + s) * n_doses + k) * n + row.  After the m retained draws tail 0 holds, as a multiset, the k_tail smallest values
+ *     of the series and tail 1 the k_tail largest; the order of the slots is not defined (each tail is a binary heap whose slot 0 is
+ *     its threshold) -- bgm_row_tail_quantiles reads the order statistics.  In / out across the calls of one run; the iteration
+ *     it == burn_in initialises every series, so the buffer need not be zeroed;
+ *   k_tail, 1 <= k_tail <= n_keep: the least value for the bounds at alpha / 2 and 1 - alpha / 2 is what bgm_row_tail_quantiles
+ *     demands (causal_hmc.tail_size), about alpha / 2 * n_keep + 2.
+ * Chain, noise counters, moments and row_draws_dev are those of bgm_causal_hmc_run_row_effects bit for bit; bgm_causal_hmc_set_mass and
+ * bgm_causal_hmc_set_partial are honoured.  A series' buffers depend on its draw sequence alone -- not on n, the grid, row_base, the
+ * rank count or where the run is cut.  A draw that enters neither tail costs two loads; one that enters costs about 2 log2 k_tail
+ * accesses.  Refusals: those of bgm_causal_hmc_run_row_effects (a binary handle BGM_E_INVALID, the LDS budget BGM_E_UNSUPPORTED), and
+ * BGM_E_INVALID naming row_tails_dev when it is NULL or k_tail when it is outside [1, n_keep].
+ * replaces: nothing in causalbgm/base.py; its intervals are np.quantile over stored draws (:640-642, :664-666). */
+BGM_API int bgm_causal_hmc_run_row_tails(bgm_handle *h, const float *x_dev, const float *y_dev, const float *v_dev, int64_t n,
+                                         int64_t row_base, float *state_dev, float *logp_dev, float *grad_dev, float *step_dev,
+                                         const float *up_dev, const float *dn_dev, int32_t n_table, float s_min, float s_max,
+                                         int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog,
+                                         uint64_t seed, uint32_t *acc_count_dev, float *draws_dev, int32_t n_keep, int32_t sample_y,
+                                         const float *x_values_dev, int32_t n_doses, float *row_moments_dev, float *row_draws_dev,
+                                         float *row_tails_dev, int32_t k_tail, void *stream);
+
+/* The two linear-interpolated quantiles of bgm_row_mean_quantiles from the tails of every series: tails_dev [2 x k_tail x n_series]
+ * float32 (the layout of bgm_causal_hmc_run_row_tails with n_series = n_doses * n, series k * n + row), tail 0 the k_tail smallest of
+ * the series' m values and tail 1 the k_tail largest, in any order -> lo_dev, hi_dev [n_series].  With vi = q (m - 1) in double,
+ * i0 = floor(vi) clamped to [0, m - 1] and i1 = min(i0 + 1, m - 1), a bound is numpy's _lerp of the order statistics i0 and i1 at
+ * vi - i0: bit for bit what bgm_row_mean_quantiles gives on the m values.  The lower bound reads the i1(q_lo) + 1 smallest values
+ * and the upper one the m - i0(q_hi) largest: a k_tail below either (or above m) answers BGM_E_INVALID naming both counts.
+ * replaces: np.quantile(..., axis) at causalbgm/base.py:640-642, 664-666, on the tails instead of the draws. */
+BGM_API int bgm_row_tail_quantiles(bgm_handle *h, const float *tails_dev, int64_t n_series, int32_t k_tail, int32_t m, double q_lo,
+                                   double q_hi, float *lo_dev, float *hi_dev, void *stream);
+
 /* bgm_causal_hmc_run with the individual treatment effect of a binary treatment summed by ROW LABEL inside the sampler: after the
  * accept decision of every iteration it >= burn_in the outcome net is evaluated at x = 1 and x = 0 on the state the chain holds,
  * exactly as bgm_causal_hmc_run_effects (BGM_EFFECT_ITE) evaluates it -- a row's y(1) - y(0) of draw d = it - burn_in is bit for bit
