@@ -16,37 +16,17 @@ extern "C" int bgm_bgm_hmc_run_rows_impute(bgm_handle *h, const bgm_hmc_args *a,
                                            int32_t add_noise, void *stream_) {
   const std::string fn = "bgm_bgm_hmc_run_rows_impute: ";
   const BgmTrajOpts traj{max_trajectory, jitter, n_steps_dev};
+  const BgmImputeOpts opts{moments_dev, cells_dev, slot_dev, k_slots, n_keep, add_noise};
   bool go;
-  int rc = bgm_hmc_rows_check(fn, h, a, up_dev, dn_dev, n_table, s_min, s_max, &traj, &go);
+  int rc = bgm_hmc_impute_check(fn, h, a, up_dev, dn_dev, n_table, s_min, s_max, &traj, opts, &go);
   if (rc || !go) return rc;
-  if (!moments_dev) { bgm_set_error(fn + "NULL pointer moments_dev"); return BGM_E_INVALID; }
-  if (cells_dev && !slot_dev) { bgm_set_error(fn + "cells_dev needs slot_dev"); return BGM_E_INVALID; }
-  if (cells_dev && k_slots < 1) { bgm_set_error(fn + "cells_dev needs k_slots >= 1"); return BGM_E_INVALID; }
-  if (n_keep < 1) { bgm_set_error(fn + "n_keep must be >= 1"); return BGM_E_INVALID; }
-  if (add_noise != 0 && add_noise != 1) { bgm_set_error(fn + "add_noise must be 0 or 1"); return BGM_E_INVALID; }
-  if (a->burn_in < 0 || (long long)a->it_begin + a->n_iters > (long long)a->burn_in + n_keep) {
-    bgm_set_error(fn + "it_begin + n_iters = " + std::to_string((long long)a->it_begin + a->n_iters) + " lies beyond burn_in + n_keep = " +
-                  std::to_string((long long)a->burn_in + n_keep));
-    return BGM_E_INVALID;
-  }
   BgmState *s = bst(h);
-  if (gxb_wanted(s)) {
-    bgm_set_error(fn + "the fused imputation (predictive moments inside the per-chain HMC kernel) exists for trunks [64] x 3 / [64] x 5 "
-                  "with z_dim <= 16; this shape runs on the general-width engine, which has the shared step and stored draws only");
-    return BGM_E_UNSUPPORTED;
-  }
-  if (s->precision != 0) {
-    bgm_set_error(fn + "the fused imputation (predictive moments inside the per-chain HMC kernel) is built for fp32 only, not for split "
-                  "precision (f16x3): sample with bgm_bgm_hmc_run_rows and decode with bgm_bgm_predict_draws");
-    return BGM_E_UNSUPPORTED;
-  }
   hipStream_t stream = (hipStream_t)stream_;
   BGM_HIP_CHECK(hipSetDevice(h->device));
   rc = bgm_bgm_build_blob(h, stream);
   if (rc) return rc;
   BgmImputeHmcKArgs ka{};
-  bgm_hmc_rows_fill(ka, s, a, up_dev, dn_dev, n_table, s_min, s_max, &traj, true);
-  ka.moments = moments_dev; ka.cells = cells_dev; ka.slot = slot_dev; ka.k_slots = k_slots; ka.n_keep = n_keep; ka.add_noise = add_noise;
+  bgm_hmc_impute_fill(ka, s, a, up_dev, dn_dev, n_table, s_min, s_max, &traj, opts);
   const long long tiles = (a->n + 15) / 16;
   return bgm_bgm_dispatch(s, "BGM HMC with per-chain steps and fused imputation", [&](auto v) {
     using V = decltype(v);

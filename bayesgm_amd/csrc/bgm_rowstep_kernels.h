@@ -2,7 +2,7 @@
 //
 // replaces: the one scalar step of tfp.mcmc.SimpleStepSizeAdaptation in tfp_mcmc_sampler (bgm/base.py:798-821), opt-in; the transition
 //   is bgm_hmc_kernel's (bgm_kernels.h) and the rule is causal_hmc_kernel's (causal_hmc_kernels.h): the Robbins-Monro table of
-//   row_adapt.py, ONE fp32 multiply and a clamp after the accept decision.  One body, bgm_hmc_run<..., STEP>, serves the three kernels.
+//   row_adapt.py, ONE fp32 multiply and a clamp after the accept decision.  One body, bgm_hmc_run<..., STEP>, serves the four kernels.
 //
 // STEP 1 (bgm_hmc_rows_kernel) adds to the scalar-step transition: eps is read from row_step[row] when a wave takes up a row tile,
 // lives in a VGPR, is updated after the decision of iteration it < n_table and written back with the state.  state, logp, grad and
@@ -18,8 +18,13 @@
 // STEP 3 (bgm_hmc_rows_impute_kernel; opt-in, bgm_bgm_hmc_run_rows_impute, fp32) adds to STEP 2 a decode pass after the decision of every
 // retained iteration: the predictive value of every missing cell of the state the chain is left in, summed into shifted moments per
 // (row, cell) -- bgm_impute_decode below.  The chain itself is STEP 2's (STEP 1's with the trajectory options off), bit for bit.
+// STEP 4 (bgm_hmc_rows_impute_tails_kernel; opt-in, bgm_bgm_hmc_run_rows_impute_tails, fp32) adds to STEP 3 the two tails of every missing
+// cell that has a slot: the k_tail smallest and the k_tail largest of its predictive values, two heaps in global memory (row_tail_push,
+// row_tails.h), from which bgm_row_tail_quantiles gives the quantile pair of the stored cells bit for bit.  Chain, planes and cells are
+// STEP 3's.
 #pragma once
 #include "bgm_kernels.h"
+#include "row_tails.h"
 
 struct BgmRowHmcKArgs : BgmHmcKArgs {      // STEP 1 (BgmHmcKArgs::step is not read)
   float *row_step;           // [n] step size of every chain, in / out
@@ -39,6 +44,10 @@ struct BgmImputeHmcKArgs : BgmTrajHmcKArgs {  // STEP 3
   int k_slots, n_keep;
   int add_noise;             // 0: the head's mean instead of a draw
 };
+struct BgmImputeTailsHmcKArgs : BgmImputeHmcKArgs {  // STEP 4 (slot and k_slots are required)
+  float *tails;              // [2][k_tail][n][k_slots]: tail t, heap slot s of series row * k_slots + slot[row * p + c]; in / out, never read at d = 0
+  int k_tail;                // 1 .. n_keep
+};
 
 // STEP 3: the predictive value of every MISSING cell of the state a retained transition ends on, summarised where it is made.  The
 // trunk, the head tile and the noise are bgm_predict_kernel's (bgm_kernels.h) -- copied, not shared: that kernel's lambda also serves
@@ -47,8 +56,12 @@ struct BgmImputeHmcKArgs : BgmTrajHmcKArgs {  // STEP 3
 // row j and no other lane touches it: plain loads and stores.  Shifted sums as in causal_hmc_rowfx_kernels.h: plane 0 holds the value at
 // it == burn_in, planes 1 / 2 the sums of (x - ref) and (x - ref)^2 over the retained iterations, so launches cut anywhere add up to the
 // same bits.  Streamed variant: one walk of the head stream exactly as a gradient evaluation makes it, by EVERY wave of the workgroup.
-template <int KTQ, int NTX, int NH, class HS>
-__device__ __forceinline__ void bgm_impute_decode(const BgmImputeHmcKArgs &a, const float *lds, HS &hs, int j, int g, const f32x4 (&z)[KTQ],
+// TAILS (STEP 4, Args = BgmImputeTailsHmcKArgs): after the tile's moment stores the owner of a missing cell with a slot pushes the value
+// into the cell's two heaps, tail 0 (max-heap) first.  The series of cell (row, slot) is row * k_slots + slot, the default route's
+// [n, k_slots] indexing, and two heap slots of a series lie n * k_slots floats apart.  Nothing is carried over the iterations: d, k_tail
+// and the buffer are the whole state.  The tails add no step of the head stream.
+template <int KTQ, int NTX, int NH, bool TAILS = false, class Args, class HS>
+__device__ __forceinline__ void bgm_impute_decode(const Args &a, const float *lds, HS &hs, int j, int g, const f32x4 (&z)[KTQ],
                                                   const BgmX<NTX> &xs, long long row, unsigned rowid, bool ok, int it) {
   const BgmMeta &m = a.m;
   f32x4 h[4], h2[4];
@@ -86,17 +99,19 @@ __device__ __forceinline__ void bgm_impute_decode(const BgmImputeHmcKArgs &a, co
       ref[r] = s1[r] = s2[r] = 0.0f;
       sl[r] = -1;
       if (mine[r] && !first) { ref[r] = mo[r]; s1[r] = mo[plane + r]; s2[r] = mo[2 * plane + r]; }
-      if (mine[r] && a.cells != nullptr) sl[r] = a.slot[cell0 + r];
+      if (mine[r] && (TAILS || a.cells != nullptr)) sl[r] = a.slot[cell0 + r];
     }
     f32x4 ms[2];
     ms[0] = *reinterpret_cast<const f32x4 *>(lds + m.bhd + 16 * tx + 4 * g);
     ms[1] = *reinterpret_cast<const f32x4 *>(lds + m.bhd + 16 * (m.ntx + tx) + 4 * g);
     heads_fwd17(wl, j, g, h, ms);
     const f32x4 e = box_muller4(philox4x32_10(rowid, (unsigned)it, (unsigned)(4 * tx + g), TAG_XNOISE, a.k0, a.k1));
+    [[maybe_unused]] float xt[4];      // (TAILS: the tile's values, pushed after its stores)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float v = softplus_f(ms[1][r]) + BGM_EPS;
       const float xp = a.add_noise ? fmaf(__builtin_sqrtf(v), e[r], ms[0][r]) : ms[0][r];
+      if constexpr (TAILS) xt[r] = xp;
       if (mine[r]) {
         if (first) {
           mo[r] = xp; mo[plane + r] = 0.0f; mo[2 * plane + r] = 0.0f;
@@ -105,7 +120,18 @@ __device__ __forceinline__ void bgm_impute_decode(const BgmImputeHmcKArgs &a, co
           mo[plane + r] = s1[r] + d;
           mo[2 * plane + r] = fmaf(d, d, s2[r]);
         }
-        if (sl[r] >= 0) a.cells[(row * (long long)a.k_slots + sl[r]) * a.n_keep + (it - a.burn_in)] = xp;
+        if (sl[r] >= 0 && (!TAILS || a.cells != nullptr)) a.cells[(row * (long long)a.k_slots + sl[r]) * a.n_keep + (it - a.burn_in)] = xp;
+      }
+    }
+    if constexpr (TAILS) {
+      const long long series = a.n * (long long)a.k_slots;      // floats between two heap slots of a series
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (mine[r] && sl[r] >= 0) {
+          float *t0 = a.tails + row * (long long)a.k_slots + sl[r];
+          row_tail_push<true>(t0, series, a.k_tail, (long long)(it - a.burn_in), xt[r]);
+          row_tail_push<false>(t0 + (long long)a.k_tail * series, series, a.k_tail, (long long)(it - a.burn_in), xt[r]);
+        }
       }
     }
   };
@@ -132,11 +158,12 @@ __device__ __forceinline__ void bgm_impute_decode(const BgmImputeHmcKArgs &a, co
   }
 }
 
-// The transition of the three kernels below, once: bgm_hmc_kernel's (bgm_kernels.h) line for line, and under if constexpr what a rule adds.
+// The transition of the four kernels below, once: bgm_hmc_kernel's (bgm_kernels.h) line for line, and under if constexpr what a rule adds.
 // STEP 1 (BgmRowHmcKArgs): the step per chain.  STEP 2 (BgmTrajHmcKArgs): STEP 1 and the number of leapfrog steps per chain -- the
 // lines on li, n_taken, drift, kick and want_lp, and n_steps written back.  With every step equal and no table STEP 1 gives
 // bgm_hmc_kernel's bits; with max_traj = 0 and no jitter STEP 2 gives STEP 1's.  STEP 3 (BgmImputeHmcKArgs): STEP 2 and the decode pass of
-// bgm_impute_decode after the decision of every retained iteration; the chain is STEP 2's.
+// bgm_impute_decode after the decision of every retained iteration; the chain is STEP 2's.  STEP 4 (BgmImputeTailsHmcKArgs): STEP 3 with
+// the tails of bgm_impute_decode<..., TAILS>.
 template <int KTQ, int NTX, int NH, int WAVES, int PREC, bool X4, int STEP, class Args, class HS>
 __device__ __forceinline__ void bgm_hmc_run(Args a, float *lds, HS &hs) {
   const BgmMeta &m = a.m;
@@ -271,7 +298,7 @@ __device__ __forceinline__ void bgm_hmc_run(Args a, float *lds, HS &hs) {
       if (a.draws != nullptr && it >= a.burn_in && ok)
         bgm_store_z<KTQ>(a.draws + (long long)(it - a.burn_in) * n * m.q, m.q, row, g, z);
       if constexpr (STEP >= 3) {      // (mom, zc and gc are dead here; it >= burn_in is the same for every wave of the launch)
-        if (it >= a.burn_in) bgm_impute_decode<KTQ, NTX, NH>(a, lds, hs, j, g, z, xr, row, rowid, ok, it);
+        if (it >= a.burn_in) bgm_impute_decode<KTQ, NTX, NH, (STEP >= 4)>(a, lds, hs, j, g, z, xr, row, rowid, ok, it);
       }
     }
     if (ok) {
@@ -307,4 +334,12 @@ __global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_impute_kernel(BgmImpu
   constexpr int PREC = 0;
   constexpr bool X4 = false;
   BGM_HMC_KERNEL(3)
+}
+
+// fp32 only (instantiated in bgm_impute_tails_api.hip)
+template <int KTQ, int NTX, int NH, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void bgm_hmc_rows_impute_tails_kernel(BgmImputeTailsHmcKArgs a) {
+  constexpr int PREC = 0;
+  constexpr bool X4 = false;
+  BGM_HMC_KERNEL(4)
 }

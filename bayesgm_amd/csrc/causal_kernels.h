@@ -12,6 +12,7 @@
 // change; HBM is touched again only to emit retained draws / effects.
 #pragma once
 #include "bgm_device.h"
+#include "row_tails.h"
 
 struct CausalMeta {
   int q, p;
@@ -580,49 +581,7 @@ __device__ __forceinline__ float pick_by_group(int g, float v0, float v1, float 
 // [n_keep][n_labels]: adrf_slot[d * n_labels + c] += sum over the tile's valid rows with label c, the labels present in the tile taken
 // in the order of their lowest row, each by ONE DPP row reduction and ONE addition from lane 15.  ite is not touched.
 // TAILS (ROWS only; causal_hmc_tails_kernels.h): the lane also keeps the k_tail smallest and the k_tail largest values of its series
-// in row_tails [2][k_tail][n_doses][n] (row_tail_push).
-//
-// row_tail_push: one tail of one series, a binary heap in global memory with the tail's threshold at slot 0 -- the LARGEST of the K
-// smallest values (MAX_HEAP, tail 0) or the smallest of the K largest (tail 1).  Slot s of the series is buf[s * stride].  Draw d < K
-// appends y at slot d and sifts it up (d = 0 initialises the series: nothing is read); a later draw enters only when it is strictly
-// beyond the threshold, replaces slot 0 and is sifted down.  A draw equal to the threshold stays out, which leaves the multiset
-// right: the value is there already.  Nothing but d, K and y decides where the routine reads or writes: every slot index comes from
-// d < K or from a loop condition `index < K`, never from a stored value, so NaN / Inf can spoil a series' buffer but not leave it.
-// The loops are divergent per lane and hold no wave-level operation.
-template <bool MAX_HEAP>
-__device__ __forceinline__ bool row_tail_before(float a, float b) { return MAX_HEAP ? a > b : a < b; }     // a belongs nearer the root than b
-
-template <bool MAX_HEAP>
-__device__ __forceinline__ void row_tail_push(float *buf, long long stride, int K, long long d, float y) {
-  if (d < (long long)K) {
-    int i = (int)d;
-    while (i > 0) {                                  // sift up: i < K, strictly decreasing
-      const int p = (i - 1) >> 1;
-      const float vp = buf[p * stride];
-      if (!row_tail_before<MAX_HEAP>(y, vp)) break;
-      buf[i * stride] = vp;
-      i = p;
-    }
-    buf[i * stride] = y;
-    return;
-  }
-#ifndef BGM_TAILS_MUTATE_NO_REPLACE                  // (the mutation of DESIGN.md section 4ac: without the replace step the buffers keep the first K draws)
-  if (!row_tail_before<MAX_HEAP>(buf[0], y)) return; // the ONE load of a draw that does not enter
-  int i = 0;
-  for (int c = 1; c < K; c = 2 * i + 1) {            // sift down: c < K, i < c
-    float vc = buf[c * stride];
-    if (c + 1 < K) {
-      const float v2 = buf[(c + 1) * stride];
-      if (row_tail_before<MAX_HEAP>(v2, vc)) { vc = v2; ++c; }
-    }
-    if (!row_tail_before<MAX_HEAP>(vc, y)) break;
-    buf[i * stride] = vc;
-    i = c;
-  }
-  buf[i * stride] = y;
-#endif
-}
-
+// in row_tails [2][k_tail][n_doses][n] (row_tail_push, row_tails.h).
 template <int KT1, int KSL1, int R, int EFFECT, bool GROUPING = true, bool CACHE = false, bool EVAL_ONLY = false, bool L1MASK = true,
           bool ROWS = false, bool TAILS = false>
 __device__ __forceinline__ void causal_effects(const float *lds, const CausalMeta &m, int lane_off, int g, int j,

@@ -34,6 +34,20 @@ def _f32(t, device):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _row_tail_quantiles(eng, tails, m, q_lo, q_hi):
+    """The body of CausalEngine.row_tail_quantiles and BgmEngine.row_tail_quantiles (bgm_row_tail_quantiles)."""
+    if tails.dim() < 3 or tails.shape[0] != 2 or tails.dtype != torch.float32:
+        raise ValueError("row_tail_quantiles: tails must be float32 [2, K, ...]; got %s %r" % (tails.dtype, tuple(tails.shape)))
+    tails = tails.contiguous()
+    k_tail, shape = int(tails.shape[1]), tuple(tails.shape[2:])
+    n_series = int(np.prod(shape))
+    lo = torch.empty(shape, device=eng.device, dtype=torch.float32)
+    hi = torch.empty_like(lo)
+    _lib.check(eng.lib.bgm_row_tail_quantiles(eng.h, _ptr(tails), n_series, k_tail, int(m), float(q_lo), float(q_hi), _ptr(lo), _ptr(hi),
+                                              eng._stream()), "bgm_row_tail_quantiles")
+    return lo, hi
+
+
 class CausalEngine(object):
     """Device-side state of one CausalBGM model: packed weights + kernels."""
 
@@ -218,16 +232,7 @@ class CausalEngine(object):
         """tails [2, K, ...] float32 on the device (hmc_sample's out["tails"]: the K smallest and the K largest of every series' m
         values) -> (lo, hi), each of shape tails.shape[2:]: the quantiles row_mean_quantiles gives on the m values, bit for bit
         (bgm_row_tail_quantiles).  K below what (m, q_lo, q_hi) need (causal_hmc.tail_size) raises the library's error."""
-        if tails.dim() < 3 or tails.shape[0] != 2 or tails.dtype != torch.float32:
-            raise ValueError("row_tail_quantiles: tails must be float32 [2, K, ...]; got %s %r" % (tails.dtype, tuple(tails.shape)))
-        tails = tails.contiguous()
-        k_tail, shape = int(tails.shape[1]), tuple(tails.shape[2:])
-        n_series = int(np.prod(shape))
-        lo = torch.empty(shape, device=self.device, dtype=torch.float32)
-        hi = torch.empty_like(lo)
-        _lib.check(self.lib.bgm_row_tail_quantiles(self.h, _ptr(tails), n_series, k_tail, int(m), float(q_lo), float(q_hi), _ptr(lo), _ptr(hi),
-                                                   self._stream()), "bgm_row_tail_quantiles")
-        return lo, hi
+        return _row_tail_quantiles(self, tails, m, q_lo, q_hi)
 
     def hmc_run_group_effects(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, labels=None, n_labels=0,
                               group_partial=None, **kw):
@@ -854,6 +859,18 @@ def flatten_varnet(g):
     return np.concatenate([np.asarray(a, np.float32).ravel() for a in parts]).astype(np.float32)
 
 
+def missing_slots(x, k_slots=None):
+    """(slot int32 [n, p], k_slots) of the NaN cells of x [n, p] on the device: the k-th missing cell of a row has slot k, observed
+    cells -1 (the map of predict_draws' cells and of hmc_run_rows' cells / tails); k_slots: the largest count of a row, at least 1,
+    unless given (a width shared by all ranks)."""
+    miss = torch.isnan(x)
+    slot = (torch.cumsum(miss, dim=1, dtype=torch.int32) - 1).to(torch.int32)
+    slot.masked_fill_(~miss, -1)
+    if k_slots is None:
+        k_slots = max(1, int(miss.sum(dim=1).max().item())) if x.shape[0] else 1
+    return slot.contiguous(), int(k_slots)
+
+
 class BgmEngine(object):
     """Device-side state of one BGM generator (BaseVariationalNet, inference mode) + kernels."""
 
@@ -937,7 +954,7 @@ class BgmEngine(object):
 
     def hmc_run_rows(self, x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False, row_base=0, up=None,
                      dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_prob=None, acc_count=None, draws=None, max_trajectory=None, jitter=False,
-                     n_steps=None, moments=None, cells=None, slot=None, k_slots=0, n_keep=None, add_noise=True):
+                     n_steps=None, moments=None, cells=None, slot=None, k_slots=0, n_keep=None, add_noise=True, tails=None, k_tail=0):
         """hmc_run with a step size per chain (bgm_bgm_hmc_run_rows): step float32 [n], in / out; up / dn: the factor tables of
         row_adapt.row_adapt_factors on the device (None: the steps stay as given).
 
@@ -947,12 +964,23 @@ class BgmEngine(object):
         the values themselves as well, in predict_draws' layout.  n_keep: the retained iterations of the whole run (default: those of
         this call).  The chain is the one the call makes without these arguments, bit for bit.
 
+        tails with k_tail = K (opt-in, bgm_bgm_hmc_run_rows_impute_tails; needs moments, slot and k_slots >= 1): float32
+        [2, K, n, k_slots], in / out.  For every missing cell with a slot, tail 0 collects the K smallest and tail 1 the K largest of
+        its retained predictive values, each a heap in no sorted order (row_tail_quantiles reads them); 1 <= K <= n_keep.  Retained
+        draw 0 initialises the series it owns, nothing else of the buffer is written.  Chain, moments and cells are those of the call
+        without tails.
+
         max_trajectory / jitter / n_steps (opt-in, bgm_bgm_hmc_run_rows_traj): a number of leapfrog steps per chain, from the chain's
         own step -- capped so that step x steps stays below max_trajectory (row_adapt.leapfrog_cap), drawn uniformly from 1 .. cap
         per transition with jitter; n_steps int32 [n], in / out, gains the steps every chain took.  Every transition still costs
         n_leapfrog evaluations: the option buys mixing, not time."""
         a = self._hmc_args(x, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, acc_prob, acc_count,
                            draws)
+        if tails is not None and (moments is None or slot is None or int(k_slots) < 1):
+            raise ValueError("hmc_run_rows: tails needs moments, slot and k_slots >= 1 (the fused imputation with the slot map of its "
+                             "missing cells, bgm_bgm_hmc_run_rows_impute_tails)")
+        if tails is None and k_tail:
+            raise ValueError("hmc_run_rows: k_tail belongs to tails; got k_tail = %r without tails" % (k_tail,))
         if moments is not None or cells is not None:
             if moments is None:
                 raise ValueError("hmc_run_rows: cells needs moments (the fused imputation, bgm_bgm_hmc_run_rows_impute)")
@@ -971,6 +999,21 @@ class BgmEngine(object):
                                  % (n * int(k_slots) * keep, cells.dtype, tuple(cells.shape)))
             if slot is not None and (slot.dtype != torch.int32 or tuple(slot.shape) != (n, p) or not slot.is_contiguous()):
                 raise ValueError("hmc_run_rows: slot must be a contiguous int32 tensor [n, p]; got %s %s" % (slot.dtype, tuple(slot.shape)))
+            if tails is not None:
+                if (tails.dtype != torch.float32 or tuple(tails.shape) != (2, int(k_tail), n, int(k_slots)) or not tails.is_contiguous()
+                        or int(k_tail) < 1):
+                    raise ValueError("hmc_run_rows: tails must be a contiguous float32 tensor [2, k_tail, n, k_slots] = [2, %d, %d, %d] with "
+                                     "k_tail >= 1; got %s %s" % (int(k_tail), n, int(k_slots), tails.dtype, tuple(tails.shape)))
+                # the one way the kernel could write out of bounds: checked once per call, on the device
+                if n > 0 and int(slot.max().item()) >= int(k_slots):
+                    raise ValueError("hmc_run_rows: slot holds an entry >= k_slots = %d (max %d): the tails of that cell would lie outside "
+                                     "its row's series" % (int(k_slots), int(slot.max().item())))
+                _lib.check(self.lib.bgm_bgm_hmc_run_rows_impute_tails(self.h, C.byref(a), _ptr(up), _ptr(dn), 0 if up is None else int(up.numel()),
+                                                                      float(s_min), float(s_max), T, jit, _ptr(n_steps), _ptr(moments),
+                                                                      _ptr(cells), _ptr(slot), int(k_slots), keep, int(bool(add_noise)),
+                                                                      _ptr(tails), int(k_tail), self._stream()),
+                           "bgm_bgm_hmc_run_rows_impute_tails")
+                return
             _lib.check(self.lib.bgm_bgm_hmc_run_rows_impute(self.h, C.byref(a), _ptr(up), _ptr(dn), 0 if up is None else int(up.numel()),
                                                             float(s_min), float(s_max), T, jit, _ptr(n_steps), _ptr(moments), _ptr(cells),
                                                             _ptr(slot), int(k_slots), keep, int(bool(add_noise)), self._stream()),
@@ -995,7 +1038,8 @@ class BgmEngine(object):
                                               float(target), float(rate), self._stream()), "bgm_bgm_hmc_adapt")
 
     def hmc_sample(self, x, n_mcmc, burn_in, step_size=0.01, n_leapfrog=10, seed=42, row_base=0, want_draws=True,
-                   n_chains_global=None, reduce_fn=None, row_adapt=None, max_trajectory=None, jitter=False, impute=False, add_noise=True):
+                   n_chains_global=None, reduce_fn=None, row_adapt=None, max_trajectory=None, jitter=False, impute=False, add_noise=True,
+                   tails=None):
         """tfp_mcmc_sampler (bgm/base.py:709-830): HMC + SimpleStepSizeAdaptation over int(0.8*burn_in)
         steps, all rows one chain each.  `reduce_fn(tensor)` all-reduces the per-iteration acceptance
         statistic across ranks (the step size is shared by ALL chains).
@@ -1007,12 +1051,21 @@ class BgmEngine(object):
         then holds n_steps int32 [n] as well, the steps every chain took over the n_mcmc retained transitions.
 
         impute=True (with row_adapt only, fp32): the predictive moments of the NaN cells of x are summed inside the sampler (hmc_run_rows
-        with moments); the result holds moments float32 [3, n, p] (NaN where nothing was written) and no draws are allocated."""
+        with moments); the result holds moments float32 [3, n, p] (NaN where nothing was written) and no draws are allocated.
+        tails = K (with impute only, 1 <= K <= n_mcmc): the K smallest and the K largest predictive values of every missing cell are
+        kept as well (hmc_run_rows with tails); the result also holds tails float32 [2, K, n, k_slots] (zero where nothing was
+        written), slot int32 [n, p] (the k-th missing cell of a row has slot k, observed cells -1) and k_slots, from which
+        row_tail_quantiles gives the exact quantile bounds (K = causal_hmc.tail_size(alpha, n_mcmc))."""
         T, jit = RA.resolve_trajectory(row_adapt, max_trajectory, jitter, what="hmc_sample: max_trajectory / jitter")
         if impute:
             if row_adapt is None:
                 raise ValueError("hmc_sample: impute needs row_adapt (the fused imputation lives in the per-chain step kernel)")
             want_draws = False
+        if tails is not None:
+            if not impute:
+                raise ValueError("hmc_sample: tails belongs to impute=True (the tails of the fused imputation's predictive values)")
+            if isinstance(tails, bool) or int(tails) != tails or not 1 <= int(tails) <= int(n_mcmc):
+                raise ValueError("hmc_sample: tails must be an integer K with 1 <= K <= n_mcmc = %d; got %r" % (int(n_mcmc), tails))
         dev = self.device
         x = _f32(x, dev)
         n = x.shape[0]
@@ -1031,6 +1084,11 @@ class BgmEngine(object):
                 moments = torch.full((3, n, self.p), float("nan"), device=dev, dtype=torch.float32)
                 n_steps = torch.zeros(n, device=dev, dtype=torch.int32) if (T > 0.0 or jit) else None
                 tr = dict(max_trajectory=T if T > 0.0 else None, jitter=bool(jit))
+                tkw = {}
+                if tails is not None:
+                    slot, k_slots = missing_slots(x)
+                    tkw = dict(slot=slot, k_slots=k_slots, k_tail=int(tails),
+                               tails=torch.zeros((2, int(tails), n, k_slots), device=dev, dtype=torch.float32))
                 first = 0
                 if n_steps is not None and burn_in > 0:      # (n_steps counts the retained transitions alone, as below)
                     self.hmc_run_rows(x, state, logp, grad, step, 0, burn_in, burn_in, n_leapfrog, seed, init=True, row_base=row_base,
@@ -1039,8 +1097,10 @@ class BgmEngine(object):
                 if total > first:
                     self.hmc_run_rows(x, state, logp, grad, step, first, total - first, burn_in, n_leapfrog, seed, init=(first == 0),
                                       row_base=row_base, up=up, dn=dn, acc_prob=acc_prob, acc_count=acc_count, n_steps=n_steps,
-                                      moments=moments, n_keep=max(1, n_mcmc), add_noise=add_noise, **tr)
+                                      moments=moments, n_keep=max(1, n_mcmc), add_noise=add_noise, **tr, **tkw)
                 out = dict(state=state, logp=logp, grad=grad, row_step=step, acc_prob=acc_prob, acc_count=acc_count, draws=None, moments=moments)
+                if tails is not None:
+                    out.update(tails=tkw["tails"], slot=tkw["slot"], k_slots=tkw["k_slots"])
                 if n_steps is not None:
                     out["n_steps"] = n_steps
                 return out
@@ -1156,6 +1216,13 @@ class BgmEngine(object):
                                                    _ptr(mean), _ptr(lo), _ptr(hi), self._stream()),
                    "bgm_row_mean_quantiles")
         return mean, lo, hi
+
+    def row_tail_quantiles(self, tails, m, q_lo, q_hi):
+        """tails [2, K, n, k_slots] float32 on the device (hmc_run_rows with tails, hmc_sample's out["tails"]) -> (lo, hi) [n, k_slots]:
+        the quantiles row_mean_quantiles gives on the m stored cells of every series, bit for bit (bgm_row_tail_quantiles); series a
+        row does not use hold whatever the buffer held.  K below what (m, q_lo, q_hi) need (causal_hmc.tail_size) raises the
+        library's error."""
+        return _row_tail_quantiles(self, tails, m, q_lo, q_hi)
 
     # -- fit step functions (bgm/base.py:145-187) ---------------------------------
     def fit_begin(self, n_rows, max_batch):

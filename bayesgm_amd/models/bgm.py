@@ -13,9 +13,10 @@ import os
 import numpy as np
 import torch
 
+from .. import causal_hmc
 from .. import parallel
 from .. import row_adapt as row_adapt_mod
-from ..engine import BgmEngine
+from ..engine import BgmEngine, missing_slots
 from ..datasets import Gaussian_sampler
 
 _DEFAULTS = dict(use_bnn=False, g_units=[64] * 5, e_units=[64] * 5, dz_units=[64, 32, 8], dx_units=[64, 32, 8],
@@ -28,9 +29,35 @@ def _glorot(rs, fan_in, fan_out):
     return rs.uniform(-lim, lim, size=(fan_in, fan_out)).astype(np.float32)
 
 
+PREDICT_INTERVALS = ("normal", "quantile", "tails")
+
+
+def resolve_interval(interval, fused):
+    """predict's interval: None (the route's own: the quantile pair of the default route, the normal approximation of fused_predict),
+    'quantile' (the default route by name), 'normal' or 'tails' (fused_predict's two intervals) -> 'quantile' | 'normal' | 'tails';
+    ValueError before any device work otherwise."""
+    if interval is None:
+        return "normal" if fused else "quantile"
+    if not isinstance(interval, str) or interval not in PREDICT_INTERVALS:
+        raise ValueError("interval must be None, 'normal', 'quantile' or 'tails'; got %r" % (interval,))
+    if interval == "quantile" and fused:
+        raise ValueError("interval='quantile' names the default route (stored draws, sorted per cell) and does not go with "
+                         "fused_predict=True; its bounds without stored draws are interval='tails'")
+    if interval != "quantile" and not fused:
+        raise ValueError("interval=%r needs fused_predict=True: the moments and the tails are kept inside the sampler" % (interval,))
+    return interval
+
+
+def impute_tails_block_rows(k_tail, k_slots, max_draw_bytes):
+    """Rows of one block of predict(fused_predict=True, interval='tails'): the block's tail buffers [2 x k_tail x rows x k_slots] float32
+    stay within max_draw_bytes, rows = max_draw_bytes // (8 * k_tail * k_slots); a multiple of 16 (whole row tiles), at least 16."""
+    return causal_hmc.tails_block_rows(k_tail, k_slots, max_draw_bytes)
+
+
 class BGM(object):
     mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last tfp_mcmc_sampler(diagnostics=True)
     hmc_row_leapfrog_ = None         # per-row mean number of leapfrog steps per retained transition (NumPy float32, global row order) of the last call with max_trajectory / jitter_leapfrog; None otherwise
+    impute_tail_blocks_ = None       # row blocks of the last predict(fused_predict=True, interval='tails') on this rank; None otherwise
     hmc_row_step_ = None             # per-row HMC step sizes (NumPy, global row order) of the last predict / tfp_mcmc_sampler call with row_adapt; None when it ran without
 
     def __new__(cls, params=None, *args, **kwargs):
@@ -392,17 +419,48 @@ class BGM(object):
         return True
 
     def _predict_fused(self, data_np, miss, x, state, logp, grad, step, acc_count, n_steps, traj, alpha, n_mcmc, burn_in, n_leapfrog, seed,
-                       lo_r, _mark, _t):
+                       lo_r, _mark, _t, tails=False, max_draw_bytes=None):
         """predict's retained phase with fused_predict, from the state burn-in left: one launch over the rank's rows that keeps the
-        moments of every missing cell's predictive draws (engine.hmc_run_rows with moments), then mean, sd and the normal interval."""
+        moments of every missing cell's predictive draws (engine.hmc_run_rows with moments), then mean, sd and the normal interval.
+        tails (interval='tails'): the launch runs in row blocks of impute_tails_block_rows rows, each with the tail buffers of its
+        missing cells (engine.hmc_run_rows with tails) and the finisher (engine.row_tail_quantiles); mean and sd still come from the
+        planes, the interval is the default route's quantile pair, assembled by its code (_assemble_intervals)."""
         import statistics
         eng = self.engine
         n, p = data_np.shape
         n_loc = x.shape[0]
         mom = torch.full((3, n_loc, p), float("nan"), device=eng.device)
+        k_slots, blocks = 0, [(0, n_loc)]
+        self.impute_tail_blocks_ = None
+        if tails:      # (the slot map and its width as on the default route: the same on every rank, rows are gathered later)
+            miss_dev = torch.isnan(x)
+            k_max = miss_dev.sum(dim=1).max().reshape(1) if n_loc else torch.zeros(1, dtype=torch.int64, device=eng.device)
+            k_slots = int(parallel.all_reduce_max_(k_max).item())
+            los = torch.zeros((n_loc, max(k_slots, 1)), device=eng.device)
+            his = torch.zeros_like(los)
+            if k_slots > 0 and n_mcmc > 0:
+                k_tail = causal_hmc.tail_size(alpha, n_mcmc)
+                slot_dev, _ = missing_slots(x, k_slots)
+                rows_blk = impute_tails_block_rows(k_tail, k_slots, max_draw_bytes)
+                blocks = [(s, min(s + rows_blk, n_loc)) for s in range(0, n_loc, rows_blk)]
+                self.impute_tail_blocks_ = len(blocks)
+            _mark("slots")
         if n_loc > 0 and n_mcmc > 0:      # (the steps are frozen from here on: every iteration lies behind the table)
-            eng.hmc_run_rows(x, state, logp, grad, step, burn_in, n_mcmc, burn_in, n_leapfrog, seed, init=(burn_in == 0), row_base=lo_r,
-                             acc_count=acc_count, n_steps=n_steps, moments=mom, n_keep=n_mcmc, **traj)
+            for s, e in blocks:
+                whole = (s, e) == (0, n_loc)
+                mb = mom if whole else torch.full((3, e - s, p), float("nan"), device=eng.device)
+                kw = {}
+                if k_slots > 0:      # (zeros: the slots a row does not use are the same in every run)
+                    kw = dict(slot=slot_dev[s:e], k_slots=k_slots, k_tail=k_tail,
+                              tails=torch.zeros((2, k_tail, e - s, k_slots), device=eng.device))
+                eng.hmc_run_rows(x[s:e], state[s:e], logp[s:e], grad[s:e], step[s:e], burn_in, n_mcmc, burn_in, n_leapfrog, seed,
+                                 init=(burn_in == 0), row_base=lo_r + s, acc_count=acc_count,
+                                 n_steps=None if n_steps is None else n_steps[s:e], moments=mb, n_keep=n_mcmc, **traj, **kw)
+                if not whole:
+                    mom[:, s:e] = mb
+                if k_slots > 0:
+                    los[s:e], his[s:e] = eng.row_tail_quantiles(kw["tails"], n_mcmc, alpha / 2.0, 1.0 - alpha / 2.0)
+                del mb, kw
         _mark("sample_predict_moments")
         acc = acc_count[burn_in:].sum().double().reshape(1)
         parallel.all_reduce_sum_(acc)
@@ -425,6 +483,13 @@ class BGM(object):
             imputed_dev, sd_dev = parallel.all_gather_rows(imputed_dev, n), parallel.all_gather_rows(sd_dev, n)
         imputed, sd = imputed_dev.cpu().numpy(), sd_dev.cpu().numpy()
         self.impute_sd_ = sd
+        if tails:
+            if parallel.is_dist():
+                los, his = (parallel.all_gather_rows(a_, n) for a_ in (los, his))
+            pred_interval = self._assemble_intervals(miss, los.cpu().numpy(), his.cpu().numpy(), n)
+            _mark("intervals")
+            self.last_predict_timing = {k_: v for k_, v in _t.items() if k_ != "_last"}
+            return imputed, pred_interval
         zq = np.float32(statistics.NormalDist().inv_cdf(1.0 - alpha / 2.0))
         lo, hi = imputed - zq * sd, imputed + zq * sd
         # ---- the reference's two layouts, as in predict
@@ -437,6 +502,21 @@ class BGM(object):
         _mark("intervals")
         self.last_predict_timing = {k_: v for k_, v in _t.items() if k_ != "_last"}
         return imputed, pred_interval
+
+    @staticmethod
+    def _assemble_intervals(miss, los, his, n):
+        """The reference's pred_interval from the bounds per (row, slot) [n, k_slots] of all rows (predict's default route and
+        interval='tails'): [n, k, 2] when every row misses the same k cells, else a list of [k_i, 2] per row."""
+        same_pattern = bool(np.all(miss == miss[0]))
+        if same_pattern:
+            mi = np.where(miss[0])[0]
+            if mi.size == 0:
+                return np.zeros((n, 0, 2), dtype=np.float32)
+            return np.stack([los[:, :mi.size], his[:, :mi.size]], axis=-1)
+        k_row = miss.sum(axis=1)
+        used = np.arange(los.shape[1])[None, :] < k_row[:, None]
+        flat = np.stack([los[used], his[used]], axis=-1).astype(np.float32)          # row-major: row i's cells together
+        return np.split(flat, np.cumsum(k_row)[:-1]) if n else []
 
     def _store_diagnostics(self, draws_dev):
         from .. import diagnostics as dg         # the sampler's `diagnostics` flag shadows the module in its body
@@ -474,7 +554,7 @@ class BGM(object):
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.05, return_samples=False, bs=100, n_mcmc=5000, burn_in=5000, step_size=0.01,
                 num_leapfrog_steps=10, seed=42, max_draw_bytes=64 << 30, row_adapt=False, max_trajectory=None, jitter_leapfrog=False,
-                fused_predict=False):
+                fused_predict=False, interval=None):
         """Posterior-predictive imputation of the NaN cells (bgm/base.py:527-663).
 
         HMC burn-in (with the shared step-size adaptation) runs over ALL rows at once as in the reference;
@@ -500,11 +580,23 @@ class BGM(object):
         the normal approximation  mean -/+ z_{1 - alpha/2} sd  from the draws' mean and standard deviation (n - 1 in the
         denominator), which is off where a cell's predictive distribution is skewed or heavy-tailed.  The sd is left in
         ``self.impute_sd_`` [n, p], NaN at observed cells.  Not with ``return_samples`` and not with ``params['hmc_precision']``
-        other than 'fp32'."""
+        other than 'fp32'.
+
+        ``interval`` (None: each route's own, as above): 'quantile' names the default route and refuses ``fused_predict``; 'normal' and
+        'tails' need ``fused_predict``.  'normal' is the approximation above.  'tails' returns **the default route's quantile pair,
+        bit for bit**, without stored draws: the sampler keeps, per missing cell, the K smallest and the K largest of its predictive
+        draws (K = causal_hmc.tail_size(alpha, n_mcmc): 126 at the defaults) in two heaps and a finisher reads the two order
+        statistics of each bound.  ``max_draw_bytes`` is used again here: the retained phase runs in row blocks of
+        ``max_draw_bytes // (8 K k_slots)`` rows (whole tiles of 16, at least 16; k_slots = the largest number of missing cells of a
+        row), 8 K bytes per slot against the default route's 4 n_mcmc.  ``imputed`` and ``impute_sd_`` are those of ``fused_predict``
+        alone; blocks, ranks and ``max_draw_bytes`` change no bit.  ``self.impute_tail_blocks_`` holds the number of blocks."""
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         target = row_adapt_mod.resolve_step_target(row_adapt)
         max_traj, jit = row_adapt_mod.resolve_trajectory(target, max_trajectory, jitter_leapfrog, what="max_trajectory / jitter_leapfrog")
         fused = self._resolve_fused_predict(fused_predict, target, return_samples)
+        interval = resolve_interval(interval, fused)
+        if interval == "tails" and int(max_draw_bytes) <= 0:
+            raise ValueError("max_draw_bytes must be positive with interval='tails'; got %r" % (max_draw_bytes,))
         traj = dict(max_trajectory=max_traj if max_traj > 0.0 else None, jitter=bool(jit)) if (max_traj > 0.0 or jit) else {}
         self.hmc_row_step_ = self.hmc_row_leapfrog_ = self.impute_sd_ = None
         parallel.check_n_mcmc(n_mcmc)
@@ -556,7 +648,8 @@ class BGM(object):
         _mark("burn_in")
         if fused:
             return self._predict_fused(data_np, miss, x, state, logp, grad, step, acc_count, n_steps if traj else None, traj, alpha, n_mcmc,
-                                       burn_in, num_leapfrog_steps, seed, lo_r, _mark, _t)
+                                       burn_in, num_leapfrog_steps, seed, lo_r, _mark, _t, tails=(interval == "tails"),
+                                       max_draw_bytes=max_draw_bytes)
         # ---- sampling + predictive draws per row block (slot maps, moments and the imputation stay in HBM)
         miss_dev = torch.isnan(x)
         k_row_dev = miss_dev.sum(dim=1)
@@ -611,20 +704,7 @@ class BGM(object):
         if parallel.is_dist():
             means, los, his = (parallel.all_gather_rows(a_, n) for a_ in (means, los, his))
             imputed_dev = parallel.all_gather_rows(imputed_dev, n)
-        los, his = los.cpu().numpy(), his.cpu().numpy()
-        # ---- assemble the reference's return values
-        same_pattern = bool(np.all(miss == miss[0]))
-        if same_pattern:
-            mi = np.where(miss[0])[0]
-            if mi.size == 0:
-                pred_interval = np.zeros((n, 0, 2), dtype=np.float32)
-            else:
-                pred_interval = np.stack([los[:, :mi.size], his[:, :mi.size]], axis=-1)
-        else:
-            k_row = miss.sum(axis=1)
-            used = np.arange(los.shape[1])[None, :] < k_row[:, None]
-            flat = np.stack([los[used], his[used]], axis=-1).astype(np.float32)          # row-major: row i's cells together
-            pred_interval = np.split(flat, np.cumsum(k_row)[:-1]) if n else []
+        pred_interval = self._assemble_intervals(miss, los.cpu().numpy(), his.cpu().numpy(), n)
         _mark("intervals")
         self.last_predict_timing = {k: v for k, v in _t.items() if k != "_last"}
         if return_samples:

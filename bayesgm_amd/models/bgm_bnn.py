@@ -84,6 +84,14 @@ def _refuse_fused_predict(fused_predict):
                          "the Bayesian generator's kernels do not have; got fused_predict=%r" % (fused_predict,))
 
 
+def _refuse_interval(interval):
+    """The interval choice of BGM.predict ('normal' / 'tails' belong to fused_predict, 'quantile' names what this class always returns)."""
+    if interval is not None:
+        raise ValueError("interval is not available with params['use_bnn'] = True: 'normal' and 'tails' need fused_predict, which the "
+                         "Bayesian generator's kernels do not have, and the quantile pair is what this class returns; got interval=%r"
+                         % (interval,))
+
+
 class BGMBayes(BGM):
     def __init__(self, params, timestamp=None, random_seed=None, device=None):
         self.params = params
@@ -429,13 +437,14 @@ class BGMBayes(BGM):
     # ------------------------------------------------------------------ predict
     def predict(self, data, alpha=0.05, return_samples=False, bs=100, n_mcmc=5000, burn_in=5000, step_size=0.01,
                 num_leapfrog_steps=10, seed=42, max_draw_bytes=16 << 30, row_adapt=False, max_trajectory=None, jitter_leapfrog=False,
-                fused_predict=False):
+                fused_predict=False, interval=None):
         """Posterior-predictive imputation of the NaN cells (bgm/base.py:527-663).  HMC over ALL rows as in the reference
         (one generator call per gradient evaluation), then one predictive generator call per block of `bs` rows.  row_adapt,
-        max_trajectory, jitter_leapfrog, fused_predict: BGM's keywords, refused here for anything but their defaults."""
+        max_trajectory, jitter_leapfrog, fused_predict, interval: BGM's keywords, refused here for anything but their defaults."""
         _refuse_row_adapt(row_adapt)
         _refuse_trajectory(max_trajectory, jitter_leapfrog)
         _refuse_fused_predict(fused_predict)
+        _refuse_interval(interval)
         assert 0 < alpha < 1, "The significance level 'alpha' must be greater than 0 and less than 1."
         parallel.check_n_mcmc(n_mcmc)
         self._warn_fresh_noise()

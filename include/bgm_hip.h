@@ -802,6 +802,32 @@ BGM_API int bgm_bgm_hmc_run_rows_impute(bgm_handle *h, const bgm_hmc_args *args,
                                         float *moments_dev, float *cells_dev, const int32_t *slot_dev, int32_t k_slots, int32_t n_keep,
                                         int32_t add_noise, void *stream);
 
+/* bgm_bgm_hmc_run_rows_impute with the two TAILS of every missing cell kept beside its moments (opt-in, fp32): exact quantile bounds
+ * per cell without stored draws.  The arguments of bgm_bgm_hmc_run_rows_impute plus
+ *   tails_dev [2 x k_tail x n x k_slots] float32 (required): for the missing cell c of row r with slot_dev[r * p + c] = k >= 0, heap
+ *     slot s of tail t is element ((t * k_tail + s) * n + r) * k_slots + k -- series r * k_slots + k, the [n, k_slots] indexing of
+ *     cells_dev, two slots of a series n * k_slots floats apart.  After the m retained iterations tail 0 holds, as a multiset, the k_tail
+ *     smallest predictive values of the cell and tail 1 the k_tail largest; the order of the slots is not defined (each tail is a
+ *     binary heap whose slot 0 is its threshold) -- bgm_row_tail_quantiles(tails_dev, n * k_slots, k_tail, m, ...) reads the order
+ *     statistics and gives what bgm_row_mean_quantiles gives on cells_dev, bit for bit.  In / out across the calls of one run; the
+ *     iteration it == burn_in initialises every series it owns, so the buffer need not be zeroed.  Series of slots a row does not use
+ *     (k >= the row's missing cells), observed cells, columns beyond p and iterations it < burn_in write nothing;
+ *   k_tail, 1 <= k_tail <= n_keep: the least value for the bounds at alpha / 2 and 1 - alpha / 2 is what bgm_row_tail_quantiles
+ *     demands (causal_hmc.tail_size), about alpha / 2 * n_keep + 2.
+ * slot_dev and k_slots >= 1 are required here (cells_dev stays optional), and every entry of slot_dev must be below k_slots: the
+ * kernel does not check it.  Chain, moments_dev and cells_dev are those of bgm_bgm_hmc_run_rows_impute bit for bit.  A series' buffers
+ * depend on its value sequence alone -- not on n, the grid, row_base, the rank count or where the run is cut.  A value that enters
+ * neither tail costs two loads; one that enters costs about 2 log2 k_tail accesses.
+ * BGM_E_INVALID, naming the argument: everything bgm_bgm_hmc_run_rows_impute refuses, in its order; then tails_dev == NULL, slot_dev ==
+ * NULL, k_slots < 1, k_tail outside [1, n_keep].  BGM_E_UNSUPPORTED (the handle stays usable): split precision and the general-width
+ * engine, as bgm_bgm_hmc_run_rows_impute.
+ * replaces: np.quantile over the predictive draws in BGM.predict, bgm/base.py:527-663, on the tails instead of the draws (opt-in). */
+BGM_API int bgm_bgm_hmc_run_rows_impute_tails(bgm_handle *h, const bgm_hmc_args *args, const float *up_dev, const float *dn_dev,
+                                              int32_t n_table, float s_min, float s_max, float max_trajectory, int32_t jitter,
+                                              int32_t *n_steps_dev, float *moments_dev, float *cells_dev, const int32_t *slot_dev,
+                                              int32_t k_slots, int32_t n_keep, int32_t add_noise, float *tails_dev, int32_t k_tail,
+                                              void *stream);
+
 /* Posterior-predictive draws x ~ N(mu(z_d), sigma^2(z_d)) for draws_dev [n_draws x n x q]:
  * full_dev [n_draws x n x p] (or NULL) and / or cells_dev [(row*k_slots + slot)*n_draws + d] for
  * the cells with slot_dev[row*p + c] >= 0 (or NULL); var_full_dev [n_draws x n x p] receives sigma^2
