@@ -106,6 +106,7 @@ struct bgm_handle {
   bool gram_valid = false;
   bool mh_direct = false;
   bool mh_all_ksteps = false;  // BGM_MH_ALL_KSTEPS at bgm_create: the first layers of f and h issue every K-step (CausalMeta::l1f / l1h / l1b all ones)
+  bool mh_mfma_tails = false;  // BGM_MH_MFMA_TAILS at bgm_create: the keep phase's dose passes run f's 32 -> 8 -> 2 tail on the matrix pipe (the instances without VTAILS)
   CausalMeta gmeta{};
   // split-precision (bf16 x 3) sampling blob (causal_bx3_api.hip); precision: 0 fp32 (default), 1 bf16x3, 2 f16x3 (bgm_causal_set_precision)
   int precision = 0;

@@ -37,6 +37,10 @@ extern "C" int bgm_create(bgm_handle **out, int device) {
   // BGM_MH_ALL_KSTEPS=1: the first layers of f and h issue the K-steps that hold only structural zeros as well (A/B runs)
   const char *all_ks = std::getenv("BGM_MH_ALL_KSTEPS");
   h->mh_all_ksteps = all_ks != nullptr && std::strcmp(all_ks, "0") != 0;
+  // BGM_MH_MFMA_TAILS=1: the fused keep kernel evaluates the tail of f in its dose passes on the matrix pipe instead of the vector
+  // ALU (A/B runs, fallback); the chains do not depend on it
+  const char *mfma_tails = std::getenv("BGM_MH_MFMA_TAILS");
+  h->mh_mfma_tails = mfma_tails != nullptr && std::strcmp(mfma_tails, "0") != 0;
   *out = h;
   return BGM_OK;
 }
@@ -226,9 +230,12 @@ int causal_pack_forward(bgm_handle *h, const HostNet &G, const HostNet &F, const
   m.wf2 = take(64 * 32); m.bf2 = take(32); m.wf3 = take(32 * 16); m.bf3 = take(16); m.wf4 = take(16 * 16); m.bf4 = take(16);
   m.wh2 = take(64 * 32); m.bh2 = take(32); m.wh3 = take(32 * 16); m.bh3 = take(16); m.wh4 = take(16 * 16); m.bh4 = take(16);
   m.wxf = take(64);
+  const int layers = off;                                     // the layers themselves: the size the message names
+  m.vf3 = take(4 * 8 * 8); m.vf4 = take(8 * 2 + 8 + 2);      // filled in the sampling copy only (causal_scale_blob_kernel)
   m.total = off;
   if ((size_t)m.total * 4 > 160 * 1024) {
-    bgm_set_error("model does not fit the 160 KiB LDS-resident layout (" + std::to_string(m.total * 4) + " B); p <= 207 with default widths");
+    const std::string copy = (size_t)layers * 4 <= 160 * 1024 ? " beside the " + std::to_string((m.total - layers) * 4) + " B vector-ALU copy of f's tail" : "";
+    bgm_set_error("model does not fit the 160 KiB LDS-resident layout (" + std::to_string(layers * 4) + " B)" + copy + "; p <= 207 with default widths");
     return BGM_E_UNSUPPORTED;
   }
   blob.assign(m.total, 0.0f);
@@ -294,6 +301,18 @@ static __global__ void causal_scale_blob_kernel(const float *src, float *dst, Ca
       dst[i] = c < 2 ? src[b4[k] + c] : 0.0f;
       return;
     }
+  }
+  // vector-ALU copy of f's tail (causal_dose_passes_valu): the same scaled values as the matrix copy above, in the natural feature
+  // order of the forward blob (src[wf3 + 16 feature + output], src[wf4 + 16 input + output])
+  if (in(m.vf3, 256)) {                  // [lane group g][local input 4 u + r][output]: input feature 16 u + 4 g + r
+    const int e = i - m.vf3, g = e >> 6, l = (e >> 3) & 7, o = e & 7;
+    dst[i] = src[m.wf3 + (16 * (l >> 2) + 4 * g + (l & 3)) * 16 + o] * BGM_LRS_W;
+    return;
+  }
+  if (in(m.vf4, 28)) {                   // [input][output] of layer 4, bias of layer 3 [8], bias of layer 4 [2]
+    const int e = i - m.vf4;
+    dst[i] = e < 16 ? src[m.wf4 + (e >> 1) * 16 + (e & 1)] * BGM_LRS_W : e < 24 ? src[m.bf3 + e - 16] : e < 26 ? src[m.bf4 + e - 24] : 0.0f;
+    return;
   }
   const bool scaled = in(m.wg, m.n_gh * 4096) || in(m.wgl, 64 * 16 * NTL) || in(m.wf2, 64 * 32) || in(m.wh2, 64 * 32);
   dst[i] = scaled ? src[i] * BGM_LRS_W : src[i];
@@ -371,7 +390,7 @@ static int bgm_causal_gram_blob(bgm_handle *h, hipStream_t stream) {
   const int shift = (gm.bgl + 132) - m.wf2;           // the f / h part follows [a0 | w_sig | b_sig + padding]
   for (int CausalMeta::*f : {&CausalMeta::wf2, &CausalMeta::bf2, &CausalMeta::wf3, &CausalMeta::bf3, &CausalMeta::wf4, &CausalMeta::bf4,
                              &CausalMeta::wh2, &CausalMeta::bh2, &CausalMeta::wh3, &CausalMeta::bh3, &CausalMeta::wh4, &CausalMeta::bh4,
-                             &CausalMeta::wxf, &CausalMeta::total})
+                             &CausalMeta::wxf, &CausalMeta::vf3, &CausalMeta::vf4, &CausalMeta::total})
     gm.*f += shift;
   std::vector<float> gb((size_t)gm.total, 0.0f);
   std::copy(sb.begin(), sb.begin() + m.wgl, gb.begin());
@@ -495,9 +514,14 @@ template <int EFFECT>
 static int launch_mh(bgm_handle *h, const CausalMhKArgs &ka, int grid, int lds, hipStream_t stream) {
   return bgm_causal_dispatch(h, "MH kernel", [&](auto s) {
     using S = decltype(s);
-    return bgm_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2)>
-                            : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT>,
-                      grid, MH_WAVES, lds, stream, ka);
+    // (EFFECT 1: f's tail in the dose passes on the vector ALU unless BGM_MH_MFMA_TAILS asked for the matrix-pipe instances)
+    return bgm_causal_with_tails(EFFECT == 1 && !h->mh_mfma_tails, [&](auto vt) {
+      constexpr bool VT = EFFECT == 1 && decltype(vt)::value;
+      constexpr bool VT_G = VT && causal_valu_tails(S::KT1, S::NTL, S::NTL > 2), VT_D = VT && causal_valu_tails(S::KT1, S::NTL, false);
+      return bgm_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2), false, VT_G>
+                              : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, false, false, VT_D>,
+                        grid, MH_WAVES, lds, stream, ka);
+    });
   });
 }
 

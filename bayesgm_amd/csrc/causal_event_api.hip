@@ -115,9 +115,12 @@ int bgm_causal_event_finish(bgm_handle *h, const CausalMhKArgs &ka, int grid, in
   // the outcome net f alone (its first layer depends on KT1, KSL1; g's NTL plays no part)
   const int rc = bgm_causal_dispatch(h, "event-form outcome-net kernel", [&](auto s) {
     using S = decltype(s);
-    const int lds = 4 * (16 * S::KT1 * 64 + 64 + 64 * 32 + 32 + 32 * 16 + 16 + 16 * 16 + 16 + 64);
+    // the tail of f where the fused keep kernel of this handle and shape has it (launch_mh in causal_api.hip, causal_rowadapt_api.hip;
+    // the conditional-prior instances keep the matrix-pipe tails): the event form stands in for that kernel bit for bit
+    const bool vt = effect != BGM_EFFECT_ITE && !h->mh_mfma_tails && !h->prior_seg && causal_valu_tails(S::KT1, S::NTL, ka.uc != nullptr, ka.row_scale != nullptr);
+    const int lds = 4 * (16 * S::KT1 * 64 + 64 + 64 * 32 + 32 + 32 * 16 + 16 + 16 * 16 + 16 + 64 + (vt ? 256 + 28 : 0));
     return bgm_launch(effect == BGM_EFFECT_ITE ? causal_event_f_ite_kernel<S::KT1, S::KSL1, FW, WPS>
-                                               : causal_event_f_kernel<S::KT1, S::KSL1, FW, WPS>,
+                      : vt ? causal_event_f_kernel<S::KT1, S::KSL1, FW, WPS, true> : causal_event_f_kernel<S::KT1, S::KSL1, FW, WPS>,
                       grid * MH_WAVES * WPS / FW, FW, lds, stream, fa);
   });
   if (rc) return rc;

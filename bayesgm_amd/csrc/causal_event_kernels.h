@@ -36,7 +36,9 @@ struct CausalEventFArgs {
 // Only the outcome net's weights go to LDS (16-20 KB of the ~150 KB sampling blob: first layer, x row, the 64 -> 32 -> 8 -> 2 tail), so
 // that four 4-wave workgroups share a CU instead of one 8-wave workgroup: the dose passes are short dependent MFMA chains, and it is
 // other waves that fill their gaps.  WPS waves deal a slot's event tiles among themselves.
-template <int KT1, int KSL1, int WAVES, int WPS>
+// VTAILS: the tail of f on the vector ALU, exactly as the fused keep kernel of the same handle evaluates it (causal_dose_passes_valu in
+// causal_kernels.h; bgm_causal_event_finish chooses with the fused kernel's rule), so that the pairs are the fused kernel's bit for bit.
+template <int KT1, int KSL1, int WAVES, int WPS, bool VTAILS = false>
 __global__ __launch_bounds__(64 * WAVES) void causal_event_f_kernel(CausalEventFArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   CausalMeta m = a.m;
@@ -51,6 +53,7 @@ __global__ __launch_bounds__(64 * WAVES) void causal_event_f_kernel(CausalEventF
     m.w1f = put(a.m.w1f, 16 * KT1 * 64); m.b1f = put(a.m.b1f, 64);
     m.wf2 = put(a.m.wf2, 64 * 32); m.bf2 = put(a.m.bf2, 32); m.wf3 = put(a.m.wf3, 32 * 16); m.bf3 = put(a.m.bf3, 16);
     m.wf4 = put(a.m.wf4, 16 * 16); m.bf4 = put(a.m.bf4, 16); m.wxf = put(a.m.wxf, 64);
+    if constexpr (VTAILS) { m.vf3 = put(a.m.vf3, 256); m.vf4 = put(a.m.vf4, 28); }
     __syncthreads();
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -76,8 +79,8 @@ __global__ __launch_bounds__(64 * WAVES) void causal_event_f_kernel(CausalEventF
     const unsigned rowid[1] = {0u};
     const bool valid[1] = {true};
     float2 *out = a.ev_out + ((slot * a.ev_cap + e0) >> 4) * (long long)n_calls * 64;
-    causal_effects<KT1, KSL1, 1, 1, true, true, true>(lds, m, lane_off, g, j, lane, zs, rowid, valid, 0ll, 16ll, 0u, 0ll, 1, 0, a.n_doses,
-                                                      a.x_values, nullptr, nullptr, 0u, 0u, out);
+    causal_effects<KT1, KSL1, 1, 1, true, true, true, true, false, false, VTAILS>(lds, m, lane_off, g, j, lane, zs, rowid, valid, 0ll, 16ll, 0u, 0ll, 1,
+                                                                                  0, a.n_doses, a.x_values, nullptr, nullptr, 0u, 0u, out);
   }
 }
 

@@ -11,6 +11,9 @@
 // LDS, shared by the block's waves.  Per transition only the Philox counters
 // change; HBM is touched again only to emit retained draws / effects.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "bgm_device.h"
 #include "row_tails.h"
 
@@ -27,6 +30,9 @@ struct CausalMeta {
   int wf2, bf2, wf3, bf3, wf4, bf4;
   int wh2, bh2, wh3, bh3, wh4, bh4;
   int wxf;              // f L1 x-row, accumulator layout [64]
+  // vector-ALU copy of f's layers 3 and 4 (sampling copies only, causal_scale_blob_kernel; read by causal_dose_passes_valu):
+  int vf3;              // [lane group g][local input 4 u + r = feature 16 u + 4 g + r][8 outputs], scaled like wf3
+  int vf4;              // [8 inputs][2 outputs] scaled like wf4, then layer 3's bias [8], then layer 4's bias [2] (+ 2 of padding)
   int total;            // blob floats
   // First-layer K-steps to issue, bit s = K-step s (extended input features 4 s .. 4 s + 3): the steps in which the net takes at least
   // one feature.  From z_dims alone (causal_pack_forward), never from weight values; every other step multiplies packed zeros.
@@ -37,6 +43,15 @@ struct CausalMeta {
 // registers on top of KT1 = 2) the masked forms made the Gram instances spill 72 bytes per lane where they had 12 (0 -> 12 in the
 // event form's transition kernel).  Compile-time; bgm_causal_mh_info counts every K-step for them.
 __host__ __device__ constexpr bool causal_l1_masked(int KT1, int PRIOR) { return !(PRIOR != 0 && KT1 > 1); }
+
+// The fused keep instantiations (causal_mh_kernel<EFFECT 1>) that run the tail of f in their dose passes on the vector ALU (VTAILS):
+// every one that gained no scratch by it.  Left on the matrix pipe: the Gram instances with a two-tile first layer (0 -> 20 bytes per
+// lane), the direct form at 7 output tiles (0 -> 56 and 64 -> 80 bytes; it runs only under BGM_MH_DIRECT_LIKELIHOOD), with the
+// per-chain proposal scale also the two-tile first layer at 2 output tiles (0 -> 20), and every instance with the conditional prior
+// (0 -> 44 in its Gram instances, 0 -> 28 / 100 at 2 output tiles).  Compile-time, like causal_l1_masked.
+__host__ __device__ constexpr bool causal_valu_tails(int KT1, int NTL, bool GRAM, bool ROWADAPT = false) {
+  return !(KT1 > 1 && GRAM) && !(NTL == 7 && !GRAM) && !(ROWADAPT && KT1 > 1 && NTL == 2);
+}
 
 struct CausalMhKArgs {
   const float *blob;    // packed weights (global)
@@ -582,8 +597,188 @@ __device__ __forceinline__ float pick_by_group(int g, float v0, float v1, float 
 // in the order of their lowest row, each by ONE DPP row reduction and ONE addition from lane 15.  ite is not touched.
 // TAILS (ROWS only; causal_hmc_tails_kernels.h): the lane also keeps the k_tail smallest and the k_tail largest values of its series
 // in row_tails [2][k_tail][n_doses][n] (row_tail_push, row_tails.h).
+// ---------------------------------------------------------------------------
+// VTAILS: the dose passes of the grouped dose-response sums with the 32 -> 8 -> 2 tail of f on the vector ALU (the MH kernels'
+// retained phase).  On the matrix pipe the tail of a pass is 40 of its 168 instructions for 1 088 MACs per chain: half of the M
+// rows of 32 -> 8 and fourteen of the sixteen of 8 -> 2 are padding.  Here
+//   layer 3: after layer 2 lane (j, g) holds features 16 u + 4 g + r of chain j for the pass's four doses -- 8 of the 32 inputs.  It
+//            forms the 8 partial outputs over its own inputs (64 FMAs per dose, weights m.vf3), then two exchange steps with a fixed
+//            addition order sum the partials AND hand each dose to its owner: with lane ^ 32 (v_permlane32_swap: lanes 0-31 keep
+//            doses 0 / 1, lanes 32-63 doses 2 / 3), then with lane ^ 16 (v_permlane16_swap: lane group g keeps dose g).  Every owner
+//            adds ((g0 + g2) + (g1 + g3)), then the bias;
+//   layer 4: 8 lrelu_s and 16 FMAs in the owner (weights m.vf4): (mu, s) of its own dose and chain, what the grouped finish wants.
+// The tail and the finish of pass kb - 1 are written, K-step by K-step, between the layer-2 MFMAs of pass kb (vt_tail_step<S> after
+// K-step S), so they issue in the gaps of this wave's own matrix instructions; the last pass drains after the loop.  Noise words,
+// cache entries, reduction over the rows and the atomics are those of causal_effects' GROUPED finish, so causal_effects_cached
+// replays a pass bit for bit.  EVAL_ONLY (causal_event_f_kernel) stops at the (mean, sd) pairs: the same instructions up to there, so
+// the event form of the retained phase stays bit-identical to the fused kernel it stands in for.
+// ---------------------------------------------------------------------------
+template <int... S, class F>
+__device__ __forceinline__ void vt_static_for(std::integer_sequence<int, S...>, F &&f) { (f(std::integral_constant<int, S>{}), ...); }
+
+struct VtTail {
+  float act[4][8];      // lrelu_s of the pass's layer-2 outputs: [dose][local input 4 u + r]
+  float p[4][8];        // layer-3 partials [dose][output]; after the exchanges p[0][.] = the owner's sums
+  float mu, sr, tot;     // raw outputs of layer 4; the (masked) y of the lane's dose, then its sum over the rows
+  int k;                // the dose this lane group owns in the pass
+  bool own;             // its noise word comes from the lane group's own Philox call
+};
+
+// sum of v0 and v1 across the lane pairs of a swap: the owner of v0's dose (low half / even row) and the owner of v1's
+__device__ __forceinline__ float vt_swap32_add(float v0, float v1) {
+  const auto s = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1), false, false);
+  return __builtin_bit_cast(float, (unsigned)s[0]) + __builtin_bit_cast(float, (unsigned)s[1]);
+}
+__device__ __forceinline__ float vt_swap16_add(float v0, float v1) {
+  const auto s = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1), false, false);
+  return __builtin_bit_cast(float, (unsigned)s[0]) + __builtin_bit_cast(float, (unsigned)s[1]);
+}
+
+// Step S (0 .. 15) of the tail + finish of one pass.  Steps 0-10: three (input, dose) groups of 8 layer-3 FMAs each (32 groups);
+// 11: exchange with lane ^ 32; 12: exchange with lane ^ 16, bias; 13: layer 4; 14: softplus / sqrt / noise; 15: the row reduction.
+template <int S, bool CACHE, bool EVAL_ONLY>
+__device__ __forceinline__ void vt_tail_step(VtTail &T, const float *w3v, const float *w4v, int lane, int pass, float sig2_y, int sample_y,
+                                             bool valid, int nd, f32x4 &nz, int g, float2 *cache) {
+  if constexpr (S <= 10) {
+#pragma unroll
+    for (int grp = 3 * S; grp < (3 * S + 3 < 32 ? 3 * S + 3 : 32); ++grp) {
+      const int l = grp >> 2, e = grp & 3;
+      const f32x4 wa = *reinterpret_cast<const f32x4 *>(w3v + 8 * l), wb = *reinterpret_cast<const f32x4 *>(w3v + 8 * l + 4);
+      const float a = T.act[e][l];
+#pragma unroll
+      for (int o = 0; o < 8; ++o) {
+        const float w = o < 4 ? wa[o & 3] : wb[o & 3];
+        T.p[e][o] = l == 0 ? w * a : fmaf(w, a, T.p[e][o]);
+      }
+    }
+  } else if constexpr (S == 11) {
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+      T.p[0][o] = vt_swap32_add(T.p[0][o], T.p[2][o]);
+      T.p[1][o] = vt_swap32_add(T.p[1][o], T.p[3][o]);
+    }
+  } else if constexpr (S == 12) {
+    const f32x4 ba = *reinterpret_cast<const f32x4 *>(w4v + 16), bb = *reinterpret_cast<const f32x4 *>(w4v + 20);
+#pragma unroll
+    for (int o = 0; o < 8; ++o) T.p[0][o] = vt_swap16_add(T.p[0][o], T.p[1][o]) + (o < 4 ? ba[o & 3] : bb[o & 3]);
+  } else if constexpr (S == 13) {
+    const f32x4 b4 = *reinterpret_cast<const f32x4 *>(w4v + 24);
+    float mu = b4[0], sr = b4[1];
+#pragma unroll
+    for (int o4 = 0; o4 < 4; ++o4) {
+      const f32x4 w = *reinterpret_cast<const f32x4 *>(w4v + 4 * o4);      // rows 2 o4, 2 o4 + 1 of [8][2]
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float a = lrelu_s(T.p[0][2 * o4 + h]);
+        mu = fmaf(w[2 * h], a, mu);
+        sr = fmaf(w[2 * h + 1], a, sr);
+      }
+    }
+    T.mu = mu; T.sr = sr;
+  } else if constexpr (S == 14) {
+    const float s2 = (sig2_y > 0.0f) ? sig2_y : softplus_f(T.sr) + BGM_EPS;
+    const float sd_m = __builtin_sqrtf(s2);
+    if constexpr (CACHE) cache[pass * 64 + lane] = make_float2(T.mu, sd_m);        // for causal_effects_cached
+    if constexpr (EVAL_ONLY) return;                                               // (causal_event_f_kernel: the pairs are all that is wanted)
+    const float noise = T.own ? nz[0] : pick_by_group(g, nz[0], nz[1], nz[2], nz[3]);
+    if (T.own) nz = f32x4{nz[1], nz[2], nz[3], nz[0]};
+    const float y = sample_y ? fmaf(sd_m, noise, T.mu) : T.mu;
+    T.tot = (valid && T.k < nd) ? y : 0.0f;
+  } else if constexpr (!EVAL_ONLY) {
+    T.tot = sum_over_j_to_lane15(T.tot);
+  }
+}
+
+// layer 2 of one pass (64 -> 32 at the doses xk, first-layer activations formed at their K-step as in causal_effects); fill(S) is
+// written after the MFMAs of K-step S
+template <class F>
+__device__ __forceinline__ void vt_layer2(const float *lds, const CausalMeta &m, int lane_off, int g, const f32x4 (&base)[4],
+                                          const f32x4 (&wx)[4], const float (&xk)[4], f32x4 (&a2)[4][2], F &&fill) {
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const f32x4 b = *reinterpret_cast<const f32x4 *>(lds + m.bf2 + 16 * u + 4 * g);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a2[e][u] = b;
+  }
+  const float *w2 = lds + m.wf2 + lane_off * 2;
+  vt_static_for(std::make_integer_sequence<int, 16>{}, [&](auto S) {
+    constexpr int s = decltype(S)::value, t = s >> 2, r = s & 3;
+    AFrag<2> af;
+    af.load(w2 + (16 * t + r) * 16 * 2);
+    float bop[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bop[e] = lrelu_s_pinned(fmaf(wx[t][r], xk[e], base[t][r]));
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a2[e][u] = BGM_MFMA(af.get(u), bop[e], a2[e][u]);
+    fill(S);
+  });
+}
+
+template <bool CACHE, bool EVAL_ONLY>
+__device__ __forceinline__ void causal_dose_passes_valu(const float *lds, const CausalMeta &m, int lane_off, int g, int j, int lane,
+                                                        const f32x4 (&base)[4], const f32x4 (&wx)[4], unsigned rowid, bool valid,
+                                                        unsigned it, long long d, int sample_y, int nd, const float *x_values,
+                                                        float *adrf_slot, unsigned k0, unsigned k1, float2 *cache) {
+  const int n_calls = (nd + 3) >> 2, n_own = n_calls & ~3;
+  if (n_calls == 0) return;
+  const float *w3v = lds + m.vf3 + 64 * g, *w4v = lds + m.vf4;
+  f32x4 nz = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4 a2[4][2];
+  VtTail T;
+  auto doses = [&](int kb, float (&xk)[4]) {
+    const bool own = kb < n_own;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int k = own ? 4 * ((kb & ~3) + e) + (kb & 3) : 4 * kb + e;
+      xk[e] = x_values[k < nd ? k : nd - 1];
+    }
+  };
+  // outcome noise of pass kb: its lane group's own call (renewed every fourth pass), or the call shared by the remainder passes
+  auto noise = [&](int kb) {
+    const bool own = kb < n_own;
+    if (!EVAL_ONLY && sample_y && (!own || (kb & 3) == 0)) nz = box_muller4(philox4x32_10(rowid, it, (unsigned)(own ? (kb & ~3) + g : kb), TAG_YNOISE, k0, k1));
+  };
+  auto open_tail = [&](int pass) {       // the pass whose layer 2 is in a2
+    T.own = pass < n_own;
+    T.k = T.own ? 4 * ((pass & ~3) + g) + (pass & 3) : 4 * pass + g;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int l = 0; l < 8; ++l) T.act[e][l] = lrelu_s(a2[e][l >> 2][l & 3]);
+  };
+  auto emit = [&]() {
+    if constexpr (EVAL_ONLY) return;
+    if (j == 15 && T.k < nd) unsafeAtomicAdd(adrf_slot + (long long)d * nd + T.k, T.tot);
+  };
+  {
+    float xk[4];
+    doses(0, xk);
+    vt_layer2(lds, m, lane_off, g, base, wx, xk, a2, [](auto) {});
+    noise(0);
+  }
+  for (int kb = 1; kb < n_calls; ++kb) {
+    BGM_NO_HOIST();
+    float xk[4];
+    doses(kb, xk);
+    open_tail(kb - 1);
+    vt_layer2(lds, m, lane_off, g, base, wx, xk, a2, [&](auto S) {
+      vt_tail_step<decltype(S)::value, CACHE, EVAL_ONLY>(T, w3v, w4v, lane, kb - 1, m.sig2_y, sample_y, valid, nd, nz, g, cache);
+    });
+    emit();
+    noise(kb);
+  }
+  BGM_NO_HOIST();
+  open_tail(n_calls - 1);
+  vt_static_for(std::make_integer_sequence<int, 16>{}, [&](auto S) {
+    vt_tail_step<decltype(S)::value, CACHE, EVAL_ONLY>(T, w3v, w4v, lane, n_calls - 1, m.sig2_y, sample_y, valid, nd, nz, g, cache);
+  });
+  emit();
+}
+
 template <int KT1, int KSL1, int R, int EFFECT, bool GROUPING = true, bool CACHE = false, bool EVAL_ONLY = false, bool L1MASK = true,
-          bool ROWS = false, bool TAILS = false>
+          bool ROWS = false, bool TAILS = false, bool VTAILS = false>
 __device__ __forceinline__ void causal_effects(const float *lds, const CausalMeta &m, int lane_off, int g, int j,
                                                int lane, const f32x4 (&zs)[R][KT1], const unsigned (&rowid)[R],
                                                const bool (&valid)[R], long long row0, long long n, unsigned it,
@@ -614,6 +809,12 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
   const int nd = ARMS ? (CACHE && n_doses == 0 ? 0 : 2) : n_doses;     // (CACHE: n_doses = 0 switches the evaluation off)
   constexpr int DB = ARMS ? 2 : 4;  // doses evaluated per pass (independent MFMA chains)
   constexpr bool GROUPED = (EFFECT == 1 && R == 1 && GROUPING);   // lane group g finishes dose e = g of a pass (see above)
+  if constexpr (VTAILS) {     // the same passes with f's tail on the vector ALU, one pass behind layer 2 (above)
+    static_assert(GROUPED && !ROWS && (CACHE || !EVAL_ONLY), "VTAILS: the grouped dose-response sums of the MH kernels and of their event form");
+    causal_dose_passes_valu<CACHE, EVAL_ONLY>(lds, m, lane_off, g, j, lane, base[0], wx, rowid[0], valid[0], it, d, sample_y, nd, x_values, adrf_slot,
+                                   k0, k1, cache);
+    return;
+  }
   const int n_calls = (nd + 3) >> 2, n_own = GROUPED ? (n_calls & ~3) : 0;   // Philox calls [0, n_own) in groups of four
   f32x4 nz[R];
 #pragma unroll
@@ -861,9 +1062,12 @@ __device__ __forceinline__ void causal_event_append(const CausalMhKArgs &a, int 
 // lanes of a chain read the same word).  No LDS is used for it.  The variants that were compiled and rejected -- the scale in LDS, both
 // factors by wave-uniform loads ahead of the networks -- and the register figures are in DESIGN.md section 4m.  Compile-time, so that
 // the fixed-scale instantiations keep their bits.
-template <int KT1, int KSL1, int NTL, int R, int WAVES, int EFFECT, int PRIOR = 0, bool GRAM = false, bool ROWADAPT = false>
+// VTAILS (EFFECT 1, one row tile per wave): the retained phase's dose passes run f's 32 -> 8 -> 2 tail on the vector ALU
+// (causal_dose_passes_valu); the transition, and with it every chain, is the same code either way.
+template <int KT1, int KSL1, int NTL, int R, int WAVES, int EFFECT, int PRIOR = 0, bool GRAM = false, bool ROWADAPT = false, bool VTAILS = false>
 __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) {
   static_assert(PRIOR == 0 || R == 1, "conditional prior: one row tile per wave");
+  static_assert(!VTAILS || (EFFECT == 1 && R == 1), "VTAILS: the grouped dose-response sums");
   constexpr bool L1M = causal_l1_masked(KT1, PRIOR);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const CausalMeta &m = a.m;
@@ -1056,7 +1260,7 @@ __global__ __launch_bounds__(64 * WAVES) void causal_mh_kernel(CausalMhKArgs a) 
           float *adrf_slot = a.adrf_partial + slot * (long long)a.n_doses * a.n_keep;
           const bool skip = a.eff_skip && eff_cached && accmask == 0ull;                // wave-uniform: nobody moved
           // (the evaluation is switched off through its trip count: its first layer -- 4 MFMAs per K-step of m.l1b -- still runs)
-          causal_effects<KT1, KSL1, R, EFFECT, true, true, false, L1M>(lds, m, lane_off, g, j, lane, zs, rowid, valid, row0, n, (unsigned)it, d, a.n_keep,
+          causal_effects<KT1, KSL1, R, EFFECT, true, true, false, L1M, false, false, VTAILS>(lds, m, lane_off, g, j, lane, zs, rowid, valid, row0, n, (unsigned)it, d, a.n_keep,
                                                             a.sample_y, skip ? 0 : a.n_doses, a.x_values, adrf_slot, a.ite, a.k0, a.k1, cache);
           if (skip) causal_effects_cached(g, j, lane, rowid[0], valid[0], (unsigned)it, d, a.sample_y, a.n_doses, adrf_slot, a.k0, a.k1, cache);
           eff_cached = true;

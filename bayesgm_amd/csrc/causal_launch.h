@@ -81,3 +81,10 @@ static int bgm_causal_with_effect(int effect, F &&f) {
   if (effect == BGM_EFFECT_ITE) return f(std::integral_constant<int, 2>{});
   return f(std::integral_constant<int, 0>{});
 }
+
+// Where f's 32 -> 8 -> 2 tail runs in the dose passes of the fused keep kernel, as the kernels' VTAILS template argument:
+// f(std::true_type) = vector ALU (the default), f(std::false_type) = matrix pipe (BGM_MH_MFMA_TAILS at bgm_create)
+template <class F>
+static int bgm_causal_with_tails(bool valu, F &&f) {
+  return valu ? f(std::true_type{}) : f(std::false_type{});
+}

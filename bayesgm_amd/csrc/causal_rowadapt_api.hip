@@ -27,9 +27,13 @@ int bgm_causal_rowadapt_mh_launch(bgm_handle *h, const CausalMhKArgs &ka, int ef
     return bgm_causal_dispatch(h, "per-chain proposal scale: MH kernel", [&](auto s) {
       using S = decltype(s);
       constexpr int EFFECT = decltype(e)::value;
-      return bgm_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2), true>
-                              : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, false, true>,
-                        grid, MH_WAVES, lds, stream, ka);
+      return bgm_causal_with_tails(EFFECT == 1 && !h->mh_mfma_tails, [&](auto vt) {      // (as in causal_api.hip, launch_mh)
+        constexpr bool VT = EFFECT == 1 && decltype(vt)::value;
+        constexpr bool VT_G = VT && causal_valu_tails(S::KT1, S::NTL, S::NTL > 2, true), VT_D = VT && causal_valu_tails(S::KT1, S::NTL, false, true);
+        return bgm_launch(ka.uc ? causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, (S::NTL > 2), true, VT_G>
+                                : causal_mh_kernel<S::KT1, S::KSL1, S::NTL, MH_R, MH_WAVES, EFFECT, 0, false, true, VT_D>,
+                          grid, MH_WAVES, lds, stream, ka);
+      });
     });
   });
 }
