@@ -58,9 +58,15 @@ def _sample(eng, x, y, v, xs, sample_y, cache, **kw):
         eng.set_outcome_cache(True)
 
 
-def _check(m, new, old, x, y, v, n_doses, keys=("state", "logp", "acc_count", "draws"), **kw):
-    xs = np.linspace(0.0, 3.0, n_doses)
+def _check(m, new, old, x, y, v, n_doses, keys=("state", "logp", "acc_count", "draws"), xs=None, expect=None, **kw):
+    """The checks of the module docstring on one panel.  xs: the doses (default: linspace(0, 3, n_doses)).  expect: what the instance
+    table says about this engine pair (tests/test_gpu_valu_tails_instances.py): 'mfma' = both ran the same matrix-pipe instance, so the
+    ADRFs are equal to the last bit; 'valu' = the new engine ran the vector-ALU instance, so they are not.  Returns the worst
+    |ADRF - oracle64| of the new engine, of the old engine, and the worst difference between the two."""
+    xs = np.linspace(0.0, 3.0, n_doses) if xs is None else xs
+    assert len(xs) == n_doses
     m64 = OC.cast_model(m, np.float64)
+    worst = np.zeros(3)
     for sample_y in (True, False):
         out_n = _sample(new, x, y, v, xs, sample_y, False, **kw)
         out_o = _sample(old, x, y, v, xs, sample_y, False, **kw)
@@ -78,6 +84,10 @@ def _check(m, new, old, x, y, v, n_doses, keys=("state", "logp", "acc_count", "d
         print("sample_y=%d: worst |adrf - oracle64| vector-ALU tails %.3e, matrix-pipe tails %.3e, between the two %.3e"
               % (sample_y, e_n, e_o, np.abs(a_n - a_o).max()))
         assert e_n <= TOL and e_o <= TOL, (sample_y, e_n, e_o)
+        if expect is not None:
+            assert np.array_equal(a_n, a_o) == (expect == "mfma"), (expect, sample_y)
+        worst = np.maximum(worst, [e_n, e_o, np.abs(a_n - a_o).max()])
+    return tuple(worst)
 
 
 @pytest.mark.parametrize("n_doses", [1, 3, 4, 16, 17, 20])
