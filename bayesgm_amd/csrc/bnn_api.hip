@@ -10,6 +10,7 @@
 #include "bnn_kernels.h"
 #include "bnn_state.h"
 #include "egm_chain_bnn.h"
+#include "fit_epoch_host.h"
 
 // ---- iterative-update steps as row-tile chains (egm_chain_bnn.h) when the shapes are the compiled ones
 struct BnnFitChain {
@@ -265,11 +266,6 @@ extern "C" int bgm_bnn_grad_exchange(bgm_handle *h, float *buf_dev, int32_t to_s
   return BGM_OK;
 }
 
-static float adam_lr_t(float lr, long long t_) {
-  const double t = (double)t_;
-  return (float)((double)lr * std::sqrt(1.0 - std::pow((double)BNN_ADAM_B2, t)) / (1.0 - std::pow((double)BNN_ADAM_B1, t)));
-}
-
 static void bnn_base_args(BnnState *s, BnnArgs &a, int batch, int batch_global, uint64_t seed, uint32_t stream_id) {
   for (int k = 0; k < 4; ++k) a.net[k] = s->net[k];
   a.theta = s->theta_dev; a.m = s->m_dev; a.v = s->v_dev; a.grad = s->grad_dev;
@@ -320,10 +316,8 @@ static void bnn_theta_launch(BnnState *s, BnnArgs &a, int batch, int parts, hipS
     auto kc = fc->t0 == 2 ? bnn_theta_chain_kernel<13, 2, true, 2> : fc->pad ? bnn_theta_chain_kernel<13, 2, true>
               : batch == 32 ? (fc->ntl == 13 ? bnn_theta_chain_kernel<13, 2> : bnn_theta_chain_kernel<7, 2>)
                           : (fc->ntl == 13 ? bnn_theta_chain_kernel<13, 1> : bnn_theta_chain_kernel<7, 1>);
-    static const bool one_wg = std::getenv("BGM_FIT_ONE_WG") != nullptr;
-    if (batch == 32 && !fc->pad && fc->t0 == 1 && !one_wg) {      // row tiles and networks on their own workgroups (see ecb_theta_chain)
-      static const bool no_ws = std::getenv("BGM_FIT_NO_WORKERS") != nullptr;
-      if (no_ws) {
+    if (batch == 32 && !fc->pad && fc->t0 == 1 && !fit_dev_switches().one_wg) {      // row tiles and networks on their own workgroups (see ecb_theta_chain)
+      if (fit_dev_switches().no_workers) {
         auto ks = fc->ntl == 13 ? bnn_theta_chain_kernel<13, 1> : bnn_theta_chain_kernel<7, 1>;
         hipLaunchKernelGGL(ks, dim3(2, 3), dim3(BNN_THREADS), 64 * sizeof(float), st, a, fc->tab_theta, fc->ws, EcbRider{});
       } else {      // g's last layer over the idle waves of its workgroup (ecb_theta_chain<WS>); bgm_bnn_fit_epoch: + the rider workgroups
@@ -380,7 +374,7 @@ extern "C" int bgm_bnn_theta_step(bgm_handle *h, const float *data_z, const int3
   bnn_base_args(s, a, batch, batch_global, seed, stream_id);
   a.data_z = data_z; a.idx = idx; a.x_ = x; a.y_ = y; a.v_ = v;
   a.apply = apply; a.out = out;
-  if (apply) { s->t_theta += 1; a.adam = BnnAdam{adam_lr_t(lr_theta, s->t_theta), BNN_ADAM_B1, BNN_ADAM_B2, BNN_ADAM_EPS}; }
+  if (apply) { s->t_theta += 1; a.adam = BnnAdam{adam_lr_t(lr_theta, s->t_theta, BNN_ADAM_B1, BNN_ADAM_B2), BNN_ADAM_B1, BNN_ADAM_B2, BNN_ADAM_EPS}; }
   bnn_theta_launch(s, a, batch, 3, (hipStream_t)stream_);
   BGM_HIP_CHECK(hipGetLastError());
   if (apply) { s->packed_valid = false; s->bnf_valid = false; }
@@ -393,7 +387,7 @@ extern "C" int bgm_bnn_theta_apply(bgm_handle *h, float lr_theta, void *stream_)
   BnnState *s = bst(h);
   BGM_HIP_CHECK(hipSetDevice(h->device));
   s->t_theta += 1;
-  const BnnAdam ad{adam_lr_t(lr_theta, s->t_theta), BNN_ADAM_B1, BNN_ADAM_B2, BNN_ADAM_EPS};
+  const BnnAdam ad{adam_lr_t(lr_theta, s->t_theta, BNN_ADAM_B1, BNN_ADAM_B2), BNN_ADAM_B1, BNN_ADAM_B2, BNN_ADAM_EPS};
   for (int k : {BNN_G, BNN_H, BNN_F}) {   // the encoder is not trained by the iterative updates
     const BnnNet &n = s->net[k];
     hipLaunchKernelGGL(bnn_adam_kernel, dim3((n.n_params + 255) / 256), dim3(256), 0, (hipStream_t)stream_, s->theta_dev + n.off,
@@ -438,7 +432,7 @@ extern "C" int bgm_bnn_z_step(bgm_handle *h, const float *x, const float *y, con
     fused_rows = fc->z_prepared && !dz_out && lazy != 0 && batch == 32 && !fc->pad && fc->t0 == 1;
     EcbZRows zr{};
     if (fused_rows) {
-      zr = EcbZRows{data_z, zm, zv, adam_lr_t(lr_z, s->t_z + 1), BNN_ADAM_B1, BNN_ADAM_B2, BNN_ADAM_EPS, lazy == 2 ? s->tlast_dev : nullptr, (int)(s->t_z + 1)};
+      zr = EcbZRows{data_z, zm, zv, adam_lr_t(lr_z, s->t_z + 1, BNN_ADAM_B1, BNN_ADAM_B2), BNN_ADAM_B1, BNN_ADAM_B2, BNN_ADAM_EPS, lazy == 2 ? s->tlast_dev : nullptr, (int)(s->t_z + 1)};
       zsy.done_ctr = fc->sync_zr.done_ctr;
     }
     if (!fc->z_prepared)
@@ -446,11 +440,9 @@ extern "C" int bgm_bnn_z_step(bgm_handle *h, const float *x, const float *y, con
     auto kc = fc->t0 == 2 ? bnn_z_chain_kernel<13, 2, true, 2> : fc->pad ? bnn_z_chain_kernel<13, 2, true>
               : batch == 32 ? (fc->ntl == 13 ? bnn_z_chain_kernel<13, 2> : bnn_z_chain_kernel<7, 2>)
                           : (fc->ntl == 13 ? bnn_z_chain_kernel<13, 1> : bnn_z_chain_kernel<7, 1>);
-    static const bool one_wg = std::getenv("BGM_FIT_ONE_WG") != nullptr;
     const size_t lds_z = (32 + 2 * batch + 4 * 16 * fc->t0 * batch) * sizeof(float);
-    if (batch == 32 && !fc->pad && fc->t0 == 1 && !one_wg) {      // one row tile per workgroup (see ecb_z_chain)
-      static const bool no_ws = std::getenv("BGM_FIT_NO_WORKERS") != nullptr;
-      if (no_ws) {
+    if (batch == 32 && !fc->pad && fc->t0 == 1 && !fit_dev_switches().one_wg) {      // one row tile per workgroup (see ecb_z_chain)
+      if (fit_dev_switches().no_workers) {
         auto ks = fc->ntl == 13 ? bnn_z_chain_kernel<13, 1> : bnn_z_chain_kernel<7, 1>;
         hipLaunchKernelGGL(ks, dim3(2), dim3(BNN_THREADS), lds_z, stream, a, fc->tab_z, fc->ws_z, zsy, zr);
       } else {      // the mean call's last layer over the idle waves, the variance-head call on its one column (ecb_z_chain<WS>)
@@ -484,7 +476,7 @@ extern "C" int bgm_bnn_z_step(bgm_handle *h, const float *x, const float *y, con
   BGM_HIP_CHECK(hipGetLastError());
   if (dz_out) return BGM_OK;    // gradient only (parity tests)
   s->t_z += 1;
-  const float lr_t = adam_lr_t(lr_z, s->t_z);
+  const float lr_t = adam_lr_t(lr_z, s->t_z, BNN_ADAM_B1, BNN_ADAM_B2);
   const int q = s->q;
   const long long n = (long long)n_rows * q;
   const int nb = batch * q;
@@ -506,12 +498,6 @@ extern "C" int bgm_bnn_z_step(bgm_handle *h, const float *x, const float *y, con
   return BGM_OK;
 }
 
-static int bnn_z_sync_impl(bgm_handle *h, float *data_z, float *zm, float *zv, const int32_t *idx, int64_t n_rows, int32_t batch, float lr_z,
-                           void *stream_, int t_to_ofs, bool mark);
-extern "C" int bgm_bnn_z_sync(bgm_handle *h, float *data_z, float *zm, float *zv, const int32_t *idx, int64_t n_rows, int32_t batch,
-                              float lr_z, void *stream_) {
-  return bnn_z_sync_impl(h, data_z, zm, zv, idx, n_rows, batch, lr_z, stream_, 0, true);
-}
 // t_to_ofs: the rows are brought to step t_z + t_to_ofs (a minibatch that many latent steps ahead, bgm_bnn_fit_epoch);
 // mark = false: the caller guarantees the latent step of these rows follows (bnn_z_rows_kernel stamps them)
 static int bnn_z_sync_impl(bgm_handle *h, float *data_z, float *zm, float *zv, const int32_t *idx, int64_t n_rows, int32_t batch, float lr_z,
@@ -550,6 +536,11 @@ static int bnn_z_sync_impl(bgm_handle *h, float *data_z, float *zm, float *zv, c
   return BGM_OK;
 }
 
+extern "C" int bgm_bnn_z_sync(bgm_handle *h, float *data_z, float *zm, float *zv, const int32_t *idx, int64_t n_rows, int32_t batch,
+                              float lr_z, void *stream_) {
+  return bnn_z_sync_impl(h, data_z, zm, zv, idx, n_rows, batch, lr_z, stream_, 0, true);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // A list of minibatches with the loop inside the library (single process).  replaces: the loop body causalbgm/base.py:490-505 with
 // use_bnn for the minibatches perm[0 .. n_use) taken `batch` rows at a time: bgm_bnn_z_sync (lazy = 2), bgm_bnn_theta_step(apply = 1),
@@ -559,20 +550,6 @@ static int bnn_z_sync_impl(bgm_handle *h, float *data_z, float *zm, float *zv, c
 // backward chains of minibatch k + 1 (both read the parameters of step k + 1; disjoint rows of the latent table); the gradient-tile
 // kernel of minibatch k + 1, which applies Adam, waits for it.  Results are those of the sequential order.
 // ---------------------------------------------------------------------------------------------------------------------------
-// a device-side wait of the previous bgm_bnn_fit_epoch call gave up (fit_sync.h): that call's results are void
-static int bnn_epoch_check(bgm_handle *h, hipStream_t stream) {
-  if (!h->epoch_ctr) return BGM_OK;
-  unsigned c[4];
-  BGM_HIP_CHECK(hipMemcpyAsync(c, h->epoch_ctr, sizeof(c), hipMemcpyDeviceToHost, stream));
-  BGM_HIP_CHECK(hipStreamSynchronize(stream));
-  if (!c[2]) return BGM_OK;
-  BGM_HIP_CHECK(hipMemset(h->epoch_ctr, 0, sizeof(c)));
-  h->epoch_theta_done = h->epoch_z_done = 0;
-  bgm_set_error("bgm_bnn_fit_epoch: a device-side ordering wait timed out in the previous call (its updates are unordered); "
-                "BGM_FIT_NO_FLAGS=1 orders the two streams with HIP events instead");
-  return BGM_E_HIP;
-}
-
 extern "C" int bgm_bnn_fit_epoch(bgm_handle *h, const float *x, const float *y, const float *v, float *data_z, float *zm, float *zv,
                                  const int32_t *perm, int64_t n_rows, int64_t n_use, int32_t batch, float lr_theta, float lr_z, int32_t lazy,
                                  uint64_t seed, uint32_t stream_id0, float *out_t, float *out_z, int32_t *n_done, void *stream_) {
@@ -583,45 +560,24 @@ extern "C" int bgm_bnn_fit_epoch(bgm_handle *h, const float *x, const float *y, 
   hipStream_t sA = (hipStream_t)stream_;
   BGM_HIP_CHECK(hipSetDevice(h->device));
   BnnFitChain *fc = static_cast<BnnFitChain *>(s->chain);
-  static const bool no_overlap = std::getenv("BGM_FIT_NO_OVERLAP") != nullptr;
+  const FitDevSwitches &sw = fit_dev_switches();
   const bool chains = fc && (batch == 32 || (batch == 16 && !fc->pad));
   // (the general-width step kernels overlap as well -- latent step k beside the reading part of theta step k + 1, own workspace slices --
   // ordered by HIP events; the device-side counters belong to the row-tile chains)
   static const bool one_launch = std::getenv("BGM_BNN_STEP_ONE_LAUNCH") != nullptr;
-  const bool overlap = !no_overlap && lazy != 0 && (chains || (!one_launch && s->kl_part_dev));
-  if (overlap && !h->epoch_stream) {
-    BGM_HIP_CHECK(hipStreamCreateWithFlags(&h->epoch_stream, hipStreamNonBlocking));
-    for (int k = 0; k < 4; ++k) {
-      BGM_HIP_CHECK(hipEventCreateWithFlags(&h->epoch_ev_t[k], hipEventDisableTiming));
-      BGM_HIP_CHECK(hipEventCreateWithFlags(&h->epoch_ev_z[k], hipEventDisableTiming));
-    }
-  }
+  const bool overlap = !sw.no_overlap && lazy != 0 && (chains || (!one_launch && s->kl_part_dev));
+  if (overlap && (rc = epoch_streams_begin(h))) return rc;
   hipStream_t sB = overlap ? h->epoch_stream : sA;
   long long k = 0;
   // Ordering of the two streams by counters in device memory the kernels wait on / advance themselves (fit_sync.h) instead of HIP
   // events (4-6 us of command-processor time per record / wait pair in the stream it sits in); the replay of a minibatch's pending
   // latent steps runs two minibatches ahead on the second stream (in front of the latent phase k - 2, whose completion the
   // gradient-tile kernel k - 1 waits for), and the latent step itself stamps the rows (no mark launch).  BGM_FIT_NO_FLAGS: events.
-  static const bool no_flags = std::getenv("BGM_FIT_NO_FLAGS") != nullptr;
-  bool flags = overlap && !no_flags && chains;
-  if (flags) {
-    if (!h->epoch_ctr) {
-      BGM_HIP_CHECK(hipMalloc((void **)&h->epoch_ctr, sizeof(unsigned) * 8));
-      BGM_HIP_CHECK(hipMemsetAsync(h->epoch_ctr, 0, sizeof(unsigned) * 8, sA));
-      h->epoch_theta_done = h->epoch_z_done = 0;
-    } else if ((rc = bnn_epoch_check(h, sA))) return rc;
-    if (!h->epoch_flags_ok || h->epoch_probe_stream != (void *)sA) {      // once per handle and caller stream: do the two streams run side by side (fit_sync.h)?
-      int ok = 0;
-      BGM_HIP_CHECK(fit_sync_probe(sA, sB, h->epoch_ctr + 4, &ok));
-      h->epoch_flags_ok = ok ? 1 : -1;
-      h->epoch_probe_stream = (void *)sA;
-    }
-    if (h->epoch_flags_ok < 0) flags = false;      // (a profiler serialising kernels, one hardware queue): HIP events
-  }
+  bool flags = false;
+  if (overlap && !sw.no_flags && chains && (rc = epoch_flags_begin(h, sA, sB, "bgm_bnn_fit_epoch", &flags))) return rc;
   int *err = flags ? (int *)(h->epoch_ctr + 2) : nullptr;
   static const bool no_ahead = std::getenv("BGM_BNN_NO_AHEAD") != nullptr;
-  static const bool one_wg_env = std::getenv("BGM_FIT_ONE_WG") != nullptr, no_ws_env = std::getenv("BGM_FIT_NO_WORKERS") != nullptr;
-  const bool ahead_ok = flags && !no_ahead && fc && batch == 32 && !fc->pad && fc->t0 == 1 && !one_wg_env && !no_ws_env && lazy != 0;
+  const bool ahead_ok = flags && !no_ahead && fc && batch == 32 && !fc->pad && fc->t0 == 1 && !sw.one_wg && !sw.no_workers && lazy != 0;
   if (fc) { fc->theta_prepared = fc->z_prepared = fc->riders_on = false; }
   const int q = s->q;
   const unsigned dw_blocks = fc ? (unsigned)((fc->n_tiles + ECH_WAVES - 1) / ECH_WAVES + 1) : 0, zr_blocks = (unsigned)((batch * q + 255) / 256);
@@ -669,7 +625,7 @@ extern "C" int bgm_bnn_fit_epoch(bgm_handle *h, const float *x, const float *y, 
     bnn_base_args(s, a, b, 0, seed, s0);
     a.data_z = data_z; a.idx = idx; a.x_ = x; a.y_ = y; a.v_ = v; a.apply = 1; a.out = out_t;
     s->t_theta += 1;
-    a.adam = BnnAdam{adam_lr_t(lr_theta, s->t_theta), BNN_ADAM_B1, BNN_ADAM_B2, BNN_ADAM_EPS};
+    a.adam = BnnAdam{adam_lr_t(lr_theta, s->t_theta, BNN_ADAM_B1, BNN_ADAM_B2), BNN_ADAM_B1, BNN_ADAM_B2, BNN_ADAM_EPS};
     // noise ahead (EcbRider): this minibatch's theta launch prepares the noise of its own latent phase and of the next theta phase
     const bool ride = ov && ahead_ok;
     if (ride) {
@@ -720,7 +676,7 @@ extern "C" int bgm_bnn_fit_epoch(bgm_handle *h, const float *x, const float *y, 
   }
   if (n_done) *n_done = (int32_t)k;
   // a device-side wait that gave up voids THIS call: reported now, before the caller evaluates or checkpoints the state
-  return flags ? bnn_epoch_check(h, sA) : BGM_OK;
+  return flags ? epoch_check(h, sA, "bgm_bnn_fit_epoch") : BGM_OK;
 }
 
 // This rank's share of a data-parallel epoch (models/causalbgm_bnn.py under torch.distributed): per minibatch the steps of the host loop
@@ -764,7 +720,7 @@ extern "C" int bgm_bnn_end(bgm_handle *h, void *stream_) {
   if (!h->bnn_state) return BGM_OK;
   BGM_HIP_CHECK(hipSetDevice(h->device));
   BGM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream_));
-  const int rc_epoch = bnn_epoch_check(h, (hipStream_t)stream_);
+  const int rc_epoch = epoch_check(h, (hipStream_t)stream_, "bgm_bnn_fit_epoch");
   bgm_bnn_free_state(h);
   return rc_epoch;
 }

@@ -10,11 +10,11 @@
 #include "gx_host.h"
 #include "fit_kernels.h"
 #include "fit_chain.h"
+#include "fit_epoch_host.h"
 
-#include <cstdlib>
 #include <vector>
 
-// ---- row-tile-chain step kernels (fit_chain.h) for the reference batch sizes
+// ---- row-tile-chain step kernels (fit_chain.h) for the reference batch sizes: the session's buffers and base arguments
 struct FitChainState {
   FitChainArgs base{};
   int ntl = 0;
@@ -22,13 +22,15 @@ struct FitChainState {
   bool pad = false;      // the 13-tile kernels on a narrower p + 1 (B = 32 only)
   float *thetaT = nullptr, *ws = nullptr;
   float *theta_x[3] = {}, *thetaT_x[3] = {};        // further parameter buffers + their transposed mirrors (bgm_causal_fit_epoch)
-  const float *theta_use = nullptr, *thetaT_use = nullptr;   // when set: the buffers the next chain launch reads
   float *ws_z = nullptr;   // the latent phase's own stash, so that it may overlap the next minibatch's theta phase (bgm_causal_fit_epoch)
   int *tiles = nullptr, *mirror_dst = nullptr;
-  FitSync sync_t{}, sync_z{};     // device-side ordering of the next theta-phase / latent-phase launch (bgm_causal_fit_epoch)
-  const int *rp_idx = nullptr, *rp_tlast = nullptr; int rp_n = 0, rp_t_to = 0; float rp_lr = 0.0f;   // rider of the next latent-phase launch
-  int last_z_blocks = 0;          // workgroups of the last latent-phase launch (what its done counter advanced by)
-  FitAdamTheta fused{};    // fused.on: the next theta-phase launch applies the Adam step in its gradient-tile kernel (bgm_causal_fit_epoch)
+};
+// what one launch of the chains takes beyond the session's base arguments (all unset: a launch of the step functions called one by one)
+struct FitChainStep {
+  const float *theta = nullptr, *thetaT = nullptr;   // when set: the parameter buffer pair the launch reads (bgm_causal_fit_epoch's ring)
+  FitSync sync{};          // device-side ordering of this launch
+  FitAdamTheta fused{};    // theta phase, fused.on: the gradient-tile kernel applies the Adam step
+  const int *rp_idx = nullptr, *rp_tlast = nullptr; int rp_n = 0, rp_t_to = 0; float rp_lr = 0.0f;   // latent phase: rows the rider workgroups replay
 };
 static void fit_chain_free(bgm_handle *h) {
   FitChainState *c = static_cast<FitChainState *>(h->fit_chain);
@@ -56,7 +58,7 @@ static int fit_chain_setup(bgm_handle *h, const std::vector<float> &theta) {
   const int t0 = q <= 16 ? 1 : 2;
   const int ntl = ((ntl_need == 13 || ntl_need == 7) && t0 == 1) ? ntl_need : 13;
   FitChainArgs a{};
-  bool ok = !std::getenv("BGM_FIT_NO_CHAIN") && q <= 32 && ntl_need <= 13 && fit_fill_mlp(G, a.g, 0) && fit_fill_mlp(F, a.f, ng) &&
+  bool ok = !fit_dev_switches().no_chain && q <= 32 && ntl_need <= 13 && fit_fill_mlp(G, a.g, 0) && fit_fill_mlp(F, a.f, ng) &&
             fit_fill_mlp(H, a.h, ng + nf);
   ok = ok && a.g.n_layers >= 3 && a.g.dims[0] == q && a.g.dims[a.g.n_layers] == p + 1;
   for (int l = 1; ok && l < a.g.n_layers; ++l) ok = a.g.dims[l] == 64;
@@ -115,94 +117,56 @@ static int fit_chain_setup(bgm_handle *h, const std::vector<float> &theta) {
   c->base = a;
   return BGM_OK;
 }
-// one launch of the chains; Z_MODE 0 also the gradient tiles into `grad`
-static void fit_chain_launch(FitChainState *c, FitChainArgs &a, int batch, int z_mode, hipStream_t stream) {
-  if (c->theta_use) { a.theta = c->theta_use; a.thetaT = c->thetaT_use; }
-  a.ad = z_mode ? FitAdamTheta{} : c->fused;
-  a.sy = z_mode ? c->sync_z : c->sync_t;
-  static const bool one_wg_ = std::getenv("BGM_FIT_ONE_WG") != nullptr;
-  a.n_valid = batch;                                 // rows of this minibatch; the tile rows behind them are masked
-  const int nb = batch <= 16 ? 1 : 2;                // row tiles (the padded / two-k-tile instantiations are compiled for two only)
-  // latent phase: workgroups of the chains, then the riders that replay a later minibatch's rows (bgm_causal_fit_epoch)
-  const int nchain = (c->t0 != 2 && !c->pad && nb == 2 && !one_wg_ && (c->ntl == 13 || c->ntl == 7)) ? 2 : 1;
-  const int rpb = (z_mode && c->rp_n > 0 && a.zm) ? (int)(((long long)c->rp_n * a.q * 16 + ECH_THREADS - 1) / ECH_THREADS) : 0;
-  a.rp_first = nchain; a.rp_n = rpb ? c->rp_n : 0; a.rp_idx = c->rp_idx; a.rp_t_to = c->rp_t_to; a.rp_lr = c->rp_lr; a.rp_tlast = c->rp_tlast;
-  if (z_mode) c->last_z_blocks = nchain + rpb;
-#define FC(NTL_, NB_) \
-  if (c->ntl == NTL_ && nb == NB_) { \
-    if (z_mode) hipLaunchKernelGGL((fit_chain_kernel<4, NTL_, 4, 2, 1, NB_, 1>), dim3(nchain + rpb), dim3(ECH_THREADS), 0, stream, a); \
-    else { \
-      hipLaunchKernelGGL((fit_chain_kernel<4, NTL_, 4, 2, 1, NB_, 0>), dim3(1, one_wg_ ? 1 : 3), dim3(ECH_THREADS), 0, stream, a); \
-      hipLaunchKernelGGL(fit_chain_dw_kernel<NB_>, dim3((a.n_tiles + ECH_WAVES - 1) / ECH_WAVES), dim3(ECH_THREADS), 0, stream, a); \
-    } \
-  }
-  if (c->t0 == 2) {
-    if (z_mode) hipLaunchKernelGGL((fit_chain_kernel<4, 13, 4, 2, 1, 2, 1, true, 2>), dim3(nchain + rpb), dim3(ECH_THREADS), 0, stream, a);
-    else {
-      hipLaunchKernelGGL((fit_chain_kernel<4, 13, 4, 2, 1, 2, 0, true, 2>), dim3(1), dim3(ECH_THREADS), 0, stream, a);
-      hipLaunchKernelGGL(fit_chain_dw_kernel<2>, dim3((a.n_tiles + ECH_WAVES - 1) / ECH_WAVES), dim3(ECH_THREADS), 0, stream, a);
-    }
-    return;
-  }
-  if (c->pad) {
-    if (z_mode) hipLaunchKernelGGL((fit_chain_kernel<4, 13, 4, 2, 1, 2, 1, true>), dim3(nchain + rpb), dim3(ECH_THREADS), 0, stream, a);
-    else {
-      hipLaunchKernelGGL((fit_chain_kernel<4, 13, 4, 2, 1, 2, 0, true>), dim3(1), dim3(ECH_THREADS), 0, stream, a);
-      hipLaunchKernelGGL(fit_chain_dw_kernel<2>, dim3((a.n_tiles + ECH_WAVES - 1) / ECH_WAVES), dim3(ECH_THREADS), 0, stream, a);
-    }
-    return;
-  }
-  // 17..32 rows: the two row tiles on two workgroups -- on one CU the six chain waves share one address unit for their weight
-  // streams (83.0 -> 77.4 us per minibatch at N = 1e6) -- and, in the theta phase (no cross-network term), one network per workgroup
-  // as well (-> 75.8 us); the gradient tiles run over both row tiles as before.  BGM_FIT_ONE_WG=1: everything in one workgroup (dev A/B)
-  static const bool one_wg = std::getenv("BGM_FIT_ONE_WG") != nullptr;
-  static const bool no_ws = std::getenv("BGM_FIT_NO_WORKERS") != nullptr;      // dev A/B: g's last layer on the chain wave alone
-  if (nb == 2 && !one_wg && (c->ntl == 13 || c->ntl == 7)) {
-#define FS(NTL_) \
-    if (c->ntl == NTL_) { \
-      if (z_mode) { \
-        if (no_ws) hipLaunchKernelGGL((fit_chain_kernel<4, NTL_, 4, 2, 1, 1, 1>), dim3(nchain + rpb), dim3(ECH_THREADS), 0, stream, a); \
-        else hipLaunchKernelGGL((fit_chain_kernel<4, NTL_, 4, 2, 1, 1, 1, false, 1, true>), dim3(nchain + rpb), dim3(ECH_THREADS), 0, stream, a); \
-      } else { \
-        if (no_ws) hipLaunchKernelGGL((fit_chain_kernel<4, NTL_, 4, 2, 1, 1, 0>), dim3(2, 3), dim3(ECH_THREADS), 0, stream, a); \
-        else hipLaunchKernelGGL((fit_chain_kernel<4, NTL_, 4, 2, 1, 1, 0, false, 1, true>), dim3(2, 3), dim3(ECH_THREADS), 0, stream, a); \
-        hipLaunchKernelGGL(fit_chain_dw_kernel<2>, dim3((a.n_tiles + ECH_WAVES - 1) / ECH_WAVES), dim3(ECH_THREADS), 0, stream, a); \
-      } \
-    }
-    FS(13) FS(7)
-#undef FS
-    return;
-  }
-  if (nb == 1 && !one_wg && !no_ws && (c->ntl == 13 || c->ntl == 7)) {      // <= 16 rows (a rank's share under data parallelism): the same worker split
-#define FW(NTL_) \
-    if (c->ntl == NTL_) { \
-      if (z_mode) hipLaunchKernelGGL((fit_chain_kernel<4, NTL_, 4, 2, 1, 1, 1, false, 1, true>), dim3(nchain + rpb), dim3(ECH_THREADS), 0, stream, a); \
-      else { \
-        hipLaunchKernelGGL((fit_chain_kernel<4, NTL_, 4, 2, 1, 1, 0, false, 1, true>), dim3(1, 3), dim3(ECH_THREADS), 0, stream, a); \
-        hipLaunchKernelGGL(fit_chain_dw_kernel<1>, dim3((a.n_tiles + ECH_WAVES - 1) / ECH_WAVES), dim3(ECH_THREADS), 0, stream, a); \
-      } \
-    }
-    FW(13) FW(7)
-#undef FW
-    return;
-  }
-  FC(13, 2) FC(13, 1) FC(7, 2) FC(7, 1)
-#undef FC
+// the kernels of a variant (fit_launch.h FitVariant): latent phase, theta phase, gradient tiles
+using FitChainFn = void (*)(FitChainArgs);
+struct FitChainKernels { FitChainFn z, theta, dw; };
+template <int NTL, int NB, int DW_NB, bool PAD = false, int T0 = 1, bool WS = false>
+static FitChainKernels fit_chain_kernels_of() {
+  return {fit_chain_kernel<4, NTL, 4, 2, 1, NB, 1, PAD, T0, WS>, fit_chain_kernel<4, NTL, 4, 2, 1, NB, 0, PAD, T0, WS>, fit_chain_dw_kernel<DW_NB>};
+}
+// (rows in the order of the enum, which is the order the unit has always instantiated them in: the order of the kernels in a module
+// moves the register allocation of some of them, see causal_launch.h -- scripts/compare_code_objects.py after any change here)
+static FitChainKernels fit_chain_kernels(FitVariant v) {
+  static const FitChainKernels k[] = {
+      fit_chain_kernels_of<13, 2, 2, true, 2>(), fit_chain_kernels_of<13, 2, 2, true>(),                              // T2, PAD
+      fit_chain_kernels_of<13, 1, 2>(), fit_chain_kernels_of<13, 1, 2, false, 1, true>(),                             // FSN13, FS13
+      fit_chain_kernels_of<7, 1, 2>(), fit_chain_kernels_of<7, 1, 2, false, 1, true>(),                               // FSN7, FS7
+      fit_chain_kernels_of<13, 1, 1, false, 1, true>(), fit_chain_kernels_of<7, 1, 1, false, 1, true>(),              // FW13, FW7
+      fit_chain_kernels_of<13, 2, 2>(), fit_chain_kernels_of<13, 1, 1>(), fit_chain_kernels_of<7, 2, 2>(), fit_chain_kernels_of<7, 1, 1>()};      // FC
+  return k[(int)v];
+}
+// -D FITC_CLOCK (development): where the first chain wave's cycles went, at the 300th and 301st launch (fit_chain.h g_fitc)
+static void fit_chain_clock_report(int z_mode, hipStream_t stream) {
 #ifdef FITC_CLOCK
-  {
-    static int calls = 0;
-    if (++calls == 300 || calls == 301) {
-      hipStreamSynchronize(stream);
-      unsigned long long t[64];
-      hipMemcpyFromSymbol(t, HIP_SYMBOL(g_fitc), sizeof(t));
-      fprintf(stderr, "[FITC z_mode=%d] in %llu | L0 %llu | hidden fwd %llu (", z_mode, t[1] - t[0], t[2] - t[1], t[3] - t[2]);
-      for (int l = 1; l <= 4; ++l) fprintf(stderr, "k%llu+e%llu ", t[30 + 2 * l] - (l == 1 ? t[2] : t[31 + 2 * (l - 1)]), t[31 + 2 * l] - t[30 + 2 * l]);
-      fprintf(stderr, ") | last %llu | loss %llu | bwd last %llu | hidden bwd %llu (", t[4] - t[3], t[6] - t[5], t[7] - t[6], t[8] - t[7]);
-      for (int l = 4; l >= 1; --l) fprintf(stderr, "k%llu+e%llu ", t[40 + 2 * l] - (l == 4 ? t[7] : t[41 + 2 * (l + 1)]), t[41 + 2 * l] - t[40 + 2 * l]);
-      fprintf(stderr, ") | tail %llu | end %llu | total %llu\n", t[9] - t[8], t[10] - t[9], t[10] - t[0]);
-    }
-  }
+  static int calls = 0;
+  if (++calls != 300 && calls != 301) return;
+  hipStreamSynchronize(stream);
+  unsigned long long t[64];
+  hipMemcpyFromSymbol(t, HIP_SYMBOL(g_fitc), sizeof(t));
+  fprintf(stderr, "[FITC z_mode=%d] in %llu | L0 %llu | hidden fwd %llu (", z_mode, t[1] - t[0], t[2] - t[1], t[3] - t[2]);
+  for (int l = 1; l <= 4; ++l) fprintf(stderr, "k%llu+e%llu ", t[30 + 2 * l] - (l == 1 ? t[2] : t[31 + 2 * (l - 1)]), t[31 + 2 * l] - t[30 + 2 * l]);
+  fprintf(stderr, ") | last %llu | loss %llu | bwd last %llu | hidden bwd %llu (", t[4] - t[3], t[6] - t[5], t[7] - t[6], t[8] - t[7]);
+  for (int l = 4; l >= 1; --l) fprintf(stderr, "k%llu+e%llu ", t[40 + 2 * l] - (l == 4 ? t[7] : t[41 + 2 * (l + 1)]), t[41 + 2 * l] - t[40 + 2 * l]);
+  fprintf(stderr, ") | tail %llu | end %llu | total %llu\n", t[9] - t[8], t[10] - t[9], t[10] - t[0]);
 #endif
+}
+// One launch of the chains on `batch` rows; z_mode 0: the theta phase, and the gradient tiles into a.grad behind it.  Returns the
+// workgroups of the chain kernel (latent phase: the chains, then the riders that replay a later minibatch's rows -- what the launch's
+// done counter advances by).
+static int fit_chain_launch(const FitChainState *c, FitChainArgs &a, int batch, int z_mode, const FitChainStep &st, hipStream_t stream) {
+  const FitChainPlan pl = fit_chain_plan(c->ntl, c->t0, c->pad, batch, fit_dev_switches().one_wg, fit_dev_switches().no_workers);
+  const FitChainKernels k = fit_chain_kernels(pl.id);
+  if (st.theta) { a.theta = st.theta; a.thetaT = st.thetaT; }
+  a.ad = z_mode ? FitAdamTheta{} : st.fused;
+  a.sy = st.sync;
+  a.n_valid = batch;                                 // rows of this minibatch; the tile rows behind them are masked
+  const int rpb = (z_mode && st.rp_n > 0 && a.zm) ? (int)(((long long)st.rp_n * a.q * 16 + ECH_THREADS - 1) / ECH_THREADS) : 0;
+  a.rp_first = pl.nchain; a.rp_n = rpb ? st.rp_n : 0; a.rp_idx = st.rp_idx; a.rp_t_to = st.rp_t_to; a.rp_lr = st.rp_lr; a.rp_tlast = st.rp_tlast;
+  const dim3 grid = z_mode ? dim3(pl.nchain + rpb) : dim3(pl.grid_x, pl.grid_y);
+  hipLaunchKernelGGL(z_mode ? k.z : k.theta, grid, dim3(ECH_THREADS), 0, stream, a);
+  if (!z_mode) hipLaunchKernelGGL(k.dw, dim3((a.n_tiles + ECH_WAVES - 1) / ECH_WAVES), dim3(ECH_THREADS), 0, stream, a);
+  fit_chain_clock_report(z_mode, stream);
+  return (int)(grid.x * grid.y);
 }
 
 static constexpr int FIT_WAVES = 8;
@@ -336,12 +300,12 @@ extern "C" int bgm_causal_fit_begin(bgm_handle *h, int64_t n_rows, int32_t max_b
   BGM_HIP_CHECK(hipMemset(h->m1_dev, 0, sizeof(float) * np));
   BGM_HIP_CHECK(hipMemset(h->m2_dev, 0, sizeof(float) * np));
   h->t_theta = 0; h->t_z = 0;
-  if (gx) {
-    rc = gx_fit_begin(h, n_rows, max_batch, stream);
-    if (rc) { fit_free(h); return rc; }
-    h->fit_active = true;
-    return BGM_OK;
-  }
+  auto begin_gx = [&] {      // the session of the general-width engine
+    const int rc_ = gx_fit_begin(h, n_rows, max_batch, stream);
+    if (rc_) fit_free(h); else h->fit_active = true;
+    return rc_;
+  };
+  if (gx) return begin_gx();
   if (chain_only) {
     // default hidden widths, but no LDS-resident blob holds the model: the row-tile chains where they apply (minibatches of at most 32
     // rows, v_dim <= 207), the general-width engine otherwise (any minibatch size, any v_dim)
@@ -367,10 +331,7 @@ extern "C" int bgm_causal_fit_begin(bgm_handle *h, int64_t n_rows, int32_t max_b
       for (void *p : {(void *)h->tables_dev, (void *)h->ws_dev, (void *)h->pos_dev}) if (p) hipFree(p);
       h->tables_dev = nullptr; h->ws_dev = nullptr; h->pos_dev = nullptr; h->fit_active = false;
     }
-    rc = gx_fit_begin(h, n_rows, max_batch, stream);
-    if (rc) { fit_free(h); return rc; }
-    h->fit_active = true;
-    return BGM_OK;
+    return begin_gx();
   }
   // ---- transposed blob
   fit_layout_backward(h, h->fit_meta);
@@ -481,13 +442,15 @@ extern "C" int bgm_causal_fit_begin(bgm_handle *h, int64_t n_rows, int32_t max_b
   return fit_chain_setup(h, theta);
 }
 
-static int fit_grid(const bgm_handle *h, int B) {
-  const int tiles = (B + 15) / 16;
-  return std::max(1, std::min((tiles + FIT_WAVES - 1) / FIT_WAVES, h->n_cus));
-}
+// the rows of one minibatch, as the step functions take them
+struct FitBatch { const float *x, *y, *v, *data_z; const int32_t *idx; int64_t row_lo; int32_t batch, batch_global; };
 
-static int launch_fwd_bwd(bgm_handle *h, FitKArgs &ka, hipStream_t stream) {
-  const int grid = fit_grid(h, ka.B);
+static int launch_fwd_bwd(bgm_handle *h, const FitBatch &b, int z_mode, double *loss, hipStream_t stream) {
+  FitKArgs ka{};
+  ka.m = h->meta; ka.bm = h->fit_meta; ka.ws = h->fit_ws; ka.wsp = h->ws_dev;
+  ka.x = b.x; ka.y = b.y; ka.v = b.v; ka.data_z = b.data_z; ka.idx = b.idx; ka.row_lo = b.row_lo; ka.B = b.batch;
+  ka.inv_B = 1.0f / (float)b.batch_global; ka.z_mode = z_mode; ka.loss = loss;
+  const int grid = std::max(1, std::min(((b.batch + 15) / 16 + FIT_WAVES - 1) / FIT_WAVES, h->n_cus));      // a wave per 16-row tile
   return bgm_causal_dispatch(h, "fit kernel", [&](auto s) {
     using S = decltype(s);
     ka.blob = h->blob_dev;
@@ -505,31 +468,33 @@ static int fit_check(bgm_handle *h, const void *x, const void *y, const void *v,
   return BGM_OK;
 }
 
-extern "C" int bgm_causal_fit_theta_grad(bgm_handle *h, const float *x, const float *y, const float *v,
-                                         const float *data_z, const int32_t *idx, int64_t row_lo, int32_t batch,
-                                         int32_t batch_global, float *grad, double *loss, void *stream_) {
-  int rc = fit_check(h, x, y, v, data_z, batch, batch_global, "bgm_causal_fit_theta_grad");
-  if (rc) return rc;
-  if (!grad) { bgm_set_error("bgm_causal_fit_theta_grad: grad_dev is NULL"); return BGM_E_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
-  BGM_HIP_CHECK(hipSetDevice(h->device));
-  if (FitChainState *fc = static_cast<FitChainState *>(h->fit_chain); fc && batch <= 32) {
-    FitChainArgs ca = fc->base;
-    ca.x = x; ca.y = y; ca.v = v; ca.data_z = data_z; ca.idx = idx; ca.row_lo = row_lo; ca.inv_B = 1.0f / (float)batch_global;
-    ca.loss = loss; ca.grad = grad;
-    fit_chain_launch(fc, ca, batch, 0, stream);
+// z_mode 1: the latent gradient into the session's dz rows, on the latent phase's own stash
+static FitChainArgs fit_chain_args(const bgm_handle *h, const FitChainState *fc, const FitBatch &b, int z_mode, double *loss) {
+  FitChainArgs ca = fc->base;
+  ca.x = b.x; ca.y = b.y; ca.v = b.v; ca.data_z = b.data_z; ca.idx = b.idx; ca.row_lo = b.row_lo; ca.inv_B = 1.0f / (float)b.batch_global;
+  ca.loss = loss;
+  if (z_mode) { ca.dz = h->ws_dev + h->fit_ws.dz; ca.ws = fc->ws_z; }
+  return ca;
+}
+// the session's row-tile chains when they take a minibatch of this size, else NULL
+static FitChainState *fit_chains_for(const bgm_handle *h, int batch) {
+  return batch <= 32 ? static_cast<FitChainState *>(h->fit_chain) : nullptr;
+}
+
+static int fit_theta_grad(bgm_handle *h, const FitBatch &b, float *grad, double *loss, const FitChainStep &st, hipStream_t stream) {
+  if (FitChainState *fc = fit_chains_for(h, b.batch)) {
+    FitChainArgs ca = fit_chain_args(h, fc, b, 0, loss);
+    ca.grad = grad;
+    fit_chain_launch(fc, ca, b.batch, 0, st, stream);
     BGM_HIP_CHECK(hipGetLastError());
     return BGM_OK;
   }
-  FitKArgs ka{};
-  ka.m = h->meta; ka.bm = h->fit_meta; ka.ws = h->fit_ws; ka.wsp = h->ws_dev;
-  ka.x = x; ka.y = y; ka.v = v; ka.data_z = data_z; ka.idx = idx; ka.row_lo = row_lo; ka.B = batch;
-  ka.inv_B = 1.0f / (float)batch_global; ka.z_mode = 0; ka.loss = loss;
-  rc = gx_fit_active(h) ? gx_fit_grads(h, x, y, v, data_z, idx, row_lo, batch, batch_global, 0, grad, loss, stream) : launch_fwd_bwd(h, ka, stream);
+  int rc = gx_fit_active(h) ? gx_fit_grads(h, b.x, b.y, b.v, b.data_z, b.idx, b.row_lo, b.batch, b.batch_global, 0, grad, loss, stream)
+                            : launch_fwd_bwd(h, b, 0, loss, stream);
   if (rc) return rc;
   DwArgs dw = h->dw;
-  dw.ws = h->ws_dev; dw.partial = h->partial_dev; dw.B = batch; dw.rows_per_slice = h->rows_per_slice;
-  const int n_slices = (batch + h->rows_per_slice - 1) / h->rows_per_slice;
+  dw.ws = h->ws_dev; dw.partial = h->partial_dev; dw.B = b.batch; dw.rows_per_slice = h->rows_per_slice;
+  const int n_slices = (b.batch + h->rows_per_slice - 1) / h->rows_per_slice;
   hipLaunchKernelGGL(fit_dw_kernel, dim3(n_slices, dw.n_layers, fit_dw_chunks(dw)), dim3(256), 0, stream, dw);
   BGM_HIP_CHECK(hipGetLastError());
   const int np = h->n_params;
@@ -538,14 +503,22 @@ extern "C" int bgm_causal_fit_theta_grad(bgm_handle *h, const float *x, const fl
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;
 }
+extern "C" int bgm_causal_fit_theta_grad(bgm_handle *h, const float *x, const float *y, const float *v,
+                                         const float *data_z, const int32_t *idx, int64_t row_lo, int32_t batch,
+                                         int32_t batch_global, float *grad, double *loss, void *stream_) {
+  int rc = fit_check(h, x, y, v, data_z, batch, batch_global, "bgm_causal_fit_theta_grad");
+  if (rc) return rc;
+  if (!grad) { bgm_set_error("bgm_causal_fit_theta_grad: grad_dev is NULL"); return BGM_E_INVALID; }
+  BGM_HIP_CHECK(hipSetDevice(h->device));
+  return fit_theta_grad(h, FitBatch{x, y, v, data_z, idx, row_lo, batch, batch_global}, grad, loss, FitChainStep{}, (hipStream_t)stream_);
+}
 
 extern "C" int bgm_causal_fit_theta_apply(bgm_handle *h, const float *grad, float lr_theta, void *stream_) {
   if (!h || !h->fit_active) { bgm_set_error("bgm_causal_fit_theta_apply: call bgm_causal_fit_begin first"); return BGM_E_STATE; }
   if (!grad) { bgm_set_error("bgm_causal_fit_theta_apply: grad_dev is NULL"); return BGM_E_INVALID; }
   BGM_HIP_CHECK(hipSetDevice(h->device));
   h->t_theta += 1;
-  const double t = (double)h->t_theta;
-  const float lr_t = (float)((double)lr_theta * std::sqrt(1.0 - std::pow((double)ADAM_B2, t)) / (1.0 - std::pow((double)ADAM_B1, t)));
+  const float lr_t = adam_lr_t(lr_theta, h->t_theta, ADAM_B1, ADAM_B2);
   const int np = h->n_params;
   const int *tb = h->tables_dev;
   hipLaunchKernelGGL(fit_adam_theta_kernel, dim3((np + 255) / 256), dim3(256), 0, (hipStream_t)stream_, h->theta_dev,
@@ -559,9 +532,19 @@ extern "C" int bgm_causal_fit_theta_apply(bgm_handle *h, const float *grad, floa
   return BGM_OK;
 }
 
-extern "C" int bgm_causal_fit_z_step(bgm_handle *h, const float *x, const float *y, const float *v, float *data_z,
-                                     float *zm, float *zv, const int32_t *idx, int64_t row_lo, int32_t batch,
-                                     int32_t batch_global, float lr_z, int32_t lazy, double *loss, void *stream_) {
+// the latent gradient of a minibatch into the session's dz rows; *chain_blocks: the workgroups of the chain kernel, where the chains ran
+static int fit_z_grads(bgm_handle *h, const FitBatch &b, FitChainArgs *chain_args, double *loss, const FitChainStep &st, hipStream_t stream,
+                       int *chain_blocks) {
+  if (FitChainState *fc = fit_chains_for(h, b.batch)) {
+    *chain_blocks = fit_chain_launch(fc, *chain_args, b.batch, 1, st, stream);
+    return BGM_OK;
+  }
+  if (gx_fit_active(h)) return gx_fit_grads(h, b.x, b.y, b.v, b.data_z, b.idx, b.row_lo, b.batch, b.batch_global, 1, nullptr, loss, stream);
+  return launch_fwd_bwd(h, b, 1, loss, stream);
+}
+
+static int fit_z_step_check(bgm_handle *h, const float *x, const float *y, const float *v, const float *data_z, const float *zm, const float *zv,
+                            const int32_t *idx, int32_t batch, int32_t batch_global, int32_t lazy) {
   int rc = fit_check(h, x, y, v, data_z, batch, batch_global, "bgm_causal_fit_z_step");
   if (rc) return rc;
   if (!zm || !zv) { bgm_set_error("bgm_causal_fit_z_step: NULL Adam slots"); return BGM_E_INVALID; }
@@ -575,54 +558,48 @@ extern "C" int bgm_causal_fit_z_step(bgm_handle *h, const float *x, const float 
     bgm_set_error("bgm_causal_fit_z_step: rows have pending replay steps; flush with bgm_causal_fit_z_sync(idx = NULL) before changing mode");
     return BGM_E_STATE;
   }
-  hipStream_t stream = (hipStream_t)stream_;
-  BGM_HIP_CHECK(hipSetDevice(h->device));
-  FitKArgs ka{};
-  ka.m = h->meta; ka.bm = h->fit_meta; ka.ws = h->fit_ws; ka.wsp = h->ws_dev;
-  ka.x = x; ka.y = y; ka.v = v; ka.data_z = data_z; ka.idx = idx; ka.row_lo = row_lo; ka.B = batch;
-  ka.inv_B = 1.0f / (float)batch_global; ka.z_mode = 1; ka.loss = loss;
+  return BGM_OK;
+}
+// data_z: b.data_z, writable
+static int fit_z_step(bgm_handle *h, const FitBatch &b, float *data_z, float *zm, float *zv, float lr_z, int32_t lazy, double *loss,
+                      const FitChainStep &st, hipStream_t stream, int *chain_blocks) {
+  FitChainState *fc = fit_chains_for(h, b.batch);
+  FitChainArgs ca{};
   bool pos_set = false, adam_fused = false;
-  if (FitChainState *fc = static_cast<FitChainState *>(h->fit_chain); fc && batch <= 32) {
-    FitChainArgs ca = fc->base;
-    ca.x = x; ca.y = y; ca.v = v; ca.data_z = data_z; ca.idx = idx; ca.row_lo = row_lo; ca.inv_B = ka.inv_B;
-    ca.loss = loss; ca.dz = h->ws_dev + h->fit_ws.dz; ca.ws = fc->ws_z;
+  if (fc) {
+    ca = fit_chain_args(h, fc, b, 1, loss);
     if (!lazy) { ca.pos = h->pos_dev; ca.pos_n = h->fit_rows; ca.epoch = (int)((h->t_z + 1) & 0x3FFFFFFF); pos_set = true; }
     else {                      // the batch rows' Adam step rides on the chain kernel's epilogue
-      const double t1 = (double)(h->t_z + 1);
       ca.zm = zm; ca.zv = zv; ca.z_out = data_z; ca.t_last = lazy == 2 ? h->tlast_dev : nullptr; ca.t_now = (int)(h->t_z + 1);
-      ca.lr_t = (float)((double)lr_z * std::sqrt(1.0 - std::pow((double)ADAM_B2, t1)) / (1.0 - std::pow((double)ADAM_B1, t1)));
+      ca.lr_t = adam_lr_t(lr_z, h->t_z + 1, ADAM_B1, ADAM_B2);
       ca.b1 = ADAM_B1; ca.b2 = ADAM_B2; ca.eps = ADAM_EPS;
       adam_fused = true;
     }
-    fit_chain_launch(fc, ca, batch, 1, stream);
-    rc = BGM_OK;
-  } else if (gx_fit_active(h)) rc = gx_fit_grads(h, x, y, v, data_z, idx, row_lo, batch, batch_global, 1, nullptr, loss, stream);
-  else rc = launch_fwd_bwd(h, ka, stream);
+  }
+  int rc = fit_z_grads(h, b, &ca, loss, st, stream, chain_blocks);
   if (rc) return rc;
   h->t_z += 1;
   if (adam_fused) { BGM_HIP_CHECK(hipGetLastError()); return BGM_OK; }
-  const double t = (double)h->t_z;
-  const float lr_t = (float)((double)lr_z * std::sqrt(1.0 - std::pow((double)ADAM_B2, t)) / (1.0 - std::pow((double)ADAM_B1, t)));
-  const int q = h->q;
+  const float lr_t = adam_lr_t(lr_z, h->t_z, ADAM_B1, ADAM_B2);
   const float *dz = h->ws_dev + h->fit_ws.dz;
-  if (lazy == 2) {
-    const long long n = (long long)batch * q;
-    hipLaunchKernelGGL(fit_adam_z_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, data_z, zm, zv, dz,
-                       h->tlast_dev, h->fit_rows, q, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, 2, idx, batch, (int)h->t_z);
-  } else if (lazy) {
-    const long long n = (long long)batch * q;
-    hipLaunchKernelGGL(fit_adam_z_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, data_z, zm, zv, dz,
-                       h->pos_dev, h->fit_rows, q, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, 1, idx, batch, 0);
-  } else {
-    const int epoch = (int)(h->t_z & 0x3FFFFFFF);      // stamps of earlier steps never match (2^30 steps before a wrap)
-    if (!pos_set)      // (the chain kernel of the latent phase has written the map already)
-      hipLaunchKernelGGL(fit_set_pos_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, h->pos_dev, h->fit_rows, idx, batch, epoch);
-    const long long n = h->fit_rows * q;
-    hipLaunchKernelGGL(fit_adam_z_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, data_z, zm, zv, dz,
-                       h->pos_dev, h->fit_rows, q, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, 0, idx, batch, epoch);
-  }
+  // dense: every row of the table, through the map of the batch rows' positions; stamps of earlier steps never match (2^30 steps before a wrap)
+  const int stamp = lazy == 2 ? (int)h->t_z : lazy ? 0 : (int)(h->t_z & 0x3FFFFFFF);
+  if (!lazy && !pos_set)      // (else the chain kernel of the latent phase has written the map already)
+    hipLaunchKernelGGL(fit_set_pos_kernel, dim3((b.batch + 255) / 256), dim3(256), 0, stream, h->pos_dev, h->fit_rows, b.idx, b.batch, stamp);
+  const long long n = (lazy ? (long long)b.batch : h->fit_rows) * h->q;
+  hipLaunchKernelGGL(fit_adam_z_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, data_z, zm, zv, dz,
+                     lazy == 2 ? h->tlast_dev : h->pos_dev, h->fit_rows, h->q, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, (int)lazy, b.idx, b.batch, stamp);
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;
+}
+extern "C" int bgm_causal_fit_z_step(bgm_handle *h, const float *x, const float *y, const float *v, float *data_z,
+                                     float *zm, float *zv, const int32_t *idx, int64_t row_lo, int32_t batch,
+                                     int32_t batch_global, float lr_z, int32_t lazy, double *loss, void *stream_) {
+  int rc = fit_z_step_check(h, x, y, v, data_z, zm, zv, idx, batch, batch_global, lazy), blocks = 0;
+  if (rc) return rc;
+  BGM_HIP_CHECK(hipSetDevice(h->device));
+  return fit_z_step(h, FitBatch{x, y, v, data_z, idx, row_lo, batch, batch_global}, data_z, zm, zv, lr_z, lazy, loss, FitChainStep{},
+                    (hipStream_t)stream_, &blocks);
 }
 
 // the replay launches: rows idx[0 .. n_sel) (NULL: all rows) of (z, zm, zv) brought from their t_last to step t_to
@@ -637,17 +614,11 @@ static int fit_z_sync_rows(bgm_handle *h, float *data_z, float *zm, float *zv, c
                      h->tlast_dev, h->q, idx, n_sel, t_to, lr_z, ADAM_B1, ADAM_B2, ADAM_EPS);
   if (!mark) { BGM_HIP_CHECK(hipGetLastError()); return BGM_OK; }
   if (!idx) hipLaunchKernelGGL(fit_fill_int_kernel, dim3((unsigned)((n_sel + 255) / 256)), dim3(256), 0, stream, h->tlast_dev, n_sel, t_to);
-  else hipLaunchKernelGGL(fit_mark_rows_kernel, dim3((unsigned)((n_sel + 255) / 256)), dim3(256), 0, stream, h->tlast_dev, idx, n_sel, t_to);
+  else fit_mark_rows(h, idx, (int)n_sel, t_to, stream);
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;
 }
 
-static int fit_z_sync_impl(bgm_handle *h, float *data_z, float *zm, float *zv, const int32_t *idx, int32_t batch, float lr_z, void *stream_,
-                           bool mark);
-extern "C" int bgm_causal_fit_z_sync(bgm_handle *h, float *data_z, float *zm, float *zv, const int32_t *idx, int32_t batch, float lr_z,
-                                     void *stream_) {
-  return fit_z_sync_impl(h, data_z, zm, zv, idx, batch, lr_z, stream_, true);
-}
 static int fit_z_sync_impl(bgm_handle *h, float *data_z, float *zm, float *zv, const int32_t *idx, int32_t batch, float lr_z, void *stream_,
                            bool mark) {
   if (!h || !h->fit_active) { bgm_set_error("bgm_causal_fit_z_sync: call bgm_causal_fit_begin first"); return BGM_E_STATE; }
@@ -663,6 +634,10 @@ static int fit_z_sync_impl(bgm_handle *h, float *data_z, float *zm, float *zv, c
   if (rc) return rc;
   h->z_synced = idx ? h->t_z + 1 : -2;               // -2: flushed, any mode may follow
   return BGM_OK;
+}
+extern "C" int bgm_causal_fit_z_sync(bgm_handle *h, float *data_z, float *zm, float *zv, const int32_t *idx, int32_t batch, float lr_z,
+                                     void *stream_) {
+  return fit_z_sync_impl(h, data_z, zm, zv, idx, batch, lr_z, stream_, true);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -684,45 +659,76 @@ static int fit_z_sync_impl(bgm_handle *h, float *data_z, float *zm, float *zv, c
 // events (46.8 / 45.6 / 45.8 us: the events, not the dependency distance, were the cost); a release fence by every wave of the
 // gradient-tile kernel before its count (39.2 us: 272 L2 write-back sweeps; one per workgroup is enough).
 // ---------------------------------------------------------------------------------------------------------------------------
-// a device-side wait of the previous bgm_causal_fit_epoch call gave up (FitSync): that call's results are void
-static int fit_epoch_check(bgm_handle *h, hipStream_t stream) {
-  if (!h->epoch_ctr) return BGM_OK;
-  unsigned c[4];
-  BGM_HIP_CHECK(hipMemcpyAsync(c, h->epoch_ctr, sizeof(c), hipMemcpyDeviceToHost, stream));
-  BGM_HIP_CHECK(hipStreamSynchronize(stream));
-  if (!c[2]) return BGM_OK;
-  BGM_HIP_CHECK(hipMemset(h->epoch_ctr, 0, sizeof(c)));
-  h->epoch_theta_done = h->epoch_z_done = 0;
-  bgm_set_error("bgm_causal_fit_epoch: a device-side ordering wait timed out in the previous call (its updates are unordered); "
-                "BGM_FIT_NO_FLAGS=1 orders the two streams with HIP events instead");
-  return BGM_E_HIP;
+// The order between the parameter stream sA (theta phases) and the second stream sB (latent phases) of one epoch call, one method per
+// dependency.  With flags a method fills the FitSync of the launch that waits or counts (device counters: epoch_ctr[0] theta phases
+// done, [1] latent phases done, [2] a wait gave up); without, it issues the HIP event record / wait.  Minibatch k uses slot k % D of
+// the ring, and of the events.
+struct FitEpochOrder {
+  bgm_handle *h;
+  hipStream_t sA, sB;
+  FitEpochMode m;
+  bool flags;
+  unsigned zt[4] = {0, 0, 0, 0};   // the latent counter's value once minibatch (slot)'s kernel is done
+  int *err() const { return (int *)(h->epoch_ctr + 2); }
+  int hop(hipEvent_t ev, hipStream_t from, hipStream_t to) {      // `to` goes on behind what `from` holds now
+    BGM_HIP_CHECK(hipEventRecord(ev, from));
+    BGM_HIP_CHECK(hipStreamWaitEvent(to, ev, 0));
+    return BGM_OK;
+  }
+  int wait_latent(long long k) {      // (events) sA behind the latent phase k - D
+    if (k >= m.D) BGM_HIP_CHECK(hipStreamWaitEvent(sA, h->epoch_ev_z[k % m.D], 0));
+    return BGM_OK;
+  }
+  // the second stream starts behind everything queued on the caller's so far (incl. the first replay)
+  int start() { return m.overlap ? hop(h->epoch_ev_t[1], sA, sB) : BGM_OK; }
+  // Theta phase k may overwrite ring slot k % D: the latent phase k - D has read it.  Chained, the theta chains wait at their entry
+  // (*sy, or the event): the riders of that latent phase replayed minibatch k's rows as well.  The launch that applies Adam counts the
+  // phase done: the gradient tiles when fused, else (data parallel) the Adam launch, adam_sync().
+  int theta_may_overwrite_slot(long long k, FitSync *sy) {
+    if (flags) *sy = FitSync{k >= m.D ? h->epoch_ctr + 1 : nullptr, zt[k % m.D], m.fuse ? h->epoch_ctr : nullptr, err()};
+    return m.chained && !flags ? wait_latent(k) : BGM_OK;
+  }
+  // ... not chained: nothing rode on that latent phase, only the Adam launch waits (an event)
+  int adam_may_overwrite_slot(long long k) { return m.overlap && !m.chained ? wait_latent(k) : BGM_OK; }
+  FitSync adam_sync() const { return FitSync{nullptr, 0u, h->epoch_ctr, err()}; }      // (the chains of this minibatch have waited already)
+  // theta phase k is done once `blocks` more workgroups have counted / at this point of sA
+  int theta_done(long long k, unsigned blocks) {
+    if (flags) h->epoch_theta_done += blocks;
+    else if (m.overlap) BGM_HIP_CHECK(hipEventRecord(h->epoch_ev_t[k % m.D], sA));
+    return BGM_OK;
+  }
+  // latent phase k waits for the Adam step k, in its kernel (*sy; the replay rides along) or by the event just recorded
+  int latent_waits_for_adam(long long k, FitSync *sy) {
+    if (flags) *sy = FitSync{h->epoch_ctr, h->epoch_theta_done, h->epoch_ctr + 1, err()};
+    else if (m.overlap) BGM_HIP_CHECK(hipStreamWaitEvent(sB, h->epoch_ev_t[k % m.D], 0));
+    return BGM_OK;
+  }
+  // latent phase k (and the replay issued behind it) is done once `blocks` more workgroups have counted / at this point of sB
+  int latent_done(long long k, int blocks) {
+    if (flags) zt[k % m.D] = h->epoch_z_done += (unsigned)blocks;
+    else if (m.overlap) BGM_HIP_CHECK(hipEventRecord(h->epoch_ev_z[k % m.D], sB));
+    return BGM_OK;
+  }
+  // whatever follows on the caller's stream sees the last latent phase
+  int join() { return m.overlap ? hop(h->epoch_ev_z[0], sB, sA) : BGM_OK; }
+};
+
+static FitAdamTheta fit_adam_theta(const bgm_handle *h, const FitChainState *fc, float lr_t, float *theta_out, float *mirror) {
+  const int *tbl = h->tables_dev;
+  const size_t np = (size_t)h->n_params;
+  FitAdamTheta ad{};
+  ad.on = 1; ad.lr_t = lr_t; ad.b1 = ADAM_B1; ad.b2 = ADAM_B2; ad.eps = ADAM_EPS;
+  ad.m1 = h->m1_dev; ad.m2 = h->m2_dev; ad.theta_out = theta_out;
+  ad.fwd_blob = h->blob_dev; ad.bwd_blob = h->bblob_dev; ad.mirror = mirror;
+  ad.fwd_dst = tbl; ad.fwd_dst2 = tbl + np; ad.bwd_dst = tbl + 2 * np; ad.mirror_dst = fc->mirror_dst;
+  return ad;
 }
 
 // comm != NULL (bgm_causal_fit_epoch_dp): this rank's share of a data-parallel epoch -- every rank calls with its own rows and the
 // same n_use / batch; a minibatch is `batch` local rows of a GLOBAL minibatch of batch * world rows (gradients scaled 1 / (b * world)),
 // and the fused g|f|h gradient is summed over the ranks (ncclAllReduce on the parameter stream) between the gradient tiles and the Adam
 // step, so all ranks take identical steps.  The Adam step is then its own launch (it cannot ride on the tiles: the sum sits between),
-// the streams are ordered by HIP events, the latent phase of minibatch k still runs beside the theta phase of k + 1.
-static int fit_epoch_impl(bgm_handle *h, const float *x, const float *y, const float *v, float *data_z, float *zm, float *zv,
-                          const int32_t *perm, int64_t n_use, int32_t batch, float lr_theta, float lr_z, int32_t lazy,
-                          double *loss, double *loss_z, void *comm, int world, void *stream_);
-
-extern "C" int bgm_causal_fit_epoch(bgm_handle *h, const float *x, const float *y, const float *v, float *data_z, float *zm, float *zv,
-                                    const int32_t *perm, int64_t n_use, int32_t batch, float lr_theta, float lr_z, int32_t lazy,
-                                    double *loss, double *loss_z, void *stream_) {
-  return fit_epoch_impl(h, x, y, v, data_z, zm, zv, perm, n_use, batch, lr_theta, lr_z, lazy, loss, loss_z, nullptr, 1, stream_);
-}
-
-extern "C" int bgm_causal_fit_epoch_dp(bgm_handle *h, const float *x, const float *y, const float *v, float *data_z, float *zm, float *zv,
-                                       const int32_t *perm, int64_t n_use, int32_t batch, float lr_theta, float lr_z, int32_t lazy,
-                                       double *loss, double *loss_z, void *comm, void *stream_) {
-  if (!comm) { bgm_set_error("bgm_causal_fit_epoch_dp: NULL communicator (bgm_comm_create)"); return BGM_E_INVALID; }
-  int world = 0, rank = 0;
-  int rc = bgm_comm_world(comm, &world, &rank);
-  if (rc) return rc;
-  return fit_epoch_impl(h, x, y, v, data_z, zm, zv, perm, n_use, batch, lr_theta, lr_z, lazy, loss, loss_z, comm, world, stream_);
-}
-
+// the latent phase of minibatch k still runs beside the theta phase of k + 1.
 static int fit_epoch_impl(bgm_handle *h, const float *x, const float *y, const float *v, float *data_z, float *zm, float *zv,
                           const int32_t *perm, int64_t n_use, int32_t batch, float lr_theta, float lr_z, int32_t lazy,
                           double *loss, double *loss_z, void *comm, int world, void *stream_) {
@@ -735,27 +741,16 @@ static int fit_epoch_impl(bgm_handle *h, const float *x, const float *y, const f
     BGM_HIP_CHECK(hipMalloc(&h->epoch_grad, sizeof(float) * h->n_params));
     h->epoch_grad_n = h->n_params;
   }
-  static const bool no_overlap = std::getenv("BGM_FIT_NO_OVERLAP") != nullptr;       // dev A/B
-  const bool overlap = !no_overlap && lazy != 0 && h->fit_chain != nullptr && batch <= 32;
-  if (overlap && !h->epoch_stream) {
-    BGM_HIP_CHECK(hipStreamCreateWithFlags(&h->epoch_stream, hipStreamNonBlocking));
-    for (int k = 0; k < 4; ++k) {
-      BGM_HIP_CHECK(hipEventCreateWithFlags(&h->epoch_ev_t[k], hipEventDisableTiming));
-      BGM_HIP_CHECK(hipEventCreateWithFlags(&h->epoch_ev_z[k], hipEventDisableTiming));
-    }
-  }
-  hipStream_t sB = overlap ? h->epoch_stream : sA;
-  int rc = BGM_OK;
-  long long k = 0;
-  // D parameter buffers in a ring: step k's Adam reads buffer k % D and writes the next one, so the latent phase of minibatch k (reading
-  // the new buffer) holds up nothing before the parameter update of minibatch k + D - 1, which overwrites the buffer the latent phase
-  // k - 1 read.  With D = 2 the cycle  latent phase k -> (event) -> theta phase k + 2 -> (event) -> latent phase k + 2  carries two
-  // cross-stream hops of ~10 us per two minibatches (46.3 us per minibatch measured = 36 + 10); D = 4 spreads them over four.
-  static const int depth_env = std::getenv("BGM_FIT_EPOCH_DEPTH") ? std::atoi(std::getenv("BGM_FIT_EPOCH_DEPTH")) : 4;
-  const int D = overlap ? std::min(4, std::max(2, depth_env)) : 1;
   FitChainState *fc = static_cast<FitChainState *>(h->fit_chain);
+  const FitEpochMode m = fit_epoch_mode(lazy, fc != nullptr, batch, comm != nullptr, fit_dev_switches());
+  const bool overlap = m.overlap, chained = m.chained, fuse = m.fuse, ahead = m.ahead;
+  const int D = m.D;
+  int rc = BGM_OK;
+  if (overlap && (rc = epoch_streams_begin(h))) return rc;
+  hipStream_t sB = overlap ? h->epoch_stream : sA;
+  // the ring: the session's own buffers (what the chains' base arguments name), then the further ones
   const int np = h->n_params;
-  float *tb[4] = {h->theta_dev, nullptr, nullptr, nullptr}, *tTb[4] = {overlap ? fc->thetaT : nullptr, nullptr, nullptr, nullptr};
+  float *tb[4] = {h->theta_dev, nullptr, nullptr, nullptr}, *tTb[4] = {fc ? fc->thetaT : nullptr, nullptr, nullptr, nullptr};
   for (int d = 1; d < D; ++d) {
     if (!fc->theta_x[d - 1]) {
       BGM_HIP_CHECK(hipMalloc((void **)&fc->theta_x[d - 1], sizeof(float) * np));
@@ -765,136 +760,77 @@ static int fit_epoch_impl(bgm_handle *h, const float *x, const float *y, const f
     BGM_HIP_CHECK(hipMemcpyAsync(tTb[d], fc->thetaT, sizeof(float) * ((size_t)np + 64), hipMemcpyDeviceToDevice, sA));   // (rows no parameter maps to)
   }
   int cur = 0;
-  static const bool no_fuse = std::getenv("BGM_FIT_NO_FUSED_ADAM") != nullptr;       // dev A/B: separate Adam launch + explicit row marks
-  // chained: the machinery of the row-tile chains (replay ahead, device-side ordering, rows stamped by the latent step) is on;
-  // fuse: the Adam step rides on the gradient-tile kernel -- not under data parallelism, where the all-reduce sits between the tiles
-  // and Adam: there the step is its own launch that waits / counts like the tiles would (fit_adam_theta_sync_kernel)
-  const bool chained = overlap && !no_fuse, fuse = chained && !comm;
-  // Replay mode: the pending zero-gradient steps of minibatch j's rows are replayed D minibatches ahead, on the second stream behind
-  // the latent phase j - D -- off the parameter stream's critical path (replay + chains + gradient tiles), and covered by the event the
-  // theta phase j waits for anyway.  Legal because the minibatches of one call are disjoint: nothing touches those rows in between,
-  // and the step a replay runs to (the latent step count when minibatch j starts) is known in advance.
-  static const bool no_ahead = std::getenv("BGM_FIT_NO_REPLAY_AHEAD") != nullptr;    // dev A/B
-  const bool ahead = chained && lazy == 2 && !no_ahead;
+  bool flags = false;
+  if (m.wants_flags && (rc = epoch_flags_begin(h, sA, sB, "bgm_causal_fit_epoch", &flags))) return rc;
+  FitEpochOrder order{h, sA, sB, m, flags};
   const long long tz0 = h->t_z, n_mb = (n_use + batch - 1) / batch;
-  // Ordering between the two streams without events (each record / wait pair costs the stream it sits in 4-6 us of command-processor
-  // time: 45.0 us per minibatch with them, 34.7 with the dependencies dropped -- unsafe, measured for the bound): the gradient-tile
-  // kernel counts its workgroups into a device counter the latent phase's kernel spins on at entry, and the latent kernel's workgroups
-  // (chains + replay riders) count into a second one the theta phase D minibatches later waits for (fit_types.h FitSync).
-  static const bool no_flags = std::getenv("BGM_FIT_NO_FLAGS") != nullptr;           // dev A/B: HIP events
-  bool flags = chained && !no_flags && (lazy != 2 || ahead);
-  unsigned zt[4] = {0, 0, 0, 0};   // the latent counter's value once minibatch (slot)'s kernel is done
-  if (flags) {
-    if (!h->epoch_ctr) {
-      BGM_HIP_CHECK(hipMalloc((void **)&h->epoch_ctr, sizeof(unsigned) * 8));
-      BGM_HIP_CHECK(hipMemsetAsync(h->epoch_ctr, 0, sizeof(unsigned) * 8, sA));
-      h->epoch_theta_done = h->epoch_z_done = 0;
-    } else if ((rc = fit_epoch_check(h, sA))) return rc;
-    if (!h->epoch_flags_ok || h->epoch_probe_stream != (void *)sA) {      // once per handle and caller stream: do the two streams run side by side (fit_sync.h)?
-      int ok = 0;
-      BGM_HIP_CHECK(fit_sync_probe(sA, sB, h->epoch_ctr + 4, &ok));
-      h->epoch_flags_ok = ok ? 1 : -1;
-      h->epoch_probe_stream = (void *)sA;
-    }
-    if (h->epoch_flags_ok < 0) flags = false;      // (a profiler serialising kernels, one hardware queue): HIP events
-  }
-  long long replayed = 0;          // minibatches [k, replayed) have been replayed but not stepped
+  long long k = 0, replayed = 0;          // minibatches [k, replayed) have been replayed but not stepped
+  auto rows_of = [&](long long j) { return (int)std::min<int64_t>(batch, n_use - j * batch); };
   auto replay = [&](long long j, hipStream_t st) -> int {
     if (j >= n_mb) return BGM_OK;
-    const int bj = (int)std::min<int64_t>(batch, n_use - j * batch);
     replayed = j + 1;
-    return fit_z_sync_rows(h, data_z, zm, zv, perm + j * batch, bj, (int)(tz0 + j), lr_z, st, false);
+    return fit_z_sync_rows(h, data_z, zm, zv, perm + j * batch, rows_of(j), (int)(tz0 + j), lr_z, st, false);
   };
   auto mark_pending = [&](hipStream_t st) {      // a failure: the rows replayed ahead count as current to the step they were brought to
     if (lazy != 2 || !chained) return;
-    for (long long j = k; j < std::max(replayed, k + 1) && j < n_mb; ++j)
-      fit_mark_rows(h, perm + j * batch, (int)std::min<int64_t>(batch, n_use - j * batch), tz0 + j, st);
+    for (long long j = k; j < std::max(replayed, k + 1) && j < n_mb; ++j) fit_mark_rows(h, perm + j * batch, rows_of(j), tz0 + j, st);
   };
-  for (int64_t i = 0; i < n_use; i += batch, ++k) {
-    const int32_t *idx = perm + i;
-    const int b = (int)std::min<int64_t>(batch, n_use - i);
+  for (; k < n_mb; ++k) {
+    const int32_t *idx = perm + k * batch;
+    const int b = rows_of(k);
+    const FitBatch mb{x, y, v, data_z, idx, 0, b, b * world};
     // (the replayed rows are stamped by the latent step below; only a failure in between needs the explicit mark)
     if (lazy == 2 && (!ahead || k == 0) && (rc = fit_z_sync_impl(h, data_z, zm, zv, idx, b, lr_z, sA, !chained))) break;
-    if (ahead && k == 0) {
-      for (int d = 1; d < D && !rc; ++d) rc = replay(d, sA);
-      if (rc) break;
-    }
-    if (overlap && k == 0) {       // the second stream starts behind everything queued on the caller's so far (incl. the first replay)
-      BGM_HIP_CHECK(hipEventRecord(h->epoch_ev_t[1], sA));
-      BGM_HIP_CHECK(hipStreamWaitEvent(sB, h->epoch_ev_t[1], 0));
-    }
-    if (overlap) { fc->theta_use = tb[cur]; fc->thetaT_use = tTb[cur]; }
-    const int *tbl = h->tables_dev;
-    const double t = (double)(h->t_theta + 1);
-    const float lr_t = (float)((double)lr_theta * std::sqrt(1.0 - std::pow((double)ADAM_B2, t)) / (1.0 - std::pow((double)ADAM_B1, t)));
-    if (fuse) {                    // the Adam step rides on the gradient-tile kernel: it writes the other buffer, which the latent
-      if (flags) {               // ... phase k - D (same slot) has read: waited for in the chain kernel itself (and the rows' replay with it)
-        fc->sync_t = FitSync{k >= D ? h->epoch_ctr + 1 : nullptr, zt[k % D], h->epoch_ctr, (int *)(h->epoch_ctr + 2)};
-      } else if (k >= D) BGM_HIP_CHECK(hipStreamWaitEvent(sA, h->epoch_ev_z[k % D], 0));
-      FitAdamTheta &ad = fc->fused;
-      ad.on = 1; ad.lr_t = lr_t; ad.b1 = ADAM_B1; ad.b2 = ADAM_B2; ad.eps = ADAM_EPS;
-      ad.m1 = h->m1_dev; ad.m2 = h->m2_dev; ad.theta_out = tb[(cur + 1) % D];
-      ad.fwd_blob = h->blob_dev; ad.bwd_blob = h->bblob_dev; ad.mirror = tTb[(cur + 1) % D];
-      ad.fwd_dst = tbl; ad.fwd_dst2 = tbl + np; ad.bwd_dst = tbl + 2 * (size_t)np; ad.mirror_dst = fc->mirror_dst;
-    } else if (chained && flags) {   // (data parallel) the chains wait as above -- their rows were replayed by the riders of the latent
-      // phase k - D, whose buffer the Adam launch below overwrites -- but nothing of this launch counts the step done: Adam does
-      fc->sync_t = FitSync{k >= D ? h->epoch_ctr + 1 : nullptr, zt[k % D], nullptr, (int *)(h->epoch_ctr + 2)};
-    } else if (chained && k >= D) BGM_HIP_CHECK(hipStreamWaitEvent(sA, h->epoch_ev_z[k % D], 0));      // (the same under HIP events)
-    rc = bgm_causal_fit_theta_grad(h, x, y, v, data_z, idx, 0, b, b * world, h->epoch_grad, loss, sA);
-    if (fuse) fc->fused.on = 0;
-    if (chained) fc->sync_t = FitSync{};
+    for (int d = 1; ahead && k == 0 && d < D && !rc; ++d) rc = replay(d, sA);
+    if (rc) break;
+    if (k == 0 && (rc = order.start())) return rc;
+    // ---- theta phase on sA: chains, gradient tiles, (all-reduce,) Adam from ring slot cur into the next one
+    const float lr_t = adam_lr_t(lr_theta, h->t_theta + 1, ADAM_B1, ADAM_B2);
+    const int nxt = (cur + 1) % D;
+    FitChainStep ts{tb[cur], tTb[cur]};
+    if ((rc = order.theta_may_overwrite_slot(k, &ts.sync))) return rc;
+    if (fuse) ts.fused = fit_adam_theta(h, fc, lr_t, tb[nxt], tTb[nxt]);
+    if (!(rc = fit_check(h, x, y, v, data_z, b, b * world, "bgm_causal_fit_theta_grad"))) rc = fit_theta_grad(h, mb, h->epoch_grad, loss, ts, sA);
     if (!rc && comm) rc = bgm_comm_enqueue_all_reduce(comm, h->epoch_grad, np, sA);      // C1: the fused g|f|h gradient, summed over the ranks
     if (rc) { hipStreamSynchronize(sB); mark_pending(sA); break; }
-    if (flags && fuse) h->epoch_theta_done += (unsigned)((fc->base.n_tiles + ECH_WAVES - 1) / ECH_WAVES);      // (the gradient-tile kernel's workgroups)
     if (overlap) {
-      if (!fuse && flags) {       // (data parallel) the step as its own launch, ordered on the device like the fused tiles
-        const FitSync sy{nullptr, 0u, h->epoch_ctr, (int *)(h->epoch_ctr + 2)};      // (the chains of this minibatch have waited already)
-        const int ab = (np + 1023) / 1024;
-        hipLaunchKernelGGL(fit_adam_theta_sync_kernel, dim3(ab), dim3(1024), 0, sA, tb[cur], h->m1_dev, h->m2_dev, h->epoch_grad, np, lr_t,
-                           ADAM_B1, ADAM_B2, ADAM_EPS, h->blob_dev, h->bblob_dev, tbl, tbl + np, tbl + 2 * (size_t)np, tTb[(cur + 1) % D], fc->mirror_dst,
-                           tb[(cur + 1) % D], sy);
-        BGM_HIP_CHECK(hipGetLastError());
-        h->epoch_theta_done += (unsigned)ab;
-      } else if (!fuse) {
-        if (k >= D && !chained) BGM_HIP_CHECK(hipStreamWaitEvent(sA, h->epoch_ev_z[k % D], 0));       // latent phase k - D (same slot): it read the buffer written now
-        hipLaunchKernelGGL(fit_adam_theta_kernel, dim3((np + 255) / 256), dim3(256), 0, sA, tb[cur], h->m1_dev, h->m2_dev, h->epoch_grad, np, lr_t,
-                           ADAM_B1, ADAM_B2, ADAM_EPS, h->blob_dev, h->bblob_dev, tbl, tbl + np, tbl + 2 * (size_t)np, tTb[(cur + 1) % D], fc->mirror_dst,
-                           tb[(cur + 1) % D]);
+      unsigned counted = (unsigned)((fc->base.n_tiles + ECH_WAVES - 1) / ECH_WAVES);      // (fused: the gradient-tile kernel's workgroups)
+      if (!fuse) {
+        const FitAdamTheta ad = fit_adam_theta(h, fc, lr_t, tb[nxt], tTb[nxt]);
+        if (flags) {       // (data parallel) the step as its own launch, ordered on the device like the fused tiles
+          counted = (unsigned)((np + 1023) / 1024);
+          hipLaunchKernelGGL(fit_adam_theta_sync_kernel, dim3(counted), dim3(1024), 0, sA, tb[cur], ad.m1, ad.m2, h->epoch_grad, np, lr_t, ad.b1, ad.b2,
+                             ad.eps, ad.fwd_blob, ad.bwd_blob, ad.fwd_dst, ad.fwd_dst2, ad.bwd_dst, ad.mirror, ad.mirror_dst, ad.theta_out, order.adam_sync());
+        } else {
+          if ((rc = order.adam_may_overwrite_slot(k))) return rc;
+          hipLaunchKernelGGL(fit_adam_theta_kernel, dim3((np + 255) / 256), dim3(256), 0, sA, tb[cur], ad.m1, ad.m2, h->epoch_grad, np, lr_t, ad.b1, ad.b2,
+                             ad.eps, ad.fwd_blob, ad.bwd_blob, ad.fwd_dst, ad.fwd_dst2, ad.bwd_dst, ad.mirror, ad.mirror_dst, ad.theta_out);
+        }
         BGM_HIP_CHECK(hipGetLastError());
       }
       h->t_theta += 1;
       h->sblob_valid = false; h->det_valid = false;
-      cur = (cur + 1) % D;
-      fc->theta_use = tb[cur]; fc->thetaT_use = tTb[cur];
-      if (!flags) {
-        BGM_HIP_CHECK(hipEventRecord(h->epoch_ev_t[k % D], sA));
-        BGM_HIP_CHECK(hipStreamWaitEvent(sB, h->epoch_ev_t[k % D], 0));
-      }
+      cur = nxt;
+      if ((rc = order.theta_done(k, counted))) return rc;
     } else if ((rc = bgm_causal_fit_theta_apply(h, h->epoch_grad, lr_theta, sA))) break;
+    // ---- latent phase on sB, reading slot cur; with flags its riders replay minibatch k + D
     if (ahead) h->z_synced = h->t_z + 1;       // (minibatch k's rows were replayed to step tz0 + k = t_z)
-    if (flags) {                               // the latent phase waits for this minibatch's Adam step in the kernel; the replay rides along
-      fc->sync_z = FitSync{h->epoch_ctr, h->epoch_theta_done, h->epoch_ctr + 1, (int *)(h->epoch_ctr + 2)};
-      if (ahead && k + D < n_mb) {
-        fc->rp_idx = perm + (k + D) * batch; fc->rp_n = (int)std::min<int64_t>(batch, n_use - (k + D) * batch);
-        fc->rp_t_to = (int)(tz0 + k + D); fc->rp_lr = lr_z; fc->rp_tlast = h->tlast_dev;
-        replayed = k + D + 1;
-      }
+    FitChainStep zs{tb[cur], tTb[cur]};
+    if ((rc = order.latent_waits_for_adam(k, &zs.sync))) return rc;
+    if (flags && ahead && k + D < n_mb) {
+      zs.rp_idx = perm + (k + D) * batch; zs.rp_n = rows_of(k + D);
+      zs.rp_t_to = (int)(tz0 + k + D); zs.rp_lr = lr_z; zs.rp_tlast = h->tlast_dev;
+      replayed = k + D + 1;
     }
-    rc = bgm_causal_fit_z_step(h, x, y, v, data_z, zm, zv, idx, 0, b, b * world, lr_z, lazy, loss_z, sB);
-    if (flags) {
-      fc->sync_z = FitSync{}; fc->rp_n = 0;
-      if (!rc) { h->epoch_z_done += (unsigned)fc->last_z_blocks; zt[k % D] = h->epoch_z_done; }
-    }
+    int z_blocks = 0;
+    if (!(rc = fit_z_step_check(h, x, y, v, data_z, zm, zv, idx, b, b * world, lazy)))
+      rc = fit_z_step(h, mb, data_z, zm, zv, lr_z, lazy, loss_z, zs, sB, &z_blocks);
     if (rc) { mark_pending(sB); break; }
     if (ahead && !flags && (rc = replay(k + D, sB))) { ++k; mark_pending(sB); break; }
-    if (overlap && !flags) BGM_HIP_CHECK(hipEventRecord(h->epoch_ev_z[k % D], sB));
+    if ((rc = order.latent_done(k, z_blocks))) return rc;
   }
   if (overlap) {
-    fc->theta_use = nullptr; fc->thetaT_use = nullptr;
-    if (k > 0) {      // join: whatever follows on the caller's stream sees the last latent phase ...
-      BGM_HIP_CHECK(hipEventRecord(h->epoch_ev_z[0], sB));
-      BGM_HIP_CHECK(hipStreamWaitEvent(sA, h->epoch_ev_z[0], 0));
-    }
+    if (k > 0 && (rc = order.join())) return rc;
     if (cur != 0) {   // ... and the parameters in the session's own buffers
       BGM_HIP_CHECK(hipMemcpyAsync(h->theta_dev, tb[cur], sizeof(float) * np, hipMemcpyDeviceToDevice, sA));
       BGM_HIP_CHECK(hipMemcpyAsync(fc->thetaT, tTb[cur], sizeof(float) * ((size_t)np + 64), hipMemcpyDeviceToDevice, sA));
@@ -902,8 +838,23 @@ static int fit_epoch_impl(bgm_handle *h, const float *x, const float *y, const f
   }
   // a device-side wait that gave up voids THIS call: say so now, before the caller evaluates or checkpoints the state (one small read
   // per epoch behind the join above)
-  if (flags && !rc) rc = fit_epoch_check(h, sA);
+  if (flags && !rc) rc = epoch_check(h, sA, "bgm_causal_fit_epoch");
   return rc;
+}
+
+extern "C" int bgm_causal_fit_epoch(bgm_handle *h, const float *x, const float *y, const float *v, float *data_z, float *zm, float *zv,
+                                    const int32_t *perm, int64_t n_use, int32_t batch, float lr_theta, float lr_z, int32_t lazy,
+                                    double *loss, double *loss_z, void *stream_) {
+  return fit_epoch_impl(h, x, y, v, data_z, zm, zv, perm, n_use, batch, lr_theta, lr_z, lazy, loss, loss_z, nullptr, 1, stream_);
+}
+
+extern "C" int bgm_causal_fit_epoch_dp(bgm_handle *h, const float *x, const float *y, const float *v, float *data_z, float *zm, float *zv,
+                                       const int32_t *perm, int64_t n_use, int32_t batch, float lr_theta, float lr_z, int32_t lazy,
+                                       double *loss, double *loss_z, void *comm, void *stream_) {
+  if (!comm) { bgm_set_error("bgm_causal_fit_epoch_dp: NULL communicator (bgm_comm_create)"); return BGM_E_INVALID; }
+  int world = 0, rank = 0;
+  if (int rc = bgm_comm_world(comm, &world, &rank)) return rc;
+  return fit_epoch_impl(h, x, y, v, data_z, zm, zv, perm, n_use, batch, lr_theta, lr_z, lazy, loss, loss_z, comm, world, stream_);
 }
 
 extern "C" int bgm_causal_get_weights(bgm_handle *h, int net_id, float *theta_host, int64_t count, void *stream_) {
@@ -931,19 +882,11 @@ extern "C" int bgm_causal_fit_z_grad(bgm_handle *h, const float *x, const float 
   if (!dz_out) { bgm_set_error("bgm_causal_fit_z_grad: dz_out_dev is NULL"); return BGM_E_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   BGM_HIP_CHECK(hipSetDevice(h->device));
-  FitKArgs ka{};
-  ka.m = h->meta; ka.bm = h->fit_meta; ka.ws = h->fit_ws; ka.wsp = h->ws_dev;
-  ka.x = x; ka.y = y; ka.v = v; ka.data_z = data_z; ka.idx = idx; ka.row_lo = row_lo; ka.B = batch;
-  ka.inv_B = 1.0f / (float)batch_global; ka.z_mode = 1; ka.loss = loss;
-  if (FitChainState *fc = static_cast<FitChainState *>(h->fit_chain); fc && batch <= 32) {
-    FitChainArgs ca = fc->base;
-    ca.x = x; ca.y = y; ca.v = v; ca.data_z = data_z; ca.idx = idx; ca.row_lo = row_lo; ca.inv_B = ka.inv_B;
-    ca.loss = loss; ca.dz = h->ws_dev + h->fit_ws.dz; ca.ws = fc->ws_z;
-    fit_chain_launch(fc, ca, batch, 1, stream);
-    rc = BGM_OK;
-  } else if (gx_fit_active(h)) rc = gx_fit_grads(h, x, y, v, data_z, idx, row_lo, batch, batch_global, 1, nullptr, loss, stream);
-  else rc = launch_fwd_bwd(h, ka, stream);
-  if (rc) return rc;
+  const FitBatch b{x, y, v, data_z, idx, row_lo, batch, batch_global};
+  FitChainArgs ca{};
+  if (FitChainState *fc = fit_chains_for(h, batch)) ca = fit_chain_args(h, fc, b, 1, loss);
+  int blocks = 0;
+  if ((rc = fit_z_grads(h, b, &ca, loss, FitChainStep{}, stream, &blocks))) return rc;
   BGM_HIP_CHECK(hipMemcpyAsync(dz_out, h->ws_dev + h->fit_ws.dz, sizeof(float) * (size_t)batch * h->q, hipMemcpyDeviceToDevice, stream));
   return BGM_OK;
 }
@@ -973,7 +916,7 @@ extern "C" int bgm_causal_fit_end(bgm_handle *h, void *stream_) {
   if (!h->fit_active) return BGM_OK;
   BGM_HIP_CHECK(hipSetDevice(h->device));
   BGM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream_));
-  const int rc_epoch = fit_epoch_check(h, (hipStream_t)stream_);      // (reported after the session is closed)
+  const int rc_epoch = epoch_check(h, (hipStream_t)stream_, "bgm_causal_fit_epoch");      // (reported after the session is closed)
   size_t off = 0;
   for (int id : {BGM_NET_G, BGM_NET_F, BGM_NET_H}) {   // theta order g | f | h
     HostNet &n = h->nets[id];
@@ -1185,8 +1128,7 @@ extern "C" int bgm_bgm_fit_theta_apply(bgm_handle *h, const float *grad, float l
   BgmState *s = bst(h);
   BGM_HIP_CHECK(hipSetDevice(h->device));
   s->t_theta += 1;
-  const double t = (double)s->t_theta;
-  const float lr_t = (float)((double)lr_theta * std::sqrt(1.0 - std::pow((double)ADAM_B2, t)) / (1.0 - std::pow((double)ADAM_B1, t)));
+  const float lr_t = adam_lr_t(lr_theta, s->t_theta, ADAM_B1, ADAM_B2);
   const int np = s->n_params;
   const int *tb = s->tables_dev;
   // moving mean/var sit in theta but receive a zero gradient (m = v = 0 -> no Adam movement)
@@ -1210,8 +1152,7 @@ extern "C" int bgm_bgm_fit_z_step(bgm_handle *h, const float *x, float *data_z, 
   const int q = s->cfg.z_dim;
   float *dz = s->ws_dev + s->fit_ws.dz;
   s->t_z += 1;
-  const double t = (double)s->t_z;
-  const float lr_t = (float)((double)lr_z * std::sqrt(1.0 - std::pow((double)ADAM_B2, t)) / (1.0 - std::pow((double)ADAM_B1, t)));
+  const float lr_t = adam_lr_t(lr_z, s->t_z, ADAM_B1, ADAM_B2);
   // batch-norm backward -> d loss / d z (+ the prior term), and the fresh-slot Adam step on the batch rows in the same launch
   hipLaunchKernelGGL(bgm_bn_bwd_kernel, dim3(1), dim3(256), 0, stream, s->ws_dev, s->fit_ws, s->bn_dev, batch, q, 16 * s->KTQ,
                      1.0f / (float)(s->batch_global > 0 ? s->batch_global : batch), data_z, idx, (float *)nullptr, dz, 1, data_z, lr_t,

@@ -4,7 +4,9 @@ bgm_causal_fit_begin, fit_chain_setup, fit_chain_launch and fit_epoch_impl in cs
 can prove from the table alone which kernel family, minibatch instantiation and ring edge every case reaches.
 
 Run as a program (`python tests/_fit_epoch_cases.py NAME ...`, on a GPU) it runs the epoch call of the named cases and prints one
-`NAME sha256` line per case: the child process of test_event_ordering_gives_the_same_bits, started with BGM_FIT_NO_FLAGS=1.
+`NAME sha256` line per case: the child process of test_event_ordering_gives_the_same_bits, started with BGM_FIT_NO_FLAGS=1.  With
+`--host` in front of the names the line carries a second digest, that of the host loop over the same minibatches in the same process:
+the child processes of test_debug_switch_keeps_the_sequential_order, one per BGM_FIT_* switch.
 
 The restatement covers g of at most five hidden layers (the forward blob of a deeper g may not fit the LDS, which changes the family:
 tests/test_gpu_causal_depth.py) and no conditional latent prior."""
@@ -58,6 +60,12 @@ assert len(BY_NAME) == len(CASES)
 
 EVENT_CASES = ["p200-z1-mb3", "p200-z1-mb9", "p200-z2-mb3", "p200-z2-mb9", "p20-z1-mb3", "p20-z1-mb9", "p20-z2-mb3", "p20-z2-mb9"]
 ORACLE_CASES = ["p200-z0-mb4", "p200-z1-mb4", "p200-z2-mb4", "t2-z0-mb4", "t2-z1-mb4", "t2-z2-mb4", "p20-z0-mb4", "p20-z1-mb4", "p20-z2-mb4"]
+# unpadded with riders, a ring that wraps twice and a 16-row tail | padded, 17-row tail, copy-back from a non-zero slot | two latent tiles
+SWITCH_CASES = ["p200-z2-mb9", "p20-z2-mb4", "t2-z1-mb4"]
+# the development switches of the fit path (read once per process): those that only change how the epoch call orders the same launches ...
+EPOCH_SWITCHES = ["BGM_FIT_NO_OVERLAP=1", "BGM_FIT_NO_FUSED_ADAM=1", "BGM_FIT_NO_REPLAY_AHEAD=1", "BGM_FIT_EPOCH_DEPTH=2", "BGM_FIT_EPOCH_DEPTH=3"]
+# ... and those that change the kernel variant or family of both the epoch call and the host loop
+VARIANT_SWITCHES = ["BGM_FIT_ONE_WG=1", "BGM_FIT_NO_WORKERS=1", "BGM_FIT_NO_CHAIN=1"]
 OUTSIDE_CASES = ["p200-z0-mb5", "p200-z1-mb5", "p200-z2-mb5"]          # rows outside the permutation, one n_use in all three modes
 
 
@@ -149,5 +157,6 @@ def plan_of(case):
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from tests.test_gpu_fit_epoch import _run, digest
-    for name in sys.argv[1:]:
-        print(name, digest(_run(BY_NAME[name], True)), flush=True)
+    host = sys.argv[1:2] == ["--host"]
+    for name in sys.argv[1 + host:]:
+        print(name, *[digest(_run(BY_NAME[name], epoch)) for epoch in ((True, False) if host else (True,))], flush=True)

@@ -135,6 +135,12 @@ def test_the_named_subsets():
         c, pl = FE.BY_NAME[n], PLANS[n]
         assert c["p"] in (200, 20) and pl["n_mb"] in (3, 9) and c["lazy"] in (1, 2) and pl["overlap"]
     assert len({(FE.BY_NAME[n]["p"], PLANS[n]["n_mb"], FE.BY_NAME[n]["lazy"]) for n in FE.EVENT_CASES}) == 8
+    a, b, c = (PLANS[n] for n in FE.SWITCH_CASES)       # the cases every development switch is run on
+    assert not a["pad"] and a["riders"] and a["n_mb"] > 2 * a["D"] and a["sizes"][-1] == 16 and a["minibatches"][0]["inst"] == "FS13"
+    assert b["pad"] and b["t0"] == 1 and b["sizes"][-1] == 17 and b["minibatches"][0]["inst"] == "PAD"
+    assert b["n_mb"] % 3 != 0 and a["n_mb"] % 2 != 0           # a ring of three / two buffers ends on another slot: the copy-back
+    assert c["t0"] == 2 and c["overlap"] and not c["riders"] and c["minibatches"][0]["inst"] == "T2"
+    assert len(FE.EPOCH_SWITCHES) == 5 and len(FE.VARIANT_SWITCHES) == 3 and not set(FE.EPOCH_SWITCHES) & set(FE.VARIANT_SWITCHES)
     for n in FE.ORACLE_CASES:
         c, pl = FE.BY_NAME[n], PLANS[n]
         assert c["B"] == 32 and pl["sizes"] == [32, 32, 32, 17] and pl["chain"]

@@ -258,6 +258,28 @@ def test_event_ordering_gives_the_same_bits():
         assert got[name] == digest(_host_result(name)), name
 
 
+@pytest.mark.parametrize("setting", FE.EPOCH_SWITCHES + FE.VARIANT_SWITCHES)
+def test_debug_switch_keeps_the_sequential_order(setting):
+    """Every BGM_FIT_* development switch (read once per process, so one fresh child per setting): under the switch the epoch call still
+    gives the bits of the host loop run in the same process.  The switches that only reorder the epoch call's launches (no overlap, Adam
+    and replay as launches of their own, a shorter ring) must also give the bits of this process, which runs with none of them set: every
+    mode is "the sequential order bit for bit".  The switches that select another kernel variant or family change both sides alike and
+    promise nothing against the default."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    key, value = setting.split("=")
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "_fit_epoch_cases.py"), "--host"] + FE.SWITCH_CASES, cwd=root,
+                       env=dict(os.environ, **{key: value}), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    got = {w[0]: w[1:] for w in (line.split() for line in r.stdout.splitlines()) if w and w[0] in FE.BY_NAME}
+    assert sorted(got) == sorted(FE.SWITCH_CASES) and all(len(d) == 2 for d in got.values()), r.stdout[-2000:]
+    for name in FE.SWITCH_CASES:
+        print(setting, name, "epoch", got[name][0][:12], "host loop", got[name][1][:12], "default", digest(_epoch_result(name))[:12])
+    for name in FE.SWITCH_CASES:
+        assert got[name][0] == got[name][1], (setting, name)
+        if setting in FE.EPOCH_SWITCHES:
+            assert got[name][0] == digest(_epoch_result(name)), (setting, name)
+
+
 # ---- f. one anchor outside the project's kernels --------------------------------------------------------------------------
 @pytest.mark.parametrize("name", FE.ORACLE_CASES)
 def test_epoch_call_matches_the_float64_oracle(name):
