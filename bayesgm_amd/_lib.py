@@ -233,6 +233,7 @@ SYMBOLS = {
     "bgm_causal_hmc_mass_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
     "bgm_causal_hmc_set_partial": (C.c_int, [C.c_void_p, C.c_int32]),
+    "bgm_causal_hmc_set_trajectory": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
     "bgm_bgm_fit_set_global_batch": (C.c_int, [C.c_void_p, C.c_int32]),
     "bgm_bgm_egm_begin": (C.c_int, [C.c_void_p, C.POINTER(BgmEgmConfig), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_int64, C.c_void_p]),

@@ -9,6 +9,10 @@ rate) and frozen afterwards.  The kernels are csrc/causal_hmc_kernels.h.  Nothin
 from its own burn-in draws, in the windows of ``mass_windows``, and frozen afterwards; the step table restarts its Robbins-Monro gain
 at every change of the metric (``mass_schedule``).
 
+``max_trajectory`` / ``jitter_leapfrog`` (opt-in): a chain takes only as many of the ``n_leapfrog`` steps as keep step x steps below
+``max_trajectory``, and with the jitter a number uniform on 1 .. that cap per transition (``resolve_trajectory``; the cap is
+row_adapt.leapfrog_cap; csrc/causal_hmc_traj_kernels.h).
+
 ``predict_individual``: the option checks, the row blocks of ``interval='quantile'`` and ``'tails'``, the size of a tail buffer
 (``tail_size``), the finalisation of the per-row moments and the subgroup formula (``group_dose_response``) are at the end of the module.
 
@@ -69,6 +73,28 @@ def resolve(model, params, step_size, n_leapfrog, target, adapt=True):
     n_leapfrog = DEFAULT_N_LEAPFROG if n_leapfrog is None else n_leapfrog
     check_args(step_size, n_leapfrog, target)
     return float(step_size), int(n_leapfrog), (float(target) if adapt else None)
+
+
+def resolve_trajectory(max_trajectory=None, jitter=False):
+    """The trajectory options of the HMC sampler (``max_trajectory`` / ``jitter_leapfrog``; bgm_causal_hmc_set_trajectory) ->
+    (max_trajectory as a float, 0.0 = no cap; jitter as 0 / 1).  ``max_trajectory`` is None or a finite number > 0, ``jitter`` a
+    bool: the checks of row_adapt.resolve_trajectory without its row_adapt requirement, since this sampler's step is always per
+    chain.  The cap itself is row_adapt.leapfrog_cap(step, n_leapfrog, max_trajectory), taken from the chain's step alone also with
+    mass='diag' (the metric's scales have geometric mean 1, so the step keeps the size)."""
+    return RA.resolve_trajectory(DEFAULT_TARGET, max_trajectory, jitter)
+
+
+def check_trajectory(max_trajectory, jitter, hmc=True, interval=None):
+    """resolve_trajectory for predict / predict_individual / predict_new: either option belongs to sampler='hmc' and has no
+    tail-buffer kernel (interval='tails'); ValueError naming what is in the way, before a device is touched."""
+    T, jit = resolve_trajectory(max_trajectory, jitter)
+    if T > 0.0 or jit:
+        if not hmc:
+            raise ValueError("max_trajectory / jitter_leapfrog belong to sampler='hmc': the MH sampler has no trajectory (sampler='mh')")
+        if interval == "tails":
+            raise ValueError("max_trajectory / jitter_leapfrog are not available with interval='tails': the tail-buffer kernels have no "
+                             "variant with a trajectory length per chain; use interval='quantile' or 'normal'")
+    return T, jit
 
 
 def check_predict_options(sampler, q_sd, row_adapt):

@@ -162,6 +162,7 @@ extern "C" int bgm_causal_hmc_run(bgm_handle *h, const float *x, const float *y,
                            n_leapfrog, seed, acc_count, draws, n_keep, (hipStream_t)stream_};
   CausalHmcLaunch l{};
   if (int rc = bgm_causal_hmc_args(h, "bgm_causal_hmc_run", call, l)) return rc;
+  if (l.st->traj_set()) return bgm_causal_hmc_traj_launch(h, l);      // bgm_causal_hmc_set_trajectory
   if (h->hmc_partial) return bgm_causal_hmc_obs_launch(h, l);      // bgm_causal_hmc_set_partial
   if (l.st->mass.scale) return bgm_causal_hmc_mass_launch(h, l);      // bgm_causal_hmc_set_mass
   return bgm_causal_dispatch(h, "HMC kernel", [&](auto s) {

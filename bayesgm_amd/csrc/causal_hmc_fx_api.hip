@@ -49,6 +49,7 @@ extern "C" int bgm_causal_hmc_run_effects(bgm_handle *h, const float *x, const f
   if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, call, l, fx)) return rc;
   fx.sample_y = sample_y; fx.n_doses = binary ? 2 : n_doses;
   fx.x_values = x_values; fx.adrf_partial = adrf_partial; fx.ite = ite;
+  if (l.st->traj_set()) return bgm_causal_hmc_traj_fx_launch(h, l, fx, binary);      // bgm_causal_hmc_set_trajectory
   if (h->hmc_partial) return bgm_causal_hmc_obs_ite_launch(h, l, fx);      // (binary: checked above)
   return binary ? launch_fx<2>(h, l, fx) : launch_fx<1>(h, l, fx);
 }

@@ -41,6 +41,14 @@ struct CausalHmcFxArgs {
   float *ite;                         // [n][n_keep] (EFFECT 2)
 };
 
+// TRAJ (causal_hmc_traj_kernels.h; bgm_causal_hmc_set_trajectory): the number of leapfrog steps of every chain and iteration.  Only
+// the TRAJ kernels receive it.
+struct CausalHmcTrajArgs {
+  float max_traj;                     // cap on eps x L_i (> 0), or 0: none
+  int jitter;                         // 0 / 1: L_i uniform on 1 .. cap, drawn per chain and iteration
+  int *n_steps;                       // [n] += L_i of every iteration >= burn_in of this launch, or NULL
+};
+
 // floats of f's part of the sampling blob
 __host__ __device__ constexpr int chmc_fx_floats(int KT1) { return 3008 + 1024 * KT1; }
 
@@ -72,11 +80,21 @@ using chmc_arg = std::conditional_t<EFFECT == 0, T, const T &>;
 // leaves their f / h terms out; nothing else of the transition or of the effect pass, which never reads a row's own x or y, differs.
 // TAILS (causal_hmc_tails_kernels.h, with ROWS): the rows' values also enter the two tail buffers of their series, row_tails
 // [2][k_tail][n_doses][n] (causal_effects, TAILS); nothing else differs.
-template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false, bool OBS = false, bool TAILS = false>
+// TRAJ (causal_hmc_traj_kernels.h): a number of leapfrog steps per chain and iteration.  From the launch's n_leapfrog = L and the
+// chain's step eps as it stands, in fp32 and without a quotient: cap = #{l in 0 .. L-1 : l == 0 or float(l) * eps < max_traj}
+// (max_traj = 0: cap = L; with a metric still from eps alone, the scales have geometric mean 1), and with jitter L_i = 1 + min(cap
+// - 1, int(u * float(cap))), u = word it & 3 of Philox(row, it >> 2, 1, TAG_HACC) (the accept uniform is call 0), else L_i = cap.
+// Every wave owns its 16 chains and chmc_logp_grad holds no barrier, so the wave's loop runs to the largest L_i of its own real
+// rows, a uniform value.  A lane past its L_i drifts by 0 and kicks by 0 -- no selects on zc, mom, gc or lpc --: it re-evaluates
+// the point of its step L_i - 1 and reproduces that step's gradient and log posterior, so what reaches the accept decision is the
+// L_i-step proposal.  L_i depends on (eps, global row, it, seed) only, never on z or the momentum.
+template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false, bool OBS = false, bool TAILS = false, bool TRAJ = false>
 __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EFFECT> a, chmc_arg<CausalHmcMassArgs, EFFECT> ma,
                                          chmc_arg<CausalHmcFxArgs, EFFECT> fx, float *row_mom = nullptr, float *row_y = nullptr,
-                                         float *row_tails = nullptr, int k_tail = 0) {
+                                         float *row_tails = nullptr, int k_tail = 0,
+                                         chmc_arg<CausalHmcTrajArgs, EFFECT> tj = CausalHmcTrajArgs{}) {
   static_assert(!TAILS || ROWS, "TAILS: the tail buffers of the per-row dose-response");
+  static_assert(!TRAJ || (!TAILS && EFFECT != 4), "TRAJ: no twin of the tail-buffer and label-sum kernels");
   const CausalHmcMeta &m = a.m;
   const CausalMeta &mf = fx.mf;
   lds_fill(lds, a.blob, m.total);
@@ -116,6 +134,7 @@ __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EF
       chmc_load_z<KT1>(a.grad, m.q, row, g, 0.0f, gr);
       lp = a.logp[row];
     }
+    [[maybe_unused]] int n_taken = 0;      // (TRAJ: the sum of L_i over this launch's retained iterations)
     for (int it = a.it_begin; it < a.it_begin + a.n_iters; ++it) {
       BGM_NO_HOIST();
       f32x4 mom[KT1], zc[KT1], gc[KT1], sc[KT1];
@@ -136,22 +155,45 @@ __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EF
       }
       ke0 = sum_over_g(ke0);
       float lpc = lp;
-      for (int l = 0; l < a.n_leapfrog; ++l) {
+      [[maybe_unused]] int n_loop = 0;             // (TRAJ: the wave's loop bound)
+      [[maybe_unused]] int li = a.n_leapfrog;      // (TRAJ: this chain's steps of this transition, from eps as it stands)
+      if constexpr (TRAJ) {
+        if (tj.max_traj > 0.0f) {
+          li = 1;
+          for (int l = 1; l < a.n_leapfrog; ++l) li += ((float)l * eps < tj.max_traj) ? 1 : 0;
+        }
+        if (tj.jitter) {
+          const uint4 j4 = philox4x32_10(rowid[0], (unsigned)it >> 2, 1u, TAG_HACC, a.k0, a.k1);
+          const unsigned jw = (it & 2) ? ((it & 1) ? j4.w : j4.z) : ((it & 1) ? j4.y : j4.x);
+          const int k = (int)(u01_open(jw) * (float)li);
+          li = 1 + (k < li - 1 ? k : li - 1);
+        }
+        if (it >= a.burn_in) n_taken += li;
+        // the largest L_i among the wave's real rows (a row's four lane groups agree; a clamped padding row counts 1)
+        int lm = ok ? li : 1;
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) lm = max(lm, __shfl_xor(lm, off));
+        n_loop = __builtin_amdgcn_readfirstlane(lm);
+      }
+      for (int l = 0; TRAJ ? l < n_loop : l < a.n_leapfrog; ++l) {
         BGM_NO_HOIST();
         if constexpr (MASS) chmc_mass_load<KT1>(ma.scale, eoff, m.q, g, sc);
+        float drift = eps;
+        if constexpr (TRAJ) drift = l < li ? eps : 0.0f;      // (past L_i: the same point again)
 #pragma unroll
         for (int t = 0; t < KT1; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {      // (the momentum of x and of the padding is zero)
-            if constexpr (MASS) zc[t][r] = fmaf(eps * sc[t][r], mom[t][r], zc[t][r]);
-            else zc[t][r] = fmaf(eps, mom[t][r], zc[t][r]);
+            if constexpr (MASS) zc[t][r] = fmaf(drift * sc[t][r], mom[t][r], zc[t][r]);
+            else zc[t][r] = fmaf(drift, mom[t][r], zc[t][r]);
           }
         chmc_logp_grad<KT1, OBS>(lds, m, j, g, zc, u2, c, xr, yr, lpc, gc, has_x, has_y);
         if constexpr (MASS) {
           BGM_NO_HOIST();
           chmc_mass_load<KT1>(ma.scale, eoff, m.q, g, sc);
         }
-        const float kick = (l < a.n_leapfrog - 1) ? eps : 0.5f * eps;
+        float kick = (l < a.n_leapfrog - 1) ? eps : 0.5f * eps;
+        if constexpr (TRAJ) kick = (l < li - 1) ? eps : (l == li - 1) ? 0.5f * eps : 0.0f;      // (its half kick at its last step, none after)
 #pragma unroll
         for (int t = 0; t < KT1; ++t)
 #pragma unroll
@@ -218,6 +260,8 @@ __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EF
       chmc_store_z<KT1>(a.state, m.q, row, g, z[0]);
       chmc_store_z<KT1>(a.grad, m.q, row, g, gr);
       if (g == 0) { a.logp[row] = lp; a.step[row] = eps; }
+      if constexpr (TRAJ)
+        if (g == 0 && tj.n_steps != nullptr) tj.n_steps[row] += n_taken;
     }
   }
 }

@@ -22,6 +22,7 @@ extern "C" int bgm_causal_hmc_run_group_effects(bgm_handle *h, const float *x, c
                                                 float *group_partial, void *stream_) {
   if (int rc = bgm_causal_hmc_check(h, WHO)) return rc;
   if (n <= 0 || n_iters <= 0) return BGM_OK;
+  if (int rc = bgm_causal_hmc_traj_refuse(h, WHO, "the label-sum kernels")) return rc;
   const std::string who(WHO);
   if (h->hmc_partial) {
     bgm_set_error(who + ": the label sums have no kernel for partially observed rows (bgm_causal_hmc_set_partial); the treatment "

@@ -10,12 +10,31 @@ struct HmcState {
   size_t blob_cap = 0;
   CausalHmcMeta m{};
   CausalHmcMassArgs mass{};        // bgm_causal_hmc_set_mass; scale = NULL: identity mass
+  CausalHmcTrajArgs traj{};        // bgm_causal_hmc_set_trajectory; (0, 0, NULL): the kernels without TRAJ
+  bool traj_set() const { return traj.max_traj > 0.0f || traj.jitter != 0 || traj.n_steps != nullptr; }
 };
 
 static inline HmcState *bgm_causal_hmc_state(bgm_handle *h) {
   if (!h->hmc_state) h->hmc_state = new HmcState();
   return static_cast<HmcState *>(h->hmc_state);
 }
+
+// the trajectory options of the handle while any is set (bgm_causal_hmc_set_trajectory), else NULL
+static inline const CausalHmcTrajArgs *bgm_causal_hmc_traj(const bgm_handle *h) {
+  const HmcState *st = static_cast<const HmcState *>(h->hmc_state);
+  return st && st->traj_set() ? &st->traj : nullptr;
+}
+// BGM_E_UNSUPPORTED, naming the option, for an entry point whose kernels have no TRAJ twin; the handle stays usable
+int bgm_causal_hmc_traj_refuse(const bgm_handle *h, const char *who, const char *kernels);                   // causal_hmc_traj_api.hip
+// the launches of the TRAJ kernels (causal_hmc_traj_kernels.h), all of which live in causal_hmc_traj_api.hip: what the entry points
+// call while a trajectory option is set, after their own checks and with the kernel arguments they built as always.  The metric and
+// the observation pattern (bgm_causal_hmc_set_partial) are read from the handle.
+struct CausalHmcLaunch;
+struct CausalHmcRowFxArgs;
+int bgm_causal_hmc_traj_launch(bgm_handle *h, const CausalHmcLaunch &l);                                      // bgm_causal_hmc_run
+int bgm_causal_hmc_traj_fx_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx, bool binary);      // bgm_causal_hmc_run_effects
+int bgm_causal_hmc_traj_rowfx_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx,
+                                     const CausalHmcRowFxArgs &rf);                                           // bgm_causal_hmc_run_row_effects
 
 // floats of the dual-access blob (causal_hmc_api.hip, hmc_prepare): known from the shape alone, before anything is packed or launched
 static inline int bgm_causal_hmc_blob_floats(int KT1, int n_gh) {

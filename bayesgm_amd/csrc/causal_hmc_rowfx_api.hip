@@ -34,6 +34,7 @@ extern "C" int bgm_causal_hmc_run_row_effects(bgm_handle *h, const float *x, con
   if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, call, l, fx)) return rc;
   fx.sample_y = sample_y; fx.n_doses = n_doses; fx.x_values = x_values;
   const CausalHmcRowFxArgs rf{row_moments, row_draws};
+  if (l.st->traj_set()) return bgm_causal_hmc_traj_rowfx_launch(h, l, fx, rf);      // bgm_causal_hmc_set_trajectory
   if (h->hmc_partial) return bgm_causal_hmc_obs_rowfx_launch(h, l, fx, rf);      // bgm_causal_hmc_set_partial
   return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with per-row effects", [&](auto s, auto metric) {
     using S = decltype(s);

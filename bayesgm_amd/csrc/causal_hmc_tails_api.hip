@@ -20,6 +20,7 @@ extern "C" int bgm_causal_hmc_run_row_tails(bgm_handle *h, const float *x, const
                                             float *row_draws, float *row_tails, int32_t k_tail, void *stream_) {
   if (int rc = bgm_causal_hmc_check(h, WHO)) return rc;
   if (n <= 0 || n_iters <= 0) return BGM_OK;
+  if (int rc = bgm_causal_hmc_traj_refuse(h, WHO, "the tail-buffer kernels")) return rc;
   const std::string who(WHO);
   if (h->cfg.binary_treatment != 0) {
     bgm_set_error(who + ": a binary treatment has its per-row effect already: bgm_causal_hmc_run_effects (BGM_EFFECT_ITE)");

@@ -277,6 +277,18 @@ class CausalEngine(object):
         _lib.check(self.lib.bgm_causal_hmc_set_mass(self.h, _ptr(scale), _ptr(ref), _ptr(s1), _ptr(s2), int(bool(accumulate))),
                    "bgm_causal_hmc_set_mass")
 
+    def set_hmc_trajectory(self, max_trajectory=None, jitter=False, n_steps=None):
+        """The number of leapfrog steps per chain and iteration of the hmc_run calls made afterwards (bgm_causal_hmc_set_trajectory;
+        causal_hmc.resolve_trajectory): with max_trajectory = T a chain whose step is eps takes row_adapt.leapfrog_cap(eps,
+        n_leapfrog, T) steps, with jitter a number uniform on 1 .. that cap drawn per chain and iteration.  n_steps: int32 [n]
+        (device), aligned with the rows of the call, += the steps of every iteration >= burn_in.  All three off (the default):
+        back to the kernels without the option.  hmc_run_rows_tails and EFFECT_GROUP_ITE raise the library's error while set."""
+        T, jit = HM.resolve_trajectory(max_trajectory, jitter)
+        if n_steps is not None and (n_steps.dtype != torch.int32 or n_steps.dim() != 1 or not n_steps.is_contiguous()):
+            raise ValueError("set_hmc_trajectory: n_steps must be a contiguous int32 tensor [n]; got %s %r" % (n_steps.dtype, tuple(n_steps.shape)))
+        self._hmc_traj_keep = n_steps                       # keep the buffer alive while set
+        _lib.check(self.lib.bgm_causal_hmc_set_trajectory(self.h, float(T), int(jit), _ptr(n_steps)), "bgm_causal_hmc_set_trajectory")
+
     def hmc_mass_update(self, n_draws, state, scale, ref, s1, s2):
         """End of an estimation window of n_draws iterations (bgm_causal_hmc_mass_update): scale from the moments (causal_hmc.py,
         mass_update), then ref = state and s1 = s2 = 0.  n_draws = 0 only resets."""
@@ -286,7 +298,7 @@ class CausalEngine(object):
     def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
                    adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None, effect=_lib.EFFECT_NONE,
                    x_values=None, sample_y=True, row_effects=False, row_draws=False, labels=None, n_labels=None, partial=False,
-                   row_tails=None):
+                   row_tails=None, max_trajectory=None, jitter=False):
         """HMC over the latent posterior of every row, one chain per row with a step size of its own.
 
         adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
@@ -320,9 +332,24 @@ class CausalEngine(object):
         partial = True: NaN in y, or in x and y, marks what a row does not observe (new units): its chain samples p(z | x, v) or
         p(z | v) (logpost_grad).  A row with y observed and x not is refused.  Works without an effect, with EFFECT_ITE and with
         row_effects; a fully observed panel gives the run of partial = False bit for bit.
+
+        max_trajectory = T / jitter = True (set_hmc_trajectory, for this run): a chain takes as many of the n_leapfrog steps as
+        keep step x steps below T (at least one), and with jitter a number uniform on 1 .. that many, drawn per chain and
+        iteration; a wave's loop ends at the largest count of its 16 rows.  row_leapfrog [n] (float32) is the mean number of steps
+        per retained transition.  With every option off the run is the one without them, bit for bit.  row_tails and
+        EFFECT_GROUP_ITE have no such kernels: ValueError before anything is launched.
         Returns dict(draws [n_keep, n, q] | None, state, logp, grad, acc_count [burn_in + n_keep], row_step [n]) and, with a metric,
-        mass_scale [n x q]; with an effect, adrf [n_doses, n_keep], ite [n, n_keep] or group_sums [n_labels, n_keep]."""
+        mass_scale [n x q]; with an effect, adrf [n_doses, n_keep], ite [n, n_keep] or group_sums [n_labels, n_keep]; with a
+        trajectory option, n_steps [n] (int32, the steps of the retained transitions) and row_leapfrog [n] = n_steps / n_keep."""
         HM.check_args(step_size, n_leapfrog, adapt)
+        traj_T, traj_jit = HM.resolve_trajectory(max_trajectory, jitter)
+        traj = traj_T > 0.0 or traj_jit != 0
+        if traj and row_tails is not None:
+            raise ValueError("hmc_sample: max_trajectory / jitter are not available with row_tails: the tail-buffer kernels "
+                             "(hmc_run_rows_tails) have no variant with a trajectory length per chain")
+        if traj and effect == _lib.EFFECT_GROUP_ITE:
+            raise ValueError("hmc_sample: max_trajectory / jitter are not available with effect=EFFECT_GROUP_ITE: the label-sum kernels "
+                             "(hmc_run_group_effects) have no variant with a trajectory length per chain")
         diag = HM.check_mass(mass, True, adapt if adapt_table is None else True) is not None
         if diag and mass_scale is not None:
             raise ValueError("hmc_sample: mass='diag' estimates the metric; mass_scale gives a frozen one")
@@ -359,10 +386,13 @@ class CausalEngine(object):
             if tuple(scale.shape) != (n, self.q):
                 raise ValueError("hmc_sample: mass_scale must be [n x q] = %r; got %r" % ((n, self.q), tuple(scale.shape)))
         marks = [start] + ends if diag else []
+        n_steps = torch.zeros(n, device=dev, dtype=torch.int32) if traj else None
         with self._partial_rows(partial, x, y):      # the pattern is checked and the handle's flag set once, not per segment
             try:
                 if scale is not None:
                     self.set_hmc_mass(scale)
+                if traj:
+                    self.set_hmc_trajectory(max_trajectory, jitter, n_steps)
                 it = 0
                 while it < total:
                     stop = min([it + chunk, total] + [b for b in marks if b > it])
@@ -376,9 +406,13 @@ class CausalEngine(object):
             finally:
                 if scale is not None:
                     self.set_hmc_mass(None)
+                if traj:
+                    self.set_hmc_trajectory(None)
         out = dict(draws=draws, state=state, logp=logp, grad=grad, acc_count=acc, row_step=step)
         if scale is not None:
             out["mass_scale"] = scale
+        if traj:
+            out["n_steps"], out["row_leapfrog"] = n_steps, n_steps.float() / float(max(1, int(n_keep)))
         collect(out)
         return out
 

@@ -60,6 +60,7 @@ def _disc_norm(p):
 
 class CausalBGM(object):
     mcmc_diagnostics_ = None         # diagnostics.ChainDiagnostics of the last sampler call that asked for them
+    hmc_row_leapfrog_ = None         # mean leapfrog steps per retained transition of every row (NumPy [n]) of the last HMC call with max_trajectory / jitter_leapfrog; None without
     hmc_row_step_ = None             # per-row HMC step sizes (NumPy, global row order) of the last predict(sampler='hmc') / hmc_sampler call
     hmc_row_mass_ = None             # per-row, per-coordinate HMC metric scales [n, q] (NumPy, global row order) of the last mass='diag' call; None otherwise
     individual_sd_ = None            # per-row, per-dose posterior sd [n, n_doses] (NumPy float64) of the last predict_individual call
@@ -560,13 +561,15 @@ class CausalBGM(object):
         sampled by engine.hmc_sample with the route's keyword arguments ``route_kw`` -- by ``sample(x, y, v, s0)``, the caller's MH
         call, where hmc is None --; ``consume(s0, e0, x, out)`` takes what the block returned, and the block's steps, metric and
         acceptance tail are recorded.  Afterwards the acceptance rate is reported and the steps and the metric are gathered over
-        the ranks into hmc_row_step_ / hmc_row_mass_ (the MH sampler's per-row scales into mh_row_scale_, with keep_mh_scale)."""
+        the ranks into hmc_row_step_ / hmc_row_mass_ (the MH sampler's per-row scales into mh_row_scale_, with keep_mh_scale), and
+        with a trajectory option among ``route_kw`` (_traj_kw) the rows' mean leapfrog steps into hmc_row_leapfrog_."""
         burn_in, n_mcmc, seed, hmc = run
         data_x, data_y, data_v = data
         eng, n_test, total_it = self.engine, len(data_x), burn_in + n_mcmc
         scale_key, scale_attr = ("row_step", "hmc_row_step_") if hmc is not None else ("row_scale", "mh_row_scale_" if keep_mh_scale else None)
         row_scale = torch.zeros(n_test, device=eng.device, dtype=torch.float32) if scale_attr else None
         row_mass = torch.zeros((n_test, eng.q), device=eng.device, dtype=torch.float32) if hmc is not None and hmc[3] is not None else None
+        row_lf = torch.zeros(n_test, device=eng.device, dtype=torch.float32) if hmc is not None and "max_trajectory" in route_kw else None
         acc_tail = 0.0
         for (s0, e0) in blocks:
             x = self._dev(data_x[s0:e0]).reshape(-1)
@@ -581,16 +584,27 @@ class CausalBGM(object):
                 row_scale[s0:e0] = out[scale_key]
             if row_mass is not None:
                 row_mass[s0:e0] = out["mass_scale"]
+            if row_lf is not None:
+                row_lf[s0:e0] = out["row_leapfrog"]
             acc_tail += float(out["acc_count"][max(0, total_it - 100):].sum().item())
         self._report_acceptance(acc_tail, min(100, total_it), n_test, verbose)
         if row_scale is not None:
             setattr(self, scale_attr, parallel.all_reduce_sum_(row_scale).cpu().numpy())      # disjoint row sets: the sum is the gather
         if row_mass is not None:
             self.hmc_row_mass_ = parallel.all_reduce_sum_(row_mass).cpu().numpy()
+        if row_lf is not None:
+            self.hmc_row_leapfrog_ = parallel.all_reduce_sum_(row_lf).cpu().numpy()
+
+    @staticmethod
+    def _traj_kw(traj):
+        """(max_trajectory as a float, jitter as 0 / 1) of causal_hmc.check_trajectory -> the keyword arguments of engine.hmc_sample;
+        none when both are off, so that the run is the one without the options."""
+        T, jit = traj
+        return dict(max_trajectory=T if T > 0.0 else None, jitter=bool(jit)) if (T > 0.0 or jit) else {}
 
     def predict(self, data, alpha=0.01, n_mcmc=3000, burn_in=5000, x_values=None, q_sd=1.0, sample_y=True,
                 bs=10000, verbose=1, diagnose_rows=0, row_adapt=False, sampler='mh', step_size=None, n_leapfrog=None,
-                draw_budget_bytes=None, mass='identity', fused_effects=False):
+                draw_budget_bytes=None, mass='identity', fused_effects=False, max_trajectory=None, jitter_leapfrog=False):
         """Causal effects with posterior intervals from latent MCMC samples (base.py:573-668).
 
         ``sampler='hmc'`` (opt-in; ``'mh'`` is the reference's sampler and the default): the latents are sampled by Hamiltonian Monte
@@ -606,6 +620,10 @@ class CausalBGM(object):
         (``draw_budget_bytes`` has no meaning and is refused; a binary treatment keeps the cap on the ITE matrix).  Chains, steps,
         metric and seed sequence are those of the draws route, and so is the result whenever that route runs one block (several
         blocks reassociate the float32 sums over rows).  Generators too deep for the fused kernels' LDS raise the library's error.
+        ``max_trajectory = T`` / ``jitter_leapfrog=True`` (with ``sampler='hmc'``, opt-in): a chain whose adapted step is eps takes
+        only as many of the ``n_leapfrog`` steps as keep eps x steps below T (at least one), and with the jitter a number uniform on
+        1 .. that many, drawn per chain and iteration (causal_hmc.resolve_trajectory); the cure for chains whose step grew until a
+        trajectory returns to its start.  The mean steps per retained transition are left in ``self.hmc_row_leapfrog_`` [n].
 
         ``bs`` bounded the host memory of the reference; here all rows are sampled in one launch per
         segment (row-blocked only if the ITE draw matrix would exceed device memory) and the result does
@@ -620,9 +638,11 @@ class CausalBGM(object):
         chain depends on its own row only, so a rank's shard is sampled in one piece, the result does not depend on ``bs`` or the
         rank count, and ``diagnose_rows`` works.  The scales are left in ``self.mh_row_scale_``."""
         ra_target = self._row_adapt_target(row_adapt)
-        hmc, x_values, _ = self._sampling_options(
-            ("mh_row_scale_", "hmc_row_step_", "hmc_row_mass_"), lambda: hmc_mod.check_predict_options(sampler, q_sd, row_adapt),
-            (step_size, n_leapfrog, mass, burn_in), lambda use_hmc: hmc_mod.check_fused(fused_effects, use_hmc, draw_budget_bytes),
+        hmc, x_values, traj = self._sampling_options(
+            ("mh_row_scale_", "hmc_row_step_", "hmc_row_mass_", "hmc_row_leapfrog_"), lambda: hmc_mod.check_predict_options(sampler, q_sd, row_adapt),
+            (step_size, n_leapfrog, mass, burn_in),
+            lambda use_hmc: (hmc_mod.check_fused(fused_effects, use_hmc, draw_budget_bytes),
+                             hmc_mod.check_trajectory(max_trajectory, jitter_leapfrog, use_hmc))[1],
             alpha, n_mcmc, x_values)
         binary = bool(self._p['binary_treatment'])
         if not binary and x_values is None:
@@ -681,9 +701,9 @@ class CausalBGM(object):
             else:
                 sums.add_(out["adrf"].double() * float(e0 - s0))
         self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, sample=sample_mh, keep_mh_scale=ra_target is not None,
-                            **(dict(want_draws=True) if from_draws else effect_kw))
+                            **(dict(want_draws=True) if from_draws else effect_kw), **self._traj_kw(traj))
         if diagnose_rows > 0:
-            self._diagnose_rows(data, diagnose_rows, burn_in, n_mcmc, q_sd, seed, row_adapt=ra_target, hmc=hmc)
+            self._diagnose_rows(data, diagnose_rows, burn_in, n_mcmc, q_sd, seed, row_adapt=ra_target, hmc=hmc, traj_kw=self._traj_kw(traj))
         if binary:
             parallel.all_reduce_sum_(res)                         # disjoint row sets: the sum is the gather
             res = res.cpu().numpy()
@@ -694,7 +714,8 @@ class CausalBGM(object):
         return adrf.cpu().numpy(), torch.stack([lo, hi], dim=1).cpu().numpy()
 
     def predict_individual(self, data, x_values, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None, n_leapfrog=None,
-                           mass='identity', interval='normal', draw_budget_bytes=None, groups=None, verbose=1):
+                           mass='identity', interval='normal', draw_budget_bytes=None, groups=None, verbose=1, max_trajectory=None,
+                           jitter_leapfrog=False):
         """The dose-response curve of every row under a continuous treatment, with its posterior uncertainty: ``(mean [n, n_doses],
         interval [n, n_doses, 2])`` of y_i(x_k), the outcome of row i at dose ``x_values[k]``.  The reference has no counterpart
         (its continuous-treatment ``predict`` averages over the panel); a binary treatment has ``predict``'s ITE.
@@ -715,24 +736,30 @@ class CausalBGM(object):
         whose ``rows x n_doses x K x 8`` bytes fit ``draw_budget_bytes``; ``mean``, the sd and ``groups`` as with ``'normal'``.
 
         ``groups`` (int labels [n], optional): ``self.group_dose_response_ = {label: (mean_g, sd_g)}``, the curve of every subgroup
-        (causal_hmc.group_dose_response).  Under torch.distributed the rows are sharded by rank and the results gathered."""
-        hmc, x_values, _ = self._sampling_options(
-            ("hmc_row_step_", "hmc_row_mass_", "individual_sd_", "group_dose_response_"), None, (step_size, n_leapfrog, mass, burn_in),
-            lambda _: hmc_mod.check_individual(bool(self._p['binary_treatment']), x_values, interval, draw_budget_bytes), alpha, n_mcmc,
+        (causal_hmc.group_dose_response).  Under torch.distributed the rows are sharded by rank and the results gathered.
+
+        ``max_trajectory`` / ``jitter_leapfrog``: as in ``predict(sampler='hmc')``, ``self.hmc_row_leapfrog_`` set as there; refused
+        with ``interval='tails'``, whose kernels have no such variant."""
+        hmc, x_values, traj = self._sampling_options(
+            ("hmc_row_step_", "hmc_row_mass_", "hmc_row_leapfrog_", "individual_sd_", "group_dose_response_"), None,
+            (step_size, n_leapfrog, mass, burn_in),
+            lambda _: (hmc_mod.check_individual(bool(self._p['binary_treatment']), x_values, interval, draw_budget_bytes),
+                       hmc_mod.check_trajectory(max_trajectory, jitter_leapfrog, True, interval))[1], alpha, n_mcmc,
             x_values)
         n_test = len(data[0])
         if groups is not None:
             hmc_mod.group_dose_response(np.zeros((n_test, 0)), np.zeros((n_test, 0)), groups)      # (the labels' checks, before a device is touched)
-        mean, bounds = self._individual_rows(data, x_values, alpha, (burn_in, n_mcmc, hmc), sample_y, interval, draw_budget_bytes, verbose)
+        mean, bounds = self._individual_rows(data, x_values, alpha, (burn_in, n_mcmc, hmc), sample_y, interval, draw_budget_bytes, verbose,
+                                             traj=traj)
         if groups is not None:
             self.group_dose_response_ = hmc_mod.group_dose_response(mean, self.individual_sd_, groups)
         return mean, bounds
 
-    def _individual_rows(self, data, x_values, alpha, run, sample_y, interval, draw_budget_bytes, verbose, partial=False):
+    def _individual_rows(self, data, x_values, alpha, run, sample_y, interval, draw_budget_bytes, verbose, partial=False, traj=(0.0, 0)):
         """The row blocks of predict_individual (and of predict_new for a continuous treatment, partial=True: NaN in data's x / y
         marks what a row does not observe): this rank's shard in the blocks of causal_hmc.individual_blocks, every block sampled with
         the per-row effects inside the kernel, the results gathered over the ranks -> (mean, bounds); run = (burn_in, n_mcmc, hmc);
-        sets hmc_row_step_, hmc_row_mass_ and individual_sd_."""
+        sets hmc_row_step_, hmc_row_mass_ and individual_sd_ (and, with the trajectory options traj, hmc_row_leapfrog_)."""
         burn_in, n_mcmc, hmc = run
         n_test, n_doses = len(data[0]), len(x_values)
         seed = self._begin_sampling(verbose)
@@ -752,7 +779,8 @@ class CausalBGM(object):
                 lo, hi = eng.row_tail_quantiles(out.pop("tails"), n_mcmc, alpha / 2, 1 - alpha / 2)
                 res[2, s0:e0], res[3, s0:e0] = lo.t().double(), hi.t().double()
         self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, row_effects=True, row_draws=quantile,
-                            x_values=x_values, sample_y=sample_y, partial=partial, **(dict(row_tails=k_tail) if tails else {}))
+                            x_values=x_values, sample_y=sample_y, partial=partial, **(dict(row_tails=k_tail) if tails else {}),
+                            **self._traj_kw(traj))
         res = parallel.all_reduce_sum_(res).cpu().numpy()
         mean, sd = res[0], res[1]
         self.individual_sd_ = sd
@@ -764,7 +792,8 @@ class CausalBGM(object):
         return mean, bounds
 
     def predict_new(self, data_v, data_x=None, x_values=None, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None,
-                    n_leapfrog=None, mass='identity', interval='normal', draw_budget_bytes=None, verbose=1):
+                    n_leapfrog=None, mass='identity', interval='normal', draw_budget_bytes=None, verbose=1, max_trajectory=None,
+                    jitter_leapfrog=False):
         """Effects for NEW units, whose outcome is not observed: the covariates ``data_v`` [n, p], perhaps the treatment ``data_x``
         [n] (None: not known for any row; NaN entries: not known for those rows), never the outcome.  The reference has no
         counterpart (its ``predict`` takes the triplet (x, y, v) of every row).
@@ -781,16 +810,21 @@ class CausalBGM(object):
         'quantile'`` gives ``predict``'s quantiles of the ITE draws, ``'normal'`` (default) ``mean -/+ z(1 - alpha/2) * sd`` of
         them (sd in ``self.individual_sd_`` [n]); the [rows x n_mcmc] ITE matrix of a block fits ``draw_budget_bytes`` (default
         2 GiB); ``'tails'`` is refused (the ITE route keeps no tails).  A row's result depends on (seed, its global row, its data) only; under torch.distributed the rows are sharded by
-        rank and the results gathered."""
+        rank and the results gathered.
+
+        ``max_trajectory`` / ``jitter_leapfrog``: as in ``predict(sampler='hmc')``, ``self.hmc_row_leapfrog_`` set as there; refused
+        with ``interval='tails'``.  The posterior of a new unit is close to the prior, so its chain's step grows furthest: these
+        are the rows the cap is for."""
         binary = bool(self._p['binary_treatment'])
-        hmc, x_values, (data_v, data_x, data_y) = self._sampling_options(
-            ("hmc_row_step_", "hmc_row_mass_", "individual_sd_"), None, (step_size, n_leapfrog, mass, burn_in),
-            lambda _: hmc_mod.check_new(binary, data_v, data_x, x_values, interval, draw_budget_bytes), alpha, n_mcmc,
+        hmc, x_values, ((data_v, data_x, data_y), traj) = self._sampling_options(
+            ("hmc_row_step_", "hmc_row_mass_", "hmc_row_leapfrog_", "individual_sd_"), None, (step_size, n_leapfrog, mass, burn_in),
+            lambda _: (hmc_mod.check_new(binary, data_v, data_x, x_values, interval, draw_budget_bytes),
+                       hmc_mod.check_trajectory(max_trajectory, jitter_leapfrog, True, interval)), alpha, n_mcmc,
             None if binary else x_values)
         data = (data_x, data_y, data_v)
         if not binary:
             return self._individual_rows(data, x_values, alpha, (burn_in, n_mcmc, hmc), sample_y, interval, draw_budget_bytes, verbose,
-                                         partial=True)
+                                         partial=True, traj=traj)
         n_test = len(data_x)
         seed = self._begin_sampling(verbose)
         eng = self.engine
@@ -805,7 +839,7 @@ class CausalBGM(object):
             res[0, s0:e0], res[2, s0:e0], res[3, s0:e0] = mean.double(), lo.double(), hi.double()
             res[1, s0:e0] = ite.double().std(dim=1) if n_mcmc > 1 else 0.0
         self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, effect=_lib.EFFECT_ITE, sample_y=sample_y,
-                            partial=True)
+                            partial=True, **self._traj_kw(traj))
         res = parallel.all_reduce_sum_(res).cpu().numpy()
         mean, sd = res[0], res[1]
         self.individual_sd_ = sd
@@ -932,7 +966,7 @@ class CausalBGM(object):
         row_adapt_mod.check_supported(type(self).__name__, self._p)
         return self._row_adapt_target(target_acceptance_rate)
 
-    def _diagnose_rows(self, data, k, burn_in, n_mcmc, q_sd, seed, row_adapt=None, hmc=None):
+    def _diagnose_rows(self, data, k, burn_in, n_mcmc, q_sd, seed, row_adapt=None, hmc=None, traj_kw=None):
         """Re-run the chains of k rows of predict's panel with their draws kept (the Philox stream is keyed by the global row, so
         with the same seed and row_base these are the chains predict ran) and store their diagnostics.  Every rank computes the
         same windows; no collectives and no new seed."""
@@ -942,7 +976,8 @@ class CausalBGM(object):
         for (s0, e0) in self._diagnose_windows(len(data_x), k):
             xyv = (self._dev(data_x[s0:e0]).reshape(-1), self._dev(data_y[s0:e0]).reshape(-1), self._dev(data_v[s0:e0]))
             if hmc is not None:
-                out = eng.hmc_sample(*xyv, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2], mass=hmc[3])
+                out = eng.hmc_sample(*xyv, burn_in, n_mcmc, hmc[0], hmc[1], seed, want_draws=True, row_base=s0, adapt=hmc[2], mass=hmc[3],
+                                     **(traj_kw or {}))
             else:
                 out = eng.mh_sample(*xyv, burn_in, n_mcmc, q_sd, seed, want_draws=True, row_base=s0, row_adapt=row_adapt)
             parts.append(out["draws"])
@@ -989,7 +1024,8 @@ class CausalBGM(object):
         return out["draws"].cpu().numpy()
 
     def hmc_sampler(self, data, n_keep=3000, burn_in=5000, step_size=hmc_mod.DEFAULT_STEP_SIZE, n_leapfrog=hmc_mod.DEFAULT_N_LEAPFROG,
-                    target_acceptance_rate=hmc_mod.DEFAULT_TARGET, adapt=True, diagnostics=False, mass='identity', partial=False):
+                    target_acceptance_rate=hmc_mod.DEFAULT_TARGET, adapt=True, diagnostics=False, mass='identity', partial=False,
+                    max_trajectory=None, jitter_leapfrog=False):
         """Posterior samples of Z, shape (n_keep, n, q), by Hamiltonian Monte Carlo on get_log_posterior: ``n_leapfrog`` steps per
         transition, identity mass, one chain per row.  ``adapt=True``: every chain adapts a step size of its own during burn-in
         towards ``target_acceptance_rate``, starting from ``step_size`` (causal_hmc.py); the retained chain is plain HMC.  The steps
@@ -997,17 +1033,24 @@ class CausalBGM(object):
         coordinate from its own burn-in draws, in windows, and keeps it afterwards (a diagonal metric, causal_hmc.py); the scales
         are left in ``self.hmc_row_mass_`` [n, q].  diagnostics=True: as in metropolis_hastings_sampler.  ``partial=True``: NaN in
         ``data_y``, or in ``data_x`` and ``data_y``, marks what a row does not observe; its chain samples p(z | x, v) or p(z | v)
-        (``predict_new``).  A row with its outcome observed and its treatment not is refused."""
+        (``predict_new``).  A row with its outcome observed and its treatment not is refused.  ``max_trajectory`` /
+        ``jitter_leapfrog``: as in ``predict(sampler='hmc')``; the mean steps per retained transition are left in
+        ``self.hmc_row_leapfrog_``."""
         step_size, n_leapfrog, target = hmc_mod.resolve(type(self).__name__, self._p, step_size, n_leapfrog, target_acceptance_rate, adapt)
         mass = hmc_mod.check_mass(mass, True, adapt, burn_in)
+        traj_kw = self._traj_kw(hmc_mod.check_trajectory(max_trajectory, jitter_leapfrog))
         self.hmc_row_step_ = None
         self.hmc_row_mass_ = None
+        self.hmc_row_leapfrog_ = None
         data_x, data_y, data_v = data
         if partial:
             hmc_mod.check_partial_rows(np.asarray(data_x, np.float32).reshape(-1), np.asarray(data_y, np.float32).reshape(-1))
         out = self.engine.hmc_sample(self._dev(data_x).reshape(-1), self._dev(data_y).reshape(-1), self._dev(data_v), burn_in, n_keep,
-                                     step_size, n_leapfrog, self._next_seed(), want_draws=True, adapt=target, mass=mass, partial=bool(partial))
+                                     step_size, n_leapfrog, self._next_seed(), want_draws=True, adapt=target, mass=mass, partial=bool(partial),
+                                     **traj_kw)
         self.hmc_row_step_ = out["row_step"].cpu().numpy()
+        if traj_kw:
+            self.hmc_row_leapfrog_ = out["row_leapfrog"].cpu().numpy()
         if mass is not None:
             self.hmc_row_mass_ = out["mass_scale"].cpu().numpy()
         tot = burn_in + n_keep

@@ -544,6 +544,24 @@ BGM_API int bgm_causal_hmc_mass_update(bgm_handle *h, int64_t n, int32_t n_draws
  * replaces: nothing in causalbgm/base.py; the reference's predict (:573-668) takes the training triplet (x, y, v) of every row. */
 BGM_API int bgm_causal_hmc_set_partial(bgm_handle *h, int32_t on);
 
+/* A number of leapfrog steps per chain and iteration for the HMC calls made afterwards (opt-in; (0, 0, NULL), the default: today's
+ * kernels).  From a call's n_leapfrog = L and the chain's step eps as it stands (the adapting one during burn-in), in float32 and
+ * without a quotient: cap = the number of l in 0 .. L-1 with l == 0 or float(l) * eps < max_trajectory (max_trajectory = 0: cap =
+ * L; with a metric the cap is still taken from eps alone, since the metric's scales have geometric mean 1).  jitter = 1: at
+ * iteration it the chain takes L_i = 1 + min(cap - 1, int(u * float(cap))) steps, u = word it & 3 of Philox(row_base + row, it >> 2,
+ * 1, TAG_HACC) (the accept uniform stays call 0); jitter = 0: L_i = cap.  The proposal that reaches the accept decision is the
+ * point after L_i steps.  L_i depends on (eps, global row, it, seed) only, so with eps frozen after burn-in every retained
+ * transition is a valid HMC kernel, and launch cuts, row_base, row blocks and the rank count change no bit.  A wave's leapfrog loop
+ * ends at the largest L_i of its own 16 rows, so a capped run costs fewer gradient evaluations.  n_steps_dev [n] int32 (may be
+ * NULL), aligned with the rows of the call like state_dev: += L_i for every iteration >= burn_in.  It must stay valid while set.
+ * Read by bgm_causal_hmc_run, bgm_causal_hmc_run_effects and bgm_causal_hmc_run_row_effects, with or without a metric and the
+ * observation pattern of bgm_causal_hmc_set_partial; signatures, RNG streams and launch cuts are unchanged, and a cap that never
+ * binds gives the run without the option bit for bit.  While anything is set, bgm_causal_hmc_run_row_tails and
+ * bgm_causal_hmc_run_group_effects answer BGM_E_UNSUPPORTED naming the option.  A negative or non-finite max_trajectory or a
+ * jitter other than 0 / 1: BGM_E_INVALID naming the argument.  Refuses what bgm_causal_logpost_grad refuses.
+ * replaces: nothing in causalbgm/base.py; max_trajectory / jitter_leapfrog of bgm_bgm_hmc_run_rows_traj for this sampler. */
+BGM_API int bgm_causal_hmc_set_trajectory(bgm_handle *h, float max_trajectory, int32_t jitter, int32_t *n_steps_dev);
+
 /* ------------------------------------------------------------------------------------------
  * CausalBGM.fit step functions (iterative theta / Z updates).
  * replaces: update_g_net :156-180, update_h_net :183-214, update_f_net :217-243,
