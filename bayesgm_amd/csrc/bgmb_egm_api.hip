@@ -7,45 +7,16 @@
 #include "bgm_host.h"
 #include "bgmb_state.h"
 #include "bgmb_egm_kernels.h"
+#include "egm_host.h"
 
 static constexpr float VEGM_B1 = 0.5f, VEGM_B2 = 0.9f, VEGM_ADAM_EPS = 1e-7f;   // bgm/base.py:82-85, Keras epsilon
 
-struct BgmbEgmState {
-  bgm_bgm_egm_config cfg{};
-  BgmbEgmArgs base{};
-  size_t n_g = 0, n_e = 0, n_gen = 0, n_dz = 0, n_dx = 0, n_disc = 0, ws_floats = 0, enc_ws_per_block = 0;
-  long long t_g = 0, t_d = 0;
-  float *dev = nullptr;
-  float *enc_ws = nullptr;
-  int enc_blocks = 0;
-};
+using BgmbEgmState = BgmEgmSession<BgmbEgmArgs>;
 
-void bgm_bvn_egm_free(void *p) {
-  if (!p) return;
-  BgmbEgmState *s = static_cast<BgmbEgmState *>(p);
-  if (s->dev) hipFree(s->dev);
-  if (s->enc_ws) hipFree(s->enc_ws);
-  delete s;
-}
+void bgm_bvn_egm_free(void *p) { delete static_cast<BgmbEgmState *>(p); }
 
 static BgmbState *vst(bgm_handle *h) { return static_cast<BgmbState *>(h->bvn_state); }
 static BgmbEgmState *vest(bgm_handle *h) { return (h && h->bvn_state) ? static_cast<BgmbEgmState *>(vst(h)->egm) : nullptr; }
-
-static int vfill_disc(EgmDisc &d, int in_dim, int n_hidden, const int32_t *units) {
-  d.n_hidden = n_hidden;
-  d.dims[0] = in_dim;
-  for (int l = 0; l < n_hidden; ++l) d.dims[l + 1] = units[l];
-  d.dims[n_hidden + 1] = 1;
-  int o = 0;
-  for (int l = 0; l <= n_hidden; ++l) { d.w[l] = o; o += d.dims[l] * d.dims[l + 1]; }
-  for (int l = 0; l <= n_hidden; ++l) { d.b[l] = o; o += d.dims[l + 1]; }
-  for (int l = 0; l < n_hidden; ++l) { d.gamma[l] = o; o += d.dims[l + 1]; }
-  for (int l = 0; l < n_hidden; ++l) { d.beta[l] = o; o += d.dims[l + 1]; }
-  d.n_params = o;
-  egm_finish_disc(d);
-  d.fixed_norm = 0;
-  return o;
-}
 
 extern "C" int bgm_bvn_egm_begin(bgm_handle *h, const bgm_bgm_egm_config *cfg, const float *theta_e_host, int64_t count_e,
                                  const float *theta_dz_host, int64_t count_dz, const float *theta_dx_host, int64_t count_dx,
@@ -68,28 +39,11 @@ extern "C" int bgm_bvn_egm_begin(bgm_handle *h, const bgm_bgm_egm_config *cfg, c
   a.g = bs->net;
   a.q = q; a.p = p;
   s->n_g = (size_t)bs->n_params;
-  EgmMlp &e = a.e;
-  e.n_layers = cfg->n_hidden_e + 1;
-  e.dims[0] = p;
-  for (int i = 0; i < cfg->n_hidden_e; ++i) e.dims[i + 1] = cfg->e_units[i];
-  e.dims[cfg->n_hidden_e + 1] = q;
-  e.off = (int)s->n_g;
-  egm_finish_mlp(e);
-  size_t ne = 0;
-  for (int l = 0; l < e.n_layers; ++l) ne += (size_t)e.dims[l] * e.dims[l + 1] + e.dims[l + 1];
-  s->n_e = ne;
-  s->n_gen = s->n_g + s->n_e;
-  s->n_dz = (size_t)vfill_disc(a.dz, q, cfg->n_hidden_dz, cfg->dz_units);
-  s->n_dx = (size_t)vfill_disc(a.dx, p, cfg->n_hidden_dx, cfg->dx_units);
-  a.dz.fixed_norm = a.dx.fixed_norm = h->disc_norm;
-  s->n_disc = s->n_dz + s->n_dx;
-  if ((int64_t)s->n_e != count_e || (int64_t)s->n_dz != count_dz || (int64_t)s->n_dx != count_dx) {
-    const std::string msg = "bgm_bvn_egm_begin: expected " + std::to_string(s->n_e) + " / " + std::to_string(s->n_dz) + " / " +
-                            std::to_string(s->n_dx) + " encoder / dz / dx parameters";
+  if (int rc = bgm_egm_describe(*s, "bgm_bvn_egm_begin", q, p, h->disc_norm, count_e, count_dz, count_dx)) {
     bgm_bvn_egm_free(bs->egm); bs->egm = nullptr;
-    bgm_set_error(msg);
-    return BGM_E_INVALID;
+    return rc;
   }
+  const EgmMlp &e = a.e;
   int wmax = std::max(bs->wmax, std::max(q, 2 * p));
   auto scan = [&](const int *dims, int n_layers) { size_t t = 0; for (int l = 0; l <= n_layers; ++l) { wmax = std::max(wmax, dims[l]); t += dims[l] + 4; } return t; };
   const size_t we = scan(e.dims, e.n_layers);
@@ -101,31 +55,11 @@ extern "C" int bgm_bvn_egm_begin(bgm_handle *h, const bgm_bgm_egm_config *cfg, c
   // gradient-penalty scratch of the wider discriminator, scratch rows
   const size_t widths = 2 * we + 10 * (size_t)p + 2 * (size_t)q + 11 * std::max(wdz, wdx) + 12 * (size_t)wmax + 64;
   s->ws_floats = 2 * bnn_cache_floats(a.g, B) + (size_t)B * widths + s->n_disc + 8192;
-  const size_t total = 4 * s->n_gen + 4 * s->n_disc + s->ws_floats + 256;
-  BGM_HIP_CHECK(hipMalloc(&s->dev, total * sizeof(float)));
-  BGM_HIP_CHECK(hipMemset(s->dev, 0, total * sizeof(float)));
-  float *pp = s->dev;
-  auto take = [&](size_t n) { float *r = pp; pp += (n + 3) / 4 * 4; return r; };
-  a.theta_g = take(s->n_gen); a.m_g = take(s->n_gen); a.v_g = take(s->n_gen); a.grad_g = take(s->n_gen);
-  a.theta_d = take(s->n_disc); a.m_d = take(s->n_disc); a.v_d = take(s->n_disc); a.grad_d = take(s->n_disc);
-  a.ws = take(s->ws_floats);
+  if (int rc = bgm_egm_allocate(*s, 256, we, h->n_cus, theta_e_host, theta_dz_host, theta_dx_host)) return rc;
   BGM_HIP_CHECK(hipMemcpy(a.theta_g, bs->theta_dev, s->n_g * sizeof(float), hipMemcpyDeviceToDevice));
-  BGM_HIP_CHECK(hipMemcpy(a.theta_g + s->n_g, theta_e_host, s->n_e * sizeof(float), hipMemcpyHostToDevice));
-  BGM_HIP_CHECK(hipMemcpy(a.theta_d, theta_dz_host, s->n_dz * sizeof(float), hipMemcpyHostToDevice));
-  BGM_HIP_CHECK(hipMemcpy(a.theta_d + s->n_dz, theta_dx_host, s->n_dx * sizeof(float), hipMemcpyHostToDevice));
-  s->enc_blocks = h->n_cus;
-  s->enc_ws_per_block = (size_t)64 * (we + 8) + 64;
-  BGM_HIP_CHECK(hipMalloc(&s->enc_ws, s->enc_ws_per_block * s->enc_blocks * sizeof(float)));
+  s->core.set_adam(cfg->lr, VEGM_B1, VEGM_B2, VEGM_ADAM_EPS);
   return BGM_OK;
 }
-
-static EgmAdam vegm_adam(float lr, long long t) {
-  EgmAdam ad;
-  ad.b1 = VEGM_B1; ad.b2 = VEGM_B2; ad.eps = VEGM_ADAM_EPS;
-  ad.lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)VEGM_B2, (double)t)) / (1.0 - std::pow((double)VEGM_B1, (double)t)));
-  return ad;
-}
-static constexpr int VEGM_LDS = 64 * (int)sizeof(float);
 
 extern "C" int bgm_bvn_egm_disc_step(bgm_handle *h, const float *z_dev, const float *x_dev, const float *noise_dev, float eps_z,
                                      float eps_x, uint64_t seed, uint32_t stream_id, int32_t apply, float *out_dev, void *stream_) {
@@ -136,9 +70,8 @@ extern "C" int bgm_bvn_egm_disc_step(bgm_handle *h, const float *z_dev, const fl
   BgmbEgmArgs a = s->base;
   a.z = z_dev; a.x = x_dev; a.n1 = noise_dev; a.n2 = nullptr; a.eps_z = eps_z; a.eps_x = eps_x; a.out = out_dev; a.apply = apply ? 1 : 0;
   a.k0 = (uint32_t)(seed & 0xFFFFFFFFull); a.k1 = (uint32_t)(seed >> 32); a.stream = stream_id;
-  if (apply) s->t_d += 1;
-  a.adam = vegm_adam(s->cfg.lr, std::max<long long>(1, s->t_d));
-  hipLaunchKernelGGL(bgmb_egm_disc_step_kernel, dim3(1), dim3(EGM_THREADS), VEGM_LDS, (hipStream_t)stream_, a);
+  a.adam = s->core.adam(1, apply != 0);
+  hipLaunchKernelGGL(bgmb_egm_disc_step_kernel, dim3(1), dim3(EGM_THREADS), BGM_EGM_LDS, (hipStream_t)stream_, a);
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;
 }
@@ -153,61 +86,28 @@ extern "C" int bgm_bvn_egm_gen_step(bgm_handle *h, const float *z_dev, const flo
   BgmbEgmArgs a = s->base;
   a.z = z_dev; a.x = x_dev; a.n1 = noise1_dev; a.n2 = noise2_dev; a.eps_z = a.eps_x = 0.0f; a.out = out_dev; a.apply = apply ? 1 : 0;
   a.k0 = (uint32_t)(seed & 0xFFFFFFFFull); a.k1 = (uint32_t)(seed >> 32); a.stream = stream_id;
-  if (apply) s->t_g += 1;
-  a.adam = vegm_adam(s->cfg.lr, std::max<long long>(1, s->t_g));
-  hipLaunchKernelGGL(bgmb_egm_gen_step_kernel, dim3(1), dim3(EGM_THREADS), VEGM_LDS, (hipStream_t)stream_, a);
+  a.adam = s->core.adam(0, apply != 0);
+  hipLaunchKernelGGL(bgmb_egm_gen_step_kernel, dim3(1), dim3(EGM_THREADS), BGM_EGM_LDS, (hipStream_t)stream_, a);
   BGM_HIP_CHECK(hipGetLastError());
   return BGM_OK;
-}
-
-static int vegm_region(BgmbEgmState *s, int32_t what, float **ptr, size_t *n) {
-  switch (what) {
-    case 0: *ptr = s->base.theta_g; *n = s->n_gen; return BGM_OK;
-    case 1: *ptr = s->base.theta_d; *n = s->n_disc; return BGM_OK;
-    case 2: *ptr = s->base.grad_g; *n = s->n_gen; return BGM_OK;
-    case 3: *ptr = s->base.grad_d; *n = s->n_disc; return BGM_OK;
-    default: bgm_set_error("bgm_bvn_egm_read/write: what must be 0..3"); return BGM_E_INVALID;
-  }
 }
 
 extern "C" int bgm_bvn_egm_read(bgm_handle *h, int32_t what, float *host, int64_t count, void *stream_) {
   BgmbEgmState *s = vest(h);
   if (!s || !host) { bgm_set_error("bgm_bvn_egm_read: no session / NULL"); return BGM_E_STATE; }
-  float *src; size_t n;
-  int rc = vegm_region(s, what, &src, &n);
-  if (rc) return rc;
-  if ((size_t)count != n) { bgm_set_error("bgm_bvn_egm_read: expected " + std::to_string(n) + " floats"); return BGM_E_INVALID; }
-  BGM_HIP_CHECK(hipSetDevice(h->device));
-  BGM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream_));
-  BGM_HIP_CHECK(hipMemcpy(host, src, n * sizeof(float), hipMemcpyDeviceToHost));
-  return BGM_OK;
+  return egm_read(s->core, h->device, "bgm_bvn_egm_read", "bgm_bvn_egm_read/write", what, host, count, (hipStream_t)stream_);
 }
 
 extern "C" int bgm_bvn_egm_write(bgm_handle *h, int32_t what, const float *host, int64_t count, void *stream_) {
   BgmbEgmState *s = vest(h);
   if (!s || !host) { bgm_set_error("bgm_bvn_egm_write: no session / NULL"); return BGM_E_STATE; }
-  float *dst; size_t n;
-  int rc = vegm_region(s, what, &dst, &n);
-  if (rc) return rc;
-  if (what > 1 || (size_t)count != n) { bgm_set_error("bgm_bvn_egm_write: parameters only, expected " + std::to_string(n) + " floats"); return BGM_E_INVALID; }
-  BGM_HIP_CHECK(hipSetDevice(h->device));
-  BGM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream_));
-  BGM_HIP_CHECK(hipMemcpy(dst, host, n * sizeof(float), hipMemcpyHostToDevice));
-  return BGM_OK;
+  return egm_write(s->core, h->device, "bgm_bvn_egm_write", "bgm_bvn_egm_read/write", what, host, count, (hipStream_t)stream_);
 }
 
 extern "C" int bgm_bvn_egm_encode(bgm_handle *h, const float *x_dev, int64_t n, float *z_dev, void *stream_) {
   BgmbEgmState *s = vest(h);
   if (!s) { bgm_set_error("bgm_bvn_egm_encode: no session"); return BGM_E_STATE; }
-  if (n <= 0) return BGM_OK;
-  if (!x_dev || !z_dev) { bgm_set_error("bgm_bvn_egm_encode: NULL pointer"); return BGM_E_INVALID; }
-  BGM_HIP_CHECK(hipSetDevice(h->device));
-  const int B = 64;
-  const int grid = (int)std::max<long long>(1, std::min<long long>((n + B - 1) / B, s->enc_blocks));
-  hipLaunchKernelGGL(bgm_egm_encode_kernel, dim3(grid), dim3(EGM_THREADS), VEGM_LDS, (hipStream_t)stream_, s->base.e, s->base.theta_g, x_dev,
-                     (long long)n, z_dev, s->enc_ws, (long long)s->enc_ws_per_block, B);
-  BGM_HIP_CHECK(hipGetLastError());
-  return BGM_OK;
+  return bgm_egm_encode(*s, bgm_egm_encode_kernel, h->device, "bgm_bvn_egm_encode", x_dev, n, z_dev, (hipStream_t)stream_);
 }
 
 // copy the session's generator into the bvn session (its Adam slots are untouched)

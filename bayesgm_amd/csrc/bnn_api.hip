@@ -80,14 +80,13 @@ static void bnn_chain_free(BnnState *s) {
 }
 static int bnn_chain_setup(BnnState *s) {
   if (std::getenv("BGM_BNN_NO_CHAIN") || !ecb_shapes_ok(s->net, s->q, s->p, false)) return BGM_OK;
-  const int ntl_need = (s->p + 1 + 15) / 16, B = 32;
-  const int t0 = s->q <= 16 ? 1 : 2;
-  const int ntl = ((ntl_need == 13 || ntl_need == 7) && t0 == 1) ? ntl_need : 13;
+  const ChainExtent x = chain_extent(s->q, s->p);
+  const int ntl = x.ntl, B = 32;
   BnnFitChain *c = new BnnFitChain();
   s->chain = c;
   c->ntl = ntl;
-  c->t0 = t0;
-  c->pad = ntl != ntl_need || t0 == 2;
+  c->t0 = x.t0;
+  c->pad = x.pad;
   EcbTab tt{}, tz{};
   std::vector<int> tiles, none;
   const int tnet[3] = {BNN_G, BNN_H, BNN_F}, tso[3] = {0, 0, 0}, trained[3] = {BNN_G, BNN_H, BNN_F};

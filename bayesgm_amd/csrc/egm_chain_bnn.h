@@ -8,6 +8,7 @@
 #pragma once
 #include "bnn_kernels.h"
 #include "egm_chain_gen.h"
+#include "egm_plan.h"
 
 // x with the sign of every (row, feature) flipped where the bit string that starts at word w0 of the row's sign words has a 1
 // (bnn_sign); feature 16 t + 4 g + r of the tile layout = bit (16 (t & 1) + 4 g + r) of word w0 + (t >> 1)
@@ -1593,26 +1594,8 @@ inline size_t ecb_build_tab(const BnnNet *nets, const int *call_net, const int *
   tab.n_tiles = (int)(tiles.size() / ECB_TILE_INTS);
   return off + 64;
 }
-// shapes the row-tile chains are compiled for
+// shapes the row-tile chains are compiled for (egm_plan.h)
+inline BnnNetDims ecb_dims(const BnnNet &n) { return {{n.dims, n.n_layers}, n.bn_fixed, n.heads, n.mv}; }
 inline bool ecb_shapes_ok(const BnnNet *nets, int q, int p, bool need_e) {
-  bool ok = q <= 32;               // one latent input tile, or two (B = 32, 13-tile kernels)
-  const int ntl = (p + 1 + 15) / 16;
-  ok = ok && ntl <= 13;            // 13 and 7 are compiled exactly; anything narrower runs the 13-tile kernels with masked columns
-  for (int k = 0; k < 4; ++k) {
-    if (k == BNN_E && !need_e) continue;
-    ok = ok && nets[k].bn_fixed == 1 && !nets[k].heads && !nets[k].mv;
-  }
-  const BnnNet &G = nets[BNN_G], &E = nets[BNN_E];
-  ok = ok && G.n_layers >= 3 && G.dims[0] == q && G.dims[G.n_layers] == p + 1;
-  for (int l = 1; l < G.n_layers; ++l) ok = ok && G.dims[l] == 64;
-  if (need_e) {
-    ok = ok && E.n_layers >= 3 && E.dims[E.n_layers] == q && E.dims[0] == p;
-    for (int l = 1; l < E.n_layers; ++l) ok = ok && E.dims[l] == 64;
-  }
-  for (int k : {BNN_F, BNN_H}) {
-    const BnnNet &m = nets[k];
-    ok = ok && m.n_layers == 4 && m.dims[0] <= 16 && m.dims[1] == 64 && m.dims[2] == 32 && m.dims[3] >= 1 && m.dims[3] <= 16 && m.dims[4] >= 1 &&
-         m.dims[4] <= 16;
-  }
-  return ok;
+  return bnn_chain_shapes_ok(ecb_dims(nets[BNN_G]), ecb_dims(nets[BNN_E]), ecb_dims(nets[BNN_F]), ecb_dims(nets[BNN_H]), q, p, need_e);
 }

@@ -11,6 +11,7 @@
 #include "fit_kernels.h"
 #include "fit_chain.h"
 #include "fit_epoch_host.h"
+#include "egm_host.h"
 
 #include <vector>
 
@@ -54,24 +55,20 @@ static bool fit_fill_mlp(const HostNet &n, EgmMlp &m, int off) {
 static int fit_chain_setup(bgm_handle *h, const std::vector<float> &theta) {
   const HostNet &G = h->nets[BGM_NET_G], &F = h->nets[BGM_NET_F], &H = h->nets[BGM_NET_H];
   const int ng = (int)G.count(), nf = (int)F.count(), np = h->n_params, q = h->q, p = h->p;
-  const int ntl_need = (p + 1 + 15) / 16;
-  const int t0 = q <= 16 ? 1 : 2;
-  const int ntl = ((ntl_need == 13 || ntl_need == 7) && t0 == 1) ? ntl_need : 13;
+  const ChainExtent x = chain_extent(q, p);
+  const int ntl = x.ntl;
   FitChainArgs a{};
-  bool ok = !fit_dev_switches().no_chain && q <= 32 && ntl_need <= 13 && fit_fill_mlp(G, a.g, 0) && fit_fill_mlp(F, a.f, ng) &&
-            fit_fill_mlp(H, a.h, ng + nf);
-  ok = ok && a.g.n_layers >= 3 && a.g.dims[0] == q && a.g.dims[a.g.n_layers] == p + 1;
-  for (int l = 1; ok && l < a.g.n_layers; ++l) ok = a.g.dims[l] == 64;
-  for (const EgmMlp *m : {&a.f, &a.h})
-    ok = ok && m->n_layers == 4 && m->dims[0] <= 16 && m->dims[1] == 64 && m->dims[2] == 32 && m->dims[3] >= 1 && m->dims[3] <= 16 && m->dims[4] == 2;
+  // g with 64-wide hidden layers onto p + 1 outputs, the heads 64-32-(1..16) onto their mean / variance pair
+  const bool ok = !fit_dev_switches().no_chain && q <= 32 && x.ntl_need <= 13 && fit_fill_mlp(G, a.g, 0) && fit_fill_mlp(F, a.f, ng) &&
+                  fit_fill_mlp(H, a.h, ng + nf) && chain_trunk_ok(egm_dims(a.g), 3, q, p + 1) && chain_head_ok(egm_dims(a.f), 2, 2) &&
+                  chain_head_ok(egm_dims(a.h), 2, 2);
   if (!ok) return BGM_OK;
   FitChainState *c = new FitChainState();
   h->fit_chain = c;
   c->ntl = ntl;
-  c->t0 = t0;
-  c->pad = ntl != ntl_need || t0 == 2;
+  c->t0 = x.t0;
+  c->pad = x.pad;
   const int B = 32;
-  auto tl = [](int n) { return (n + 15) / 16; };
   size_t off = 0;
   auto take = [&](size_t n) { const size_t r = off; off += (n + 3) / 4 * 4; return (int)r; };
   const EgmMlp *nets[3] = {&a.g, &a.f, &a.h};
@@ -81,23 +78,12 @@ static int fit_chain_setup(bgm_handle *h, const std::vector<float> &theta) {
   for (int k = 0; k < 3; ++k) {
     const EgmMlp &m = *nets[k];
     for (int l = 0; l < m.n_layers; ++l) {
-      xw[k][l] = 16 * tl(m.dims[l]); dw[k][l] = 16 * tl(m.dims[l + 1]);
+      xw[k][l] = 16 * chain_tiles(m.dims[l]); dw[k][l] = 16 * chain_tiles(m.dims[l + 1]);
       if (k == 0 && l == m.n_layers - 1) dw[k][l] = 16 * ntl;
       a.xo[k][l] = take((size_t)B * xw[k][l]); a.dofs[k][l] = take((size_t)B * dw[k][l]);
     }
-    for (int l = 0; l < m.n_layers; ++l) {
-      const int ni = m.dims[l], no = m.dims[l + 1];
-      for (int f = 0; f < ni; ++f)
-        for (int o = 0; o < no; ++o) {
-          mdst[m.woff[l] + f * no + o] = m.woff[l] + o * ni + f;
-          tT[m.woff[l] + (size_t)o * ni + f] = theta[m.woff[l] + (size_t)f * no + o];
-        }
-      for (int u = 0; u < tl(ni); ++u)
-        for (int v = 0; v < tl(no); ++v) {
-          int e[ECG_TILE_INTS] = {a.xo[k][l], -1, a.dofs[k][l], -1, xw[k][l], dw[k][l], u, v, m.woff[l], ni, no, u == 0 ? m.woff[l] + ni * no : -1, 0, 0, 0, 0};
-          tiles.insert(tiles.end(), e, e + ECG_TILE_INTS);
-        }
-    }
+    egm_mirror_add(m, theta.data(), tT, mdst);
+    egm_tiles_add(m, a.xo[k], nullptr, a.dofs[k], nullptr, xw[k], dw[k], tiles);
   }
   a.n_tiles = (int)(tiles.size() / ECG_TILE_INTS);
   BGM_HIP_CHECK(hipMalloc((void **)&c->ws, sizeof(float) * (off + 64)));

@@ -2,7 +2,8 @@
 tests/test_gpu_egm_edges.py, and the builders of the cases' inputs (TEST INFRASTRUCTURE; tests/test_egm_edges_host.py shows on the CPU
 what every case reaches and keeps the restatement in step with the C++ text).
 
-plan() restates bgm_causal_egm_begin and the kernel choice of bgm_causal_egm_disc_step / _gen_step (csrc/egm_api.hip) together with the
+plan() restates egm_plan (csrc/egm_plan.h: chain_extent, chain_disc_ok, chain_trunk_ok, chain_head_ok, egm_arena), which
+bgm_causal_egm_begin (csrc/egm_api.hip) evaluates once for the kernels of bgm_causal_egm_disc_step / _gen_step, together with the
 LDS sizes of the register-chained kernels (ech_layout / ech_disc_lds_floats in csrc/egm_chain.h, ecg_lds_floats in csrc/egm_chain_gen.h).
 
 Routes of the discriminator step           Routes of the generator step
@@ -86,7 +87,7 @@ def arena_floats(q, B, dz_units):
 
 
 def plan(p, z_dims, B, dz_units, g_units, e_units, f_units, h_units, fixed_norm, no_chain=False, no_chain_gen=False):
-    """bgm_causal_egm_begin for a session it accepts -> Plan(arena bytes incl. the 64 reduction words, disc_lds, t0, routes, chain LDS)."""
+    """egm_plan for a session bgm_causal_egm_begin accepts -> Plan(arena bytes incl. the 64 reduction words, disc_lds, t0, routes, chain LDS)."""
     q = sum(z_dims)
     assert B_MIN <= B <= B_MAX and 1 <= len(dz_units) <= EGM_MAX_LAYERS - 1
     for units in (g_units, e_units, f_units, h_units):

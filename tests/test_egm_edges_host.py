@@ -1,5 +1,5 @@
 """What the cases of tests/test_gpu_egm_edges.py reach, shown without a device from the restated host plan of tests/_egm_edges_ref.py
-(bgm_causal_egm_begin and the kernel choice of the two step entry points, csrc/egm_api.hip), and the conditions the float64 oracle alone
+(egm_plan of csrc/egm_plan.h, which bgm_causal_egm_begin evaluates, and the kernel tables of csrc/egm_api.hip), and the conditions the float64 oracle alone
 puts on their inputs: finite losses, gradients that are not all rounding noise, a live last column behind every mask.
 
 The batches beyond the ones the project's tolerances were set on (B >= 40) get the oracle itself in float32 here: its deviation from
@@ -139,10 +139,21 @@ def test_switches(c):
 # ---------------------------------------------------------------------------------------------------------------------------
 # the restatement against the C++ text
 # ---------------------------------------------------------------------------------------------------------------------------
+def _static_asserts(src):
+    """the conditions of a header's static_asserts, without their messages"""
+    return " ".join(re.findall(r"static_assert\((.*?),\s*\"", src, re.S))
+
+
 def test_restated_constants_are_the_sources():
-    api, ker, chain, gen = _src("egm_api.hip"), _src("egm_kernels.h"), _src("egm_chain.h"), _src("egm_chain_gen.h")
-    lim = re.findall(r"<=\s*(\d+)\s*\*\s*1024", api)
-    assert lim == ["160", "160"] and E.LDS_LIMIT == 160 * 1024          # disc_lds and the chain's own size
+    """The plan moved from the text of egm_api.hip into csrc/egm_plan.h (chain_extent, the predicates, egm_arena, egm_plan); the kernel
+    tables and the calls of the LDS-size functions stay in egm_api.hip.  Where egm_plan.h pins a fact in a static_assert, the assert is
+    looked for instead of the expression text."""
+    api, plan, ker, chain, gen = _src("egm_api.hip"), _src("egm_plan.h"), _src("egm_kernels.h"), _src("egm_chain.h"), _src("egm_chain_gen.h")
+    pins = _static_asserts(plan)
+    assert "constexpr int EGM_LDS_LIMIT = 160 * 1024;" in plan and E.LDS_LIMIT == 160 * 1024
+    # disc_lds and the chain's own size: both against the one limit
+    assert "(64 + arena) * sizeof(float) <= (size_t)EGM_LDS_LIMIT" in plan and "chain_disc_bytes <= (size_t)EGM_LDS_LIMIT" in plan
+    assert "<= 160 * 1024" not in api and len(re.findall(r"160 \* 1024", plan)) == 1
     lo, hi = re.search(r"cfg->batch_size < (\d+) \|\| cfg->batch_size > (\d+)", api).groups()
     assert (int(lo), int(hi)) == (E.B_MIN, E.B_MAX)
     assert int(re.search(r"#define EGM_THREADS (\d+)", ker).group(1)) == E.EGM_THREADS
@@ -150,34 +161,49 @@ def test_restated_constants_are_the_sources():
     assert int(re.search(r"#define ECH_ROLE_WAVES (\d+)", chain).group(1)) == E.ECH_ROLE_WAVES
     assert re.search(r"L < 1 \|\| L > EGM_MAX_LAYERS", api)
     # the tile rules of the discriminator chain
-    t1, t2 = re.search(r"\(d\.dims\[1\] \+ 15\) / 16 == (\d+) && \(d\.dims\[2\] \+ 15\) / 16 == (\d+)", api).groups()
-    d3lo, d3hi = re.search(r"d\.dims\[3\] >= (\d+) && d\.dims\[3\] <= (\d+)", api).groups()
+    t1, t2 = re.search(r"chain_tiles\(d\[1\]\) == (\d+) && chain_tiles\(d\[2\]\) == (\d+)", plan).groups()
+    d3lo, d3hi = re.search(r"d\[3\] >= (\d+) &&\s+d\[3\] <= (\d+)", plan).groups()
     assert (int(t1), int(t2), int(d3lo), int(d3hi)) == (E.CHAIN_T[0], E.CHAIN_T[1], 1, 16 * E.CHAIN_T[2])
-    assert re.search(r"\(B == 16 \|\| B == 32\)", api) and E.CHAIN_BATCHES == (16, 32)
-    assert re.search(r"d\.fixed_norm && L == 3 && d\.dims\[0\] <= 32 && \(t0 == 1 \|\| B == 32\)", api)
-    assert re.search(r"const int t0 = h->q <= 16 \? 1 : 2;", api)
-    assert re.search(r"chain = chain && a\.e\.dims\[l\] == 64;", api) and re.search(r"chain = chain && a\.g\.dims\[l\] == 64;", api)
+    assert "constexpr int chain_tiles(int n) { return (n + 15) / 16; }" in plan
+    assert re.search(r"\(B == 16 \|\| B == 32\)", plan) and E.CHAIN_BATCHES == (16, 32)
+    assert re.search(r"fixed_norm && n_hidden == 3 && d\[0\] <= 32 && \(d\[0\] <= 16 \|\| B == 32\)", plan)
+    assert re.search(r"const int ntl_need = \(p \+ 16\) / 16, t0 = q <= 16 \? 1 : 2;", plan)
+    assert "if (n.dims[l] != 64) return false;" in plan          # chain_hidden64, asked of e and of g:
+    assert "chain_trunk_ok(s.e, 2, -1, s.q)" in plan and "chain_trunk_ok(s.g, 2, s.q, -1)" in plan and "&& chain_hidden64(n);" in plan
     assert set(re.findall(r"ech_disc_lds_floats<([\d, ]+)>\(d, B\)", api)) == {"4, 2, 1", "4, 2, 1, 2"}
     assert set(re.findall(r"ecg_lds_floats<([\d, ]+)>\(d, B\)", api)) == {"4, 2, 1", "4, 2, 1, 2"}
     # ... of the generator chain
-    assert re.search(r"const int ntl_need = \(h->p \+ 1 \+ 15\) / 16;", api)
-    assert re.search(r"\(\(ntl_need == 13 \|\| ntl_need == 7\) && s->chain_t0 == 1\) \? ntl_need : 13;", api) and E.GEN_EXTENTS == (13, 7)
-    assert re.search(r"s->chain_disc_lds > 0 && ntl_need <= 13 && \(ntl == ntl_need \|\| B == 32\)", api)
-    assert re.search(r"m->n_layers == 4 && m->dims\[0\] <= 16 && m->dims\[1\] == 64 && m->dims\[2\] == 32 && m->dims\[3\] >= 1 && m->dims\[3\] <= 16", api)
+    assert re.search(r"const int ntl = \(\(ntl_need == 13 \|\| ntl_need == 7\) && t0 == 1\) \? ntl_need : 13;", plan) and E.GEN_EXTENTS == (13, 7)
+    assert "return x.ntl_need <= 13 && (x.ntl == x.ntl_need || B == 32);" in plan
+    assert re.search(r"const bool gchain = dchain && chain_extent_ok\(x, s\.B\)", plan)
+    assert re.search(r"n\.n_layers == 4 && n\.dims\[0\] <= 16 && n\.dims\[1\] == 64 && n\.dims\[2\] == 32 && n\.dims\[3\] >= 1 && n\.dims\[3\] <= 16", plan)
+    assert "chain_head_ok(s.f, 1, 16) && chain_head_ok(s.h, 1, 16)" in plan
     assert E.HEAD_FIXED == (64, 32)
-    assert re.search(r"s->chain_pad = ntl != ntl_need \|\| s->chain_t0 == 2;", api)
-    # ... of the kernel choice
-    assert re.search(r"const int kt0 = \(a\.p \+ 15\) / 16;", api) and re.search(r"kt0 == 13 \?", api) and re.search(r"kt0 == 7 \?", api)
-    assert sorted(set(re.findall(r"egm_disc_chain_kernel<([\d, ]+)>", api))) == ["4, 0, 4, 2, 1, 1", "4, 0, 4, 2, 1, 2", "4, 0, 4, 2, 1, 2, 2",
-                                                                              "4, 13, 4, 2, 1, 2", "4, 7, 4, 2, 1, 2"]
-    assert sorted(set(re.findall(r"egm_gen_chain_kernel<([\w, ]+)>", api))) == ["4, 13, 4, 2, 1, 1", "4, 13, 4, 2, 1, 2", "4, 13, 4, 2, 1, 2, true",
-                                                                               "4, 13, 4, 2, 1, 2, true, 2", "4, 7, 4, 2, 1, 1", "4, 7, 4, 2, 1, 2"]
-    # the two switches and the arena pointer
-    assert 'getenv("BGM_EGM_NO_CHAIN")' in api and 'getenv("BGM_EGM_NO_CHAIN_GEN")' in api
+    assert "return {t0, ntl_need, ntl, ntl != ntl_need || t0 == 2};" in plan
+    # ... of the kernel choice: the plan's routes under the names of this file, and the kernels behind them in the same order
+    assert re.search(r"const int kt0 = chain_tiles\(s\.p\);", plan) and re.search(r"kt0 == 13 \?", plan) and re.search(r"kt0 == 7 \?", plan)
+    assert tuple(re.findall(r'"([\w-]+)"', re.search(r"EGM_DISC_ROUTE_NAMES\[\] = \{(.*?)\};", plan).group(1))) == E.DISC_ROUTES
+    assert tuple(re.findall(r'"([\w-]+)"', re.search(r"EGM_GEN_ROUTE_NAMES\[\] = \{(.*?)\};", plan).group(1))) == E.GEN_ROUTES
+    assert len(re.search(r"enum class EgmDiscRoute \{(.*?)\}", plan).group(1).split(",")) == len(E.DISC_ROUTES)
+    assert len(re.search(r"enum class EgmGenRoute \{(.*?)\}", plan).group(1).split(",")) == len(E.GEN_ROUTES)
+    assert re.findall(r"egm_disc_chain_kernel<([\d, ]+)>", api) == ["4, 0, 4, 2, 1, 2, 2", "4, 13, 4, 2, 1, 2", "4, 7, 4, 2, 1, 2", "4, 0, 4, 2, 1, 2",
+                                                                    "4, 0, 4, 2, 1, 1"]          # the rows of egm_disc_kernel, in the enum's order
+    assert re.findall(r"egm_gen_chain_kernel<([\w, ]+)>", api) == ["4, 13, 4, 2, 1, 2, true, 2", "4, 13, 4, 2, 1, 2, true", "4, 13, 4, 2, 1, 2",
+                                                                   "4, 7, 4, 2, 1, 2", "4, 13, 4, 2, 1, 1", "4, 7, 4, 2, 1, 1"]
+    # ... pinned at the edges by the header itself
+    for want in ("routes(95, 10, 32) == Routes{D::CHAIN_32_STREAM, G::CHAIN_PAD}", "routes(96, 10, 32) == Routes{D::CHAIN_32_STREAM, G::CHAIN_32_N7}",
+                 "routes(111, 10, 32) == Routes{D::CHAIN_32_K7, G::CHAIN_32_N7}", "routes(112, 10, 32) == Routes{D::CHAIN_32_K7, G::CHAIN_PAD}",
+                 "routes(191, 10, 32) == Routes{D::CHAIN_32_STREAM, G::CHAIN_PAD}", "routes(192, 10, 32) == Routes{D::CHAIN_32_STREAM, G::CHAIN_32_N13}",
+                 "routes(207, 10, 32) == Routes{D::CHAIN_32_K13, G::CHAIN_32_N13}", "routes(208, 10, 32) == Routes{D::CHAIN_32_K13, G::STEP}",
+                 "egm_arena(39, 3, DZ_DEF).lds_bytes == 162560", "(64 + egm_arena(40, 3, DZ_DEF).floats) * sizeof(float) == 166688"):
+        assert want in pins, want
+    # the two switches (read when a session begins, egm_switches_now) and the arena pointer
+    assert 'getenv("BGM_EGM_NO_CHAIN")' in plan and 'getenv("BGM_EGM_NO_CHAIN_GEN")' in plan and "egm_switches_now()" in api
+    assert "!sw.no_chain &&" in plan and "!sw.no_chain_gen;" in plan and "getenv" not in api
     assert "float *arena = a.disc_lds ? (egm_lds + 64) : wp;" in ker
     # the arena formula and the chains' LDS sizes, as text
-    assert "((size_t)(2 * B + 1) * dsum + B + 3) / 4 * 4" in api and "((size_t)B * dall + (size_t)(5 * B + 1) * dsum + 3) / 4 * 4 + 3 * (size_t)B * dmax" in api
-    assert "cache + std::max(cache + 2 * (size_t)B * dmax, gp)" in api and "(64 + arena) * sizeof(float) <= 160 * 1024" in api
+    assert "((size_t)(2 * B + 1) * dsum + B + 3) / 4 * 4" in plan and "((size_t)B * dall + (size_t)(5 * B + 1) * dsum + 3) / 4 * 4 + 3 * (size_t)B * dmax" in plan
+    assert "cache + std::max(cache + 2 * (size_t)B * dmax, gp)" in plan
     assert "64 + ech_layout<T1, T2, T3, T0>(d).total + ECH_ROLE_WAVES * D::SLOT + 16 * T0 * B + (T0 > 1 ? 3 : 4) * B * D::SW" in chain
     assert "XW = 16 * (T0 + T1 + T2), DW = 16 * (T1 + T2 + T3), SW = XW + DW" in chain and "SLOT = 2 * SL + 16 * T3 + 16" in chain
     assert "P.ld0 = 16 * T1 + 4; P.ld1 = 16 * T2 + 4; P.ld2 = 16 * T3 + 4;" in chain and "P.lt0 = 16 * T0 + 4; P.lt1 = 16 * T1 + 4; P.lt2 = 16 * T2 + 4;" in chain

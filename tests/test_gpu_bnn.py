@@ -300,10 +300,12 @@ def test_evaluate_matches_oracle(binary, p):
     eng.close()
 
 
-@pytest.mark.parametrize("p,B", [(100, 32), (100, 16), (50, 4)])
+@pytest.mark.parametrize("p,B", [(100, 32), (100, 16), (50, 4), (200, 16), (210, 16)])
 def test_egm_split_step_equals_fused_step(p, B):
     """Data-parallel form of the warm start with Bayesian nets: step(apply = 0) + bgm_bnn_egm_grad + bgm_bnn_egm_apply takes the Adam
-    steps of the fused step (chains at p = 100; B = 4: a rank's share of a 32-row minibatch at 8 GPUs, the phase-machine kernels)."""
+    steps of the fused step (chains at p = 100; B = 4: a rank's share of a 32-row minibatch at 8 GPUs, the phase-machine kernels).
+    B = 16 at p = 200 and p = 210: the one-row-tile discriminator chain with the 13-tile encoder chain and with the general encoder
+    (14 input tiles), routes B16_E13 and B16_E0 of bnn_egm_plan (csrc/egm_plan.h; the table of routes and tests is in DESIGN.md 4ag)."""
     from oracle import egm as OE
     res = []
     for split in (False, True):
@@ -350,11 +352,13 @@ def test_egm_split_step_equals_fused_step(p, B):
 
 @pytest.mark.parametrize("binary,disc_norm,p,zd", [(False, "batch", 50, ZD), (True, "batch", 50, ZD), (False, "fixed", 50, ZD), (True, "fixed", 50, ZD),
                                                    (False, "fixed", 100, ZD), (True, "fixed", 200, ZD), (False, "fixed", 45, ZD),
-                                                   (True, "fixed", 177, ACIC), (False, "fixed", 100, (5, 5, 5, 5))])
+                                                   (True, "fixed", 177, ACIC), (False, "fixed", 100, (5, 5, 5, 5)), (False, "fixed", 50, (5, 5, 5, 5))])
 def test_egm_steps_match_oracle(binary, disc_norm, p, zd):
     """EGM warm-start steps with Bayesian nets: gradients of the discriminator step and of the nine-call generator step.
     disc_norm = "fixed" (the models' default): the discriminator passes of the step run as register-chained row tiles; at
-    p = 100 / 200 (with the inference-mode input normalisation of `_model`, when it has it) so does the Flipout encoder call."""
+    p = 100 / 200 (with the inference-mode input normalisation of `_model`, when it has it) so does the Flipout encoder call.
+    q = 20 at p = 50 (batch statistics in the nets): the two-latent-tile discriminator chain with the general encoder, route T2_E0 of
+    bnn_egm_plan (csrc/egm_plan.h)."""
     from oracle import egm as OE
     from bayesgm_amd.engine import CausalEngine
     m = _model(binary, z_dims=zd, p=p)
