@@ -16,6 +16,9 @@ row_adapt.leapfrog_cap; csrc/causal_hmc_traj_kernels.h).
 ``predict_individual``: the option checks, the row blocks of ``interval='quantile'`` and ``'tails'``, the size of a tail buffer
 (``tail_size``), the finalisation of the per-row moments and the subgroup formula (``group_dose_response``) are at the end of the module.
 
+``predict_dose_effect``: the contrast of every dose against a baseline dose (csrc/causal_hmc_contrast_kernels.h); its own checks are
+``check_dose_effect`` and ``check_partial_panel``, everything else is predict_individual's.
+
 ``predict_average``: the option checks, the internal row labels and the combiner of the per-draw label sums into ATE / ATT / ATC
 (``combine_average_effects``) follow them.
 
@@ -271,6 +274,24 @@ def check_individual(binary, x_values, interval, draw_budget_bytes):
                          "are sampled in one piece")
 
 
+def check_dose_effect(binary, x_values, baseline, interval, draw_budget_bytes):
+    """The options of predict_dose_effect that are its own: a continuous treatment, x_values, a finite scalar baseline, and
+    interval / draw_budget_bytes by predict_individual's rules -> baseline as a float; ValueError otherwise."""
+    if binary:
+        raise ValueError("predict_dose_effect is the contrast between two doses of a continuous treatment; a binary treatment has "
+                         "its per-row effect already: predict's ITE")
+    if x_values is None:
+        raise ValueError("predict_dose_effect needs x_values: the doses whose outcome is compared with the baseline's")
+    try:
+        b = float(baseline) if np.ndim(baseline) == 0 and not isinstance(baseline, (bool, str)) else float("nan")
+    except (TypeError, ValueError):
+        b = float("nan")
+    if not np.isfinite(b):
+        raise ValueError("baseline must be a finite scalar, the dose every other dose is compared with; got %r" % (baseline,))
+    check_individual(False, x_values, interval, draw_budget_bytes)
+    return b
+
+
 def individual_block_rows(n_keep, n_doses, budget_bytes=None):
     """Rows of one block of predict_individual(interval='quantile'): the block's outcome draws [rows x n_doses x n_keep] float32
     stay within the budget; a multiple of 16 (whole row tiles), at least 16."""
@@ -413,6 +434,18 @@ def check_partial_rows(x, y):
         row = int(bad.nonzero()[0].reshape(-1)[0])
         raise ValueError("partial=True: row %d has its outcome y observed and its treatment x not (NaN); the outcome term f(z, x) "
                          "needs the treatment -- drop y (NaN) or give x" % row)
+
+
+def check_partial_panel(data_x, data_y, data_v):
+    """partial=True of predict_dose_effect, before a device is touched -> (x [n], y [n], v [n, p]) float32 with NaN in x / y where
+    a row does not observe them: the pattern rule of check_partial_rows and, as in check_new, no NaN among the covariates."""
+    x, y = np.asarray(data_x, np.float32).reshape(-1), np.asarray(data_y, np.float32).reshape(-1)
+    v = np.asarray(data_v, np.float32)
+    if np.isnan(v).any():
+        raise ValueError("partial=True: data_v holds NaN in row %d; missing covariates are not modelled (only the treatment and the "
+                         "outcome may be unobserved)" % int(np.flatnonzero(np.isnan(v).reshape(len(v), -1).any(axis=1))[0]))
+    check_partial_rows(x, y)
+    return x, y, v
 
 
 def check_new(binary, data_v, data_x, x_values, interval, draw_budget_bytes):

@@ -597,6 +597,13 @@ __device__ __forceinline__ float pick_by_group(int g, float v0, float v1, float 
 // in the order of their lowest row, each by ONE DPP row reduction and ONE addition from lane 15.  ite is not touched.
 // TAILS (ROWS only; causal_hmc_tails_kernels.h): the lane also keeps the k_tail smallest and the k_tail largest values of its series
 // in row_tails [2][k_tail][n_doses][n] (row_tail_push, row_tails.h).
+// CONTRAST (ROWS only; causal_hmc_contrast_kernels.h): besides the curve, the difference to the baseline dose, c = y(x_k) - y(x_0), is
+// kept per (row, dose).  Dose 0 of a draw is finished in pass 0 by lane group 0 (own or shared pass alike), so after pass 0 every lane
+// reads y0 from the lane of group 0 that holds its row -- one cross-lane read executed by all 64 lanes, outside the valid branch --
+// and keeps it in a register over the draw's remaining passes.  c is ONE float32 subtraction of the two rounded values (y is pinned
+// first, so it cannot be folded into the fmaf that forms y, and row_mom receives the y it always did); its shifted moments go to
+// row_cmom [3][n_doses][n] by the rule of row_mom, and row_y / row_tails record c instead of y.  At dose 0 c is exactly 0.  With
+// sample_y the two doses carry their own independent noise words, as the two arms of the binary ITE do.
 // ---------------------------------------------------------------------------
 // VTAILS: the dose passes of the grouped dose-response sums with the 32 -> 8 -> 2 tail of f on the vector ALU (the MH kernels'
 // retained phase).  On the matrix pipe the tail of a pass is 40 of its 168 instructions for 1 088 MACs per chain: half of the M
@@ -778,7 +785,7 @@ __device__ __forceinline__ void causal_dose_passes_valu(const float *lds, const 
 }
 
 template <int KT1, int KSL1, int R, int EFFECT, bool GROUPING = true, bool CACHE = false, bool EVAL_ONLY = false, bool L1MASK = true,
-          bool ROWS = false, bool TAILS = false, bool VTAILS = false>
+          bool ROWS = false, bool TAILS = false, bool VTAILS = false, bool CONTRAST = false>
 __device__ __forceinline__ void causal_effects(const float *lds, const CausalMeta &m, int lane_off, int g, int j,
                                                int lane, const f32x4 (&zs)[R][KT1], const unsigned (&rowid)[R],
                                                const bool (&valid)[R], long long row0, long long n, unsigned it,
@@ -786,11 +793,12 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
                                                const float *x_values, float *adrf_slot, float *ite, unsigned k0,
                                                unsigned k1, float2 *cache = nullptr, float *ite_c = nullptr,
                                                float *row_mom = nullptr, float *row_y = nullptr, int label = 0,
-                                               float *row_tails = nullptr, int k_tail = 0) {
+                                               float *row_tails = nullptr, int k_tail = 0, float *row_cmom = nullptr) {
   // ite_c (EFFECT == 2, one row tile per wave, CACHE): [4] registers of the caller receiving (mean, sd) of the two arms
   static_assert(!ROWS || (EFFECT == 1 && R == 1 && GROUPING && !CACHE && !EVAL_ONLY), "ROWS: the grouped finish of the dose-response sums");
   static_assert(EFFECT != 4 || (R == 1 && !CACHE && !EVAL_ONLY && !ROWS), "EFFECT 4: the label sums of one row tile per wave");
   static_assert(!TAILS || ROWS, "TAILS: the tail buffers of the per-row dose-response");
+  static_assert(!CONTRAST || ROWS, "CONTRAST: the contrasts of the per-row dose-response against its dose 0");
   constexpr bool ARMS = (EFFECT == 2 || EFFECT == 4);   // the two arms x = 1, x = 0 of a binary treatment
   BGM_NO_HOIST();
   f32x4 z0in[R][KT1];
@@ -819,6 +827,7 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
   f32x4 nz[R];
 #pragma unroll
   for (int rr = 0; rr < R; ++rr) nz[rr] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  [[maybe_unused]] float y0 = 0.0f;            // (CONTRAST: y of the lane's row at dose 0 of this draw, from pass 0 on)
   for (int kb = 0; kb < n_calls; ++kb) {       // one pass of DB doses per Philox call
     BGM_NO_HOIST();
     const bool own = kb < n_own;
@@ -920,6 +929,13 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
       if (own) nz[0] = f32x4{nz[0][1], nz[0][2], nz[0][3], nz[0][0]};
       float y = sample_y ? fmaf(sd_m, noise, mu_m) : mu_m;
       if constexpr (ROWS) {
+        [[maybe_unused]] float c = 0.0f;
+        if constexpr (CONTRAST) {
+          asm volatile("" : "+v"(y));                 // the rounded y, as the curve planes receive it
+          if (kb == 0) y0 = __shfl(y, j);             // (wave-uniform) lane j = (row j, lane group 0) holds dose 0: all 64 lanes read
+          c = y - y0;
+        }
+        const float rec = CONTRAST ? c : y;           // what the draws and the tails record
         if (valid[0] && k < nd) {
           const long long row = row0 + j, plane = (long long)nd * n;
           long long off = (long long)k * n + row;
@@ -932,12 +948,22 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
             rf[plane] += dv;
             rf[2 * plane] = fmaf(dv, dv, rf[2 * plane]);
           }
-          if (row_y) row_y[(row * nd + k) * (long long)n_keep + d] = y;
+          if constexpr (CONTRAST) {
+            float *cf = row_cmom + off;
+            if (d == 0) {
+              cf[0] = c; cf[plane] = 0.0f; cf[2 * plane] = 0.0f;
+            } else {
+              const float dv = c - cf[0];
+              cf[plane] += dv;
+              cf[2 * plane] = fmaf(dv, dv, cf[2 * plane]);
+            }
+          }
+          if (row_y) row_y[(row * nd + k) * (long long)n_keep + d] = rec;
           if constexpr (TAILS) {
             const long long series = plane;          // floats between two slots of a series: [2][k_tail][n_doses][n]
             float *t0 = row_tails + off;
-            row_tail_push<true>(t0, series, k_tail, d, y);
-            row_tail_push<false>(t0 + (long long)k_tail * series, series, k_tail, d, y);
+            row_tail_push<true>(t0, series, k_tail, d, rec);
+            row_tail_push<false>(t0 + (long long)k_tail * series, series, k_tail, d, rec);
           }
         }
         continue;

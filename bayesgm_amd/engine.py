@@ -228,6 +228,30 @@ class CausalEngine(object):
                                                              0 if row_tails is None else int(row_tails.shape[1]), self._stream()),
                        "bgm_causal_hmc_run_row_tails")
 
+    def hmc_run_rows_contrasts(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
+                               row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
+                               sample_y=True, x_values=None, row_moments=None, row_cmoments=None, contrast_draws=None,
+                               contrast_tails=None, partial=False):
+        """hmc_run_rows_effects with the contrast of every dose against the baseline x_values[0] kept beside the curve
+        (bgm_causal_hmc_run_row_contrasts): c_i(k) = y_i(x_k) - y_i(x_0) of every retained draw, one float32 subtraction inside the
+        kernel.  row_cmoments [3, n_doses, n] float32 receives its shifted sums (the rule of row_moments, in / out across
+        segments); optionally contrast_draws [n, n_doses, n_keep] the differences themselves and contrast_tails [2, K, n_doses, n]
+        their K smallest and K largest (hmc_run_rows_tails' layout, 1 <= K <= n_keep).  Chain and row_moments are those of
+        hmc_run_rows_effects bit for bit.  The library refuses the call while a trajectory option is set."""
+        n_doses = 0 if x_values is None else int(x_values.numel())
+        if contrast_tails is not None and (contrast_tails.dim() != 4 or contrast_tails.shape[0] != 2 or contrast_tails.dtype != torch.float32
+                                           or not contrast_tails.is_contiguous()
+                                           or tuple(contrast_tails.shape[2:]) != (n_doses, v.shape[0])):
+            raise ValueError("hmc_run_rows_contrasts: contrast_tails must be a contiguous float32 tensor [2, K, n_doses, n] = "
+                             "[2, K, %d, %d]; got %s %r" % (n_doses, v.shape[0], contrast_tails.dtype, tuple(contrast_tails.shape)))
+        with self._partial_rows(partial, x, y):
+            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
+                                  s_max, acc_count, draws, n_keep)
+            _lib.check(self.lib.bgm_causal_hmc_run_row_contrasts(*args, int(bool(sample_y)), _ptr(x_values), n_doses, _ptr(row_moments),
+                                                                 _ptr(row_cmoments), _ptr(contrast_draws), _ptr(contrast_tails),
+                                                                 0 if contrast_tails is None else int(contrast_tails.shape[1]),
+                                                                 self._stream()), "bgm_causal_hmc_run_row_contrasts")
+
     def row_tail_quantiles(self, tails, m, q_lo, q_hi):
         """tails [2, K, ...] float32 on the device (hmc_sample's out["tails"]: the K smallest and the K largest of every series' m
         values) -> (lo, hi), each of shape tails.shape[2:]: the quantiles row_mean_quantiles gives on the m values, bit for bit
@@ -298,7 +322,7 @@ class CausalEngine(object):
     def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
                    adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None, effect=_lib.EFFECT_NONE,
                    x_values=None, sample_y=True, row_effects=False, row_draws=False, labels=None, n_labels=None, partial=False,
-                   row_tails=None, max_trajectory=None, jitter=False):
+                   row_tails=None, max_trajectory=None, jitter=False, row_contrasts=False):
         """HMC over the latent posterior of every row, one chain per row with a step size of its own.
 
         adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
@@ -329,6 +353,14 @@ class CausalEngine(object):
         from which row_tail_quantiles gives the exact quantile bounds (K = causal_hmc.tail_size(alpha, n_keep)); chain, moments
         and row_draws are those of the run without it.
 
+        row_contrasts = True (with row_effects): x_values[0] is a baseline dose, and the contrast c_i(k) = y_i(x_k) - y_i(x_0) of
+        every retained state is summarised inside the sampler as well (hmc_run_rows_contrasts) into contrast_mean / contrast_sd
+        [n, n_doses] (float64; column 0 is exactly 0); row_mean / row_sd and the chain are those of the run without it.  The
+        optional buffers then hold the contrasts, not the values: row_draws = True returns contrast_draws [n, n_doses, n_keep] (the
+        float32 difference of the columns k and 0 of the row_draws of a run without row_contrasts) and row_tails = K their tails.
+        With sample_y the two doses carry independent noise.  Not available for a binary treatment (it has EFFECT_ITE) or with
+        max_trajectory / jitter: ValueError before a device is touched.
+
         partial = True: NaN in y, or in x and y, marks what a row does not observe (new units): its chain samples p(z | x, v) or
         p(z | v) (logpost_grad).  A row with y observed and x not is refused.  Works without an effect, with EFFECT_ITE and with
         row_effects; a fully observed panel gives the run of partial = False bit for bit.
@@ -347,6 +379,15 @@ class CausalEngine(object):
         if traj and row_tails is not None:
             raise ValueError("hmc_sample: max_trajectory / jitter are not available with row_tails: the tail-buffer kernels "
                              "(hmc_run_rows_tails) have no variant with a trajectory length per chain")
+        if row_contrasts:
+            if not row_effects:
+                raise ValueError("hmc_sample: row_contrasts belongs to row_effects=True")
+            if traj:
+                raise ValueError("hmc_sample: max_trajectory / jitter are not available with row_contrasts: the dose-contrast kernels "
+                                 "(hmc_run_rows_contrasts) have no variant with a trajectory length per chain")
+            if self.binary:
+                raise ValueError("hmc_sample: row_contrasts is the contrast between two doses of a continuous treatment; a binary "
+                                 "treatment has its per-row effect already (effect=EFFECT_ITE)")
         if traj and effect == _lib.EFFECT_GROUP_ITE:
             raise ValueError("hmc_sample: max_trajectory / jitter are not available with effect=EFFECT_GROUP_ITE: the label-sum kernels "
                              "(hmc_run_group_effects) have no variant with a trajectory length per chain")
@@ -376,7 +417,8 @@ class CausalEngine(object):
         acc = torch.zeros(total, device=dev, dtype=torch.int32)
         draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
         chunk = total if chunk is None else max(1, int(chunk))
-        launch, route_kw, collect = self._hmc_route(n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails)
+        launch, route_kw, collect = self._hmc_route(n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails,
+                                                    row_contrasts)
         scale = moments = None
         if diag:
             scale = torch.ones((n, self.q), device=dev, dtype=torch.float32)
@@ -419,7 +461,7 @@ class CausalEngine(object):
     # The result routes of hmc_sample, one per kind of result.  Each checks what is its own, allocates its buffers and returns
     # (launch, kw, collect): the engine method that runs a segment, the keyword arguments it takes besides the common ones, and
     # the function that adds the route's keys to the returned dict.
-    def _hmc_route(self, n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails=None):
+    def _hmc_route(self, n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails=None, row_contrasts=False):
         kinds = {_lib.EFFECT_NONE: self._route_none, _lib.EFFECT_ADRF: self._route_adrf, _lib.EFFECT_ITE: self._route_ite,
                  _lib.EFFECT_GROUP_ITE: self._route_group_ite}
         if effect not in kinds:
@@ -430,7 +472,9 @@ class CausalEngine(object):
         if row_effects:
             if effect != _lib.EFFECT_NONE:
                 raise ValueError("hmc_sample: row_effects and effect exclude each other (the panel's ADRF is the mean of the rows' curves)")
-            return self._route_rows(n, n_keep, x_values, row_draws, row_tails)
+            return self._route_rows(n, n_keep, x_values, row_draws, row_tails, row_contrasts)
+        if row_contrasts:
+            raise ValueError("hmc_sample: row_contrasts belongs to row_effects=True")
         if row_draws:
             raise ValueError("hmc_sample: row_draws belongs to row_effects=True")
         if row_tails is not None:
@@ -472,7 +516,7 @@ class CausalEngine(object):
         return (self.hmc_run, dict(effect=_lib.EFFECT_GROUP_ITE, labels=lab, n_labels=n_lab, group_partial=part),
                 lambda out: out.update(group_partial=part, group_sums=self.adrf_reduce(part, n_slots, n_lab, n_keep, 1.0)))
 
-    def _route_rows(self, n, n_keep, x_values, row_draws, row_tails=None):
+    def _route_rows(self, n, n_keep, x_values, row_draws, row_tails=None, row_contrasts=False):
         if self.binary:
             raise ValueError("hmc_sample: row_effects is the dose-response of a continuous treatment; a binary treatment has its "
                              "per-row effect already (effect=EFFECT_ITE)")
@@ -486,14 +530,21 @@ class CausalEngine(object):
             if isinstance(row_tails, bool) or int(row_tails) != row_tails or not 1 <= int(row_tails) <= int(n_keep):
                 raise ValueError("hmc_sample: row_tails must be an integer K with 1 <= K <= n_keep = %d; got %r" % (int(n_keep), row_tails))
             tails = torch.empty((2, int(row_tails), xv.numel(), n), device=self.device, dtype=torch.float32)      # draw 0 initialises it
+        cmom = torch.zeros((3, xv.numel(), n), device=self.device, dtype=torch.float32) if row_contrasts else None
 
         def collect(out):
             mean, sd = HM.row_moments_finalize(mom[0], mom[1], mom[2], n_keep)
             out["row_mean"], out["row_sd"] = mean.t().contiguous(), sd.t().contiguous()
+            if cmom is not None:
+                mean, sd = HM.row_moments_finalize(cmom[0], cmom[1], cmom[2], n_keep)
+                out["contrast_mean"], out["contrast_sd"] = mean.t().contiguous(), sd.t().contiguous()
             if row_y is not None:
-                out["row_draws"] = row_y
+                out["contrast_draws" if row_contrasts else "row_draws"] = row_y
             if tails is not None:
                 out["tails"] = tails
+        if row_contrasts:      # the draws and the tails, where asked for, are those of the contrasts
+            return (self.hmc_run_rows_contrasts,
+                    dict(x_values=xv, row_moments=mom, row_cmoments=cmom, contrast_draws=row_y, contrast_tails=tails), collect)
         if tails is not None:
             return self.hmc_run_rows_tails, dict(x_values=xv, row_moments=mom, row_draws=row_y, row_tails=tails), collect
         return self.hmc_run_rows_effects, dict(x_values=xv, row_moments=mom, row_draws=row_y), collect

@@ -760,6 +760,15 @@ class CausalBGM(object):
         marks what a row does not observe): this rank's shard in the blocks of causal_hmc.individual_blocks, every block sampled with
         the per-row effects inside the kernel, the results gathered over the ranks -> (mean, bounds); run = (burn_in, n_mcmc, hmc);
         sets hmc_row_step_, hmc_row_mass_ and individual_sd_ (and, with the trajectory options traj, hmc_row_leapfrog_)."""
+        (mean, sd), bounds, _ = self._row_series(data, x_values, alpha, run, sample_y, interval, draw_budget_bytes, verbose, partial, traj)
+        self.individual_sd_ = sd
+        return mean, bounds
+
+    def _row_series(self, data, x_values, alpha, run, sample_y, interval, draw_budget_bytes, verbose, partial=False, traj=(0.0, 0),
+                    contrasts=False):
+        """What _individual_rows and predict_dose_effect share -> ((mean, sd) of y_i(x_k), bounds, None).  contrasts=True: x_values[0]
+        is the baseline, the kernels also keep c_i(k) = y_i(x_k) - y_i(x_0) per draw (hmc_sample, row_contrasts), the stored draws
+        and the tails are those of c, and the result is ((mean, sd) of y, bounds of c, (mean, sd) of c)."""
         burn_in, n_mcmc, hmc = run
         n_test, n_doses = len(data[0]), len(x_values)
         seed = self._begin_sampling(verbose)
@@ -768,28 +777,85 @@ class CausalBGM(object):
         quantile, tails = interval == 'quantile', interval == 'tails'
         k_tail = hmc_mod.tail_size(alpha, n_mcmc) if tails else None
         blocks = hmc_mod.individual_blocks([(lo_r, hi_r)] if hi_r > lo_r else [], n_mcmc, n_doses, interval, draw_budget_bytes, k_tail)
-        res = torch.zeros((4 if quantile or tails else 2, n_test, n_doses), device=eng.device, dtype=torch.float64)      # mean, sd(, lower, upper): this rank's rows filled
+        nb = 4 if quantile or tails else 2
+        # mean, sd(, lower, upper)(, contrast mean, contrast sd): this rank's rows filled
+        res = torch.zeros((nb + (2 if contrasts else 0), n_test, n_doses), device=eng.device, dtype=torch.float64)
+        draws_key = "contrast_draws" if contrasts else "row_draws"
 
         def consume(s0, e0, x, out):
             res[0, s0:e0], res[1, s0:e0] = out["row_mean"], out["row_sd"]
+            if contrasts:
+                res[nb, s0:e0], res[nb + 1, s0:e0] = out["contrast_mean"], out["contrast_sd"]
             if quantile:
-                _, lo, hi = eng.row_mean_quantiles(out.pop("row_draws").reshape((e0 - s0) * n_doses, n_mcmc), alpha / 2, 1 - alpha / 2)
+                _, lo, hi = eng.row_mean_quantiles(out.pop(draws_key).reshape((e0 - s0) * n_doses, n_mcmc), alpha / 2, 1 - alpha / 2)
                 res[2, s0:e0], res[3, s0:e0] = lo.reshape(e0 - s0, n_doses).double(), hi.reshape(e0 - s0, n_doses).double()
             if tails:      # [2, K, n_doses, rows] -> bounds [n_doses, rows]
                 lo, hi = eng.row_tail_quantiles(out.pop("tails"), n_mcmc, alpha / 2, 1 - alpha / 2)
                 res[2, s0:e0], res[3, s0:e0] = lo.t().double(), hi.t().double()
         self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, row_effects=True, row_draws=quantile,
                             x_values=x_values, sample_y=sample_y, partial=partial, **(dict(row_tails=k_tail) if tails else {}),
-                            **self._traj_kw(traj))
+                            **(dict(row_contrasts=True) if contrasts else {}), **self._traj_kw(traj))
         res = parallel.all_reduce_sum_(res).cpu().numpy()
         mean, sd = res[0], res[1]
-        self.individual_sd_ = sd
+        contrast = (res[nb], res[nb + 1]) if contrasts else None
         if quantile or tails:
             bounds = np.stack([res[2], res[3]], axis=-1)
         else:
             z = NormalDist().inv_cdf(1.0 - alpha / 2)
-            bounds = np.stack([mean - z * sd, mean + z * sd], axis=-1)
-        return mean, bounds
+            c_mean, c_sd = contrast if contrasts else (mean, sd)
+            bounds = np.stack([c_mean - z * c_sd, c_mean + z * c_sd], axis=-1)
+        return (mean, sd), bounds, contrast
+
+    dose_effect_sd_ = None           # predict_dose_effect: posterior sd [n, n_doses] of the contrasts
+    dose_effect_curve_ = None        # predict_dose_effect: (mean, sd), each [n, 1 + n_doses], of y_i at [baseline] + x_values
+    group_dose_effect_ = None        # predict_dose_effect(groups=...): {label: (mean [n_doses], sd [n_doses])}; None otherwise
+
+    def predict_dose_effect(self, data, x_values, baseline, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None,
+                            n_leapfrog=None, mass='identity', interval='normal', draw_budget_bytes=None, groups=None, partial=False,
+                            verbose=1):
+        """The effect of a dose against a baseline dose for every row under a continuous treatment, with its posterior uncertainty:
+        ``(effect [n, n_doses], interval [n, n_doses, 2])`` of y_i(x_values[k]) - y_i(baseline), what row i gains at dose
+        ``x_values[k]`` over ``baseline`` (a finite scalar).  The reference has no counterpart; a binary treatment has ``predict``'s
+        ITE.  ``predict_individual`` cannot give this: its moments and tails describe every dose alone, while the two doses of a
+        contrast are evaluated on the same latent draw and are strongly correlated.  Here the sampling kernel forms the difference
+        on every retained draw and keeps its moments (and, where asked, its draws or its tails), so nothing of size ``n_mcmc`` is
+        stored with ``interval='normal'`` or ``'tails'``.
+
+        The latents are sampled as in ``predict_individual`` (``step_size``, ``n_leapfrog``, ``mass`` and the seed sequence as there;
+        ``self.hmc_row_step_`` / ``self.hmc_row_mass_`` set as there) at the doses ``[baseline] + x_values``; the baseline's own
+        column, exactly zero, is dropped from what is returned.  ``self.dose_effect_sd_`` [n, n_doses] is the sd of the contrasts and
+        ``self.dose_effect_curve_ = (mean, sd)``, each [n, 1 + n_doses], the curve of y_i at ``[baseline] + x_values``: what
+        ``predict_individual`` returns there, bit for bit.
+
+        ``interval``: ``'normal'`` | ``'quantile'`` | ``'tails'`` with ``predict_individual``'s meanings and row blocks
+        (``draw_budget_bytes``), applied to the series of the contrast; ``'tails'`` gives the bounds of ``'quantile'`` bit for bit.
+        With ``sample_y=True`` the interval is that of the DIFFERENCE OF TWO INDEPENDENT PREDICTIVE DRAWS: the outcomes at the two
+        doses share the latent draw and carry their own outcome noise, as the two arms of the binary ITE do; ``sample_y=False``
+        gives the interval of the difference of the two conditional means.
+
+        ``groups`` (int labels [n], optional): ``self.group_dose_effect_ = {label: (mean_g, sd_g)}`` of the contrast
+        (causal_hmc.group_dose_response).  ``partial=True``: NaN in ``data``'s y, or x and y, marks what a row does not observe, as
+        in ``hmc_sampler(..., partial=True)`` -- new units: what would this patient gain from dose b over dose a; a row with its
+        outcome observed and its treatment not, and NaN among the covariates, are refused.  The trajectory options are not taken:
+        the contrast kernels have no such variant."""
+        hmc, x_values, baseline = self._sampling_options(
+            ("hmc_row_step_", "hmc_row_mass_", "hmc_row_leapfrog_", "dose_effect_sd_", "dose_effect_curve_", "group_dose_effect_"), None,
+            (step_size, n_leapfrog, mass, burn_in),
+            lambda _: hmc_mod.check_dose_effect(bool(self._p['binary_treatment']), x_values, baseline, interval, draw_budget_bytes),
+            alpha, n_mcmc, x_values)
+        n_test = len(data[0])
+        if groups is not None:
+            hmc_mod.group_dose_response(np.zeros((n_test, 0)), np.zeros((n_test, 0)), groups)      # (the labels' checks, before a device is touched)
+        if partial:
+            data = hmc_mod.check_partial_panel(*data)
+        doses = np.concatenate([[baseline], x_values.reshape(-1)])
+        curve, bounds, (c_mean, c_sd) = self._row_series(data, doses, alpha, (burn_in, n_mcmc, hmc), sample_y, interval, draw_budget_bytes,
+                                                         verbose, partial=bool(partial), contrasts=True)
+        self.dose_effect_curve_ = curve
+        effect, self.dose_effect_sd_, bounds = c_mean[:, 1:], c_sd[:, 1:], bounds[:, 1:]
+        if groups is not None:
+            self.group_dose_effect_ = hmc_mod.group_dose_response(effect, self.dose_effect_sd_, groups)
+        return effect, bounds
 
     def predict_new(self, data_v, data_x=None, x_values=None, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None,
                     n_leapfrog=None, mass='identity', interval='normal', draw_budget_bytes=None, verbose=1, max_trajectory=None,

@@ -465,6 +465,36 @@ BGM_API int bgm_causal_hmc_run_row_tails(bgm_handle *h, const float *x_dev, cons
                                          const float *x_values_dev, int32_t n_doses, float *row_moments_dev, float *row_draws_dev,
                                          float *row_tails_dev, int32_t k_tail, void *stream);
 
+/* bgm_causal_hmc_run_row_effects with the CONTRAST of every dose against a baseline dose kept beside the curve: what row i gains at
+ * dose x_k over dose x_0, c_i(k) = y_i(x_k) - y_i(x_0), with its posterior spread and quantiles, without stored draws.  The marginal
+ * moments and tails of the two calls above cannot give that: both doses are evaluated on the same latent draw, so the difference is
+ * formed per retained draw inside the sampler (one float32 subtraction of the two values) and summarised like the values themselves.
+ * Dose 0 of x_values_dev is the baseline.  The arguments of bgm_causal_hmc_run_row_tails, with
+ *   row_moments_dev [3 x n_doses x n] float32 (required): the shifted sums of y_i(x_k), those of bgm_causal_hmc_run_row_effects;
+ *   row_cmoments_dev [3 x n_doses x n] float32 (required): the same sums of c -- plane 0 = ref, c at retained draw 0 (written by the
+ *     iteration it == burn_in, which also zeroes the other two), plane 1 = sum of (c - ref), plane 2 = sum of (c - ref)^2; finalise as
+ *     there.  At dose 0 c is exactly 0 on every draw.  In / out across the calls of one run;
+ *   contrast_draws_dev [n x n_doses x n_keep] float32 or NULL: contrast_draws_dev[(row * n_doses + k) * n_keep + d] = c, the layout of
+ *     row_draws_dev;
+ *   contrast_tails_dev [2 x k_tail x n_doses x n] float32 or NULL: the tails of every series of c, the layout and the rules of
+ *     row_tails_dev (bgm_row_tail_quantiles reads them); k_tail, 1 <= k_tail <= n_keep, is used with it and ignored without.
+ * Chain, noise counters and row_moments_dev are those of bgm_causal_hmc_run_row_effects bit for bit, and contrast_draws_dev is the
+ * float32 difference of its row_draws_dev columns k and 0; bgm_causal_hmc_set_mass and bgm_causal_hmc_set_partial are honoured.  With
+ * sample_y the two doses carry their own independent noise words (dose k: word k & 3 of Philox call k >> 2), as the two arms of
+ * BGM_EFFECT_ITE do: c is then the difference of two independent predictive draws on one latent draw.  Every (row, dose) has one
+ * owner lane, so a run cut at any iteration is bit-identical to one call.  While bgm_causal_hmc_set_trajectory has anything set the
+ * call answers BGM_E_UNSUPPORTED naming the option (the contrast kernels have no such variant).  Refusals otherwise: those of
+ * bgm_causal_hmc_run_row_effects / bgm_causal_hmc_run_row_tails in their order, and BGM_E_INVALID naming row_cmoments_dev when it is
+ * NULL.
+ * replaces: nothing in causalbgm/base.py; for a continuous treatment the reference has the panel's ADRF only (:671-763). */
+BGM_API int bgm_causal_hmc_run_row_contrasts(bgm_handle *h, const float *x_dev, const float *y_dev, const float *v_dev, int64_t n,
+                                             int64_t row_base, float *state_dev, float *logp_dev, float *grad_dev, float *step_dev,
+                                             const float *up_dev, const float *dn_dev, int32_t n_table, float s_min, float s_max,
+                                             int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog,
+                                             uint64_t seed, uint32_t *acc_count_dev, float *draws_dev, int32_t n_keep, int32_t sample_y,
+                                             const float *x_values_dev, int32_t n_doses, float *row_moments_dev, float *row_cmoments_dev,
+                                             float *contrast_draws_dev, float *contrast_tails_dev, int32_t k_tail, void *stream);
+
 /* The two linear-interpolated quantiles of bgm_row_mean_quantiles from the tails of every series: tails_dev [2 x k_tail x n_series]
  * float32 (the layout of bgm_causal_hmc_run_row_tails with n_series = n_doses * n, series k * n + row), tail 0 the k_tail smallest of
  * the series' m values and tail 1 the k_tail largest, in any order -> lo_dev, hi_dev [n_series].  With vi = q (m - 1) in double,
