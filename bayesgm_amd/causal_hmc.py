@@ -19,6 +19,9 @@ row_adapt.leapfrog_cap; csrc/causal_hmc_traj_kernels.h).
 ``predict_dose_effect``: the contrast of every dose against a baseline dose (csrc/causal_hmc_contrast_kernels.h); its own checks are
 ``check_dose_effect`` and ``check_partial_panel``, everything else is predict_individual's.
 
+``predict_best_dose``: the choice among the doses, compared per retained draw (csrc/causal_hmc_choice_kernels.h); its own checks are
+``check_best_dose`` / ``check_threshold``, its finishing helpers ``choice_finalize`` and ``group_dose_choice``.
+
 ``predict_average``: the option checks, the internal row labels and the combiner of the per-draw label sums into ATE / ATT / ATC
 (``combine_average_effects``) follow them.
 
@@ -344,6 +347,78 @@ def group_dose_response(mean, sd, groups):
         rows = labels == g
         m_g = int(rows.sum())
         out[int(g)] = (mean[rows].sum(axis=0) / m_g, np.sqrt((sd[rows] ** 2).sum(axis=0)) / m_g)
+    return out
+
+
+# ---- predict_best_dose: the choice among the doses, compared per retained draw (csrc/causal_hmc_choice_kernels.h) -----------------
+def check_threshold(threshold):
+    """None, or a finite scalar -> None or float; ValueError otherwise."""
+    if threshold is None:
+        return None
+    try:
+        t = float(threshold) if np.ndim(threshold) == 0 and not isinstance(threshold, (bool, str)) else float("nan")
+    except (TypeError, ValueError):
+        t = float("nan")
+    if not np.isfinite(t):
+        raise ValueError("threshold must be None or a finite scalar, the outcome a dose is asked to exceed; got %r" % (threshold,))
+    return t
+
+
+def check_best_dose(binary, x_values, threshold):
+    """The options of predict_best_dose that are its own: a continuous treatment, x_values and a finite threshold (or None) ->
+    threshold as a float or None; ValueError otherwise."""
+    if binary:
+        raise ValueError("predict_best_dose is the choice among the doses of a continuous treatment; a binary treatment has "
+                         "its per-row effect already: predict's ITE")
+    if x_values is None:
+        raise ValueError("predict_best_dose needs x_values: the doses among which every row's best is looked for")
+    return check_threshold(threshold)
+
+
+def check_choice_kernel(q, metric, partial):
+    """The one combination the dose-choice kernels are not built for (csrc/causal_hmc_choice_api.hip): a metric together with
+    partially observed rows at more than 11 latent features, where that instantiation would need scratch memory.  ValueError."""
+    if metric and partial and int(q) + 1 > 12:
+        raise ValueError("the dose choice is not available with a metric (mass='diag' / mass_scale) together with partial=True at more "
+                         "than 11 latent features (here %d): that kernel cannot be had without scratch memory and is not built; use "
+                         "mass='identity', or fully observed rows" % int(q))
+
+
+def choice_finalize(best_count, best_ref, best_s1, mean, n_keep, maximize=True):
+    """The sampler's per-row choice planes -> (prob_best [n, n_doses], expected_best [n], regret [n, n_doses]), float64 NumPy.
+    best_count [n, n_doses] = the retained draws at which dose k was the row's best, (best_ref, best_s1) [n] the shifted sum of the
+    best outcome (ref = that of draw 0, s1 = sum of best - ref), mean [n, n_doses] the posterior mean of every dose, n_keep the
+    number of retained draws.  prob_best = best_count / n_keep; expected_best = ref + s1 / n_keep; regret_k = expected_best -
+    mean_k (mean_k - expected_best when minimising): what is lost in expectation by giving dose k instead of the draw's best.
+    It is not clipped: both terms are float32 sums, so a value may be negative by their rounding and by nothing else."""
+    to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    count, ref, s1, mean = (np.asarray(to_np(a), np.float64) for a in (best_count, best_ref, best_s1, mean))
+    m = int(n_keep)
+    if m < 1:
+        raise ValueError("choice_finalize: n_keep must be at least 1; got %r" % (n_keep,))
+    if count.shape != mean.shape or count.ndim != 2 or ref.shape != (count.shape[0],) or s1.shape != ref.shape:
+        raise ValueError("choice_finalize: best_count and mean [n, n_doses], best_ref and best_s1 [n]; got %r, %r, %r, %r" %
+                         (count.shape, mean.shape, ref.shape, s1.shape))
+    expected = ref + s1 / m
+    regret = expected[:, None] - mean if maximize else mean - expected[:, None]
+    return count / m, expected, regret
+
+
+def group_dose_choice(choice, prob_best, groups):
+    """Subgroup summaries of the choice: choice [n] (dose index per row), prob_best [n, n_doses] and int labels [n] ->
+    {label: (share [n_doses], mean_prob [n_doses])}, float64: the share of the group's rows whose choice is dose k, and the mean
+    over the group's rows of prob_best."""
+    prob = np.asarray(prob_best, np.float64)
+    choice = np.asarray(choice)
+    labels = np.asarray(groups)
+    if labels.shape != (prob.shape[0],) or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError("groups must be integer labels of shape [n] = (%d,); got %s of shape %r" % (prob.shape[0], labels.dtype, labels.shape))
+    out = {}
+    for g in np.unique(labels):
+        rows = labels == g
+        m_g = int(rows.sum())
+        out[int(g)] = (np.bincount(choice[rows].astype(np.int64), minlength=prob.shape[1])[:prob.shape[1]] / float(m_g),
+                       prob[rows].sum(axis=0) / m_g)
     return out
 
 

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libbgm_hip.so")
-SOURCES = ["causal_api.hip", "causal_event_api.hip", "causal_bx3_api.hip", "causal_prior_api.hip", "causal_rowadapt_api.hip", "causal_hmc_api.hip", "causal_hmc_mass_api.hip", "causal_hmc_fx_api.hip", "causal_hmc_rowfx_api.hip", "causal_hmc_gfx_api.hip", "causal_hmc_obs_api.hip", "causal_hmc_tails_api.hip", "causal_hmc_contrast_api.hip", "causal_hmc_traj_api.hip", "aux_kernels.hip", "fit_api.hip", "bgm_api.hip", "bgm_rowstep_api.hip", "bgm_impute_api.hip", "bgm_impute_tails_api.hip", "egm_api.hip", "bgm_egm_api.hip", "bnn_api.hip", "bnn_sample_api.hip", "bprior_api.hip", "bnf_api.hip", "bnx_api.hip", "bnf_det_api.hip", "gx_api.hip", "gx_bgm_api.hip", "bnn_egm_api.hip", "bnn_egm_gen_chain_a.hip", "bnn_egm_gen_chain_b.hip", "bnn_egm_gen_chain_c.hip", "bnn_egm_gen_chain_d.hip", "bgmb_api.hip", "bgmb_egm_api.hip", "bgmf_api.hip", "bnw_api.hip", "comm_api.hip", "sdr_api.hip", "chain_diag_api.hip"]
+SOURCES = ["causal_api.hip", "causal_event_api.hip", "causal_bx3_api.hip", "causal_prior_api.hip", "causal_rowadapt_api.hip", "causal_hmc_api.hip", "causal_hmc_mass_api.hip", "causal_hmc_fx_api.hip", "causal_hmc_rowfx_api.hip", "causal_hmc_gfx_api.hip", "causal_hmc_obs_api.hip", "causal_hmc_tails_api.hip", "causal_hmc_contrast_api.hip", "causal_hmc_choice_api.hip", "causal_hmc_traj_api.hip", "aux_kernels.hip", "fit_api.hip", "bgm_api.hip", "bgm_rowstep_api.hip", "bgm_impute_api.hip", "bgm_impute_tails_api.hip", "egm_api.hip", "bgm_egm_api.hip", "bnn_api.hip", "bnn_sample_api.hip", "bprior_api.hip", "bnf_api.hip", "bnx_api.hip", "bnf_det_api.hip", "gx_api.hip", "gx_bgm_api.hip", "bnn_egm_api.hip", "bnn_egm_gen_chain_a.hip", "bnn_egm_gen_chain_b.hip", "bnn_egm_gen_chain_c.hip", "bnn_egm_gen_chain_d.hip", "bgmb_api.hip", "bgmb_egm_api.hip", "bgmf_api.hip", "bnw_api.hip", "comm_api.hip", "sdr_api.hip", "chain_diag_api.hip"]
 # every header in this directory (a new one cannot be forgotten) and the public one: the early "library is current" test in build()
 HEADERS = sorted(f for f in os.listdir(HERE) if f.endswith((".h", ".inc"))) + [os.path.join("..", "..", "include", "bgm_hip.h")]
 FLAGS = os.environ.get("BGM_EXTRA_FLAGS", "").split() + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-munsafe-fp-atomics",

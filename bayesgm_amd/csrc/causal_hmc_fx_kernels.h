@@ -90,14 +90,18 @@ using chmc_arg = std::conditional_t<EFFECT == 0, T, const T &>;
 // L_i-step proposal.  L_i depends on (eps, global row, it, seed) only, never on z or the momentum.
 // CONTRAST (causal_hmc_contrast_kernels.h, with ROWS): the rows' differences to dose 0 are kept beside their curves, in row_cmom
 // [3][n_doses][n], and row_y / row_tails record them instead of the values (causal_effects, CONTRAST); nothing else differs.
+// CHOICE (causal_hmc_choice_kernels.h, with ROWS): which dose is the row's best at every retained draw is counted beside its curve, in
+// the planes of ch (causal_effects, CHOICE); nothing else differs.
 template <int KT1, int KSL1, int WAVES, int EFFECT, bool MASS, bool ROWS = false, bool OBS = false, bool TAILS = false, bool TRAJ = false,
-          bool CONTRAST = false>
+          bool CONTRAST = false, bool CHOICE = false>
 __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EFFECT> a, chmc_arg<CausalHmcMassArgs, EFFECT> ma,
                                          chmc_arg<CausalHmcFxArgs, EFFECT> fx, float *row_mom = nullptr, float *row_y = nullptr,
                                          float *row_tails = nullptr, int k_tail = 0,
-                                         chmc_arg<CausalHmcTrajArgs, EFFECT> tj = CausalHmcTrajArgs{}, float *row_cmom = nullptr) {
+                                         chmc_arg<CausalHmcTrajArgs, EFFECT> tj = CausalHmcTrajArgs{}, float *row_cmom = nullptr,
+                                         chmc_arg<CausalChoiceArgs, EFFECT> ch = CausalChoiceArgs{}) {
   static_assert(!TAILS || ROWS, "TAILS: the tail buffers of the per-row dose-response");
   static_assert(!CONTRAST || (ROWS && !TRAJ), "CONTRAST: the per-row dose-response; no twin with TRAJ");
+  static_assert(!CHOICE || (ROWS && !TAILS && !TRAJ && !CONTRAST), "CHOICE: the per-row dose-response; no twin with TAILS, TRAJ or CONTRAST");
   static_assert(!TRAJ || (!TAILS && EFFECT != 4), "TRAJ: no twin of the tail-buffer and label-sum kernels");
   const CausalHmcMeta &m = a.m;
   const CausalMeta &mf = fx.mf;
@@ -253,11 +257,11 @@ __device__ __forceinline__ void chmc_run(float *lds, chmc_arg<CausalHmcKArgs, EF
       if constexpr (EFFECT != 0) if (it >= a.burn_in) {    // (wave-uniform) infer_from_latent_posterior on the state the chain holds after this decision
         int label = 0;
         if constexpr (EFFECT == 4) label = reinterpret_cast<const int *>(fx.ite)[row];
-        causal_effects<KT1, KSL1, 1, EFFECT, true, false, false, true, ROWS, TAILS, false, CONTRAST>(
+        causal_effects<KT1, KSL1, 1, EFFECT, true, false, false, true, ROWS, TAILS, false, CONTRAST, CHOICE>(
             lds_f, mf, lane_off, g, j, lane, z, rowid, valid, row0, n, (unsigned)it, (long long)(it - a.burn_in), fx.n_keep, fx.sample_y,
             fx.n_doses, fx.x_values,
             ROWS ? nullptr : fx.adrf_partial + slot * (long long)fx.n_doses * fx.n_keep /* unused when EFFECT == 2 */, fx.ite, a.k0, a.k1,
-            nullptr, nullptr, row_mom, row_y, label, row_tails, k_tail, row_cmom);
+            nullptr, nullptr, row_mom, row_y, label, row_tails, k_tail, row_cmom, ch);
       }
     }
     if (ok) {

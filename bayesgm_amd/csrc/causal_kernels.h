@@ -604,6 +604,22 @@ __device__ __forceinline__ float pick_by_group(int g, float v0, float v1, float 
 // first, so it cannot be folded into the fmaf that forms y, and row_mom receives the y it always did); its shifted moments go to
 // row_cmom [3][n_doses][n] by the rule of row_mom, and row_y / row_tails record c instead of y.  At dose 0 c is exactly 0.  With
 // sample_y the two doses carry their own independent noise words, as the two arms of the binary ITE do.
+// CHOICE (ROWS only; causal_hmc_choice_kernels.h): besides the curve, which dose is the row's best at every retained draw.  y is pinned
+// as under CONTRAST.  The owner lane of (row, k) counts y > threshold in ch.above [n_doses][n] (when given).  Every lane keeps the pair
+// (best, best_k) of sign * y over ITS OWN doses of the draw -- valid rows and k < n_doses only: a padded lane evaluates the last dose
+// again and must never win --, -inf and an invalid index to begin with; sign = +-1, so the product is exact.  After the last pass one
+// exchange over the four lane groups (xor 16, xor 32; all 64 lanes, outside the valid branch) leaves in every lane of row j the
+// row's best value and the LOWEST dose index that attains it: the rule compares k, it does not rest on the order the doses arrive
+// in (own passes visit k = 4 (c4 + g) + p4, shared passes k = 4 kb + g).  NaN never wins; a row of NaNs counts nothing.  Lane (j, 0)
+// owns column [:, row] of ch.best_count [n_doses][n] and of ch.best_mom [2][n] for the whole run: at draw 0 it zeroes its n_doses
+// counters and writes ref = best (the unsigned y) and s1 = 0, afterwards s1 += best - ref, and best_count[best_k][row] += 1 by plain
+// load and store.  No atomics, and no access of one lane is ordered against another's.
+struct CausalChoiceArgs {
+  unsigned *best_count;               // [n_doses][n]
+  float *best_mom;                    // [2][n]: ref, s1 of the draw's best y
+  unsigned *above;                    // [n_doses][n], or NULL
+  float sign, threshold;              // +1 maximise / -1 minimise; y > threshold is counted
+};
 // ---------------------------------------------------------------------------
 // VTAILS: the dose passes of the grouped dose-response sums with the 32 -> 8 -> 2 tail of f on the vector ALU (the MH kernels'
 // retained phase).  On the matrix pipe the tail of a pass is 40 of its 168 instructions for 1 088 MACs per chain: half of the M
@@ -785,7 +801,7 @@ __device__ __forceinline__ void causal_dose_passes_valu(const float *lds, const 
 }
 
 template <int KT1, int KSL1, int R, int EFFECT, bool GROUPING = true, bool CACHE = false, bool EVAL_ONLY = false, bool L1MASK = true,
-          bool ROWS = false, bool TAILS = false, bool VTAILS = false, bool CONTRAST = false>
+          bool ROWS = false, bool TAILS = false, bool VTAILS = false, bool CONTRAST = false, bool CHOICE = false>
 __device__ __forceinline__ void causal_effects(const float *lds, const CausalMeta &m, int lane_off, int g, int j,
                                                int lane, const f32x4 (&zs)[R][KT1], const unsigned (&rowid)[R],
                                                const bool (&valid)[R], long long row0, long long n, unsigned it,
@@ -793,12 +809,14 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
                                                const float *x_values, float *adrf_slot, float *ite, unsigned k0,
                                                unsigned k1, float2 *cache = nullptr, float *ite_c = nullptr,
                                                float *row_mom = nullptr, float *row_y = nullptr, int label = 0,
-                                               float *row_tails = nullptr, int k_tail = 0, float *row_cmom = nullptr) {
+                                               float *row_tails = nullptr, int k_tail = 0, float *row_cmom = nullptr,
+                                               const CausalChoiceArgs &ch = CausalChoiceArgs{}) {
   // ite_c (EFFECT == 2, one row tile per wave, CACHE): [4] registers of the caller receiving (mean, sd) of the two arms
   static_assert(!ROWS || (EFFECT == 1 && R == 1 && GROUPING && !CACHE && !EVAL_ONLY), "ROWS: the grouped finish of the dose-response sums");
   static_assert(EFFECT != 4 || (R == 1 && !CACHE && !EVAL_ONLY && !ROWS), "EFFECT 4: the label sums of one row tile per wave");
   static_assert(!TAILS || ROWS, "TAILS: the tail buffers of the per-row dose-response");
   static_assert(!CONTRAST || ROWS, "CONTRAST: the contrasts of the per-row dose-response against its dose 0");
+  static_assert(!CHOICE || (ROWS && !TAILS && !CONTRAST), "CHOICE: the best dose of the per-row dose-response; no twin with TAILS or CONTRAST");
   constexpr bool ARMS = (EFFECT == 2 || EFFECT == 4);   // the two arms x = 1, x = 0 of a binary treatment
   BGM_NO_HOIST();
   f32x4 z0in[R][KT1];
@@ -828,6 +846,8 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
 #pragma unroll
   for (int rr = 0; rr < R; ++rr) nz[rr] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   [[maybe_unused]] float y0 = 0.0f;            // (CONTRAST: y of the lane's row at dose 0 of this draw, from pass 0 on)
+  [[maybe_unused]] float best = -__builtin_inff();     // (CHOICE: the largest sign * y among the lane's own doses of this draw ...
+  [[maybe_unused]] int best_k = 0x7fffffff;            //  ... and the lowest dose index attaining it)
   for (int kb = 0; kb < n_calls; ++kb) {       // one pass of DB doses per Philox call
     BGM_NO_HOIST();
     const bool own = kb < n_own;
@@ -936,6 +956,11 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
           c = y - y0;
         }
         const float rec = CONTRAST ? c : y;           // what the draws and the tails record
+        if constexpr (CHOICE) {
+          asm volatile("" : "+v"(y));                 // the rounded y, as the curve planes and row_y receive it
+          const float sy = ch.sign * y;               // exact
+          if (valid[0] && k < nd && (sy > best || (sy == best && k < best_k))) { best = sy; best_k = k; }
+        }
         if (valid[0] && k < nd) {
           const long long row = row0 + j, plane = (long long)nd * n;
           long long off = (long long)k * n + row;
@@ -957,6 +982,12 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
               cf[plane] += dv;
               cf[2 * plane] = fmaf(dv, dv, cf[2 * plane]);
             }
+          }
+          if constexpr (CHOICE) if (ch.above) {       // (wave-uniform)
+            unsigned *ab = ch.above + off;
+            const unsigned hit = y > ch.threshold ? 1u : 0u;
+            if (d == 0) ab[0] = hit;
+            else ab[0] += hit;
           }
           if (row_y) row_y[(row * nd + k) * (long long)n_keep + d] = rec;
           if constexpr (TAILS) {
@@ -1010,6 +1041,42 @@ __device__ __forceinline__ void causal_effects(const float *lds, const CausalMet
         const long long row = row0 + 16 * rr + j;
         if (g == 0 && row < n) ite[row * (long long)n_keep + d] = yk[0][rr] - yk[1][rr];
       }
+    }
+  }
+  if constexpr (CHOICE) {                        // after the draw's last pass: the row's best over the four lane groups
+#pragma unroll
+    for (int sh = 16; sh <= 32; sh <<= 1) {        // all 64 lanes
+      const float ob = __shfl_xor(best, sh);
+      const int ok = __shfl_xor(best_k, sh);
+      const bool take = (ob > best) | ((ob == best) & (ok < best_k));
+      best = take ? ob : best;
+      best_k = take ? ok : best_k;
+    }
+    // Lane (j, 0) is the one owner of column [:, row] of both planes.  The tile's first row is the same in all lanes: taken as a scalar,
+    // every address below is a scalar base plus the lane's 4 j bytes, so the block needs no 64-bit address per lane (registers: DESIGN 4ai).
+    const long long r0 = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(row0 >> 32)) << 32) |
+                                     (unsigned)__builtin_amdgcn_readfirstlane((int)row0));
+    unsigned jb = 4u * (unsigned)j;
+    asm volatile("" : "+v"(jb));                   // formed here, not hoisted to the kernel's entry and held as three 64-bit addresses
+    const bool owner = valid[0] && g == 0;
+    const float bv = ch.sign * best;               // the unsigned y again (exact)
+    float *bm_ref = reinterpret_cast<float *>(reinterpret_cast<char *>(ch.best_mom + r0) + jb);
+    float *bm_s1 = reinterpret_cast<float *>(reinterpret_cast<char *>(ch.best_mom + r0 + n) + jb);
+    if (d == 0) {                                  // (wave-uniform) the first retained draw writes every element, zeros included
+#pragma nounroll
+      for (int kk = 0; kk < nd; ++kk)
+        if (owner) *reinterpret_cast<unsigned *>(reinterpret_cast<char *>(ch.best_count + r0 + (long long)kk * n) + jb) = 0u;
+      if (owner) { *bm_ref = bv; *bm_s1 = 0.0f; }
+    }
+    const bool counts = owner && best_k < nd;      // (a row whose values were all NaN counts nothing)
+    if (counts && d != 0) *bm_s1 += bv - *bm_ref;
+    // (owners have g == 0, lanes 0 .. 15: the low word of the ballot holds them all)
+    unsigned rest = (unsigned)__ballot(counts);    // the tile's rows whose best dose has not been counted yet
+    while (rest) {                                 // one trip per distinct best dose of the tile: its plane's base is a scalar
+      const int kq = __builtin_amdgcn_readlane(best_k, __builtin_ctz(rest));
+      const bool mine = counts && best_k == kq;
+      if (mine) *reinterpret_cast<unsigned *>(reinterpret_cast<char *>(ch.best_count + r0 + (long long)kq * n) + jb) += 1u;
+      rest &= ~(unsigned)__ballot(mine);
     }
   }
 }

@@ -252,6 +252,31 @@ class CausalEngine(object):
                                                                  0 if contrast_tails is None else int(contrast_tails.shape[1]),
                                                                  self._stream()), "bgm_causal_hmc_run_row_contrasts")
 
+    def hmc_run_rows_choice(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
+                            row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
+                            sample_y=True, x_values=None, row_moments=None, row_draws=None, best_count=None, best_moments=None,
+                            above_count=None, threshold=0.0, maximize=True, partial=False):
+        """hmc_run_rows_effects with the choice among the doses kept beside the curve (bgm_causal_hmc_run_row_choice): best_count
+        [n_doses, n] int32 counts the retained draws at which dose k gave the row its best outcome (the largest y with maximize,
+        else the smallest; the lowest dose index on ties), best_moments [2, n] float32 holds ref = the best y of retained draw 0
+        and s1 = the sum of best - ref, and, optionally, above_count [n_doses, n] int32 counts the draws with y > threshold (a
+        finite number).  All are written by the first retained iteration and in / out across segments.  Chain, row_moments and
+        row_draws are those of hmc_run_rows_effects bit for bit.  The library refuses the call while a trajectory option is set."""
+        n_doses = 0 if x_values is None else int(x_values.numel())
+        for name, t, shape, dt in (("best_count", best_count, (n_doses, v.shape[0]), torch.int32),
+                                   ("best_moments", best_moments, (2, v.shape[0]), torch.float32),
+                                   ("above_count", above_count, (n_doses, v.shape[0]), torch.int32)):
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise ValueError("hmc_run_rows_choice: %s must be a contiguous %s tensor %r; got %s %r" %
+                                 (name, str(dt).replace("torch.", ""), shape, t.dtype, tuple(t.shape)))
+        with self._partial_rows(partial, x, y):
+            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
+                                  s_max, acc_count, draws, n_keep)
+            _lib.check(self.lib.bgm_causal_hmc_run_row_choice(*args, int(bool(sample_y)), _ptr(x_values), n_doses, _ptr(row_moments),
+                                                              _ptr(row_draws), _ptr(best_count), _ptr(best_moments), _ptr(above_count),
+                                                              float(threshold), int(bool(maximize)), self._stream()),
+                       "bgm_causal_hmc_run_row_choice")
+
     def row_tail_quantiles(self, tails, m, q_lo, q_hi):
         """tails [2, K, ...] float32 on the device (hmc_sample's out["tails"]: the K smallest and the K largest of every series' m
         values) -> (lo, hi), each of shape tails.shape[2:]: the quantiles row_mean_quantiles gives on the m values, bit for bit
@@ -322,7 +347,7 @@ class CausalEngine(object):
     def hmc_sample(self, x, y, v, burn_in, n_keep, step_size, n_leapfrog, seed, chunk=None, want_draws=False, row_base=0,
                    adapt=HM.DEFAULT_TARGET, adapt_table=None, mass=None, mass_windows=None, mass_scale=None, effect=_lib.EFFECT_NONE,
                    x_values=None, sample_y=True, row_effects=False, row_draws=False, labels=None, n_labels=None, partial=False,
-                   row_tails=None, max_trajectory=None, jitter=False, row_contrasts=False):
+                   row_tails=None, max_trajectory=None, jitter=False, row_contrasts=False, row_choice=False, maximize=True, threshold=None):
         """HMC over the latent posterior of every row, one chain per row with a step size of its own.
 
         adapt = target acceptance rate (None: the step stays step_size): after each of the burn_in decisions a chain multiplies its
@@ -361,6 +386,15 @@ class CausalEngine(object):
         With sample_y the two doses carry independent noise.  Not available for a binary treatment (it has EFFECT_ITE) or with
         max_trajectory / jitter: ValueError before a device is touched.
 
+        row_choice = True (with row_effects): the doses are compared on every retained state inside the sampler
+        (hmc_run_rows_choice): best_count [n, n_doses] (int64) is the number of retained draws at which dose k gave the row its best
+        outcome -- the largest with maximize, else the smallest, the lowest dose index on ties; rows sum to n_keep --, best_mean [n]
+        (float64) the posterior mean of that best outcome, and, with threshold = a finite number, above_count [n, n_doses] (int64)
+        the draws with y > threshold.  Chain, row_mean / row_sd and row_draws are those of the run without it.  With sample_y every
+        dose carries its own independent noise.  Not available with row_contrasts, row_tails, max_trajectory / jitter or a binary
+        treatment, nor with a metric (mass / mass_scale) together with partial at more than 11 latent features (that one kernel is
+        not built: causal_hmc.check_choice_kernel): ValueError before a device is touched.
+
         partial = True: NaN in y, or in x and y, marks what a row does not observe (new units): its chain samples p(z | x, v) or
         p(z | v) (logpost_grad).  A row with y observed and x not is refused.  Works without an effect, with EFFECT_ITE and with
         row_effects; a fully observed panel gives the run of partial = False bit for bit.
@@ -388,6 +422,22 @@ class CausalEngine(object):
             if self.binary:
                 raise ValueError("hmc_sample: row_contrasts is the contrast between two doses of a continuous treatment; a binary "
                                  "treatment has its per-row effect already (effect=EFFECT_ITE)")
+        if row_choice:
+            if not row_effects:
+                raise ValueError("hmc_sample: row_choice belongs to row_effects=True")
+            if row_contrasts or row_tails is not None:
+                raise ValueError("hmc_sample: row_choice is not available with row_contrasts or row_tails: the dose-choice kernels "
+                                 "(hmc_run_rows_choice) have no variant with contrasts or tail buffers")
+            if traj:
+                raise ValueError("hmc_sample: max_trajectory / jitter are not available with row_choice: the dose-choice kernels "
+                                 "(hmc_run_rows_choice) have no variant with a trajectory length per chain")
+            if self.binary:
+                raise ValueError("hmc_sample: row_choice is the choice among the doses of a continuous treatment; a binary "
+                                 "treatment has its per-row effect already (effect=EFFECT_ITE)")
+            threshold = HM.check_threshold(threshold)
+            HM.check_choice_kernel(self.q, mass not in (None, "identity") or mass_scale is not None, partial)
+        elif threshold is not None:
+            raise ValueError("hmc_sample: threshold belongs to row_choice=True")
         if traj and effect == _lib.EFFECT_GROUP_ITE:
             raise ValueError("hmc_sample: max_trajectory / jitter are not available with effect=EFFECT_GROUP_ITE: the label-sum kernels "
                              "(hmc_run_group_effects) have no variant with a trajectory length per chain")
@@ -418,7 +468,7 @@ class CausalEngine(object):
         draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
         chunk = total if chunk is None else max(1, int(chunk))
         launch, route_kw, collect = self._hmc_route(n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails,
-                                                    row_contrasts)
+                                                    row_contrasts, (bool(maximize), threshold) if row_choice else None)
         scale = moments = None
         if diag:
             scale = torch.ones((n, self.q), device=dev, dtype=torch.float32)
@@ -461,7 +511,8 @@ class CausalEngine(object):
     # The result routes of hmc_sample, one per kind of result.  Each checks what is its own, allocates its buffers and returns
     # (launch, kw, collect): the engine method that runs a segment, the keyword arguments it takes besides the common ones, and
     # the function that adds the route's keys to the returned dict.
-    def _hmc_route(self, n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails=None, row_contrasts=False):
+    def _hmc_route(self, n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails=None, row_contrasts=False,
+                   row_choice=None):
         kinds = {_lib.EFFECT_NONE: self._route_none, _lib.EFFECT_ADRF: self._route_adrf, _lib.EFFECT_ITE: self._route_ite,
                  _lib.EFFECT_GROUP_ITE: self._route_group_ite}
         if effect not in kinds:
@@ -472,7 +523,9 @@ class CausalEngine(object):
         if row_effects:
             if effect != _lib.EFFECT_NONE:
                 raise ValueError("hmc_sample: row_effects and effect exclude each other (the panel's ADRF is the mean of the rows' curves)")
-            return self._route_rows(n, n_keep, x_values, row_draws, row_tails, row_contrasts)
+            return self._route_rows(n, n_keep, x_values, row_draws, row_tails, row_contrasts, row_choice)
+        if row_choice is not None:
+            raise ValueError("hmc_sample: row_choice belongs to row_effects=True")
         if row_contrasts:
             raise ValueError("hmc_sample: row_contrasts belongs to row_effects=True")
         if row_draws:
@@ -516,7 +569,7 @@ class CausalEngine(object):
         return (self.hmc_run, dict(effect=_lib.EFFECT_GROUP_ITE, labels=lab, n_labels=n_lab, group_partial=part),
                 lambda out: out.update(group_partial=part, group_sums=self.adrf_reduce(part, n_slots, n_lab, n_keep, 1.0)))
 
-    def _route_rows(self, n, n_keep, x_values, row_draws, row_tails=None, row_contrasts=False):
+    def _route_rows(self, n, n_keep, x_values, row_draws, row_tails=None, row_contrasts=False, row_choice=None):
         if self.binary:
             raise ValueError("hmc_sample: row_effects is the dose-response of a continuous treatment; a binary treatment has its "
                              "per-row effect already (effect=EFFECT_ITE)")
@@ -531,6 +584,11 @@ class CausalEngine(object):
                 raise ValueError("hmc_sample: row_tails must be an integer K with 1 <= K <= n_keep = %d; got %r" % (int(n_keep), row_tails))
             tails = torch.empty((2, int(row_tails), xv.numel(), n), device=self.device, dtype=torch.float32)      # draw 0 initialises it
         cmom = torch.zeros((3, xv.numel(), n), device=self.device, dtype=torch.float32) if row_contrasts else None
+        best = bmom = above = None
+        if row_choice is not None:      # (maximize, threshold | None); the first retained iteration writes every element
+            best = torch.zeros((xv.numel(), n), device=self.device, dtype=torch.int32)
+            bmom = torch.zeros((2, n), device=self.device, dtype=torch.float32)
+            above = torch.zeros((xv.numel(), n), device=self.device, dtype=torch.int32) if row_choice[1] is not None else None
 
         def collect(out):
             mean, sd = HM.row_moments_finalize(mom[0], mom[1], mom[2], n_keep)
@@ -542,6 +600,16 @@ class CausalEngine(object):
                 out["contrast_draws" if row_contrasts else "row_draws"] = row_y
             if tails is not None:
                 out["tails"] = tails
+            if best is not None:
+                out["best_count"] = best.t().contiguous().long()
+                out["best_ref"], out["best_s1"] = bmom[0], bmom[1]
+                out["best_mean"] = bmom[0].double() + bmom[1].double() / float(max(1, int(n_keep)))
+                if above is not None:
+                    out["above_count"] = above.t().contiguous().long()
+        if row_choice is not None:
+            return (self.hmc_run_rows_choice,
+                    dict(x_values=xv, row_moments=mom, row_draws=row_y, best_count=best, best_moments=bmom, above_count=above,
+                         threshold=0.0 if row_choice[1] is None else row_choice[1], maximize=row_choice[0]), collect)
         if row_contrasts:      # the draws and the tails, where asked for, are those of the contrasts
             return (self.hmc_run_rows_contrasts,
                     dict(x_values=xv, row_moments=mom, row_cmoments=cmom, contrast_draws=row_y, contrast_tails=tails), collect)

@@ -765,10 +765,12 @@ class CausalBGM(object):
         return mean, bounds
 
     def _row_series(self, data, x_values, alpha, run, sample_y, interval, draw_budget_bytes, verbose, partial=False, traj=(0.0, 0),
-                    contrasts=False):
-        """What _individual_rows and predict_dose_effect share -> ((mean, sd) of y_i(x_k), bounds, None).  contrasts=True: x_values[0]
-        is the baseline, the kernels also keep c_i(k) = y_i(x_k) - y_i(x_0) per draw (hmc_sample, row_contrasts), the stored draws
-        and the tails are those of c, and the result is ((mean, sd) of y, bounds of c, (mean, sd) of c)."""
+                    contrasts=False, choice=None):
+        """What _individual_rows, predict_dose_effect and predict_best_dose share -> ((mean, sd) of y_i(x_k), bounds, None).
+        contrasts=True: x_values[0] is the baseline, the kernels also keep c_i(k) = y_i(x_k) - y_i(x_0) per draw (hmc_sample,
+        row_contrasts), the stored draws and the tails are those of c, and the result is ((mean, sd) of y, bounds of c, (mean, sd)
+        of c).  choice=(maximize, threshold | None): the kernels also compare the doses per draw (hmc_sample, row_choice), and the
+        third item is (best_count [n, n_doses], best_ref [n], best_s1 [n], above_count [n, n_doses] | None), float64."""
         burn_in, n_mcmc, hmc = run
         n_test, n_doses = len(data[0]), len(x_values)
         seed = self._begin_sampling(verbose)
@@ -781,9 +783,16 @@ class CausalBGM(object):
         # mean, sd(, lower, upper)(, contrast mean, contrast sd): this rank's rows filled
         res = torch.zeros((nb + (2 if contrasts else 0), n_test, n_doses), device=eng.device, dtype=torch.float64)
         draws_key = "contrast_draws" if contrasts else "row_draws"
+        if choice is not None:      # best_count, above_count [n, n_doses]; best_ref, best_s1 [n]: this rank's rows filled
+            cnt = torch.zeros((2, n_test, n_doses), device=eng.device, dtype=torch.float64)
+            bst = torch.zeros((2, n_test), device=eng.device, dtype=torch.float64)
 
         def consume(s0, e0, x, out):
             res[0, s0:e0], res[1, s0:e0] = out["row_mean"], out["row_sd"]
+            if choice is not None:
+                cnt[0, s0:e0], bst[0, s0:e0], bst[1, s0:e0] = out["best_count"].double(), out["best_ref"].double(), out["best_s1"].double()
+                if choice[1] is not None:
+                    cnt[1, s0:e0] = out["above_count"].double()
             if contrasts:
                 res[nb, s0:e0], res[nb + 1, s0:e0] = out["contrast_mean"], out["contrast_sd"]
             if quantile:
@@ -794,10 +803,15 @@ class CausalBGM(object):
                 res[2, s0:e0], res[3, s0:e0] = lo.t().double(), hi.t().double()
         self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, row_effects=True, row_draws=quantile,
                             x_values=x_values, sample_y=sample_y, partial=partial, **(dict(row_tails=k_tail) if tails else {}),
-                            **(dict(row_contrasts=True) if contrasts else {}), **self._traj_kw(traj))
+                            **(dict(row_contrasts=True) if contrasts else {}),
+                            **(dict(row_choice=True, maximize=choice[0], threshold=choice[1]) if choice is not None else {}),
+                            **self._traj_kw(traj))
         res = parallel.all_reduce_sum_(res).cpu().numpy()
         mean, sd = res[0], res[1]
         contrast = (res[nb], res[nb + 1]) if contrasts else None
+        if choice is not None:
+            cnt, bst = parallel.all_reduce_sum_(cnt).cpu().numpy(), parallel.all_reduce_sum_(bst).cpu().numpy()
+            contrast = (cnt[0], bst[0], bst[1], cnt[1] if choice[1] is not None else None)
         if quantile or tails:
             bounds = np.stack([res[2], res[3]], axis=-1)
         else:
@@ -856,6 +870,63 @@ class CausalBGM(object):
         if groups is not None:
             self.group_dose_effect_ = hmc_mod.group_dose_response(effect, self.dose_effect_sd_, groups)
         return effect, bounds
+
+    dose_regret_ = None              # predict_best_dose: expected regret [n, n_doses] of giving dose k
+    dose_exceed_prob_ = None         # predict_best_dose(threshold=...): P(y_i(x_k) > threshold) [n, n_doses]; None otherwise
+    dose_choice_curve_ = None        # predict_best_dose: (mean, sd), each [n, n_doses], of y_i at x_values
+    group_dose_choice_ = None        # predict_best_dose(groups=...): {label: (share [n_doses], mean prob_best [n_doses])}; None otherwise
+
+    def predict_best_dose(self, data, x_values, maximize=True, threshold=None, n_mcmc=3000, burn_in=5000, sample_y=False, step_size=None,
+                          n_leapfrog=None, mass='identity', groups=None, partial=False, verbose=1):
+        """Which dose is best for every row under a continuous treatment, and how sure the posterior is of it: ``(choice [n],
+        prob_best [n, n_doses])``.  ``prob_best[i, k]`` is the share of the ``n_mcmc`` retained draws at which dose ``x_values[k]``
+        gave row i its best outcome -- the largest with ``maximize=True``, the smallest otherwise, the lowest dose index on ties --;
+        rows sum to 1.  ``choice[i]`` is the dose index with the best posterior mean (lowest index on ties): the Bayes choice under
+        a linear utility, and the argmin of the expected regret up to float32 rounding.  The reference has no counterpart; a binary
+        treatment has ``predict``'s ITE.  None of this follows from ``predict_individual``'s moments or tails or from
+        ``predict_dose_effect``'s contrasts against one baseline: the best dose changes from draw to draw, so the sampling kernel
+        compares the doses on every retained draw and keeps counts.  Nothing of size ``n_mcmc`` is stored and this rank's shard is
+        sampled in one piece.
+
+        ``self.dose_regret_`` [n, n_doses]: what is lost in expectation by giving dose k, ``E[best] - mean_k`` (``mean_k - E[best]``
+        when minimising), with ``E[best]`` the posterior mean of the per-draw best outcome.  It is not clipped: it may be negative by
+        float32 rounding only.  ``threshold`` (a finite scalar, optional): ``self.dose_exceed_prob_`` [n, n_doses] is the posterior
+        probability that the outcome at dose k exceeds it.  ``self.dose_choice_curve_ = (mean, sd)``: what ``predict_individual``
+        returns at ``x_values``, bit for bit.
+
+        ``sample_y=False`` IS THE DEFAULT HERE: a decision compares the conditional means of the doses.  With ``sample_y=True``
+        every dose carries its own INDEPENDENT predictive noise on the shared latent draw, as in ``predict_dose_effect``:
+        ``prob_best`` is then the probability that one future outcome at dose k beats independent future outcomes at the others.
+
+        The latents are sampled as in ``predict_individual`` (``step_size``, ``n_leapfrog``, ``mass`` and the seed sequence as
+        there; ``self.hmc_row_step_`` / ``self.hmc_row_mass_`` set as there).  ``groups`` (int labels [n], optional):
+        ``self.group_dose_choice_ = {label: (share of the group's rows choosing each dose, mean prob_best)}``
+        (causal_hmc.group_dose_choice).  ``partial=True``: NaN in ``data``'s y, or x and y, marks what a row does not observe, as
+        in ``predict_dose_effect`` -- new units; ``partial=True`` with ``mass='diag'`` on a model of more than 11 latent features is
+        refused (``ValueError``): that one kernel is not built.  The trajectory options are not taken: the choice kernels have no such
+        variant."""
+        hmc, x_values, threshold = self._sampling_options(
+            ("hmc_row_step_", "hmc_row_mass_", "hmc_row_leapfrog_", "dose_regret_", "dose_exceed_prob_", "dose_choice_curve_",
+             "group_dose_choice_"), None, (step_size, n_leapfrog, mass, burn_in),
+            lambda _: hmc_mod.check_best_dose(bool(self._p['binary_treatment']), x_values, threshold), 0.5, n_mcmc, x_values)
+        n_test = len(data[0])
+        if groups is not None:
+            hmc_mod.group_dose_choice(np.zeros(n_test, np.int64), np.zeros((n_test, 0)), groups)      # (the labels' checks, before a device is touched)
+        if partial and hmc[3] is not None:      # (the one combination whose kernel is not built)
+            hmc_mod.check_choice_kernel(sum(self._p['z_dims']), True, True)
+        if partial:
+            data = hmc_mod.check_partial_panel(*data)
+        maximize = bool(maximize)
+        (mean, sd), _, (count, ref, s1, above) = self._row_series(data, x_values.reshape(-1), 0.5, (burn_in, n_mcmc, hmc), sample_y, 'normal',
+                                                                  None, verbose, partial=bool(partial), choice=(maximize, threshold))
+        self.dose_choice_curve_ = (mean, sd)
+        prob_best, _, self.dose_regret_ = hmc_mod.choice_finalize(count, ref, s1, mean, n_mcmc, maximize)
+        if above is not None:
+            self.dose_exceed_prob_ = above / float(n_mcmc)
+        choice = np.argmax(mean if maximize else -mean, axis=1)
+        if groups is not None:
+            self.group_dose_choice_ = hmc_mod.group_dose_choice(choice, prob_best, groups)
+        return choice, prob_best
 
     def predict_new(self, data_v, data_x=None, x_values=None, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None,
                     n_leapfrog=None, mass='identity', interval='normal', draw_budget_bytes=None, verbose=1, max_trajectory=None,

@@ -281,6 +281,12 @@ class IdentifiableCausalBGM(CausalBGM):
         ``predict(sampler='hmc')``, word for word."""
         self._refuse_hmc('hmc', 1.0, False, step_size, n_leapfrog, mass)
 
+    def predict_best_dose(self, data, x_values=None, maximize=True, threshold=None, n_mcmc=3000, burn_in=5000, sample_y=False, step_size=None,
+                          n_leapfrog=None, mass='identity', groups=None, partial=False, verbose=1):
+        """CausalBGM.predict_best_dose always uses the HMC sampler, which this class does not have: the refusal of
+        ``predict(sampler='hmc')``, word for word."""
+        self._refuse_hmc('hmc', 1.0, False, step_size, n_leapfrog, mass)
+
     def predict_new(self, data_v, data_x=None, x_values=None, alpha=0.01, n_mcmc=3000, burn_in=5000, sample_y=True, step_size=None,
                     n_leapfrog=None, mass='identity', interval='normal', draw_budget_bytes=None, verbose=1):
         """CausalBGM.predict_new samples the latents of new units with the HMC sampler, which this class does not have."""

@@ -495,6 +495,38 @@ BGM_API int bgm_causal_hmc_run_row_contrasts(bgm_handle *h, const float *x_dev, 
                                              const float *x_values_dev, int32_t n_doses, float *row_moments_dev, float *row_cmoments_dev,
                                              float *contrast_draws_dev, float *contrast_tails_dev, int32_t k_tail, void *stream);
 
+/* bgm_causal_hmc_run_row_effects with the CHOICE among the doses kept beside the curve: per row, at how many retained draws every dose
+ * gave the best outcome, the shifted sum of that best outcome, and, optionally, at how many draws every dose exceeded a threshold.
+ * Moments, tails and contrasts against one baseline describe every dose alone or one pair; the best dose changes from draw to draw,
+ * so the doses are compared per retained draw inside the sampler.  The arguments of bgm_causal_hmc_run_row_effects, with
+ *   best_count_dev [n_doses x n] uint32 (required): best_count_dev[k * n + row] = the retained draws at which dose k was the row's
+ *     best -- the largest y (maximize != 0) or the smallest (maximize == 0), the LOWEST dose index on ties; NaN never wins.  A row's
+ *     counts sum to the retained draws so far unless a draw's values were all NaN;
+ *   best_moments_dev [2 x n] float32 (required): plane 0 = ref, the best y of retained draw 0, plane 1 = sum of (best - ref): the
+ *     posterior mean of the best outcome is ref + s1 / n_keep;
+ *   above_count_dev [n_doses x n] uint32 or NULL: the retained draws with y > threshold, the layout of best_count_dev; threshold is
+ *     used with it (and must be finite) and ignored without.
+ * All three are written by the iteration it == burn_in (zeros included) and are in / out across the calls of one run.  Chain, noise
+ * counters, row_moments_dev and row_draws_dev are those of bgm_causal_hmc_run_row_effects bit for bit, and the counts are those of
+ * row_draws_dev's values; bgm_causal_hmc_set_mass and bgm_causal_hmc_set_partial are honoured.  With sample_y every dose carries its
+ * own independent noise word (dose k: word k & 3 of Philox call k >> 2).  Every element has one owner lane for the whole run and no
+ * atomics are used, so a run cut at any iteration is bit-identical to one call.  While bgm_causal_hmc_set_trajectory has anything
+ * set the call answers BGM_E_UNSUPPORTED naming the option (the choice kernels have no such variant).  ONE combination is not built:
+ * bgm_causal_hmc_set_mass together with bgm_causal_hmc_set_partial on a model of more than 11 latent features (the KT1 = 2 shapes)
+ * answers BGM_E_UNSUPPORTED naming itself before anything is launched -- that kernel cannot be had without scratch memory at two waves
+ * per SIMD; run it without the metric, or fully observed.  Refusals otherwise: those of
+ * bgm_causal_hmc_run_row_effects in their order, then BGM_E_INVALID naming best_count_dev / best_moments_dev when NULL, and a
+ * non-finite threshold with above_count_dev.
+ * replaces: nothing in causalbgm/base.py; for a continuous treatment the reference has the panel's ADRF only (:671-763). */
+BGM_API int bgm_causal_hmc_run_row_choice(bgm_handle *h, const float *x_dev, const float *y_dev, const float *v_dev, int64_t n,
+                                          int64_t row_base, float *state_dev, float *logp_dev, float *grad_dev, float *step_dev,
+                                          const float *up_dev, const float *dn_dev, int32_t n_table, float s_min, float s_max,
+                                          int32_t init, int32_t it_begin, int32_t n_iters, int32_t burn_in, int32_t n_leapfrog,
+                                          uint64_t seed, uint32_t *acc_count_dev, float *draws_dev, int32_t n_keep, int32_t sample_y,
+                                          const float *x_values_dev, int32_t n_doses, float *row_moments_dev, float *row_draws_dev,
+                                          uint32_t *best_count_dev, float *best_moments_dev, uint32_t *above_count_dev, float threshold,
+                                          int32_t maximize, void *stream);
+
 /* The two linear-interpolated quantiles of bgm_row_mean_quantiles from the tails of every series: tails_dev [2 x k_tail x n_series]
  * float32 (the layout of bgm_causal_hmc_run_row_tails with n_series = n_doses * n, series k * n + row), tail 0 the k_tail smallest of
  * the series' m values and tail 1 the k_tail largest, in any order -> lo_dev, hi_dev [n_series].  With vi = q (m - 1) in double,
