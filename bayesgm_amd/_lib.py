@@ -101,6 +101,14 @@ class MhInfo(C.Structure):
                 ("flop_per_row_transition", C.c_double)]
 
 
+# What every bgm_causal_hmc_run* entry point takes first (include/bgm_hip.h; CausalEngine._hmc_args marshals it): the handle, x, y, v,
+# n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in, n_leapfrog, seed, acc_count,
+# draws, n_keep.  Each declaration below extends it with the entry point's own arguments and the stream.
+_HMC_SEGMENT = ([C.c_void_p] * 4 + [C.c_int64] * 2 + [C.c_void_p] * 6 + [C.c_int32, C.c_float, C.c_float] + [C.c_int32] * 5 +
+                [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32])
+# ... and the entry points with an effect pass next: sample_y, the dose grid (or the row labels) and its length
+_HMC_EFFECT_SEGMENT = _HMC_SEGMENT + [C.c_int32, C.c_void_p, C.c_int32]
+
 # every symbol include/bgm_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "bgm_last_error": (C.c_char_p, []),
@@ -207,37 +215,17 @@ SYMBOLS = {
     "bgm_causal_effects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_uint64,
                                      C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bgm_causal_logpost_grad": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bgm_causal_hmc_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32,
-                                     C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
-    "bgm_causal_hmc_run_effects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
-                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
-                                             C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bgm_causal_hmc_run_row_effects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
-                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
-                                                 C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bgm_causal_hmc_run_row_tails": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
-                                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
-                                               C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
-    "bgm_causal_hmc_run_row_contrasts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
-                                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
-                                                   C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                                   C.c_void_p]),
-    "bgm_causal_hmc_run_row_choice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
-                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
-                                                C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_float, C.c_int32, C.c_void_p]),
+    "bgm_causal_hmc_run": (C.c_int, _HMC_SEGMENT + [C.c_void_p]),
+    "bgm_causal_hmc_run_effects": (C.c_int, _HMC_EFFECT_SEGMENT + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bgm_causal_hmc_run_row_effects": (C.c_int, _HMC_EFFECT_SEGMENT + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bgm_causal_hmc_run_row_tails": (C.c_int, _HMC_EFFECT_SEGMENT + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "bgm_causal_hmc_run_row_contrasts": (C.c_int, _HMC_EFFECT_SEGMENT + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                                         C.c_void_p]),
+    "bgm_causal_hmc_run_row_choice": (C.c_int, _HMC_EFFECT_SEGMENT + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                                                      C.c_int32, C.c_void_p]),
     "bgm_row_tail_quantiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
-    "bgm_causal_hmc_run_group_effects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
-                                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
-                                                   C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bgm_causal_hmc_run_group_effects": (C.c_int, _HMC_EFFECT_SEGMENT + [C.c_void_p, C.c_void_p]),
     "bgm_ite_group_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "bgm_causal_hmc_set_mass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "bgm_causal_hmc_mass_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -13,6 +13,9 @@ at every change of the metric (``mass_schedule``).
 ``max_trajectory``, and with the jitter a number uniform on 1 .. that cap per transition (``resolve_trajectory``; the cap is
 row_adapt.leapfrog_cap; csrc/causal_hmc_traj_kernels.h).
 
+``RESULT_KINDS``: one record per kind of result the kernels keep (panel ADRF, ITE, label sums, per-row curve, tails, contrasts,
+choice) saying which combinations with the options are built; ``result_kind`` / ``check_result`` refuse the others from it.
+
 ``predict_individual``: the option checks, the row blocks of ``interval='quantile'`` and ``'tails'``, the size of a tail buffer
 (``tail_size``), the finalisation of the per-row moments and the subgroup formula (``group_dose_response``) are at the end of the module.
 
@@ -28,8 +31,11 @@ row_adapt.leapfrog_cap; csrc/causal_hmc_traj_kernels.h).
 ``predict_new`` / ``partial=True``: rows whose outcome, or outcome and treatment, are not observed carry NaN there; the checks of the
 pattern (``check_partial_rows``) and of predict_new's own options (``check_new``) close the module.
 """
+import collections
+
 import numpy as np
 
+from . import _lib
 from . import row_adapt as RA
 
 DEFAULT_TARGET = 0.75             # the target of the project's other HMC (tfp SimpleStepSizeAdaptation, bgm/base.py:709-830)
@@ -81,6 +87,84 @@ def resolve(model, params, step_size, n_leapfrog, target, adapt=True):
     return float(step_size), int(n_leapfrog), (float(target) if adapt else None)
 
 
+# ---- what exists with what: one record per kind of result the sampler computes inside its kernels -----------------------------------
+# A kind is what one family of kernels keeps per retained draw.  Its record says how engine.hmc_sample is asked for it (`request`,
+# and `option`, the words for that in a refusal), which engine method and kernels run it (`method`, `kernels`: the words of a
+# refusal again), and which combinations are built:
+#   treatment  "continuous" / "binary": the treatment type it is for; `wrong_treatment` is the refusal for the other one
+#   traj       it has twins with a trajectory length per chain (max_trajectory / jitter)
+#   obs        it has twins for partially observed rows (partial=True)
+#   draws      it can also store the series it summarises (row_draws=True)
+#   tails      it can also keep the two tails of that series (row_tails=K)
+#   hole       q or None: the one combination of a built family that is not built -- a metric together with partial=True at more
+#              than q latent features (check_choice_kernel)
+#   late       which of "treatment" / "obs" engine.hmc_sample does not refuse before a device is touched.  They are refused once it
+#              is: the other treatment type by the per-row route (ValueError, `wrong_treatment`) or by hmc_run (ValueError for the
+#              effect of the other type), the pattern by the library at the first launch (BGM_E_UNSUPPORTED)
+# Everything else that does not exist is a ValueError of check_result, before a device is touched.  The library refuses the same
+# combinations on its own (csrc/causal_hmc_fx_host.h and the entry points); a new kind is one record here, one in
+# CausalEngine._row_routes where it is a per-row kind, and its own checks.
+ResultKind = collections.namedtuple("ResultKind", "name request option method kernels treatment wrong_treatment traj obs draws tails hole late")
+_CONTINUOUS = "hmc_sample: %s is %s of a continuous treatment; a binary treatment has its per-row effect already (effect=EFFECT_ITE)"
+RESULT_KINDS = collections.OrderedDict((k.name, k) for k in (
+    ResultKind("adrf", dict(effect=_lib.EFFECT_ADRF), "effect=EFFECT_ADRF", "hmc_run", "the fused-effect kernels", "continuous", None,
+               traj=True, obs=False, draws=False, tails=False, hole=None, late=("treatment", "obs")),
+    ResultKind("ite", dict(effect=_lib.EFFECT_ITE), "effect=EFFECT_ITE", "hmc_run", "the fused-effect kernels", "binary", None,
+               traj=True, obs=True, draws=False, tails=False, hole=None, late=("treatment",)),
+    ResultKind("group_ite", dict(effect=_lib.EFFECT_GROUP_ITE), "effect=EFFECT_GROUP_ITE", "hmc_run_group_effects", "the label-sum kernels",
+               "binary", "hmc_sample: effect=EFFECT_GROUP_ITE sums the treatment effect of a binary treatment; a continuous treatment has "
+               "its dose-response (effect=EFFECT_ADRF)", traj=False, obs=False, draws=False, tails=False, hole=None, late=("obs",)),
+    ResultKind("rows", dict(row_effects=True), "row_effects", "hmc_run_rows_effects", "the per-row kernels", "continuous",
+               _CONTINUOUS % ("row_effects", "the dose-response"), traj=True, obs=True, draws=True, tails=True, hole=None, late=("treatment",)),
+    # (asked for as rows with row_tails=K; the tails of the contrasts belong to the contrasts)
+    ResultKind("tails", dict(row_effects=True), "row_tails", "hmc_run_rows_tails", "the tail-buffer kernels", "continuous",
+               _CONTINUOUS % ("row_effects", "the dose-response"), traj=False, obs=True, draws=True, tails=True, hole=None, late=("treatment",)),
+    ResultKind("contrasts", dict(row_effects=True, row_contrasts=True), "row_contrasts", "hmc_run_rows_contrasts", "the dose-contrast kernels",
+               "continuous", _CONTINUOUS % ("row_contrasts", "the contrast between two doses"), traj=False, obs=True, draws=True, tails=True,
+               hole=None, late=()),
+    ResultKind("choice", dict(row_effects=True, row_choice=True), "row_choice", "hmc_run_rows_choice", "the dose-choice kernels",
+               "continuous", _CONTINUOUS % ("row_choice", "the choice among the doses"), traj=False, obs=True, draws=True, tails=False,
+               hole=11, late=()),
+))
+NO_TRAJECTORY = "%s (%s) have no variant with a trajectory length per chain"
+
+
+def result_kind(effect, row_effects=False, row_tails=None, row_contrasts=False, row_choice=False):
+    """The record of RESULT_KINDS that engine.hmc_sample's options ask for (None: the chain alone); ValueError for an effect that
+    is none, and for a per-row option without row_effects or beside an effect."""
+    by_effect = {_lib.EFFECT_NONE: None, _lib.EFFECT_ADRF: "adrf", _lib.EFFECT_ITE: "ite", _lib.EFFECT_GROUP_ITE: "group_ite"}
+    if effect not in by_effect:
+        raise ValueError("hmc_sample: effect must be EFFECT_NONE, EFFECT_ADRF, EFFECT_ITE or EFFECT_GROUP_ITE; got %r" % (effect,))
+    if not row_effects:
+        for name, asked in (("row_choice", row_choice), ("row_contrasts", row_contrasts)):
+            if asked:
+                raise ValueError("hmc_sample: %s belongs to row_effects=True" % name)
+        return RESULT_KINDS.get(by_effect[effect])
+    if effect != _lib.EFFECT_NONE:
+        raise ValueError("hmc_sample: row_effects and effect exclude each other (the panel's ADRF is the mean of the rows' curves)")
+    return RESULT_KINDS["choice" if row_choice else "contrasts" if row_contrasts else "tails" if row_tails is not None else "rows"]
+
+
+def check_result(kind, binary, traj=False, row_draws=False, row_tails=None, row_contrasts=False):
+    """What engine.hmc_sample refuses of a result kind (result_kind) before a device is touched, read from its record: stored
+    series and tails where the kind takes none, a trajectory option without TRAJ twins, the other treatment type.  `binary` is a
+    callable, asked only where the record needs the answer.  ValueError with the record's words."""
+    per_row = kind is not None and kind.request.get("row_effects", False)
+    if row_draws and not (kind is not None and kind.draws):
+        raise ValueError("hmc_sample: row_draws belongs to row_effects=True")
+    if row_tails is not None and not per_row:
+        raise ValueError("hmc_sample: row_tails belongs to row_effects=True")
+    if (row_tails is not None and not kind.tails) or (row_contrasts and kind.name != "contrasts"):
+        raise ValueError("hmc_sample: %s is not available with row_contrasts or row_tails: %s (%s) have no variant with contrasts or "
+                         "tail buffers" % (kind.option, kind.kernels, kind.method))
+    # (the tails of another kind are kept by that kind's kernels, and none of those has what the tail-buffer kernels lack)
+    for k in ([RESULT_KINDS["tails"]] if per_row and row_tails is not None else []) + ([kind] if kind is not None else []):
+        if traj and not k.traj:
+            raise ValueError("hmc_sample: max_trajectory / jitter are not available with %s: " % k.option + NO_TRAJECTORY % (k.kernels, k.method))
+    if kind is not None and "treatment" not in kind.late and binary() != (kind.treatment == "binary"):
+        raise ValueError(kind.wrong_treatment)
+
+
 def resolve_trajectory(max_trajectory=None, jitter=False):
     """The trajectory options of the HMC sampler (``max_trajectory`` / ``jitter_leapfrog``; bgm_causal_hmc_set_trajectory) ->
     (max_trajectory as a float, 0.0 = no cap; jitter as 0 / 1).  ``max_trajectory`` is None or a finite number > 0, ``jitter`` a
@@ -97,9 +181,10 @@ def check_trajectory(max_trajectory, jitter, hmc=True, interval=None):
     if T > 0.0 or jit:
         if not hmc:
             raise ValueError("max_trajectory / jitter_leapfrog belong to sampler='hmc': the MH sampler has no trajectory (sampler='mh')")
-        if interval == "tails":
-            raise ValueError("max_trajectory / jitter_leapfrog are not available with interval='tails': the tail-buffer kernels have no "
-                             "variant with a trajectory length per chain; use interval='quantile' or 'normal'")
+        kind = RESULT_KINDS["tails" if interval == "tails" else "rows"]
+        if not kind.traj:
+            raise ValueError("max_trajectory / jitter_leapfrog are not available with interval='%s': %s have no variant with a "
+                             "trajectory length per chain; use interval='quantile' or 'normal'" % (interval, kind.kernels))
     return T, jit
 
 
@@ -376,12 +461,14 @@ def check_best_dose(binary, x_values, threshold):
 
 
 def check_choice_kernel(q, metric, partial):
-    """The one combination the dose-choice kernels are not built for (csrc/causal_hmc_choice_api.hip): a metric together with
-    partially observed rows at more than 11 latent features, where that instantiation would need scratch memory.  ValueError."""
-    if metric and partial and int(q) + 1 > 12:
+    """The one combination the dose-choice kernels are not built for (csrc/causal_hmc_choice_api.hip; RESULT_KINDS["choice"].hole): a
+    metric together with partially observed rows at more than 11 latent features, where that instantiation would need scratch
+    memory.  ValueError."""
+    hole = RESULT_KINDS["choice"].hole
+    if metric and partial and int(q) > hole:
         raise ValueError("the dose choice is not available with a metric (mass='diag' / mass_scale) together with partial=True at more "
-                         "than 11 latent features (here %d): that kernel cannot be had without scratch memory and is not built; use "
-                         "mass='identity', or fully observed rows" % int(q))
+                         "than %d latent features (here %d): that kernel cannot be had without scratch memory and is not built; use "
+                         "mass='identity', or fully observed rows" % (hole, int(q)))
 
 
 def choice_finalize(best_count, best_ref, best_s1, mean, n_keep, maximize=True):

@@ -158,10 +158,8 @@ extern "C" int bgm_causal_hmc_run(bgm_handle *h, const float *x, const float *y,
                                   uint64_t seed, uint32_t *acc_count, float *draws, int32_t n_keep, void *stream_) {
   if (int rc = bgm_causal_hmc_check(h, "bgm_causal_hmc_run")) return rc;
   if (n <= 0 || n_iters <= 0) return BGM_OK;
-  const CausalHmcCall call{x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in,
-                           n_leapfrog, seed, acc_count, draws, n_keep, (hipStream_t)stream_};
   CausalHmcLaunch l{};
-  if (int rc = bgm_causal_hmc_args(h, "bgm_causal_hmc_run", call, l)) return rc;
+  if (int rc = bgm_causal_hmc_args(h, "bgm_causal_hmc_run", BGM_CAUSAL_HMC_CALL, l)) return rc;
   if (l.st->traj_set()) return bgm_causal_hmc_traj_launch(h, l);      // bgm_causal_hmc_set_trajectory
   if (h->hmc_partial) return bgm_causal_hmc_obs_launch(h, l);      // bgm_causal_hmc_set_partial
   if (l.st->mass.scale) return bgm_causal_hmc_mass_launch(h, l);      // bgm_causal_hmc_set_mass

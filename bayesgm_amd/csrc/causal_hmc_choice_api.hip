@@ -2,8 +2,9 @@
 // the doses kept beside the curve -- per row, how often every dose was the best of a retained draw, the best value's shifted sum and,
 // optionally, how often every dose exceeded a threshold (causal_hmc_choice_kernels.h: the CHOICE instantiations of chmc_run, with and
 // without the metric and the observation pattern; ONE of the eight combinations per shape is not built and is refused, see launch), in
-// a translation unit of its own, compiled beside those of the other HMC entry
-// points.
+// a translation unit of its own, compiled beside those of the other HMC entry points.
+// Prologue, preparation and the launch of a kernel with its metric twin are those of every entry point with an effect pass
+// (causal_hmc_fx_host.h, causal_hmc_host.h); what is this unit's own is its argument checks and the kernels it names.
 // replaces: nothing in causalbgm/base.py; the reference has no per-row quantity for a continuous treatment.
 #include <cmath>
 #include <string>
@@ -17,23 +18,22 @@ const char *WHO = "bgm_causal_hmc_run_row_choice";
 
 template <bool OBS>
 int launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx, const CausalHmcChoiceArgs &rc) {
-  std::string what = "HMC kernel with per-row dose choice";
-  if (OBS) what += " for partially observed rows";
-  return bgm_causal_hmc_dispatch(h, l.st, what, [&](auto s, auto metric) {
-    using S = decltype(s);
-    // Not shipped: the metric with the observation pattern at KT1 = 2.  hipcc gives that instantiation 256 VGPRs and 12 bytes of
-    // scratch, whatever the choice block looks like; the other seven have none.
-    if constexpr (decltype(metric)::value && OBS && S::KT1 == 2) {
-      bgm_set_error(std::string(WHO) + ": no " + what + ", with a diagonal metric, at more than 11 latent features (KT1 = 2): it cannot be "
-                    "had without scratch memory at two waves per SIMD; run it without the metric, or use "
-                    "bgm_causal_hmc_run_row_effects with row_draws_dev");
-      return (int)BGM_E_UNSUPPORTED;
-    } else if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_mass_choice_kernel<S::KT1, S::KSL1, MH_WAVES, OBS>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx,
-                        rc);
-    else
-      return bgm_launch(causal_hmc_choice_kernel<S::KT1, S::KSL1, MH_WAVES, OBS>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx, rc);
-  });
+  const std::string what = bgm_causal_hmc_obs_named(OBS, "HMC kernel with per-row dose choice");
+  return bgm_causal_hmc_launch_pair(
+      h, l, what, [](auto s) { using S = decltype(s); return causal_hmc_choice_kernel<S::KT1, S::KSL1, MH_WAVES, OBS>; },
+      [&](auto s) {
+        using S = decltype(s);
+        // Not shipped: the metric with the observation pattern at KT1 = 2.  hipcc gives that instantiation 256 VGPRs and 12 bytes of
+        // scratch, whatever the choice block looks like; the other seven have none.
+        if constexpr (OBS && S::KT1 == 2) {
+          bgm_set_error(std::string(WHO) + ": no " + what + ", with a diagonal metric, at more than 11 latent features (KT1 = 2): it cannot be "
+                        "had without scratch memory at two waves per SIMD; run it without the metric, or use "
+                        "bgm_causal_hmc_run_row_effects with row_draws_dev");
+          return (int)BGM_E_UNSUPPORTED;
+        } else {
+          return causal_hmc_mass_choice_kernel<S::KT1, S::KSL1, MH_WAVES, OBS>;
+        }
+      }, fx, rc);
 }
 }  // namespace
 
@@ -44,28 +44,19 @@ extern "C" int bgm_causal_hmc_run_row_choice(bgm_handle *h, const float *x, cons
                                              int32_t n_keep, int32_t sample_y, const float *x_values, int32_t n_doses, float *row_moments,
                                              float *row_draws, uint32_t *best_count, float *best_moments, uint32_t *above_count,
                                              float threshold, int32_t maximize, void *stream_) {
-  if (int rc = bgm_causal_hmc_check(h, WHO)) return rc;
-  if (n <= 0 || n_iters <= 0) return BGM_OK;
-  if (int rc = bgm_causal_hmc_traj_refuse(h, WHO, "the dose-choice kernels")) return rc;
+  bool go;
+  if (int rc = bgm_causal_hmc_rows_begin(h, WHO, n, n_iters, "the dose-choice kernels", x_values, n_doses, row_moments, go); rc || !go) return rc;
   const std::string who(WHO);
-  if (h->cfg.binary_treatment != 0) {
-    bgm_set_error(who + ": a binary treatment has its per-row effect already: bgm_causal_hmc_run_effects (BGM_EFFECT_ITE)");
-    return BGM_E_INVALID;
-  }
-  if (!x_values || n_doses <= 0 || !row_moments) { bgm_set_error(who + ": x_values / row_moments required"); return BGM_E_INVALID; }
   if (!best_count) { bgm_set_error(who + ": best_count_dev required"); return BGM_E_INVALID; }
   if (!best_moments) { bgm_set_error(who + ": best_moments_dev required"); return BGM_E_INVALID; }
   if (above_count && !std::isfinite(threshold)) {
     bgm_set_error(who + ": threshold must be finite when above_count_dev is given");
     return BGM_E_INVALID;
   }
-  const CausalHmcCall call{x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in,
-                           n_leapfrog, seed, acc_count, draws, n_keep, (hipStream_t)stream_};
   CausalHmcLaunch l{};
   CausalHmcFxArgs fx{};
-  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, call, l, fx)) return rc;
-  fx.sample_y = sample_y; fx.n_doses = n_doses; fx.x_values = x_values;
+  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, BGM_CAUSAL_HMC_CALL, sample_y, n_doses, x_values, l, fx)) return rc;
   const CausalHmcChoiceArgs rc{row_moments, row_draws, CausalChoiceArgs{best_count, best_moments, above_count, maximize ? 1.0f : -1.0f,
                                                                          above_count ? threshold : 0.0f}};
-  return h->hmc_partial ? launch<true>(h, l, fx, rc) : launch<false>(h, l, fx, rc);      // bgm_causal_hmc_set_partial
+  return bgm_causal_hmc_with_pattern(h, [&](auto obs) { return launch<decltype(obs)::value>(h, l, fx, rc); });
 }

@@ -1,6 +1,8 @@
 // causal_hmc_fx_api.hip -- bgm_causal_hmc_run_effects (include/bgm_hip.h): the CausalBGM HMC latent sampler with the effect pass
 // fused into the retained iterations (the EFFECT 1 / 2 instantiations of chmc_run, causal_hmc_fx_kernels.h), in a translation unit
 // of its own, compiled beside the others: bgm_causal_hmc_run (causal_hmc_api.hip, causal_hmc_mass_api.hip) never comes here.
+// Prologue, preparation and the launch of a kernel with its metric twin are those of every entry point with an effect pass
+// (causal_hmc_fx_host.h, causal_hmc_host.h); what is this unit's own is its argument checks and the kernels it names.
 // replaces: nothing in causalbgm/base.py; infer_from_latent_posterior (:671-763) runs there on stored MH draws.
 #include <string>
 
@@ -14,13 +16,9 @@ const char *WHO = "bgm_causal_hmc_run_effects";
 
 template <int EFFECT>
 int launch_fx(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx) {
-  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with fused effects", [&](auto s, auto metric) {
-    using S = decltype(s);
-    if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_mass_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx);
-    else
-      return bgm_launch(causal_hmc_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx);
-  });
+  return bgm_causal_hmc_launch_pair(
+      h, l, "HMC kernel with fused effects", [](auto s) { using S = decltype(s); return causal_hmc_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>; },
+      [](auto s) { using S = decltype(s); return causal_hmc_mass_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT>; }, fx);
 }
 
 }  // namespace
@@ -31,8 +29,8 @@ extern "C" int bgm_causal_hmc_run_effects(bgm_handle *h, const float *x, const f
                                           int32_t burn_in, int32_t n_leapfrog, uint64_t seed, uint32_t *acc_count, float *draws,
                                           int32_t n_keep, int32_t sample_y, const float *x_values, int32_t n_doses, float *adrf_partial,
                                           float *ite, void *stream_) {
-  if (int rc = bgm_causal_hmc_check(h, WHO)) return rc;
-  if (n <= 0 || n_iters <= 0) return BGM_OK;
+  bool go;
+  if (int rc = bgm_causal_hmc_begin(h, WHO, n, n_iters, nullptr, go); rc || !go) return rc;
   const std::string who(WHO);
   const bool binary = h->cfg.binary_treatment != 0;
   if (h->hmc_partial && !binary) {
@@ -42,13 +40,10 @@ extern "C" int bgm_causal_hmc_run_effects(bgm_handle *h, const float *x, const f
   }
   if (binary && !ite) { bgm_set_error(who + ": ite_dev required for binary treatment"); return BGM_E_INVALID; }
   if (!binary && (!x_values || n_doses <= 0 || !adrf_partial)) { bgm_set_error(who + ": x_values / adrf_partial required"); return BGM_E_INVALID; }
-  const CausalHmcCall call{x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in,
-                           n_leapfrog, seed, acc_count, draws, n_keep, (hipStream_t)stream_};
   CausalHmcLaunch l{};
   CausalHmcFxArgs fx{};
-  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, call, l, fx)) return rc;
-  fx.sample_y = sample_y; fx.n_doses = binary ? 2 : n_doses;
-  fx.x_values = x_values; fx.adrf_partial = adrf_partial; fx.ite = ite;
+  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, BGM_CAUSAL_HMC_CALL, sample_y, binary ? 2 : n_doses, x_values, l, fx)) return rc;
+  fx.adrf_partial = adrf_partial; fx.ite = ite;
   if (l.st->traj_set()) return bgm_causal_hmc_traj_fx_launch(h, l, fx, binary);      // bgm_causal_hmc_set_trajectory
   if (h->hmc_partial) return bgm_causal_hmc_obs_ite_launch(h, l, fx);      // (binary: checked above)
   return binary ? launch_fx<2>(h, l, fx) : launch_fx<1>(h, l, fx);

@@ -2,6 +2,8 @@
 // sampler with the individual treatment effect summed by row label inside the retained iterations, and the same sums from a stored
 // ITE matrix (causal_hmc_gfx_kernels.h: the EFFECT 4 instantiations of chmc_run), in a translation unit of its own, compiled beside
 // those of the other HMC entry points.
+// Prologue, preparation and the launch of a kernel with its metric twin are those of every entry point with an effect pass
+// (causal_hmc_fx_host.h, causal_hmc_host.h); what is this unit's own is its argument checks and the kernels it names.
 // replaces: nothing in causalbgm/base.py; infer_from_latent_posterior (:671-763) returns the ITE of every row and draw.
 #include <string>
 
@@ -20,9 +22,8 @@ extern "C" int bgm_causal_hmc_run_group_effects(bgm_handle *h, const float *x, c
                                                 int32_t burn_in, int32_t n_leapfrog, uint64_t seed, uint32_t *acc_count, float *draws,
                                                 int32_t n_keep, int32_t sample_y, const int32_t *labels, int32_t n_labels,
                                                 float *group_partial, void *stream_) {
-  if (int rc = bgm_causal_hmc_check(h, WHO)) return rc;
-  if (n <= 0 || n_iters <= 0) return BGM_OK;
-  if (int rc = bgm_causal_hmc_traj_refuse(h, WHO, "the label-sum kernels")) return rc;
+  bool go;
+  if (int rc = bgm_causal_hmc_begin(h, WHO, n, n_iters, "the label-sum kernels", go); rc || !go) return rc;
   const std::string who(WHO);
   if (h->hmc_partial) {
     bgm_set_error(who + ": the label sums have no kernel for partially observed rows (bgm_causal_hmc_set_partial); the treatment "
@@ -39,21 +40,15 @@ extern "C" int bgm_causal_hmc_run_group_effects(bgm_handle *h, const float *x, c
     return BGM_E_INVALID;
   }
   if (!labels || !group_partial) { bgm_set_error(who + ": labels / group_partial required"); return BGM_E_INVALID; }
-  const CausalHmcCall call{x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in,
-                           n_leapfrog, seed, acc_count, draws, n_keep, (hipStream_t)stream_};
   CausalHmcLaunch l{};
   CausalHmcFxArgs fx{};
-  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, call, l, fx)) return rc;
-  fx.sample_y = sample_y; fx.n_doses = n_labels;      // (the slot's stride: [n_keep][n_labels])
+  if (int rc = bgm_causal_hmc_fx_prepare(h, WHO, BGM_CAUSAL_HMC_CALL, sample_y, n_labels /* the slot's stride: [n_keep][n_labels] */, nullptr, l, fx))
+    return rc;
   fx.adrf_partial = group_partial;
   fx.ite = reinterpret_cast<float *>(const_cast<int32_t *>(labels));      // (read only, as int: chmc_run, EFFECT 4)
-  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with label sums of the treatment effect", [&](auto s, auto metric) {
-    using S = decltype(s);
-    if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_mass_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx);
-    else
-      return bgm_launch(causal_hmc_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx);
-  });
+  return bgm_causal_hmc_launch_pair(
+      h, l, "HMC kernel with label sums of the treatment effect", [](auto s) { using S = decltype(s); return causal_hmc_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>; },
+      [](auto s) { using S = decltype(s); return causal_hmc_mass_gfx_kernel<S::KT1, S::KSL1, MH_WAVES>; }, fx);
 }
 
 extern "C" int bgm_ite_group_sums(bgm_handle *h, const float *ite, const int32_t *labels, int64_t n, int32_t n_keep, int32_t n_labels,

@@ -1,5 +1,6 @@
-// causal_hmc_host.h -- host state of the CausalBGM HMC latent sampler, shared by causal_hmc_api.hip (identity mass) and
-// causal_hmc_mass_api.hip (the diagonal metric per chain).  Host only.
+// causal_hmc_host.h -- host state of the CausalBGM HMC latent sampler, shared by every causal_hmc_*_api.hip: the handle's HmcState, the
+// call and launch records of a segment, and the launch of a kernel with its metric twin by shape, metric and observation pattern
+// (bgm_causal_hmc_launch_pair).  Host only.
 #pragma once
 #include "causal_launch.h"
 #include "causal_hmc_fx_kernels.h"
@@ -59,6 +60,14 @@ struct CausalHmcCall {
   int32_t n_keep;
   hipStream_t stream;
 };
+// The call record of an extern "C" entry point, from its parameters under the names every bgm_causal_hmc_run* definition gives them
+// (those of include/bgm_hip.h without the _dev suffix, and stream_): the parameter lists are the ABI and stay spelled out, the
+// bodies name the 24 once, here.
+#define BGM_CAUSAL_HMC_CALL                                                                                                              \
+  CausalHmcCall {                                                                                                                        \
+    x, y, v, n, row_base, state, logp, grad, step, up, dn, n_table, s_min, s_max, init, it_begin, n_iters, burn_in, n_leapfrog, seed,     \
+        acc_count, draws, n_keep, (hipStream_t)stream_                                                                                    \
+  }
 
 // What preparation makes of a call: the kernel arguments of one launch, the handle's HMC state (blob, meta, metric), the grid and
 // the dynamic LDS bytes (the HMC blob; with f's part of the sampling blob behind it after bgm_causal_hmc_fx_prepare)
@@ -81,4 +90,42 @@ template <class F>
 static int bgm_causal_hmc_dispatch(const bgm_handle *h, const HmcState *st, const std::string &what, F &&f) {
   if (st->mass.scale) return bgm_causal_dispatch(h, (what + ", with a diagonal metric").c_str(), [&](auto s) { return f(s, std::true_type{}); });
   return bgm_causal_dispatch(h, what.c_str(), [&](auto s) { return f(s, std::false_type{}); });
+}
+
+// f(std::bool_constant<OBS>) by the handle's observation pattern (bgm_causal_hmc_set_partial): the one place that turns
+// bgm_handle::hmc_partial into the kernels' OBS template argument, with the words a kernel's name gets for it in an error
+template <class F>
+static int bgm_causal_hmc_with_pattern(const bgm_handle *h, F &&f) {
+  return h->hmc_partial ? f(std::true_type{}) : f(std::false_type{});
+}
+static inline std::string bgm_causal_hmc_obs_named(bool obs, const std::string &what) {
+  return obs ? what + " for partially observed rows" : what;
+}
+
+// launch(kernel) for the kernel that `pick` names for the shape tag S: pick(S{}), or pick(S{}, obs) by the handle's observation
+// pattern where the lambda takes the tag (a family whose OBS twins live in the same unit).  A pick that returns an int instead of
+// a kernel has refused that combination at its site (error set, code returned as it is): nothing is launched and no kernel is
+// instantiated for it.
+template <class Pick, class S, class L>
+static int bgm_causal_hmc_picked(const bgm_handle *h, Pick &pick, S s, L &&launch) {
+  auto go = [&](auto kernel) {
+    if constexpr (std::is_same_v<decltype(kernel), int>) return kernel;
+    else return launch(kernel);
+  };
+  if constexpr (std::is_invocable_v<Pick &, S>) return go(pick(s));
+  else return bgm_causal_hmc_with_pattern(h, [&](auto obs) { return go(pick(s, obs)); });
+}
+
+// The launch of a kernel and its twin with the metric, at every site that has both in one translation unit: plain and mass name
+// the two instantiations (generic lambdas, bgm_causal_hmc_picked; the unit that writes them is the unit that instantiates them),
+// `extra` are the kernel arguments behind l.ka, and the twin takes l.st->mass between the two.  `what` names the kernel in errors.
+template <class Plain, class Mass, class... A>
+static int bgm_causal_hmc_launch_pair(const bgm_handle *h, const CausalHmcLaunch &l, const std::string &what, Plain plain, Mass mass,
+                                      const A &...extra) {
+  return bgm_causal_hmc_dispatch(h, l.st, what, [&](auto s, auto metric) {
+    if constexpr (decltype(metric)::value)
+      return bgm_causal_hmc_picked(h, mass, s, [&](auto k) { return bgm_launch(k, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, extra...); });
+    else
+      return bgm_causal_hmc_picked(h, plain, s, [&](auto k) { return bgm_launch(k, l.grid, MH_WAVES, l.lds, l.stream, l.ka, extra...); });
+  });
 }

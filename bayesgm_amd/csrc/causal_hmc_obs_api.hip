@@ -2,6 +2,7 @@
 // partially observed rows (causal_hmc_obs_kernels.h: the OBS instantiations of chmc_logpost_run and chmc_run), in a translation
 // unit of their own, compiled beside those of the other HMC entry points: bgm_causal_logpost_grad, bgm_causal_hmc_run,
 // bgm_causal_hmc_run_effects and bgm_causal_hmc_run_row_effects come here only while the option is on.
+// Each launch is bgm_causal_hmc_launch_pair (causal_hmc_host.h) with the two kernels of this unit that it names.
 // replaces: nothing in causalbgm/base.py; the reference's predict needs the outcome of every row.
 #include <string>
 
@@ -27,31 +28,21 @@ int bgm_causal_hmc_obs_logpost(bgm_handle *h, const HmcState *st, const float *x
 }
 
 int bgm_causal_hmc_obs_launch(bgm_handle *h, const CausalHmcLaunch &l) {
-  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel for partially observed rows", [&](auto s, auto metric) {
-    using S = decltype(s);
-    if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_obs_mass_kernel<S::KT1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass);
-    else
-      return bgm_launch(causal_hmc_obs_kernel<S::KT1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka);
-  });
+  return bgm_causal_hmc_launch_pair(h, l, "HMC kernel for partially observed rows",
+                                    [](auto s) { return causal_hmc_obs_kernel<decltype(s)::KT1, MH_WAVES>; },
+                                    [](auto s) { return causal_hmc_obs_mass_kernel<decltype(s)::KT1, MH_WAVES>; });
 }
 
 int bgm_causal_hmc_obs_ite_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx) {
-  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with fused effects for partially observed rows", [&](auto s, auto metric) {
-    using S = decltype(s);
-    if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_obs_mass_ite_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx);
-    else
-      return bgm_launch(causal_hmc_obs_ite_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx);
-  });
+  return bgm_causal_hmc_launch_pair(
+      h, l, "HMC kernel with fused effects for partially observed rows",
+      [](auto s) { using S = decltype(s); return causal_hmc_obs_ite_kernel<S::KT1, S::KSL1, MH_WAVES>; },
+      [](auto s) { using S = decltype(s); return causal_hmc_obs_mass_ite_kernel<S::KT1, S::KSL1, MH_WAVES>; }, fx);
 }
 
 int bgm_causal_hmc_obs_rowfx_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx, const CausalHmcRowFxArgs &rf) {
-  return bgm_causal_hmc_dispatch(h, l.st, "HMC kernel with per-row effects for partially observed rows", [&](auto s, auto metric) {
-    using S = decltype(s);
-    if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_obs_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, fx, rf);
-    else
-      return bgm_launch(causal_hmc_obs_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx, rf);
-  });
+  return bgm_causal_hmc_launch_pair(
+      h, l, "HMC kernel with per-row effects for partially observed rows",
+      [](auto s) { using S = decltype(s); return causal_hmc_obs_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>; },
+      [](auto s) { using S = decltype(s); return causal_hmc_obs_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES>; }, fx, rf);
 }

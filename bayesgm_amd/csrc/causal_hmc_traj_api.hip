@@ -2,6 +2,8 @@
 // number of leapfrog steps per chain and iteration (causal_hmc_traj_kernels.h: the TRAJ instantiations of chmc_run), in a translation
 // unit of their own, compiled beside those of the other HMC entry points: bgm_causal_hmc_run, bgm_causal_hmc_run_effects and
 // bgm_causal_hmc_run_row_effects come here only while an option is set, after their own argument checks.
+// Each launch is bgm_causal_hmc_launch_pair (causal_hmc_host.h) with the two kernels of this unit that it names; those that take
+// the observation pattern's tag have their OBS twins here too and are chosen by the handle's pattern inside it.
 // replaces: nothing in causalbgm/base.py; the options are max_trajectory / jitter_leapfrog of the BGM imputation sampler here.
 #include <cmath>
 #include <string>
@@ -40,29 +42,16 @@ int bgm_causal_hmc_traj_refuse(const bgm_handle *h, const char *who, const char 
 namespace {
 
 std::string named(const bgm_handle *h, const char *what) {
-  return std::string(what) + " with a trajectory length per chain" + (h->hmc_partial ? " for partially observed rows" : "");
-}
-
-// f(std::bool_constant<OBS>) by the handle's observation pattern (bgm_causal_hmc_set_partial)
-template <class F>
-int with_pattern(const bgm_handle *h, F &&f) {
-  return h->hmc_partial ? f(std::true_type{}) : f(std::false_type{});
+  return bgm_causal_hmc_obs_named(h->hmc_partial, std::string(what) + " with a trajectory length per chain");
 }
 
 }  // namespace
 
 int bgm_causal_hmc_traj_launch(bgm_handle *h, const CausalHmcLaunch &l) {
   const CausalHmcTrajArgs &tj = l.st->traj;
-  return bgm_causal_hmc_dispatch(h, l.st, named(h, "HMC kernel"), [&](auto s, auto metric) {
-    using S = decltype(s);
-    return with_pattern(h, [&](auto obs) {
-      constexpr bool OBS = decltype(obs)::value;
-      if constexpr (decltype(metric)::value)
-        return bgm_launch(causal_hmc_traj_mass_kernel<S::KT1, MH_WAVES, OBS>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, l.st->mass, tj);
-      else
-        return bgm_launch(causal_hmc_traj_kernel<S::KT1, MH_WAVES, OBS>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, tj);
-    });
-  });
+  return bgm_causal_hmc_launch_pair(
+      h, l, named(h, "HMC kernel"), [](auto s, auto obs) { return causal_hmc_traj_kernel<decltype(s)::KT1, MH_WAVES, decltype(obs)::value>; },
+      [](auto s, auto obs) { return causal_hmc_traj_mass_kernel<decltype(s)::KT1, MH_WAVES, decltype(obs)::value>; }, tj);
 }
 
 namespace {
@@ -70,14 +59,10 @@ namespace {
 template <int EFFECT, bool OBS>
 int launch_fx(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx) {
   const CausalHmcTrajArgs &tj = l.st->traj;
-  return bgm_causal_hmc_dispatch(h, l.st, named(h, "HMC kernel with fused effects"), [&](auto s, auto metric) {
-    using S = decltype(s);
-    if constexpr (decltype(metric)::value)
-      return bgm_launch(causal_hmc_traj_mass_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT, OBS>, l.grid, MH_WAVES, l.lds, l.stream, l.ka,
-                        l.st->mass, fx, tj);
-    else
-      return bgm_launch(causal_hmc_traj_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT, OBS>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx, tj);
-  });
+  return bgm_causal_hmc_launch_pair(
+      h, l, named(h, "HMC kernel with fused effects"),
+      [](auto s) { using S = decltype(s); return causal_hmc_traj_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT, OBS>; },
+      [](auto s) { using S = decltype(s); return causal_hmc_traj_mass_fx_kernel<S::KT1, S::KSL1, MH_WAVES, EFFECT, OBS>; }, fx, tj);
 }
 
 }  // namespace
@@ -85,20 +70,14 @@ int launch_fx(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx
 // (the panel's dose-response with the observation pattern was refused by the entry point: it has no OBS kernel at all)
 int bgm_causal_hmc_traj_fx_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx, bool binary) {
   if (!binary) return launch_fx<1, false>(h, l, fx);
-  return h->hmc_partial ? launch_fx<2, true>(h, l, fx) : launch_fx<2, false>(h, l, fx);
+  return bgm_causal_hmc_with_pattern(h, [&](auto obs) { return launch_fx<2, decltype(obs)::value>(h, l, fx); });
 }
 
 int bgm_causal_hmc_traj_rowfx_launch(bgm_handle *h, const CausalHmcLaunch &l, const CausalHmcFxArgs &fx, const CausalHmcRowFxArgs &rf) {
   const CausalHmcTrajArgs &tj = l.st->traj;
-  return bgm_causal_hmc_dispatch(h, l.st, named(h, "HMC kernel with per-row effects"), [&](auto s, auto metric) {
-    using S = decltype(s);
-    return with_pattern(h, [&](auto obs) {
-      constexpr bool OBS = decltype(obs)::value;
-      if constexpr (decltype(metric)::value)
-        return bgm_launch(causal_hmc_traj_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES, OBS>, l.grid, MH_WAVES, l.lds, l.stream, l.ka,
-                          l.st->mass, fx, rf, tj);
-      else
-        return bgm_launch(causal_hmc_traj_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES, OBS>, l.grid, MH_WAVES, l.lds, l.stream, l.ka, fx, rf, tj);
-    });
-  });
+  return bgm_causal_hmc_launch_pair(
+      h, l, named(h, "HMC kernel with per-row effects"),
+      [](auto s, auto obs) { using S = decltype(s); return causal_hmc_traj_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES, decltype(obs)::value>; },
+      [](auto s, auto obs) { using S = decltype(s); return causal_hmc_traj_mass_rowfx_kernel<S::KT1, S::KSL1, MH_WAVES, decltype(obs)::value>; },
+      fx, rf, tj);
 }

@@ -4,8 +4,11 @@ PyTorch supplies device memory and the HIP stream only; all arithmetic of the
 hot path runs in libbgm_hip.so.  There is no CPU fallback: constructing an
 engine without a gfx950 GPU or without the built library raises.
 """
+import collections
 import contextlib
 import ctypes as C
+import functools
+import inspect
 
 import numpy as np
 import torch
@@ -46,6 +49,51 @@ def _row_tail_quantiles(eng, tails, m, q_lo, q_hi):
     _lib.check(eng.lib.bgm_row_tail_quantiles(eng.h, _ptr(tails), n_series, k_tail, int(m), float(q_lo), float(q_hi), _ptr(lo), _ptr(hi),
                                               eng._stream()), "bgm_row_tail_quantiles")
     return lo, hi
+
+
+def _check_buffer(who, name, t, dtype, shape, shown):
+    """An output buffer of a segment: None, or a contiguous tensor of `dtype` whose shape is `shape` (None: any size there);
+    ValueError naming the buffer, with `shown` for the expected shape, otherwise."""
+    if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.dim() != len(shape)
+                          or any(want is not None and have != want for have, want in zip(t.shape, shape))):
+        raise ValueError("%s: %s must be a contiguous %s tensor %s; got %s %r" %
+                         (who, name, str(dtype).replace("torch.", ""), shown, t.dtype, tuple(t.shape)))
+
+
+def _doses(sample_y, x_values):
+    """(sample_y, x_values, n_doses) of an entry point with an effect pass, marshalled for ctypes"""
+    return int(bool(sample_y)), _ptr(x_values), 0 if x_values is None else int(x_values.numel())
+
+
+# The parameters every segment of the HMC sampler takes -- CausalEngine.hmc_run and the per-row family hmc_run_rows_* --, with their
+# defaults and in the order of the C ABI's common prefix (CausalEngine._hmc_args), written once.
+_P = inspect.Parameter
+SEGMENT_PARAMS = ([_P(name, _P.POSITIONAL_OR_KEYWORD) for name in ("x", "y", "v", "state", "logp", "grad", "step", "it_begin", "n_iters",
+                                                                   "burn_in", "n_leapfrog", "seed")] +
+                  [_P(name, _P.POSITIONAL_OR_KEYWORD, default=default) for name, default in
+                   (("init", False), ("row_base", 0), ("up", None), ("dn", None), ("s_min", RA.S_MIN), ("s_max", RA.S_MAX), ("acc_count", None),
+                    ("draws", None), ("n_keep", 0))])
+
+
+def _segment_method(fn):
+    """fn(self, seg, <the method's own parameters, with defaults>) -> the public method (self, <SEGMENT_PARAMS>, <its own>,
+    partial=False), under fn's name and docstring and with that signature for inspect.  A call is bound against it, so a caller's
+    mistake (an unknown keyword, a missing argument) is the TypeError of a written-out parameter list; fn receives the bound
+    arguments as the dict `seg` (defaults applied) and its own ones again by keyword."""
+    own = list(inspect.signature(fn).parameters.values())[2:]
+    sig = inspect.Signature([_P("self", _P.POSITIONAL_OR_KEYWORD)] + SEGMENT_PARAMS + own + [_P("partial", _P.POSITIONAL_OR_KEYWORD, default=False)])
+
+    @functools.wraps(fn)
+    def method(*args, **kw):
+        bound = sig.bind(*args, **kw)
+        bound.apply_defaults()
+        seg = bound.arguments
+        return fn(seg["self"], seg, **{p.name: seg[p.name] for p in own})
+    method.__signature__ = sig
+    return method
+
+
+_RowRoute = collections.namedtuple("_RowRoute", "method buffers finish")      # CausalEngine._row_routes
 
 
 class CausalEngine(object):
@@ -158,124 +206,91 @@ class CausalEngine(object):
                                                         self._stream()), "bgm_causal_logpost_grad")
         return out, grad
 
-    def hmc_run(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False, row_base=0,
-                up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0, effect=_lib.EFFECT_NONE,
-                sample_y=True, x_values=None, adrf_partial=None, ite=None, labels=None, n_labels=0, group_partial=None, partial=False):
+    @_segment_method
+    def hmc_run(self, seg, effect=_lib.EFFECT_NONE, sample_y=True, x_values=None, adrf_partial=None, ite=None, labels=None, n_labels=0,
+                group_partial=None):
         """One segment of the HMC latent sampler for all rows (bgm_causal_hmc_run); state / logp / grad / step are in / out.
         effect = EFFECT_ADRF / EFFECT_ITE: the segment runs the kernels with the effect pass inside (bgm_causal_hmc_run_effects):
         x_values [n_doses] and adrf_partial [n_slots, n_keep, n_doses] (+=), or ite [n, n_keep], receive the effects of the
         iterations >= burn_in of this segment.  effect = EFFECT_GROUP_ITE: hmc_run_group_effects with labels / n_labels /
         group_partial.  partial=True: NaN in y, or in x and y, marks what a row does not observe (logpost_grad); EFFECT_ADRF and
         EFFECT_GROUP_ITE have no kernels for it and raise the library's error."""
-        with self._partial_rows(partial, x, y):
-            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
-                                  s_max, acc_count, draws, n_keep)
-            if effect == _lib.EFFECT_NONE:
-                _lib.check(self.lib.bgm_causal_hmc_run(*args, self._stream()), "bgm_causal_hmc_run")
-            elif effect == _lib.EFFECT_GROUP_ITE:
-                _lib.check(self.lib.bgm_causal_hmc_run_group_effects(*args, int(bool(sample_y)), _ptr(labels), int(n_labels), _ptr(group_partial),
-                                                                     self._stream()), "bgm_causal_hmc_run_group_effects")
-            elif effect == (_lib.EFFECT_ITE if self.binary else _lib.EFFECT_ADRF):
-                _lib.check(self.lib.bgm_causal_hmc_run_effects(*args, int(bool(sample_y)), _ptr(x_values),
-                                                               0 if x_values is None else int(x_values.numel()), _ptr(adrf_partial), _ptr(ite),
-                                                               self._stream()), "bgm_causal_hmc_run_effects")
-            else:
-                raise ValueError("hmc_run: effect must be EFFECT_NONE or the effect of the treatment type (EFFECT_ITE for a binary "
-                                 "treatment, EFFECT_ADRF otherwise); got %r" % (effect,))
+        if effect == _lib.EFFECT_NONE:
+            self._hmc_segment("bgm_causal_hmc_run", seg)
+        elif effect == _lib.EFFECT_GROUP_ITE:
+            self._hmc_segment("bgm_causal_hmc_run_group_effects", seg, int(bool(sample_y)), _ptr(labels), int(n_labels), _ptr(group_partial))
+        elif effect == (_lib.EFFECT_ITE if self.binary else _lib.EFFECT_ADRF):
+            self._hmc_segment("bgm_causal_hmc_run_effects", seg, *_doses(sample_y, x_values), _ptr(adrf_partial), _ptr(ite))
+        else:
+            raise ValueError("hmc_run: effect must be EFFECT_NONE or the effect of the treatment type (EFFECT_ITE for a binary "
+                             "treatment, EFFECT_ADRF otherwise); got %r" % (effect,))
 
     def _hmc_args(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min, s_max,
                   acc_count, draws, n_keep):
-        """The handle and the 24 arguments that each of the four entry points of an HMC segment takes first (include/bgm_hip.h),
-        marshalled for ctypes; the entry point's own arguments and the stream follow them."""
+        """The handle and the 24 arguments that every entry point of an HMC segment takes first (include/bgm_hip.h; the parameters
+        of SEGMENT_PARAMS in their order), marshalled for ctypes; the entry point's own arguments and the stream follow them."""
         return (self.h, _ptr(x), _ptr(y), _ptr(v), v.shape[0], int(row_base), _ptr(state), _ptr(logp), _ptr(grad), _ptr(step), _ptr(up),
                 _ptr(dn), 0 if up is None else int(up.numel()), float(s_min), float(s_max), int(bool(init)), int(it_begin), int(n_iters),
                 int(burn_in), int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(acc_count), _ptr(draws), int(n_keep))
 
-    def hmc_run_rows_effects(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
-                             row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
-                             sample_y=True, x_values=None, row_moments=None, row_draws=None, partial=False):
+    def _hmc_segment(self, entry, seg, *own):
+        """One segment through the C entry point `entry`: inside the observation pattern of seg["partial"], the common arguments of
+        seg (a segment method's bound arguments), the entry point's `own`, the stream; the library's error raises."""
+        with self._partial_rows(seg["partial"], seg["x"], seg["y"]):
+            _lib.check(getattr(self.lib, entry)(*self._hmc_args(*(seg[p.name] for p in SEGMENT_PARAMS)), *own, self._stream()), entry)
+
+    @_segment_method
+    def hmc_run_rows_effects(self, seg, sample_y=True, x_values=None, row_moments=None, row_draws=None):
         """hmc_run with the dose-response of every row kept (bgm_causal_hmc_run_row_effects; a continuous treatment): x_values
         [n_doses]; row_moments [3, n_doses, n] float32 (ref = y at retained draw 0, s1 = sum of y - ref, s2 = sum of (y - ref)^2,
         in / out across segments) and, optionally, row_draws [n, n_doses, n_keep] receive y_i(x_k) of the iterations >= burn_in of
         this segment.  partial=True: as in hmc_run."""
-        with self._partial_rows(partial, x, y):
-            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
-                                  s_max, acc_count, draws, n_keep)
-            _lib.check(self.lib.bgm_causal_hmc_run_row_effects(*args, int(bool(sample_y)), _ptr(x_values),
-                                                               0 if x_values is None else int(x_values.numel()), _ptr(row_moments),
-                                                               _ptr(row_draws), self._stream()), "bgm_causal_hmc_run_row_effects")
+        self._hmc_segment("bgm_causal_hmc_run_row_effects", seg, *_doses(sample_y, x_values), _ptr(row_moments), _ptr(row_draws))
 
-    def hmc_run_rows_tails(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
-                           row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
-                           sample_y=True, x_values=None, row_moments=None, row_draws=None, row_tails=None, partial=False):
+    @_segment_method
+    def hmc_run_rows_tails(self, seg, sample_y=True, x_values=None, row_moments=None, row_draws=None, row_tails=None):
         """hmc_run_rows_effects with the two tails of every (row, dose) series kept beside its moments
         (bgm_causal_hmc_run_row_tails): row_tails [2, K, n_doses, n] float32, in / out across segments, tail 0 the K smallest and
         tail 1 the K largest of the retained y_i(x_k), each a heap in no sorted order (row_tail_quantiles reads them); 1 <= K <=
         n_keep.  Chain, moments and row_draws are those of hmc_run_rows_effects bit for bit."""
-        if row_tails is not None and (row_tails.dim() != 4 or row_tails.shape[0] != 2 or row_tails.dtype != torch.float32
-                                      or not row_tails.is_contiguous()):
-            raise ValueError("hmc_run_rows_tails: row_tails must be a contiguous float32 tensor [2, K, n_doses, n]; got %s %r" %
-                             (row_tails.dtype, tuple(row_tails.shape)))
-        n_doses = 0 if x_values is None else int(x_values.numel())
-        if row_tails is not None and tuple(row_tails.shape[2:]) != (n_doses, v.shape[0]):
+        doses, n = _doses(sample_y, x_values), seg["v"].shape[0]
+        _check_buffer("hmc_run_rows_tails", "row_tails", row_tails, torch.float32, (2, None, None, None), "[2, K, n_doses, n]")
+        if row_tails is not None and tuple(row_tails.shape[2:]) != (doses[2], n):      # (its own words: the sizes, and the shape alone)
             raise ValueError("hmc_run_rows_tails: row_tails must be [2, K, n_doses, n] = [2, K, %d, %d]; got %r" %
-                             (n_doses, v.shape[0], tuple(row_tails.shape)))
-        with self._partial_rows(partial, x, y):
-            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
-                                  s_max, acc_count, draws, n_keep)
-            _lib.check(self.lib.bgm_causal_hmc_run_row_tails(*args, int(bool(sample_y)), _ptr(x_values), n_doses, _ptr(row_moments),
-                                                             _ptr(row_draws), _ptr(row_tails),
-                                                             0 if row_tails is None else int(row_tails.shape[1]), self._stream()),
-                       "bgm_causal_hmc_run_row_tails")
+                             (doses[2], n, tuple(row_tails.shape)))
+        self._hmc_segment("bgm_causal_hmc_run_row_tails", seg, *doses, _ptr(row_moments), _ptr(row_draws), _ptr(row_tails),
+                          0 if row_tails is None else int(row_tails.shape[1]))
 
-    def hmc_run_rows_contrasts(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
-                               row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
-                               sample_y=True, x_values=None, row_moments=None, row_cmoments=None, contrast_draws=None,
-                               contrast_tails=None, partial=False):
+    @_segment_method
+    def hmc_run_rows_contrasts(self, seg, sample_y=True, x_values=None, row_moments=None, row_cmoments=None, contrast_draws=None,
+                               contrast_tails=None):
         """hmc_run_rows_effects with the contrast of every dose against the baseline x_values[0] kept beside the curve
         (bgm_causal_hmc_run_row_contrasts): c_i(k) = y_i(x_k) - y_i(x_0) of every retained draw, one float32 subtraction inside the
         kernel.  row_cmoments [3, n_doses, n] float32 receives its shifted sums (the rule of row_moments, in / out across
         segments); optionally contrast_draws [n, n_doses, n_keep] the differences themselves and contrast_tails [2, K, n_doses, n]
         their K smallest and K largest (hmc_run_rows_tails' layout, 1 <= K <= n_keep).  Chain and row_moments are those of
         hmc_run_rows_effects bit for bit.  The library refuses the call while a trajectory option is set."""
-        n_doses = 0 if x_values is None else int(x_values.numel())
-        if contrast_tails is not None and (contrast_tails.dim() != 4 or contrast_tails.shape[0] != 2 or contrast_tails.dtype != torch.float32
-                                           or not contrast_tails.is_contiguous()
-                                           or tuple(contrast_tails.shape[2:]) != (n_doses, v.shape[0])):
-            raise ValueError("hmc_run_rows_contrasts: contrast_tails must be a contiguous float32 tensor [2, K, n_doses, n] = "
-                             "[2, K, %d, %d]; got %s %r" % (n_doses, v.shape[0], contrast_tails.dtype, tuple(contrast_tails.shape)))
-        with self._partial_rows(partial, x, y):
-            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
-                                  s_max, acc_count, draws, n_keep)
-            _lib.check(self.lib.bgm_causal_hmc_run_row_contrasts(*args, int(bool(sample_y)), _ptr(x_values), n_doses, _ptr(row_moments),
-                                                                 _ptr(row_cmoments), _ptr(contrast_draws), _ptr(contrast_tails),
-                                                                 0 if contrast_tails is None else int(contrast_tails.shape[1]),
-                                                                 self._stream()), "bgm_causal_hmc_run_row_contrasts")
+        doses, n = _doses(sample_y, x_values), seg["v"].shape[0]
+        _check_buffer("hmc_run_rows_contrasts", "contrast_tails", contrast_tails, torch.float32, (2, None, doses[2], n),
+                      "[2, K, n_doses, n] = [2, K, %d, %d]" % (doses[2], n))
+        self._hmc_segment("bgm_causal_hmc_run_row_contrasts", seg, *doses, _ptr(row_moments), _ptr(row_cmoments), _ptr(contrast_draws),
+                          _ptr(contrast_tails), 0 if contrast_tails is None else int(contrast_tails.shape[1]))
 
-    def hmc_run_rows_choice(self, x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init=False,
-                            row_base=0, up=None, dn=None, s_min=RA.S_MIN, s_max=RA.S_MAX, acc_count=None, draws=None, n_keep=0,
-                            sample_y=True, x_values=None, row_moments=None, row_draws=None, best_count=None, best_moments=None,
-                            above_count=None, threshold=0.0, maximize=True, partial=False):
+    @_segment_method
+    def hmc_run_rows_choice(self, seg, sample_y=True, x_values=None, row_moments=None, row_draws=None, best_count=None, best_moments=None,
+                            above_count=None, threshold=0.0, maximize=True):
         """hmc_run_rows_effects with the choice among the doses kept beside the curve (bgm_causal_hmc_run_row_choice): best_count
         [n_doses, n] int32 counts the retained draws at which dose k gave the row its best outcome (the largest y with maximize,
         else the smallest; the lowest dose index on ties), best_moments [2, n] float32 holds ref = the best y of retained draw 0
         and s1 = the sum of best - ref, and, optionally, above_count [n_doses, n] int32 counts the draws with y > threshold (a
         finite number).  All are written by the first retained iteration and in / out across segments.  Chain, row_moments and
         row_draws are those of hmc_run_rows_effects bit for bit.  The library refuses the call while a trajectory option is set."""
-        n_doses = 0 if x_values is None else int(x_values.numel())
-        for name, t, shape, dt in (("best_count", best_count, (n_doses, v.shape[0]), torch.int32),
-                                   ("best_moments", best_moments, (2, v.shape[0]), torch.float32),
-                                   ("above_count", above_count, (n_doses, v.shape[0]), torch.int32)):
-            if t is not None and (t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise ValueError("hmc_run_rows_choice: %s must be a contiguous %s tensor %r; got %s %r" %
-                                 (name, str(dt).replace("torch.", ""), shape, t.dtype, tuple(t.shape)))
-        with self._partial_rows(partial, x, y):
-            args = self._hmc_args(x, y, v, state, logp, grad, step, it_begin, n_iters, burn_in, n_leapfrog, seed, init, row_base, up, dn, s_min,
-                                  s_max, acc_count, draws, n_keep)
-            _lib.check(self.lib.bgm_causal_hmc_run_row_choice(*args, int(bool(sample_y)), _ptr(x_values), n_doses, _ptr(row_moments),
-                                                              _ptr(row_draws), _ptr(best_count), _ptr(best_moments), _ptr(above_count),
-                                                              float(threshold), int(bool(maximize)), self._stream()),
-                       "bgm_causal_hmc_run_row_choice")
+        doses, n = _doses(sample_y, x_values), seg["v"].shape[0]
+        for name, t, shape, dt in (("best_count", best_count, (doses[2], n), torch.int32), ("best_moments", best_moments, (2, n), torch.float32),
+                                   ("above_count", above_count, (doses[2], n), torch.int32)):
+            _check_buffer("hmc_run_rows_choice", name, t, dt, shape, repr(shape))
+        self._hmc_segment("bgm_causal_hmc_run_row_choice", seg, *doses, _ptr(row_moments), _ptr(row_draws), _ptr(best_count),
+                          _ptr(best_moments), _ptr(above_count), float(threshold), int(bool(maximize)))
 
     def row_tail_quantiles(self, tails, m, q_lo, q_hi):
         """tails [2, K, ...] float32 on the device (hmc_sample's out["tails"]: the K smallest and the K largest of every series' m
@@ -333,8 +348,7 @@ class CausalEngine(object):
         (device), aligned with the rows of the call, += the steps of every iteration >= burn_in.  All three off (the default):
         back to the kernels without the option.  hmc_run_rows_tails and EFFECT_GROUP_ITE raise the library's error while set."""
         T, jit = HM.resolve_trajectory(max_trajectory, jitter)
-        if n_steps is not None and (n_steps.dtype != torch.int32 or n_steps.dim() != 1 or not n_steps.is_contiguous()):
-            raise ValueError("set_hmc_trajectory: n_steps must be a contiguous int32 tensor [n]; got %s %r" % (n_steps.dtype, tuple(n_steps.shape)))
+        _check_buffer("set_hmc_trajectory", "n_steps", n_steps, torch.int32, (None,), "[n]")
         self._hmc_traj_keep = n_steps                       # keep the buffer alive while set
         _lib.check(self.lib.bgm_causal_hmc_set_trajectory(self.h, float(T), int(jit), _ptr(n_steps)), "bgm_causal_hmc_set_trajectory")
 
@@ -410,37 +424,14 @@ class CausalEngine(object):
         HM.check_args(step_size, n_leapfrog, adapt)
         traj_T, traj_jit = HM.resolve_trajectory(max_trajectory, jitter)
         traj = traj_T > 0.0 or traj_jit != 0
-        if traj and row_tails is not None:
-            raise ValueError("hmc_sample: max_trajectory / jitter are not available with row_tails: the tail-buffer kernels "
-                             "(hmc_run_rows_tails) have no variant with a trajectory length per chain")
-        if row_contrasts:
-            if not row_effects:
-                raise ValueError("hmc_sample: row_contrasts belongs to row_effects=True")
-            if traj:
-                raise ValueError("hmc_sample: max_trajectory / jitter are not available with row_contrasts: the dose-contrast kernels "
-                                 "(hmc_run_rows_contrasts) have no variant with a trajectory length per chain")
-            if self.binary:
-                raise ValueError("hmc_sample: row_contrasts is the contrast between two doses of a continuous treatment; a binary "
-                                 "treatment has its per-row effect already (effect=EFFECT_ITE)")
+        kind = HM.result_kind(effect, row_effects, row_tails, row_contrasts, row_choice)
+        HM.check_result(kind, lambda: self.binary, traj, row_draws, row_tails, row_contrasts)
         if row_choice:
-            if not row_effects:
-                raise ValueError("hmc_sample: row_choice belongs to row_effects=True")
-            if row_contrasts or row_tails is not None:
-                raise ValueError("hmc_sample: row_choice is not available with row_contrasts or row_tails: the dose-choice kernels "
-                                 "(hmc_run_rows_choice) have no variant with contrasts or tail buffers")
-            if traj:
-                raise ValueError("hmc_sample: max_trajectory / jitter are not available with row_choice: the dose-choice kernels "
-                                 "(hmc_run_rows_choice) have no variant with a trajectory length per chain")
-            if self.binary:
-                raise ValueError("hmc_sample: row_choice is the choice among the doses of a continuous treatment; a binary "
-                                 "treatment has its per-row effect already (effect=EFFECT_ITE)")
             threshold = HM.check_threshold(threshold)
-            HM.check_choice_kernel(self.q, mass not in (None, "identity") or mass_scale is not None, partial)
+            if kind.hole is not None:
+                HM.check_choice_kernel(self.q, mass not in (None, "identity") or mass_scale is not None, partial)
         elif threshold is not None:
             raise ValueError("hmc_sample: threshold belongs to row_choice=True")
-        if traj and effect == _lib.EFFECT_GROUP_ITE:
-            raise ValueError("hmc_sample: max_trajectory / jitter are not available with effect=EFFECT_GROUP_ITE: the label-sum kernels "
-                             "(hmc_run_group_effects) have no variant with a trajectory length per chain")
         diag = HM.check_mass(mass, True, adapt if adapt_table is None else True) is not None
         if diag and mass_scale is not None:
             raise ValueError("hmc_sample: mass='diag' estimates the metric; mass_scale gives a frozen one")
@@ -467,8 +458,8 @@ class CausalEngine(object):
         acc = torch.zeros(total, device=dev, dtype=torch.int32)
         draws = torch.empty((n_keep, n, self.q), device=dev, dtype=torch.float32) if want_draws else None
         chunk = total if chunk is None else max(1, int(chunk))
-        launch, route_kw, collect = self._hmc_route(n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails,
-                                                    row_contrasts, (bool(maximize), threshold) if row_choice else None)
+        launch, route_kw, collect = self._hmc_route(kind, n, n_keep, x_values, labels, n_labels, row_draws, row_tails,
+                                                    (bool(maximize), threshold) if row_choice else None)
         scale = moments = None
         if diag:
             scale = torch.ones((n, self.q), device=dev, dtype=torch.float32)
@@ -508,31 +499,17 @@ class CausalEngine(object):
         collect(out)
         return out
 
-    # The result routes of hmc_sample, one per kind of result.  Each checks what is its own, allocates its buffers and returns
-    # (launch, kw, collect): the engine method that runs a segment, the keyword arguments it takes besides the common ones, and
-    # the function that adds the route's keys to the returned dict.
-    def _hmc_route(self, n, n_keep, effect, x_values, labels, n_labels, row_effects, row_draws, row_tails=None, row_contrasts=False,
-                   row_choice=None):
-        kinds = {_lib.EFFECT_NONE: self._route_none, _lib.EFFECT_ADRF: self._route_adrf, _lib.EFFECT_ITE: self._route_ite,
-                 _lib.EFFECT_GROUP_ITE: self._route_group_ite}
-        if effect not in kinds:
-            raise ValueError("hmc_sample: effect must be EFFECT_NONE, EFFECT_ADRF, EFFECT_ITE or EFFECT_GROUP_ITE; got %r" % (effect,))
-        route = kinds[effect](n, n_keep, x_values, labels, n_labels)
-        if labels is not None and effect != _lib.EFFECT_GROUP_ITE:
+    # The result routes of hmc_sample, one per kind of result (causal_hmc.RESULT_KINDS; which kind the options ask for and what does
+    # not exist with it was decided there, before a device was touched).  Each checks what is its own, allocates its buffers and
+    # returns (launch, kw, collect): the engine method that runs a segment, the keyword arguments it takes besides the common ones,
+    # and the function that adds the route's keys to the returned dict.
+    def _hmc_route(self, kind, n, n_keep, x_values, labels, n_labels, row_draws, row_tails=None, row_choice=None):
+        if labels is not None and (kind is None or kind.name != "group_ite"):
             raise ValueError("hmc_sample: labels belong to effect=EFFECT_GROUP_ITE")
-        if row_effects:
-            if effect != _lib.EFFECT_NONE:
-                raise ValueError("hmc_sample: row_effects and effect exclude each other (the panel's ADRF is the mean of the rows' curves)")
-            return self._route_rows(n, n_keep, x_values, row_draws, row_tails, row_contrasts, row_choice)
-        if row_choice is not None:
-            raise ValueError("hmc_sample: row_choice belongs to row_effects=True")
-        if row_contrasts:
-            raise ValueError("hmc_sample: row_contrasts belongs to row_effects=True")
-        if row_draws:
-            raise ValueError("hmc_sample: row_draws belongs to row_effects=True")
-        if row_tails is not None:
-            raise ValueError("hmc_sample: row_tails belongs to row_effects=True")
-        return route
+        if kind is not None and kind.request.get("row_effects"):
+            return self._route_rows(kind, n, n_keep, x_values, row_draws, row_tails, row_choice)
+        route = {None: self._route_none, "adrf": self._route_adrf, "ite": self._route_ite, "group_ite": self._route_group_ite}
+        return route[kind and kind.name](n, n_keep, x_values, labels, n_labels)
 
     def _evaluate_slots(self, n):
         ns = C.c_int32()
@@ -556,9 +533,6 @@ class CausalEngine(object):
         return self.hmc_run, dict(effect=_lib.EFFECT_ITE, ite=ite), lambda out: out.update(ite=ite)
 
     def _route_group_ite(self, n, n_keep, x_values, labels, n_labels):
-        if not self.binary:
-            raise ValueError("hmc_sample: effect=EFFECT_GROUP_ITE sums the treatment effect of a binary treatment; a continuous "
-                             "treatment has its dose-response (effect=EFFECT_ADRF)")
         lab, n_lab = self._group_labels(labels, n_labels, n, "hmc_sample")
         n_slots = self._evaluate_slots(n)
         try:
@@ -569,53 +543,69 @@ class CausalEngine(object):
         return (self.hmc_run, dict(effect=_lib.EFFECT_GROUP_ITE, labels=lab, n_labels=n_lab, group_partial=part),
                 lambda out: out.update(group_partial=part, group_sums=self.adrf_reduce(part, n_slots, n_lab, n_keep, 1.0)))
 
-    def _route_rows(self, n, n_keep, x_values, row_draws, row_tails=None, row_contrasts=False, row_choice=None):
+    def _row_routes(self):
+        """The per-row kinds (causal_hmc.RESULT_KINDS): the engine method of a segment, the buffers the kind allocates beside
+        row_moments -- (keyword of that method, shape over n_doses d, n, n_keep k and the tail size K, dtype, zeroed, asked for by)
+        -- and what it adds to the result beside row_mean / row_sd.  The stored series and the tails are those of the values or,
+        for the contrasts, of the contrasts: the same buffers under the kind's own keywords and result key.  A buffer that is not
+        zeroed is written whole by the first retained iteration."""
+        f32, i32 = torch.float32, torch.int32
+        draws, tails = ("row_draws", "ndk", f32, False, "draws"), ("row_tails", "2Kdn", f32, False, "tails")
+        return {"rows": _RowRoute(self.hmc_run_rows_effects, (draws,), self._finish_rows),
+                "tails": _RowRoute(self.hmc_run_rows_tails, (draws, tails), self._finish_rows),
+                "contrasts": _RowRoute(self.hmc_run_rows_contrasts, (("row_cmoments", "3dn", f32, True, None),
+                                                                     ("contrast_draws",) + draws[1:], ("contrast_tails",) + tails[1:]),
+                                       self._finish_contrasts),
+                "choice": _RowRoute(self.hmc_run_rows_choice, (draws, ("best_count", "dn", i32, True, None), ("best_moments", "2n", f32, True, None),
+                                                               ("above_count", "dn", i32, True, "threshold")), self._finish_choice)}
+
+    def _route_rows(self, kind, n, n_keep, x_values, row_draws, row_tails=None, row_choice=None):
         if self.binary:
-            raise ValueError("hmc_sample: row_effects is the dose-response of a continuous treatment; a binary treatment has its "
-                             "per-row effect already (effect=EFFECT_ITE)")
+            raise ValueError(kind.wrong_treatment)
         if x_values is None:
             raise ValueError("hmc_sample: row_effects needs x_values")
+        if row_tails is not None and (isinstance(row_tails, bool) or int(row_tails) != row_tails or not 1 <= int(row_tails) <= int(n_keep)):
+            raise ValueError("hmc_sample: row_tails must be an integer K with 1 <= K <= n_keep = %d; got %r" % (int(n_keep), row_tails))
         xv = _f32(np.atleast_1d(np.asarray(x_values, dtype=np.float32)), self.device)
-        mom = torch.zeros((3, xv.numel(), n), device=self.device, dtype=torch.float32)      # ref, s1, s2
-        row_y = torch.empty((n, xv.numel(), n_keep), device=self.device, dtype=torch.float32) if row_draws else None
-        tails = None
-        if row_tails is not None:
-            if isinstance(row_tails, bool) or int(row_tails) != row_tails or not 1 <= int(row_tails) <= int(n_keep):
-                raise ValueError("hmc_sample: row_tails must be an integer K with 1 <= K <= n_keep = %d; got %r" % (int(n_keep), row_tails))
-            tails = torch.empty((2, int(row_tails), xv.numel(), n), device=self.device, dtype=torch.float32)      # draw 0 initialises it
-        cmom = torch.zeros((3, xv.numel(), n), device=self.device, dtype=torch.float32) if row_contrasts else None
-        best = bmom = above = None
-        if row_choice is not None:      # (maximize, threshold | None); the first retained iteration writes every element
-            best = torch.zeros((xv.numel(), n), device=self.device, dtype=torch.int32)
-            bmom = torch.zeros((2, n), device=self.device, dtype=torch.float32)
-            above = torch.zeros((xv.numel(), n), device=self.device, dtype=torch.int32) if row_choice[1] is not None else None
+        size = {"n": n, "d": xv.numel(), "k": n_keep, "K": row_tails and int(row_tails), "2": 2, "3": 3}
+        asked = dict(draws=bool(row_draws), tails=row_tails is not None, threshold=row_choice is not None and row_choice[1] is not None)
+        route = self._row_routes()[kind.name]
+        kw = dict(x_values=xv, row_moments=torch.zeros((3, xv.numel(), n), device=self.device, dtype=torch.float32))      # ref, s1, s2
+        for name, shape, dtype, zeroed, when in route.buffers:
+            make = torch.zeros if zeroed else torch.empty
+            kw[name] = make(tuple(size[c] for c in shape), device=self.device, dtype=dtype) if when is None or asked[when] else None
+        if row_choice is not None:
+            kw.update(maximize=row_choice[0], threshold=0.0 if row_choice[1] is None else row_choice[1])
 
         def collect(out):
-            mean, sd = HM.row_moments_finalize(mom[0], mom[1], mom[2], n_keep)
-            out["row_mean"], out["row_sd"] = mean.t().contiguous(), sd.t().contiguous()
-            if cmom is not None:
-                mean, sd = HM.row_moments_finalize(cmom[0], cmom[1], cmom[2], n_keep)
-                out["contrast_mean"], out["contrast_sd"] = mean.t().contiguous(), sd.t().contiguous()
-            if row_y is not None:
-                out["contrast_draws" if row_contrasts else "row_draws"] = row_y
-            if tails is not None:
-                out["tails"] = tails
-            if best is not None:
-                out["best_count"] = best.t().contiguous().long()
-                out["best_ref"], out["best_s1"] = bmom[0], bmom[1]
-                out["best_mean"] = bmom[0].double() + bmom[1].double() / float(max(1, int(n_keep)))
-                if above is not None:
-                    out["above_count"] = above.t().contiguous().long()
-        if row_choice is not None:
-            return (self.hmc_run_rows_choice,
-                    dict(x_values=xv, row_moments=mom, row_draws=row_y, best_count=best, best_moments=bmom, above_count=above,
-                         threshold=0.0 if row_choice[1] is None else row_choice[1], maximize=row_choice[0]), collect)
-        if row_contrasts:      # the draws and the tails, where asked for, are those of the contrasts
-            return (self.hmc_run_rows_contrasts,
-                    dict(x_values=xv, row_moments=mom, row_cmoments=cmom, contrast_draws=row_y, contrast_tails=tails), collect)
-        if tails is not None:
-            return self.hmc_run_rows_tails, dict(x_values=xv, row_moments=mom, row_draws=row_y, row_tails=tails), collect
-        return self.hmc_run_rows_effects, dict(x_values=xv, row_moments=mom, row_draws=row_y), collect
+            out["row_mean"], out["row_sd"] = self._row_moments(kw["row_moments"], n_keep)
+            route.finish(out, kw, n_keep)
+        return route.method, kw, collect
+
+    @staticmethod
+    def _row_moments(mom, n_keep):
+        mean, sd = HM.row_moments_finalize(mom[0], mom[1], mom[2], n_keep)
+        return mean.t().contiguous(), sd.t().contiguous()
+
+    @staticmethod
+    def _finish_rows(out, kw, n_keep, draws="row_draws", tails="row_tails"):
+        if kw[draws] is not None:
+            out[draws] = kw[draws]
+        if kw.get(tails) is not None:
+            out["tails"] = kw[tails]
+
+    def _finish_contrasts(self, out, kw, n_keep):
+        out["contrast_mean"], out["contrast_sd"] = self._row_moments(kw["row_cmoments"], n_keep)
+        self._finish_rows(out, kw, n_keep, "contrast_draws", "contrast_tails")
+
+    def _finish_choice(self, out, kw, n_keep):
+        self._finish_rows(out, kw, n_keep)
+        bmom = kw["best_moments"]
+        out["best_count"] = kw["best_count"].t().contiguous().long()
+        out["best_ref"], out["best_s1"] = bmom[0], bmom[1]
+        out["best_mean"] = bmom[0].double() + bmom[1].double() / float(max(1, int(n_keep)))
+        if kw["above_count"] is not None:
+            out["above_count"] = kw["above_count"].t().contiguous().long()
 
     def encode(self, v):
         v = _f32(v, self.device)

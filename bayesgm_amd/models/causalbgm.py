@@ -765,12 +765,15 @@ class CausalBGM(object):
         return mean, bounds
 
     def _row_series(self, data, x_values, alpha, run, sample_y, interval, draw_budget_bytes, verbose, partial=False, traj=(0.0, 0),
-                    contrasts=False, choice=None):
-        """What _individual_rows, predict_dose_effect and predict_best_dose share -> ((mean, sd) of y_i(x_k), bounds, None).
-        contrasts=True: x_values[0] is the baseline, the kernels also keep c_i(k) = y_i(x_k) - y_i(x_0) per draw (hmc_sample,
-        row_contrasts), the stored draws and the tails are those of c, and the result is ((mean, sd) of y, bounds of c, (mean, sd)
-        of c).  choice=(maximize, threshold | None): the kernels also compare the doses per draw (hmc_sample, row_choice), and the
-        third item is (best_count [n, n_doses], best_ref [n], best_s1 [n], above_count [n, n_doses] | None), float64."""
+                    kind=hmc_mod.RESULT_KINDS["rows"], **kind_kw):
+        """What _individual_rows, predict_dose_effect and predict_best_dose share -> ((mean, sd) of y_i(x_k), bounds, None).  kind
+        is the per-row record of causal_hmc.RESULT_KINDS whose kernels run (its `request` asks engine.hmc_sample for it; with
+        interval='tails' the tails are those of that kind) and kind_kw the options of hmc_sample that are the kind's own.
+        "contrasts": x_values[0] is the baseline, the kernels also keep c_i(k) = y_i(x_k) - y_i(x_0) per draw, the stored draws
+        and the tails are those of c, and the result is ((mean, sd) of y, bounds of c, (mean, sd) of c).  "choice" (kind_kw:
+        maximize, threshold | None): the kernels also compare the doses per draw, and the third item is (best_count [n, n_doses],
+        best_ref [n], best_s1 [n], above_count [n, n_doses] | None), float64."""
+        contrasts, choice = kind.name == "contrasts", kind.name == "choice"
         burn_in, n_mcmc, hmc = run
         n_test, n_doses = len(data[0]), len(x_values)
         seed = self._begin_sampling(verbose)
@@ -783,15 +786,15 @@ class CausalBGM(object):
         # mean, sd(, lower, upper)(, contrast mean, contrast sd): this rank's rows filled
         res = torch.zeros((nb + (2 if contrasts else 0), n_test, n_doses), device=eng.device, dtype=torch.float64)
         draws_key = "contrast_draws" if contrasts else "row_draws"
-        if choice is not None:      # best_count, above_count [n, n_doses]; best_ref, best_s1 [n]: this rank's rows filled
+        if choice:      # best_count, above_count [n, n_doses]; best_ref, best_s1 [n]: this rank's rows filled
             cnt = torch.zeros((2, n_test, n_doses), device=eng.device, dtype=torch.float64)
             bst = torch.zeros((2, n_test), device=eng.device, dtype=torch.float64)
 
         def consume(s0, e0, x, out):
             res[0, s0:e0], res[1, s0:e0] = out["row_mean"], out["row_sd"]
-            if choice is not None:
+            if choice:
                 cnt[0, s0:e0], bst[0, s0:e0], bst[1, s0:e0] = out["best_count"].double(), out["best_ref"].double(), out["best_s1"].double()
-                if choice[1] is not None:
+                if kind_kw["threshold"] is not None:
                     cnt[1, s0:e0] = out["above_count"].double()
             if contrasts:
                 res[nb, s0:e0], res[nb + 1, s0:e0] = out["contrast_mean"], out["contrast_sd"]
@@ -801,17 +804,14 @@ class CausalBGM(object):
             if tails:      # [2, K, n_doses, rows] -> bounds [n_doses, rows]
                 lo, hi = eng.row_tail_quantiles(out.pop("tails"), n_mcmc, alpha / 2, 1 - alpha / 2)
                 res[2, s0:e0], res[3, s0:e0] = lo.t().double(), hi.t().double()
-        self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, row_effects=True, row_draws=quantile,
-                            x_values=x_values, sample_y=sample_y, partial=partial, **(dict(row_tails=k_tail) if tails else {}),
-                            **(dict(row_contrasts=True) if contrasts else {}),
-                            **(dict(row_choice=True, maximize=choice[0], threshold=choice[1]) if choice is not None else {}),
-                            **self._traj_kw(traj))
+        self._sample_blocks(data, blocks, (burn_in, n_mcmc, seed, hmc), consume, verbose, row_draws=quantile, row_tails=k_tail,
+                            x_values=x_values, sample_y=sample_y, partial=partial, **kind.request, **kind_kw, **self._traj_kw(traj))
         res = parallel.all_reduce_sum_(res).cpu().numpy()
         mean, sd = res[0], res[1]
         contrast = (res[nb], res[nb + 1]) if contrasts else None
-        if choice is not None:
+        if choice:
             cnt, bst = parallel.all_reduce_sum_(cnt).cpu().numpy(), parallel.all_reduce_sum_(bst).cpu().numpy()
-            contrast = (cnt[0], bst[0], bst[1], cnt[1] if choice[1] is not None else None)
+            contrast = (cnt[0], bst[0], bst[1], cnt[1] if kind_kw["threshold"] is not None else None)
         if quantile or tails:
             bounds = np.stack([res[2], res[3]], axis=-1)
         else:
@@ -864,7 +864,7 @@ class CausalBGM(object):
             data = hmc_mod.check_partial_panel(*data)
         doses = np.concatenate([[baseline], x_values.reshape(-1)])
         curve, bounds, (c_mean, c_sd) = self._row_series(data, doses, alpha, (burn_in, n_mcmc, hmc), sample_y, interval, draw_budget_bytes,
-                                                         verbose, partial=bool(partial), contrasts=True)
+                                                         verbose, partial=bool(partial), kind=hmc_mod.RESULT_KINDS["contrasts"])
         self.dose_effect_curve_ = curve
         effect, self.dose_effect_sd_, bounds = c_mean[:, 1:], c_sd[:, 1:], bounds[:, 1:]
         if groups is not None:
@@ -918,7 +918,8 @@ class CausalBGM(object):
             data = hmc_mod.check_partial_panel(*data)
         maximize = bool(maximize)
         (mean, sd), _, (count, ref, s1, above) = self._row_series(data, x_values.reshape(-1), 0.5, (burn_in, n_mcmc, hmc), sample_y, 'normal',
-                                                                  None, verbose, partial=bool(partial), choice=(maximize, threshold))
+                                                                  None, verbose, partial=bool(partial), kind=hmc_mod.RESULT_KINDS["choice"],
+                                                                  maximize=maximize, threshold=threshold)
         self.dose_choice_curve_ = (mean, sd)
         prob_best, _, self.dose_regret_ = hmc_mod.choice_finalize(count, ref, s1, mean, n_mcmc, maximize)
         if above is not None:
